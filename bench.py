@@ -11,14 +11,28 @@ Workload (BASELINE.json configs[1]; per GPU, weak scaling = configs[4] at N=8):
   GraphTripleConv 128/256/128, 5+5 layers).  Inputs are resident in HBM before the timed region.  For N>1 every rank trains its
   own 64 graphs and the flat 15.5 MB fp32 gradient buffer (+ the guard element) is all-reduced (RCCL) between backward and Adam.
 
-Prints ONE JSON line (rank 0).  `value` = graphs/s over all GPUs.  `roofline` describes the dominant kernel family of that step,
-timed live with HIP events on the launch stream in a separate eager pass; `cpu_baseline` is the CPU oracle (a PyTorch-CPU port
-proven equal to the reference on the golden fixtures) timed on this box's host cores on the same batch.  At N=1 the line also
-carries the other BASELINE configs as sub-objects, each with its own `roofline` and `cpu_baseline`: `c1` (configs[0]),
-`render` (configs[2]), `spade` (configs[3]), plus `vae_large_batch`, `graph_build`, `refine`.
+Prints ONE JSON line (rank 0).  `value` = graphs/s over all GPUs, `ms_per_step` = wall-clock milliseconds of one timed step.
+A plain run does only what that figure needs: set up, warm up, time the --steps steps, write --dump-outputs, print the line.
 
-Every leg first checks the HIP path against the oracle on the leg's own inputs (`parity` keys); a failed check aborts the run
-before anything is printed.  The oracle is only ever the checker and the timed CPU baseline, never part of a GPU number.
+--dump-outputs DIR: after the timed steps, writes what the timed step computes, as float32 .npy files: losses.npy (the four loss
+values it returns), grads.npy (the flat gradient buffer) and bn_buffers.npy (the BatchNorm running statistics it updates).  The
+inputs are seeded, and the dumped step is run on a reproducible state: the model state of the timed steps is put aside, the
+checkpoint taken before the warm-up (parameters, buffers, Adam moments and step) is loaded, the same step function runs once on
+the last timed step's batch, its outputs are written and the trained state is put back.  The state the timed steps leave behind
+cannot be reproduced: the gradient sums use floating-point atomics, and Adam turns the rounding noise of gradients that are
+mathematically zero (the Linear biases in front of a BatchNorm) into +-lr steps, so that two runs are 1 % apart in the loss after
+5 steps.  One step from the checkpoint agrees between runs to rounding (measured: identical losses and BatchNorm statistics,
+gradients within 1e-7 of their largest entry).  The updated parameters are not written: Adam moves the parameters whose gradient
+is that noise by +-lr with its sign.  Nothing of this runs inside the timed region.
+
+--full adds everything else, behind the timed region: the parity check of the HIP step against the oracle before the loop, the
+20 + 100 step protocol run when --steps < 100, `kernels` / `roofline*` (the dominant kernel family timed live with HIP events in a
+separate eager pass), `cpu_baseline` (the CPU oracle, a PyTorch-CPU port proven equal to the reference on the golden fixtures,
+timed on this box's host cores on the same batch), the data-parallel diagnostics at N > 1, and at N=1 the other BASELINE configs
+as sub-objects, each with its own `roofline` and `cpu_baseline`: `c1` (configs[0]), `render` (configs[2]), `spade` (configs[3]),
+plus `vae_large_batch`, `graph_build`, `refine`, `sampling`.  Every leg there first checks the HIP path against the oracle on the
+leg's own inputs (`parity` keys); a failed check aborts the run before anything is printed.  The oracle is only ever the checker
+and the timed CPU baseline, never part of a GPU number.
 """
 import argparse
 import ctypes as C
@@ -55,6 +69,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity checks, the per-kernel / roofline pass, the CPU baselines, the data-parallel diagnostics "
+                         "and the side legs (off: only the headline loop is run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what one timed step computes from the pre-warm-up checkpoint as DIR/<name>.npy (float32)")
     ap.add_argument("--graphs", type=int, default=64, help="scene graphs per GPU per step")
     ap.add_argument("--objs", type=int, default=32)
     ap.add_argument("--triples", type=int, default=64)
@@ -1181,8 +1200,38 @@ def vae_gemm_shapes(O, T, E=64, L=5, box_dim=6, n_angle=24):
     return {"flop_step": flop, "nt_bytes_step": nt, "tn_bytes_step": tn, "linears": len(lin)}
 
 
+def checkpoint(model):
+    """parameters + buffers and the fused Adam's moments and step counter, as device copies"""
+    return ({k: t.detach().clone() for k, t in model.state_dict().items()}, model.optim_state_dict())
+
+
+def dump_outputs(dirname, model, run_step, ck0, write):
+    """One step of the timed path on the checkpoint `ck0` (see the module docstring): `run_step()` is the timed step function on
+    the last timed step's batch.  Writes the four loss values it returns, the flat gradients and the BatchNorm running statistics
+    as float32 .npy files (~16 MB at the default widths) when `write`; every rank runs the step (its collective needs them all).
+    The trained state is restored afterwards, so that what follows (--full) sees the model the timed steps left."""
+    import numpy as np
+    import torch
+    trained = checkpoint(model)
+    model.load_state_dict(ck0[0]); model.load_optim_state_dict(ck0[1])
+    losses = run_step()
+    torch.cuda.synchronize()
+    if write:
+        os.makedirs(dirname, exist_ok=True)
+        bn = [t.detach().reshape(-1).float() for k, t in model.state_dict().items() if k.endswith(("running_mean", "running_var"))]
+        arrays = {"losses": losses.detach().reshape(-1), "grads": model.flat_grads.detach(),
+                  "bn_buffers": torch.cat(bn) if bn else losses.new_zeros(0)}
+        for name, t in arrays.items():
+            np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy().astype(np.float32))
+        log("outputs of one timed step from the pre-warm-up checkpoint written to %s (%s)" % (dirname, ", ".join(sorted(arrays))))
+    model.load_state_dict(trained[0]); model.load_optim_state_dict(trained[1])
+    torch.cuda.synchronize()
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     gc.disable()                                 # collected by hand at the leg boundaries instead, see leg()
     import torch
     import torch.distributed as dist
@@ -1225,6 +1274,8 @@ def main():
     syn = importlib.import_module("3d_sln_amd.host.synthetic")
 
     if args.legs_only:
+        if not args.full:
+            raise SystemExit("bench.py: --legs-only runs side legs, which belong to --full: pass --full --legs-only")
         if world != 1:
             raise SystemExit("bench.py: --legs-only is a single-GPU mode")
         out = {"metric": "scene-graph VAE steps/sec + 256² diff-render fps, 1/2/4/8 MI355X", "value": None, "legs_only": True, "n_gpus": 1}
@@ -1252,6 +1303,7 @@ def main():
         dist.broadcast(model.flat_params, 0)
         torch.cuda.synchronize()               # the timed loop runs on a side stream
         model.params_changed()
+    ck0 = checkpoint(model) if args.dump_outputs else None       # the reproducible state the dumped step starts from
     # a ring of pre-generated batches (same shape, different graphs, different tensors): every step binds a NEW batch, so the
     # per-batch work of a real training loop - staging the inputs, int32 ids, degrees, the CSR of incident triples - is inside
     # the timed region (with ONE reused batch the host mirror skips it); inputs are resident in HBM before the clock starts
@@ -1261,7 +1313,7 @@ def main():
     O = b["objs"].shape[0]
     solo = world == 1          # the side legs, the checks and the CPU baselines are single-GPU measurements (rank 0 at N = 1 only)
     parity = None
-    if rank == 0 and solo and not args.no_check:
+    if rank == 0 and solo and args.full and not args.no_check:
         log('parity check: VAE')
         parity = check_vae(lib, torch, M, model, batch)
     if rank == 0:
@@ -1304,6 +1356,11 @@ def main():
         dt_local = time.perf_counter() - t0      # this rank's own time, before it waits for the others
         barrier()
         dt = time.perf_counter() - t0
+    final_loss = float(losses[3].item())         # the last timed step's total loss (read after the clock stopped)
+    if args.dump_outputs:
+        last = bdicts[counter[0] % len(bdicts)]      # the batch of the last timed step
+        with torch.cuda.stream(stream):
+            dump_outputs(args.dump_outputs, model, lambda: dp_step(last, 0.1, 1e-4, use_graph=use_graph, eps=eps), ck0, rank == 0)
     per_step = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
     pct = lambda q: round(per_step[min(len(per_step) - 1, int(q * len(per_step)))], 4)
     if dp:
@@ -1311,7 +1368,7 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     coll_us = None
-    if dp:                                     # the same collective on its own, after the timed region
+    if dp and args.full:                       # the same collective on its own, after the timed region
         with torch.cuda.stream(stream):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             for i in range(25):
@@ -1322,10 +1379,10 @@ def main():
         torch.cuda.synchronize()
         coll_us = round(e0.elapsed_time(e1) / 20 * 1e3, 1)
     # SURVEY.md 8(d) asks for >= 20 warm-up + >= 100 timed iterations with median / p10 / p90.  `value` is the EXACT --steps K the
-    # caller asked for; when K < 100 (the driver's short run) the same loop runs once more, behind the timed region, at the
-    # protocol's length - reported next to it, never as `value`.  Single GPU only (no extra collectives in a multi-rank run).
+    # caller asked for; under --full, when K < 100 (the driver's short run) the same loop runs once more, behind the timed region,
+    # at the protocol's length - reported next to it, never as `value`.  Single GPU only (no extra collectives in a multi-rank run).
     survey = None
-    if not dp and args.steps < 100:
+    if args.full and not dp and args.steps < 100:
         with torch.cuda.stream(stream):
             for _ in range(20):
                 losses = step()
@@ -1338,11 +1395,10 @@ def main():
         ps = sorted(m2[k].elapsed_time(m2[k + 1]) for k in range(100))
         survey = {"warmup": 20, "steps": 100, "ms_per_step_p10_p50_p90": [round(ps[10], 4), round(ps[50], 4), round(ps[90], 4)],
                   "graphs_per_s_at_p50": round(args.graphs / ps[50] * 1e3, 1)}
-    final_loss = float(losses[3].item())
     ms_per_step = dt / args.steps * 1e3
     value = args.graphs * world * args.steps / dt
     dp_diag = None
-    if dp:
+    if dp and args.full:
         # Diagnostics BEHIND the timed region (they do not enter `value`), so that the first SCALE line that exists answers what
         # DESIGN.md section 5 leaves open: (i) every rank's own wall time per step, (ii) the stand-alone all-reduce of the gradient
         # bucket on communicators created with NCCL_ALGO=Ring and =Tree (RCCL reads the variable when a communicator is
@@ -1422,7 +1478,7 @@ def main():
 
     if rank == 0:
         log('VAE loop done: %.3f ms/step' % ms_per_step)
-    if rank == 0 and args.prof_steps > 0:
+    if rank == 0 and args.full and args.prof_steps > 0:
         # ---- per-kernel-family timing, eager launches + HIP events on the launch stream -----------
         with torch.cuda.stream(stream):
             lib.check(lib.lib().sln_prof_enable(1), "prof")
@@ -1523,7 +1579,7 @@ def main():
             out["roofline_edge"] = {"kernel": "edge scatter/gather", "bound": "hbm", "achieved": round(gbs, 1),
                                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None}
 
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # ---- CPU baseline: the oracle (PyTorch-CPU port of the reference path) on the same batch, all host cores ----
         # (at N > 1 too, with a shorter sample: a SCALE line then carries its own baseline; the other ranks wait at the barrier)
         from oracle import vae_ref
@@ -1554,7 +1610,7 @@ def main():
             cdt16 = cpu_rate(16, max(5, args.cpu_steps // 2))
             out["cpu_baseline"]["value_at_16_threads"] = round(args.graphs / cdt16, 1)
 
-    if rank == 0 and solo:
+    if rank == 0 and solo and args.full:
         # the BASELINE configs first (render, SPADE), on a memory pool that has only seen the headline loop: behind the
         # large-batch points (11 GB workspaces allocated and released) the scene backward measured 0.55 instead of 0.43 ms
         if not args.no_render:
@@ -1575,7 +1631,7 @@ def main():
         if not args.no_sampling:
             leg('sampling'); out["sampling"] = sampling_leg(args, lib, torch)
         log('done')
-    if rank == 0:
+    if rank == 0 and args.full:
         # LAST key of the line: every config of the metric in one compact object (a log tail then carries both halves of
         # "VAE steps/sec + 256^2 diff-render fps", each leg's roofline fraction and its in-run parity figure)
         def dig(d, *path):
@@ -1600,6 +1656,7 @@ def main():
             "sampling_layouts_per_s": dig(out, "sampling", "layouts_per_s"),
             "large_batch_frac_mfma": dig(lb, big, "frac_mfma_whole_step") if big else None,
             "cpu_graphs_per_s": dig(out, "cpu_baseline", "value"), "n_gpus": world}
+    if rank == 0:
         print(json.dumps(out))
     if dp:
         dist.barrier()

@@ -1,61 +1,67 @@
-"""INTEGRATION.md section 2, executed: the reference's OWN factory (build_dataset_model.build_model) constructs the HIP-backed model
-when ``models.graph`` / ``models.Sg2ScVAE_model`` are aliased, with the reference model's parameter names and shapes.
-Runs only where the reference tree is mounted (the build container); read-only, no bytecode is written."""
+"""the reference's OWN factory (build_dataset_model.build_model) constructs the HIP-backed model when
+``models.graph`` / ``models.Sg2ScVAE_model`` / ``data.suncg_dataset`` are aliased, with the reference model's parameter names and
+shapes.  What the factory does was recorded from the reference by oracle/gen_golden_integration.py into
+tests/golden/integration_layout.json: the names it imports from the aliased modules, the keyword arguments it hands the model
+class, and the state_dict layout / parameter order of the reference classes built from them.  The HIP classes are held to that."""
+import importlib
 import json
 import os
-import subprocess
-import sys
+import types
 
 import pytest
-
-from conftest import ROOT
-
-REF = "/root/reference"
-
-SCRIPT = r'''
-import importlib, json, sys, types
-sys.dont_write_bytecode = True
-sys.path.insert(0, %(ref)r)
-sys.path.insert(0, %(root)r)
-import models.graph as ref_graph                       # the reference's own modules, kept under other names for the comparison
-import models.Sg2ScVAE_model as ref_vae
-_hip = lambda m: importlib.import_module("3d_sln_amd.host." + m)
-sys.modules["models.graph"] = _hip("graph")
-sys.modules["models.Sg2ScVAE_model"] = _hip("Sg2ScVAE_model")
-sys.modules["data.suncg_dataset"] = _hip("suncg_dataset")
-sys.modules.pop("build_dataset_model", None)
-import build_dataset_model as B                         # the reference's factory, now importing the aliased modules
-vocab = _hip("synthetic").default_vocab()
-args = types.SimpleNamespace(batch_size=64, train_3d=True, decoder_cat=True, embedding_dim=64, gconv_mode="feedforward", gconv_num_layers=5,
-                             mlp_normalization="batch", vec_noise_dim=0, layout_noise_dim=32, use_AE=False, multigpu=False)
-model, kwargs = B.build_model(args, vocab)
-assert type(model).__module__.startswith("3d_sln_amd.host"), type(model)
-ref = ref_vae.Sg2ScVAEModel(**kwargs)
-a = {k: tuple(v.shape) for k, v in model.state_dict().items()}
-b = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-assert a == b, sorted(set(a.items()) ^ set(b.items()))[:10]
-assert [n for n, _ in model.named_parameters()] == [n for n, _ in ref.named_parameters()]       # optimizer state is positional
-model.load_state_dict(ref.state_dict())                 # a reference checkpoint loads unchanged
 import torch
-torch.optim.Adam(model.parameters(), lr=1e-4)
-# C. the generator, constructed as testing/test_SPADE_shade.py:9 does, small width to keep the test light
-import models.SPADE_related as ref_spade
-hs = _hip("SPADE_related")
-cargs = (41, 3, 16, 8, "spectralspadelayer3x3", 64, "normal")
-g_ref, g_hip = ref_spade.SPADEGenerator4(*cargs), hs.SPADEGenerator4(*cargs)
-ga = {k: tuple(v.shape) for k, v in g_hip.state_dict().items()}
-gb = {k: tuple(v.shape) for k, v in g_ref.state_dict().items()}
-assert ga == gb, sorted(set(ga.items()) ^ set(gb.items()))[:10]
-g_hip.load_state_dict(g_ref.state_dict())
-print(json.dumps({"keys": len(a), "params": sum(p.numel() for p in model.parameters()), "spade_keys": len(ga)}))
-'''
+
+from conftest import GOLDEN
+
+HOST = "3d_sln_amd.host."
+ALIASES = {"models.graph": "graph", "models.Sg2ScVAE_model": "Sg2ScVAE_model", "data.suncg_dataset": "suncg_dataset"}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
-def test_reference_factory_builds_the_aliased_model():
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", SCRIPT % dict(ref=REF, root=ROOT)], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
-    assert out["params"] == 3879790 and out["keys"] > 200
-    assert out["spade_keys"] == 230                                # the 230-key checkpoint layout
+def _layout(module):
+    return {k: [list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in module.state_dict().items()}
+
+
+def _synthetic_checkpoint(rec, seed):
+    """a checkpoint with the reference's layout (keys, shapes, dtypes as recorded) and seeded contents"""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for k, (shape, dtype) in rec["state_dict"].items():
+        dt = getattr(torch, dtype)
+        out[k] = torch.randn(shape, generator=g).to(dt) if dt.is_floating_point else torch.randint(0, 7, shape, generator=g).to(dt)
+    return out
+
+
+@pytest.fixture(scope="module")
+def rec():
+    with open(os.path.join(GOLDEN, "integration_layout.json")) as fh:
+        return json.load(fh)
+
+
+def test_reference_factory_builds_the_aliased_model(rec):
+    mods = {name: importlib.import_module(HOST + m) for name, m in ALIASES.items()}
+    for module, names in rec["factory_imports"].items():          # what `from <alias> import ...` in the factory needs
+        assert module in mods, module
+        for n in names:
+            assert hasattr(mods[module], n), (module, n)
+    # build_model's body on the recorded arguments: Sg2ScVAEModel(**kwargs), vocab passed through
+    vocab = importlib.import_module(HOST + "synthetic").default_vocab()
+    kwargs = dict(rec["model_kwargs"], vocab=vocab)
+    assert {k: v for k, v in rec["factory_args"].items() if k in kwargs} == rec["model_kwargs"]
+    model = mods["models.Sg2ScVAE_model"].Sg2ScVAEModel(**kwargs)
+    assert type(model).__module__.startswith("3d_sln_amd.host"), type(model)
+    a, b = _layout(model), rec["vae"]["state_dict"]
+    assert a == b, sorted(set(map(str, a.items())) ^ set(map(str, b.items())))[:10]
+    assert [n for n, _ in model.named_parameters()] == rec["vae"]["parameters"]      # optimizer state is positional
+    ck = _synthetic_checkpoint(rec["vae"], 1)
+    model.load_state_dict(ck)                                      # a reference checkpoint loads unchanged
+    got = model.state_dict()
+    assert all(torch.equal(got[k].cpu(), v) for k, v in ck.items())
+    torch.optim.Adam(model.parameters(), lr=1e-4)
+    n_params = sum(p.numel() for p in model.parameters())
+    assert n_params == rec["vae"]["n_params"] == 3879790 and len(a) > 200
+    # C. the generator, constructed as testing/test_SPADE_shade.py:9 does, small width to keep the test light
+    g_hip = importlib.import_module(HOST + "SPADE_related").SPADEGenerator4(*rec["spade_args"])
+    ga, gb = _layout(g_hip), rec["spade"]["state_dict"]
+    assert ga == gb, sorted(set(map(str, ga.items())) ^ set(map(str, gb.items())))[:10]
+    g_hip.load_state_dict(_synthetic_checkpoint(rec["spade"], 2))
+    assert len(ga) == 230                                          # the 230-key checkpoint layout

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
 i=0
 for v in "$@"; do
   i=$((i+1)); rm -rf /tmp/ke_$i; mkdir -p /tmp/ke_$i
-  env $v rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ke_$i -o k -- python bench.py --no-cpu --no-check --no-dropin --large-batches= --no-graph-build --no-refine --no-render --no-spade --steps 60 --warmup 10 > /dev/null 2> /tmp/ke_$i/err
+  env $v rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ke_$i -o k -- python bench.py --full --no-cpu --no-check --no-dropin --large-batches= --no-graph-build --no-refine --no-render --no-spade --steps 60 --warmup 10 > /dev/null 2> /tmp/ke_$i/err
   f=$(find /tmp/ke_$i -name 'k_kernel_stats.csv' | head -1)
   echo "== [$v]"; python - "$f" "${KSTATS_FILTER:-.}" <<'PY'
 import csv, sys, re

@@ -5,7 +5,7 @@ cp 3d_sln_amd/libsln_hip.so /tmp/lib_keep.so
 for v in "$@"; do
   cp tools/lab/lib_$v.so 3d_sln_amd/libsln_hip.so
   rm -rf /tmp/ks_$v; mkdir -p /tmp/ks_$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$v -o k -- python bench.py --steps 3 --warmup 2 --no-spade --no-graph-build --no-refine --no-sampling --no-cpu --no-check --large-batches= --prof-steps 0 --render-iters 2 --render-warmup 1 > /dev/null 2> /tmp/ks_$v/err
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$v -o k -- python bench.py --full --steps 3 --warmup 2 --no-spade --no-graph-build --no-refine --no-sampling --no-cpu --no-check --large-batches= --prof-steps 0 --render-iters 2 --render-warmup 1 > /dev/null 2> /tmp/ks_$v/err
   f=$(find /tmp/ks_$v -name 'k_kernel_stats.csv' | head -1)
   echo "== $v"; python - "$f" <<'PY'
 import csv, sys, re

@@ -8,7 +8,7 @@ for v in "$@"; do
   for side in 1 0; do
     rm -rf /tmp/ks_$v; mkdir -p /tmp/ks_$v
     if [ $side = 0 ]; then export SLN_SCENE_NO_SIDE=1; else unset SLN_SCENE_NO_SIDE; fi
-    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$v -o k -- python bench.py --no-cpu --no-check --no-dropin --large-batches= --no-graph-build --no-refine --no-sampling --no-spade --steps 3 --warmup 2 --prof-steps 0 --render-iters 40 --render-warmup 5 > /dev/null 2> /tmp/ks_$v/err
+    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$v -o k -- python bench.py --full --no-cpu --no-check --no-dropin --large-batches= --no-graph-build --no-refine --no-sampling --no-spade --steps 3 --warmup 2 --prof-steps 0 --render-iters 40 --render-warmup 5 > /dev/null 2> /tmp/ks_$v/err
     f=$(find /tmp/ks_$v -name 'k_kernel_stats.csv' | head -1)
     echo "== $v side=$side"; python - "$f" <<'PY'
 import csv, sys, re

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp; cd ${GRAFT_REPO_ROOT:-/root/repo}
 rm -rf /tmp/prof_r; mkdir -p /tmp/prof_r
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r -o e -- python bench.py --steps 5 --warmup 2 --no-spade --no-graph-build --no-refine --no-cpu --no-check --large-batches= --render-iters 100 --render-warmup 20 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_r -o e -- python bench.py --full --steps 5 --warmup 2 --no-spade --no-graph-build --no-refine --no-cpu --no-check --large-batches= --render-iters 100 --render-warmup 20 > /dev/null 2>&1
 python - <<PY
 import csv
 rows=list(csv.DictReader(open("/tmp/prof_r/e_kernel_stats.csv")))

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp; cd ${GRAFT_REPO_ROOT:-/root/repo}
 rm -rf /tmp/prof_s; mkdir -p /tmp/prof_s
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_s -o e -- python bench.py --steps 10 --warmup 3 --no-render --no-graph-build --no-refine --no-cpu --no-check --large-batches= > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_s -o e -- python bench.py --full --steps 10 --warmup 3 --no-render --no-graph-build --no-refine --no-cpu --no-check --large-batches= > /dev/null 2>&1
 python - <<PY
 import csv
 rows=list(csv.DictReader(open("/tmp/prof_s/e_kernel_stats.csv")))

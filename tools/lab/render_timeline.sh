@@ -3,7 +3,7 @@
 # kernel, from a rocprofv3 kernel trace.   tools/lab/render_timeline.sh [ENV=VAL ...]
 cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
 rm -rf /tmp/rt; mkdir -p /tmp/rt
-env "$@" rocprofv3 --kernel-trace --output-format csv -d /tmp/rt -o k -- python bench.py --no-cpu --no-check --no-dropin --large-batches= --no-graph-build --no-refine --no-sampling --no-spade --steps 3 --warmup 2 --prof-steps 0 --render-iters 40 --render-warmup 5 > /dev/null 2> /tmp/rt/err
+env "$@" rocprofv3 --kernel-trace --output-format csv -d /tmp/rt -o k -- python bench.py --full --no-cpu --no-check --no-dropin --large-batches= --no-graph-build --no-refine --no-sampling --no-spade --steps 3 --warmup 2 --prof-steps 0 --render-iters 40 --render-warmup 5 > /dev/null 2> /tmp/rt/err
 f=$(find /tmp/rt -name 'k_kernel_trace.csv' | head -1)
 python - "$f" <<'PY'
 import csv, sys

@@ -17,7 +17,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$ROOT"
 P=/tmp/prof_$TAG          # raw rocprofv3 output stays on the box (tens of MB); only the summaries travel back
 rm -rf "$P"; mkdir -p "$P" profiles gpurun_out
 FAILED=""
-COMMON="--no-cpu --no-check --no-dropin --large-batches= --no-graph-build --no-refine --no-sampling"
+COMMON="--full --no-cpu --no-check --no-dropin --large-batches= --no-graph-build --no-refine --no-sampling"
 declare -A FLAGS
 FLAGS[vae]="$COMMON --no-render --no-spade --steps 100 --warmup 10"
 # (render / spade: --legs-only - no VAE step runs in those traces; rounds 3-5 ran 125 of them in front of the leg, and the `pct` column of
@@ -58,12 +58,12 @@ flatten "$D/trace"
 python tools/summarize_profile.py "$D" "profiles/${TAG}_render_noside"
 # the default command, all legs
 D="$P/all"; mkdir -p "$D"
-timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/trace" -o vae -- python bench.py --no-cpu "$@" > "$D/bench.json" 2> "$D/trace.err"
+timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/trace" -o vae -- python bench.py --full --no-cpu "$@" > "$D/bench.json" 2> "$D/trace.err"
 flatten "$D/trace"
 cp "$D/trace/vae_kernel_stats.csv" "profiles/${TAG}_rocprofv3_kernel_stats_raw.csv"
 # the JSON line of the plain default command (reads the traffic columns written above); written BEFORE the copy below, which used
 # to put the committed file of an earlier run over a fresh one
-python bench.py "$@" > "profiles/${TAG}_bench.json" 2> "$P/bench_default.err"
+python bench.py --full "$@" > "profiles/${TAG}_bench.json" 2> "$P/bench_default.err"
 mkdir -p gpurun_out/profiles_$TAG && cp profiles/${TAG}_* gpurun_out/profiles_$TAG/
 for leg in vae render spade render_noside all; do cp "$P/$leg/bench.json" gpurun_out/profiles_$TAG/bench_$leg.json 2>/dev/null; tail -c 300 "$P/$leg/trace.err" > gpurun_out/profiles_$TAG/err_$leg.txt 2>/dev/null; done
 ls -la profiles/${TAG}_*
