@@ -696,6 +696,22 @@ struct __align__(16) PmbStep { int lo, ofrom, ifrom; float cross; };
 // orders a wavefront's own LDS writes before its own later reads: the workgroup is ONE wavefront and LDS executes a wavefront's
 // instructions in order, so this is a compiler fence, not an s_barrier
 #define PMB_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+// ... which holds only where a 64-thread workgroup is one wavefront: GFX9 (gfx950 included) is wave64-only.  The launchers check the
+// device's warpSize as well (pmb_wave64) and refuse with SLN_E_UNSUPPORTED.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "pixel_map_backward_kernel (PMB_SYNC) needs 64-thread wavefronts: build for a GFX9 target"
+#endif
+static bool pmb_wave64() {
+  static int ws[64] = {0};                        // per device: 0 = not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  if (ws[dev] == 0) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeWarpSize, dev) != hipSuccess) return false;
+    ws[dev] = v;
+  }
+  return ws[dev] == 64;
+}
 // grid of the launch: B >= 8 (image -> XCD mapping in the kernel): one dimension, 8 * ceil(B / 8) * F * 6 workgroups; fewer images:
 // (B * F, 6, scan split)
 inline unsigned pixel_map_grid_x(int B, int F) { return (unsigned)((long)(B >= 8 ? (B + 7) / 8 * 8 * 6 : B) * F); }
@@ -1252,7 +1268,7 @@ int sln_raster_backward_rgb(const float* faces, const int32_t* face_index, const
                             int F, int image_size, int channels, float eps, float* grad_faces, void* stream) {
   if (!faces || !face_index || !rgb || !grad_rgb || !grad_faces || channels <= 0) return SLN_E_BADARG;
   if ((long)image_size * image_size >= (1L << 31)) return SLN_E_UNSUPPORTED;      // 32-bit pixel offsets inside an image
-  if (!pixel_map_grid_ok(B, F)) return SLN_E_UNSUPPORTED;
+  if (!pixel_map_grid_ok(B, F) || !pmb_wave64()) return SLN_E_UNSUPPORTED;
   const long n = (long)B * F;
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
@@ -1287,7 +1303,7 @@ int sln_raster_backward_rgb_multi(const float* faces, const int32_t* face_index,
                                   float* grad_faces, void* stream) {
   if (!faces || !face_index || !rgb_chw || !grad_chw || !mask_ws || !grad_faces || P < 1 || P > 64) return SLN_E_BADARG;
   if ((long)image_size * image_size * 3 * B >= (1L << 31)) return SLN_E_UNSUPPORTED;      // 32-bit offsets inside a pass tensor
-  if (!pixel_map_grid_ok(B, F)) return SLN_E_UNSUPPORTED;
+  if (!pixel_map_grid_ok(B, F) || !pmb_wave64()) return SLN_E_UNSUPPORTED;
   const long n = (long)B * F;
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
@@ -1830,7 +1846,7 @@ int sln_scene_backward(const float* faces, const int32_t* face_class, int B, int
   if (!faces || !face_class || !class_channel || !class_depth_channel || !workspace || !grad_final || !grad_faces) return SLN_E_BADARG;
   if (B <= 0 || F <= 0 || image_size <= 0 || num_classes <= 0 || num_classes > 64) return SLN_E_BADARG;
   if ((long)num_classes * image_size * image_size >= (1L << 30)) return SLN_E_UNSUPPORTED;   // 32-bit byte offsets inside an image's class planes (pixel_map_backward_kernel)
-  if (!pixel_map_grid_ok(B, F)) return SLN_E_UNSUPPORTED;
+  if (!pixel_map_grid_ok(B, F) || !pmb_wave64()) return SLN_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int is = image_size;
   const long plane = (long)is * is, npix = (long)B * plane, n = (long)B * F;

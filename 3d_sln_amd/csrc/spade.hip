@@ -593,23 +593,36 @@ static int launch_conv_split_finish(const ConvArgs& a, const float* part, int S,
 // A slot cannot be allocated while the caller captures the stream: such a launch FAILS with SLN_E_STATE (it used to fall back to
 // the unsplit kernel silently, whose sums round differently - results depended on the process's history): call sln_spade_prepare on
 // the stream (or run one eager forward) before capturing.
+// A split launch recorded into a capture PINS its stream's slot: the graph holds the slot's address, so neither the eviction nor
+// sln_spade_release frees it (if every slot is pinned a new stream's slot is allocated beyond the cap); the caller frees pinned
+// slots with sln_spade_release(.., SLN_SPADE_RELEASE_PINNED) once the graphs that recorded them are destroyed.
 constexpr size_t CONV_PART_BYTES = (size_t)48 << 20;
 constexpr size_t CONV_PART_SLOTS = 16;
-struct ConvPartSlot { int dev; hipStream_t st; float* p; uint64_t used; };
+struct ConvPartSlot { int dev; hipStream_t st; float* p; uint64_t used; bool pinned; };
 static std::mutex g_conv_part_mu;
 static std::vector<ConvPartSlot> g_conv_parts;
 static uint64_t g_conv_part_clock = 0;
-static int conv_part_scratch(hipStream_t st, float** out) {
+static int conv_part_scratch(hipStream_t st, float** out, bool launch) {
   *out = nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return SLN_E_STATE;
-  std::lock_guard<std::mutex> lk(g_conv_part_mu);
-  for (ConvPartSlot& e : g_conv_parts) if (e.dev == dev && e.st == st) { e.used = ++g_conv_part_clock; *out = e.p; return 0; }
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return SLN_E_STATE;
-  if (g_conv_parts.size() >= CONV_PART_SLOTS) {
-    size_t lru = 0;
-    for (size_t i = 1; i < g_conv_parts.size(); ++i) if (g_conv_parts[i].used < g_conv_parts[lru].used) lru = i;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) return SLN_E_STATE;
+  const bool capturing = cs != hipStreamCaptureStatusNone;
+  std::lock_guard<std::mutex> lk(g_conv_part_mu);
+  for (ConvPartSlot& e : g_conv_parts)
+    if (e.dev == dev && e.st == st) {
+      e.used = ++g_conv_part_clock;
+      if (capturing && launch) e.pinned = true;
+      *out = e.p;
+      return 0;
+    }
+  if (capturing) return SLN_E_STATE;
+  size_t lru = g_conv_parts.size();
+  if (g_conv_parts.size() >= CONV_PART_SLOTS)
+    for (size_t i = 0; i < g_conv_parts.size(); ++i)
+      if (!g_conv_parts[i].pinned && (lru == g_conv_parts.size() || g_conv_parts[i].used < g_conv_parts[lru].used)) lru = i;
+  if (lru < g_conv_parts.size()) {
     int cur = dev;
     if (g_conv_parts[lru].dev != cur) (void)hipSetDevice(g_conv_parts[lru].dev);
     (void)hipFree(g_conv_parts[lru].p);
@@ -618,18 +631,19 @@ static int conv_part_scratch(hipStream_t st, float** out) {
   }
   float* p = nullptr;
   if (hipMalloc(reinterpret_cast<void**>(&p), CONV_PART_BYTES) != hipSuccess) { (void)hipGetLastError(); return SLN_E_NOMEM; }
-  g_conv_parts.push_back(ConvPartSlot{dev, st, p, ++g_conv_part_clock});
+  g_conv_parts.push_back(ConvPartSlot{dev, st, p, ++g_conv_part_clock, false});
   *out = p;
   return 0;
 }
-static int conv_part_release(hipStream_t st, bool all) {
+static int conv_part_release(hipStream_t st, int flags) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return SLN_E_STATE;
+  const bool all = (flags & SLN_SPADE_RELEASE_ALL) != 0, pinned = (flags & SLN_SPADE_RELEASE_PINNED) != 0;
   std::lock_guard<std::mutex> lk(g_conv_part_mu);
   int n = 0;
   for (size_t i = 0; i < g_conv_parts.size();) {
     ConvPartSlot& e = g_conv_parts[i];
-    if (all || (e.dev == dev && e.st == st)) {
+    if ((all || (e.dev == dev && e.st == st)) && (pinned || !e.pinned)) {
       if (e.dev != dev) (void)hipSetDevice(e.dev);
       (void)hipFree(e.p);
       if (e.dev != dev) (void)hipSetDevice(dev);
@@ -660,7 +674,7 @@ int launch_conv_split(const ConvArgs& a, hipStream_t st, bool* done) {
   if (S <= 1) return 0;
   float* part = nullptr;
   *done = true;                                            // from here on the launch is the split one - or an error, never another kernel
-  { const int r = conv_part_scratch(st, &part); if (r) return r; }
+  { const int r = conv_part_scratch(st, &part, true); if (r) return r; }
   ConvArgs p = a; p.part = part; p.part_stride = (long)one;
   const int r = launch_conv_dma<BMC, KS, CEPI_BIAS_ACT, TH, 4, BLK>(p, st, S);
   return r ? r : launch_conv_split_finish(a, part, S, (long)one, st);
@@ -1326,10 +1340,10 @@ int sln_spade_conv_sums(const float* x, int B, int Cin, int H, int W, const floa
 }
 int sln_spade_prepare(void* stream) {
   float* p = nullptr;
-  return conv_part_scratch((hipStream_t)stream, &p);
+  return conv_part_scratch((hipStream_t)stream, &p, false);
 }
 int sln_spade_release(void* stream, int all) {
-  return conv_part_release((hipStream_t)stream, all != 0);
+  return conv_part_release((hipStream_t)stream, all);
 }
 
 int sln_spade_conv(const float* x, int B, int Cin, int H, int W, const float* wp, const float* bias, int rows, int rows_pad,

@@ -1689,7 +1689,12 @@ struct SlnVaeGroup {
   // that the copy in the engines' workspaces matches the parameters: set by a forward's transposition, cleared when a backward has
   // run (its fused wgrads - or the caller's optimizer right behind it - step W).  A backward that finds it clear (no forward in
   // front of it, or a second backward after one forward) transposes first.
-  bool wt_valid = false;
+  // Inside a stream capture nothing runs: a captured forward's transposition happens at replay time, so it leaves wt_valid alone and
+  // records only its capture's id (wt_capture); a captured backward skips its own transposition only behind a forward recorded in
+  // the SAME capture.  Once a backward has been captured (bwd_captured) its replays step W at times the host does not see: from
+  // then on every eager backward transposes.
+  bool wt_valid = false, bwd_captured = false;
+  unsigned long long wt_capture = 0;
   int64_t n_transposes = 0;        // W^T builds so far (diagnostics: sln_vae_group_transposes)
   // what create() redirected in every engine (outputs / gradient inputs of its decoder): put back by fail() and the destructor, so
   // that an engine used on its own afterwards does not write into the group's freed arrays
@@ -1911,6 +1916,14 @@ struct SlnVaeGroup {
     side = (want_side && (capture_side || !sln_capturing(st))) ? sln_overlapping_stream(st) : nullptr;
     struct Restore { bool& flag; bool v; ~Restore() { flag = v; } } restore{use_side, want_side};
     if (side == nullptr) use_side = false;          // none to be had (first use inside a capture): this pass on the caller's stream
+    unsigned long long cap_id = 0;
+    {
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamGetCaptureInfo(st, &cs, &cap_id) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }   // (as sln_capturing)
+      if (cs != hipStreamCaptureStatusActive) cap_id = 0;
+    }
+    const bool capturing = cap_id != 0;
+    if (capturing && &prog == &bwd) bwd_captured = true;
     for (const Launch& l : prog) {
       int r = 0;
       hipStream_t main_st = st;
@@ -1939,10 +1952,15 @@ struct SlnVaeGroup {
         case SK_DEC_ASSEMBLE_BWD: r = sln_launch_dec_assemble_bwd_multi(l.tab, l.count, l.variant, l.gx, l.smem_floats, st); break;
         case L_ZERO: r = sln_launch_zero_multi(static_cast<const MZero*>(l.tab), l.count, l.max_n16, st); break;
         case L_TRANSPOSE:
-          if (l.variant == 1 && wt_valid) break;          // backward's own transposition: only when no forward left a valid W^T
+          // backward's own transposition: only when no forward left a valid W^T (see wt_valid)
+          if (l.variant == 1 && (capturing ? wt_capture == cap_id : wt_valid && !bwd_captured)) break;
           r = sln_launch_transpose_table(static_cast<const TransposeEntry*>(l.tab), l.count, l.gx, st);
           if (!r && l.on_side && use_side) { r = (int)hipEventRecord(ev_tr, side); tr_pending = true; }
-          if (!r) { wt_valid = true; ++n_transposes; }
+          if (!r) {
+            ++n_transposes;
+            if (capturing) wt_capture = l.variant == 0 ? cap_id : 0;
+            else wt_valid = true;
+          }
           break;
         case L_BN_GRADS: r = sln_launch_bn_param_grads(static_cast<const BnTableEntry*>(l.tab), l.count, l.gx, eng[0]->cfg.recurrent ? 0 : 1, st); break;
         case L_LOG_SOFTMAX: r = sln_launch_log_softmax(logits, io.angles_pred, rows_total, n_angle, st); break;
@@ -1951,7 +1969,7 @@ struct SlnVaeGroup {
       }
       if (r) return r;
     }
-    if (&prog == &bwd) wt_valid = false;             // the parameters move behind a backward pass (fused wgrads, or the caller's step)
+    if (&prog == &bwd) { wt_valid = false; wt_capture = 0; }   // the parameters move behind a backward pass (fused wgrads, or the caller's step)
     return 0;
   }
   // a recorded step through the single-room launcher (a room whose block has no multi form)

@@ -124,9 +124,13 @@ class SPADEGenerator4(nn.Module):
     _pack_gen = 0
 
     def clear_map_cache(self):
-        """Drop the gamma|beta planes kept for the last semantic map (about 0.2 GB at 256x256) and the captured batch-1 call."""
+        """Drop the gamma|beta planes kept for the last semantic map (about 0.2 GB at 256x256) and the captured batch-1 call (whose
+        split scratch slot the library keeps pinned while a graph may replay into it: freed here, behind the graph)."""
         self._map_memo = None
-        self._b1_graph = None
+        ent, self._b1_graph = getattr(self, "_b1_graph", None), None
+        if ent is not None and ent.get("graph") is not None:
+            ent = None                                         # (destroys the graph)
+            _lib.lib().sln_spade_release(C.c_void_p(self._b1_stream.cuda_stream), 2)     # SLN_SPADE_RELEASE_PINNED
 
     # Batch-1 calls on ONE map (testing/test_SPADE_shade.py:77-79: 50 z per room): from the third consecutive call on the same
     # tensor the launch sequence is fixed - the planes are kept, nothing depends on z but the fc input - so that call is captured

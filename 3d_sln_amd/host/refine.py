@@ -899,16 +899,14 @@ class RefineBatch:
         if not torch.cuda.is_current_stream_capturing():
             L.sln_side_stream_prepare(st)
         tick("tables, buffers")
-        if self.iters > 0:
-            self._first_iterate_sizes()
-            tick("first iterate's sizes")
 
     def _first_iterate_sizes(self):
         """The size penalty holds every object to the size of the FIRST iterate (testing/test_render_refine.py:319-327: ``size_infos`` is
         what the first ``mesh_render_func`` call on ``boxes_pred`` returns; the sizes of the target render are ``unused_sizes``): one
         decoder + head + placement forward of all rooms with iteration 0's z, parameters and noise row, whose ``sizes`` become the
         rooms' targets.  Iteration 0 then measures its own sizes against themselves: a size loss of exactly 0 with zero gradient - the
-        reference's ``size_loss = 0.0`` of a first call."""
+        reference's ``size_loss = 0.0`` of a first call.  Run by ``run()`` in front of iteration 0 (eagerly, outside any capture), so
+        that edits of ``z`` or ``params`` between construction and the first ``run()`` are the first iterate's; frozen from then on."""
         L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
         _lib.check(L.sln_vae_group_decoder(self._group, st), "sln_vae_group_decoder")
         if not self._fused_head:
@@ -966,6 +964,8 @@ class RefineBatch:
         if self.k + n > self.iters:
             raise ValueError("RefineBatch was built for %d iterations (the noise of every iteration is drawn at construction)" % self.iters)
         scratch = self.loss_out.new_empty(self.R)
+        if n > 0 and self.k == 0:
+            self._first_iterate_sizes()
         for _ in range(n):
             k = self.k
             if capture:

@@ -510,9 +510,14 @@ int sln_refine_loss_backward(const SlnRefineLoss* L, const void* workspace, cons
  * sln_spade_prepare allocates `stream`'s slot now (optional: the first eager split launch on a stream does the same).  A slot cannot
  * be allocated while the stream is being captured: a split launch on a stream first seen during its capture fails with SLN_E_STATE
  * (-3) - call sln_spade_prepare (or run one eager forward) on the stream before capturing it.  An allocation failure is SLN_E_NOMEM.
- * sln_spade_release frees the slot of `stream` on the current device (all != 0: every slot of the process); it waits for the device.
- * Returns the number of slots freed.  Call it before destroying a stream that ran SPADE launches (a recycled handle would otherwise
- * inherit the slot, which is harmless, or keep 48 MB alive). */
+ * A split launch recorded while its stream is captured PINS the stream's slot: the graph holds the slot's address, so a pinned slot
+ * is never freed for a new stream (if all 16 are pinned, a new stream's slot is allocated beyond the cap) nor by a plain release.
+ * sln_spade_release frees the slot of `stream` on the current device (`all` & SLN_SPADE_RELEASE_ALL: every slot of the process)
+ * unless it is pinned; with `all` & SLN_SPADE_RELEASE_PINNED pinned slots are freed too - only once every graph that recorded a
+ * launch on them has been destroyed.  It waits for the device.  Returns the number of slots freed.  Call it before destroying a
+ * stream that ran SPADE launches (a recycled handle would otherwise inherit the slot, which is harmless, or keep 48 MB alive). */
+#define SLN_SPADE_RELEASE_ALL 1
+#define SLN_SPADE_RELEASE_PINNED 2
 int sln_spade_prepare(void* stream);
 int sln_spade_release(void* stream, int all);
 /* y = act(conv_ks(x) + bias): ks = 3 (ReflectionPad2d(1)) or 1; act 0 none, 1 ReLU, 2 LeakyReLU(slope) */

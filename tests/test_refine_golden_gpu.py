@@ -198,6 +198,22 @@ def _check_loop(g, r, losses, z_hist, boxes_hist, idx_hist, params_after, model_
         assert_close(got - p0, want - p0, "%d steps of %s" % (it, name), rtol=6e-3, atol=it * ulp)        # measured <= 2.1e-3 of the steps' size
 
 
+# The size term sum_k mean_j (s_kj - t_kj)^2 of iteration >= 1 is 1e-6 .. 1e-3: differences of sizes of order 1 that agree to a few
+# fp32 ulps of the sizes, so its error is bounded through the ulp of the sizes, not relative to the term: with per-component errors
+# e <= m ulp, |d sum d^2| <= 2 |d| |e| + |e|^2 over the 3 n components.  SIZE_ULPS = m: measured, the largest error is that of
+# refine_loop_recurrent's iteration 2 (1.2e-6 on 1.48e-3: m = 15); refine_loop's terms fit m = 8.
+SIZE_ULPS = 32
+
+
+def _check_size_terms(r, got, want, targets):
+    assert got[0] == 0.0 and want[0] == 0.0, ("room %d: iteration 0's size term is exactly 0 (the reference's size_loss = 0.0)" % r, got[0])
+    n3 = targets.size
+    e = SIZE_ULPS * float(np.spacing(np.float32(np.abs(targets).max()))) * np.sqrt(n3)
+    for k in range(1, len(want)):
+        bound = (2.0 * np.sqrt(3.0 * want[k]) * e + e * e) / 3.0
+        assert abs(got[k] - want[k]) <= bound, ("room %d: size term of iteration %d" % (r, k), got[k], want[k], bound)
+
+
 @pytest.mark.parametrize("case,rooms", [("refine_loop", [0, 1]), ("refine_loop", [1]), ("refine_loop_recurrent", [0])])
 def test_refine_batch_matches_the_reference_loop(case, rooms):
     """RefineBatch (R rooms in flight, every kernel of the device loop) against the reference's own k loop, four iterations at 96^2:
@@ -216,11 +232,17 @@ def test_refine_batch_matches_the_reference_loop(case, rooms):
             assert_close(rb.z[a:a + n].cpu(), g["room%d:z0" % r], "z0 (encoder + seed-13 draw)", rtol=1e-5, atol=0)
             assert_close(rb.noise_all[:it, a:a + n].cpu(), g["room%d:noise" % r], "noise rows", rtol=0, atol=0)
             rb.z[a:a + n] = torch.from_numpy(g["room%d:z0" % r]).cuda()
-        zs, bs, ids = [], [], []
+        zs, bs, ids, sls = [], [], [], []
         for k in range(it):
             rb.run(1)
             zs.append(rb.z.detach().cpu().numpy().copy()); bs.append(rb.boxes.detach().cpu().numpy().copy()); ids.append(rb.idx.detach().cpu().numpy().copy())
+            sls.append(rb.size_loss.detach().cpu().numpy().astype(np.float64))
         losses = rb.losses[:it].cpu().numpy()
+        for i, r in enumerate(rooms):
+            want_t = g["room%d:size_target" % r]
+            got_t = rb._size_targets[i].detach().cpu().numpy()
+            assert_close(got_t, want_t, "room %d: first-iterate size targets" % r, rtol=1e-6, atol=0)
+            _check_size_terms(r, [x[i] for x in sls], g["room%d:size" % r], want_t)
         for i, r in enumerate(rooms):
             a, n = rb.row0[i], rb.rows[i]
             names = [k[len("room%d:param:" % r):] for k in g.files if k.startswith("room%d:param:" % r)]

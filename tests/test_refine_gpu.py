@@ -733,3 +733,42 @@ def test_rooms_in_flight_at_an_image_size_the_sparse_loss_path_does_not_take():
             assert_close(res[r][0], b1.cpu().numpy(), "boxes of room %d" % r, rtol=1e-5, atol=1e-6)
     torch.cuda.synchronize()
     assert not took_flags, "expected the all-planes path at this size (if the kernels learnt to take it, this test needs another size)"
+
+
+@pytest.mark.parametrize("capture", [False, True])
+@pytest.mark.parametrize("edit", ["z", "param"])
+def test_first_iterate_size_targets_follow_edits_made_before_the_first_run(edit, capture):
+    """The size targets are the FIRST iterate's sizes (testing/test_render_refine.py:319-327), whatever the caller did to z or the
+    parameters between construction and the first run(): iteration 0's size term is exactly 0 (the reference's size_loss = 0.0)
+    and the targets are that iterate's sizes bit for bit; an edit after iteration 0 leaves them frozen."""
+    R = pkg("host.refine")
+    cfg = vae_ref.VaeConfig(embedding_dim=32, gconv_num_layers=2, mlp_normalization="batch")
+    model, _ = _room_model(cfg)
+    rooms = _random_rooms(2, cfg, seed=5)
+    bank = R.MeshBank(FURN, "cuda", seed=3)
+    rb = R.RefineBatch(model, rooms, bank=bank, image_size=96, iters=3)
+    try:
+        g = torch.Generator(device="cuda").manual_seed(21)
+        if edit == "z":
+            rb.z.add_(0.05 * torch.randn(rb.z.shape, generator=g, device="cuda"))
+        else:                                                  # one row of the box head's first Linear, in every room's copy
+            t = dict(model.named_parameters())["box_net.0.weight"]
+            off = (t.data_ptr() - model.flat_params.data_ptr()) // 4
+            k = t.shape[1]
+            row = rb.params[:, off + 3 * k:off + 4 * k]
+            row.add_(0.05 * torch.randn(row.shape, generator=g, device="cuda"))
+        rb.run(1, capture=capture)
+        torch.cuda.synchronize()
+        vis = [(r, sc.n_vis) for r, sc in enumerate(rb.scenes) if sc.n_vis]
+        assert vis
+        assert rb.size_loss.cpu().tolist() == [0.0] * rb.R, "iteration 0 measures its sizes against themselves"
+        for r, n in vis:
+            assert torch.equal(rb._size_targets[r], rb.sizes[r, :n]), "room %d: the targets are iteration 0's sizes" % r
+        frozen = [t.clone() for t in rb._size_targets]
+        rb.z.add_(0.05 * torch.randn(rb.z.shape, generator=g, device="cuda"))
+        rb.run(1, capture=capture)
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(frozen, rb._size_targets)), "targets frozen after iteration 0"
+        assert float(rb.size_loss.max()) > 0.0
+    finally:
+        rb.close()
