@@ -198,6 +198,11 @@ SIGNATURES = {
                                  C.c_void_p]),
     "sln_graph_emit": (C.c_int, [C.POINTER(SlnRoomTable), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(SlnGraphDraws),
                                  C.POINTER(SlnGraphBatch), C.c_void_p]),
+    "sln_layout_relation_acc": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_i64p, c_i64p, C.c_int, C.c_int, C.POINTER(C.c_int), c_i64p, c_i64p,
+                                          C.c_void_p]),
+    "sln_layout_spread": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sln_layout_l1": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, C.c_void_p]),
+    "sln_layout_baselines": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_i64p, c_f32p, C.c_void_p]),
     "sln_scene_live_channels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sln_scene_backward": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_float, C.c_void_p, c_f32p, c_f32p, C.c_void_p]),

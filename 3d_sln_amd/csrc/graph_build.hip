@@ -228,6 +228,161 @@ __global__ __launch_bounds__(64) void graph_draw_kernel(SlnRoomTable tab, const 
   }
 }
 
+// ---- evaluation of layouts (reference testing/test_acc_mean_std.py:10-125, testing/test_utils.py:93-152) ----------------------------
+struct PredTable { int t[16]; };          // compute_rel's relation order -> the vocabulary's predicate index (-1: name not in the vocabulary)
+
+// restore_box (test_utils.py:119-132) for one row, without touching the caller's tensor: a non-room row is scaled by the first room
+// row at or after it (x by its [3], y by [4], z by [5], float32); room rows and rows behind the last room row keep their values.
+__device__ __forceinline__ Box restored_row(const float* L, const int64_t* __restrict__ objs, int O, int i, int room_cls) {
+  Box b = load_box(L + (size_t)i * 6);
+  if (objs[i] == room_cls) return b;
+  int j = i + 1;
+  while (j < O && objs[j] != room_cls) ++j;
+  if (j < O) {
+    const float* r = L + (size_t)j * 6;
+    const float sx = r[3], sy = r[4], sz = r[5];
+    b.x0 *= sx; b.x1 *= sx; b.y0 *= sy; b.y1 *= sy; b.z0 *= sz; b.z1 *= sz;
+  }
+  return b;
+}
+
+// scene_graph_acc (test_utils.py:135-152) for S layouts at once: grid (triple blocks, S), one triple per thread.  rel = 16: compute_rel
+// returned None (a NaN centre difference makes atan2 NaN and no sector matches; the builder's compute_rel falls through to 'front').
+__global__ __launch_bounds__(256) void layout_rel_kernel(const float* __restrict__ boxes, int O, const int64_t* __restrict__ objs,
+                                                         const int64_t* __restrict__ triples, int T, int room_cls, PredTable tab,
+                                                         unsigned long long* __restrict__ good, unsigned long long* __restrict__ conf) {
+  const int s = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+  bool hit = false;
+  if (t < T) {
+    const int64_t a = triples[3 * (size_t)t], pg = triples[3 * (size_t)t + 1], b = triples[3 * (size_t)t + 2];
+    if (a >= 0 && a < O && b >= 0 && b < O) {
+      const float* L = boxes + (size_t)s * O * 6;
+      int rel;
+      if (objs[b] == room_cls) {
+        rel = P_IN_ROOM;                                         // utils.py:41-42, before any geometry
+      } else {
+        const Box bs = restored_row(L, objs, O, (int)a, room_cls), bo = restored_row(L, objs, O, (int)b, room_cls);
+        rel = compute_rel(bs, bo);
+        const float dx = (bs.x0 + bs.x1) / 2.f - (bo.x0 + bo.x1) / 2.f, dz = (bs.z0 + bs.z1) / 2.f - (bo.z0 + bo.z1) / 2.f;
+        if (rel != P_ON && rel != P_SURROUND && rel != P_INSIDE && (__builtin_isnan(dx) || __builtin_isnan(dz))) rel = 16;
+      }
+      hit = rel < 16 && tab.t[rel] >= 0 && (int64_t)tab.t[rel] == pg;
+      if (conf) {
+        int row = -1;
+        for (int r = 0; r < 16; ++r) row = (row < 0 && tab.t[r] >= 0 && (int64_t)tab.t[r] == pg) ? r : row;
+        if (row >= 0) atomicAdd(conf + ((size_t)s * 16 + row) * 17 + rel, 1ull);
+      }
+    }
+  }
+  const unsigned long long m = __ballot(hit);                    // integer counts: one atomic per wavefront, order-independent
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(good + s, (unsigned long long)__popcll(m));
+}
+
+// fixed-order block sum of NV fp64 values (blockDim.x = NT): the same tree every launch
+template <int NV, int NT>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double (*sh)[NT]) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) sh[k][tid] = v[k];
+  __syncthreads();
+  for (int w = NT / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) sh[k][tid] += sh[k][tid + w];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < NV; ++k) v[k] = sh[k][0];
+}
+
+// get_std (test_acc_mean_std.py:39-69) of one batch: per element (angle bin, position x/y/z, size x/y/z of every row) the population
+// std over the S samples, two-pass in fp64; then the mean over the elements of each kind.  One workgroup: fixed element-to-thread
+// assignment and a fixed reduction tree, so the figures are bit-identical run to run.  out[0..2] += (angle, position, size).
+// 1024 threads: the per-element passes are a chain of dependent loads (latency-bound); 256 threads took 71 us at O = 640, S = 10.
+__global__ __launch_bounds__(1024) void layout_spread_kernel(const float* __restrict__ boxes, const int64_t* __restrict__ bins, int S, int O,
+                                                            double* __restrict__ out) {
+  __shared__ double sh[3][1024];
+  double acc[3] = {0.0, 0.0, 0.0};
+  const size_t so = (size_t)O * 6;
+  for (int e = threadIdx.x; e < 7 * O; e += 1024) {
+    int kind, r, c;
+    if (e < O) { kind = 0; r = e; c = 0; }
+    else { const int e2 = e - O; kind = 1 + e2 / (3 * O); r = (e2 % (3 * O)) / 3; c = e2 % 3; }
+    double sum = 0.0;
+    for (int k = 0; k < S; ++k) {
+      const float* p = boxes + k * so + (size_t)r * 6 + c;
+      const double v = kind == 0 ? (double)bins[(size_t)k * O + r] : kind == 1 ? (double)(p[0] / 2.f + p[3] / 2.f) : (double)fabsf(p[0] - p[3]);
+      sum += v;
+    }
+    const double mean = sum / S;
+    double ss = 0.0;
+    for (int k = 0; k < S; ++k) {
+      const float* p = boxes + k * so + (size_t)r * 6 + c;
+      const double v = kind == 0 ? (double)bins[(size_t)k * O + r] : kind == 1 ? (double)(p[0] / 2.f + p[3] / 2.f) : (double)fabsf(p[0] - p[3]);
+      ss += (v - mean) * (v - mean);
+    }
+    acc[kind] += sqrt(ss / S);
+  }
+  block_sum<3, 1024>(acc, sh);
+  if (threadIdx.x == 0) {
+    out[0] += acc[0] / O;
+    out[1] += acc[1] / (3.0 * O);
+    out[2] += acc[2] / (3.0 * O);
+  }
+}
+
+// F.l1_loss(layout, gt) of each of S layouts (test_acc_mean_std.py:111-113): fp64 sum of the float32 |a - b|, fixed tree; out[s] += mean
+__global__ __launch_bounds__(256) void layout_l1_kernel(const float* __restrict__ boxes, const float* __restrict__ gt, int O, double* __restrict__ out) {
+  __shared__ double sh[1][256];
+  const int s = blockIdx.x;
+  const size_t n = (size_t)O * 6;
+  const float* L = boxes + s * n;
+  double acc[1] = {0.0};
+  for (size_t i = threadIdx.x; i < n; i += 256) acc[0] += (double)fabsf(L[i] - gt[i]);
+  block_sum<1, 256>(acc, sh);
+  if (threadIdx.x == 0) out[s] += acc[0] / (double)n;
+}
+
+// The two baselines of get_acc_l1 (test_acc_mean_std.py:108-110): out[0] = random_scene (test_utils.py:93-116: room rows copied, every
+// other row re-centred at a uniform (x, y, z) with its own extent), out[1] = boxes + float32(hstack([off, off])), off ~ N(0, 0.1).
+// Draws: injected (uni / nrm [O, 3]; only the non-room rows of uni are read) or, with key != NULL, Philox keyed by key[0..1] in device
+// memory, one counter per row.
+__global__ __launch_bounds__(64) void layout_baselines_kernel(const float* __restrict__ gt, const int64_t* __restrict__ objs, int O, int room_cls,
+                                                              const float* __restrict__ uni, const float* __restrict__ nrm,
+                                                              const long long* __restrict__ key, float* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= O) return;
+  float u[3], n[3];
+  if (key) {
+    const unsigned long long k0 = (unsigned long long)key[0], k1 = (unsigned long long)key[1];
+    unsigned int c[4] = {(unsigned int)i, (unsigned int)(k1 >> 32), (unsigned int)k1, 0x3c6ef372u};
+    gb_philox(c, (unsigned int)k0, (unsigned int)(k0 >> 32));
+    unsigned int d[4] = {(unsigned int)i, (unsigned int)(k1 >> 32), (unsigned int)k1, 0xa54ff53au};
+    gb_philox(d, (unsigned int)k0, (unsigned int)(k0 >> 32));
+    for (int q = 0; q < 3; ++q) u[q] = (float)(c[q] >> 8) * 5.9604644775390625e-08f;                      // [0, 1)
+    // Box-Muller on (0, 1] x [0, 1): two normal pairs, three used
+    const float r0 = sqrtf(-2.f * logf((float)((d[0] >> 8) + 1u) * 5.9604644775390625e-08f));
+    const float r1 = sqrtf(-2.f * logf((float)((d[2] >> 8) + 1u) * 5.9604644775390625e-08f));
+    const float a0 = 6.2831853071795865f * ((float)(d[1] >> 8) * 5.9604644775390625e-08f);
+    const float a1 = 6.2831853071795865f * ((float)(d[3] >> 8) * 5.9604644775390625e-08f);
+    n[0] = 0.1f * (r0 * cosf(a0)); n[1] = 0.1f * (r0 * sinf(a0)); n[2] = 0.1f * (r1 * cosf(a1));
+  } else {
+    for (int q = 0; q < 3; ++q) { u[q] = uni[(size_t)i * 3 + q]; n[q] = nrm[(size_t)i * 3 + q]; }
+  }
+  const float* g = gt + (size_t)i * 6;
+  float* rnd = out + (size_t)i * 6;
+  float* per = out + ((size_t)O + i) * 6;
+  const bool room = objs[i] == room_cls;
+  for (int q = 0; q < 3; ++q) {
+    const float h = (g[q + 3] - g[q]) / 2.f;
+    rnd[q] = room ? g[q] : u[q] - h;
+    rnd[q + 3] = room ? g[q + 3] : u[q] + h;
+    per[q] = g[q] + n[q];
+    per[q + 3] = g[q + 3] + n[q];
+  }
+}
+
 }  // namespace
 
 extern "C" int sln_graph_draw(const SlnRoomTable* tab, const int* room_idx, int B, const int* offsets, const int64_t* key,
@@ -259,6 +414,46 @@ extern "C" int sln_graph_emit(const SlnRoomTable* tab, const int* room_idx, int 
   if (B == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(graph_emit_kernel, dim3(B), dim3(64), 0, st, *tab, room_idx, B, offsets, *draws, *out);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sln_layout_relation_acc(const float* boxes, int S, int O, int box_dim, const int64_t* objs, const int64_t* triples, int T, int room_cls,
+                                       const int* pred_table_host, int64_t* good, int64_t* confusion, void* stream) {
+  if (!boxes || !objs || !pred_table_host || !good || S < 0 || O < 0 || T < 0 || box_dim != 6 || (T > 0 && !triples)) return -1;
+  if (S == 0 || T == 0 || O == 0) return 0;
+  if (S > 65535) return -1;
+  PredTable tab;
+  for (int r = 0; r < 16; ++r) tab.t[r] = pred_table_host[r];
+  hipLaunchKernelGGL(layout_rel_kernel, dim3((T + 255) / 256, S), dim3(256), 0, static_cast<hipStream_t>(stream), boxes, O, objs, triples, T,
+                     room_cls, tab, reinterpret_cast<unsigned long long*>(good), reinterpret_cast<unsigned long long*>(confusion));
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sln_layout_spread(const float* boxes, const int64_t* angle_bins, int S, int O, int box_dim, double* out, void* stream) {
+  if (!boxes || !angle_bins || !out || S < 1 || O < 0 || box_dim != 6 || O > (1 << 27)) return -1;
+  if (O == 0) return 0;
+  hipLaunchKernelGGL(layout_spread_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), boxes, angle_bins, S, O, out);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sln_layout_l1(const float* boxes, int S, int O, int box_dim, const float* gt, double* out, void* stream) {
+  if (!boxes || !gt || !out || S < 0 || O < 0 || box_dim != 6) return -1;
+  if (S == 0 || O == 0) return 0;
+  hipLaunchKernelGGL(layout_l1_kernel, dim3(S), dim3(256), 0, static_cast<hipStream_t>(stream), boxes, gt, O, out);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sln_layout_baselines(const float* gt, const int64_t* objs, int O, int box_dim, int room_cls, const float* uniforms,
+                                    const float* normals, const int64_t* key, float* out, void* stream) {
+  if (!gt || !objs || !out || O < 0 || box_dim != 6) return -1;
+  if (!key && (!uniforms || !normals)) return -1;
+  if (O == 0) return 0;
+  hipLaunchKernelGGL(layout_baselines_kernel, dim3((O + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), gt, objs, O, room_cls,
+                     uniforms, normals, reinterpret_cast<const long long*>(key), out);
   SLN_CHECK_LAUNCH();
   return 0;
 }

@@ -1,0 +1,325 @@
+"""Layout evaluation on the device - the ``--measure_acc_l1_std`` mode of the reference's ``test.py``
+(``testing/test_acc_mean_std.py:10-125``: ``get_acc_l1`` and ``get_std``) without a host round trip per batch.
+
+  * ``relation_acc``  - scene_graph_acc (testing/test_utils.py:135-152: restore_box + compute_rel + compare by name) of S layouts
+    in one launch (sln_layout_relation_acc), with an optional predicate confusion table;
+  * ``layout_l1``     - F.l1_loss of S layouts against the ground truth (sln_layout_l1);
+  * ``layout_spread`` - the get_std figures of one batch from its Nsample decodes (sln_layout_spread);
+  * ``baselines``     - the random and perturbed layouts of get_acc_l1 (sln_layout_baselines), draws injected or drawn on the device;
+  * ``measure_acc_l1_std`` - the whole mode: the nine figures the reference prints, read back once at the end.
+
+The ``*_torch`` functions restate each kernel in torch ops for CPU tensors (the host-side tests), as ``sampling.layout_heatmap``
+does for the heat-map kernel.
+"""
+import ctypes as C
+import pickle
+
+import numpy as np
+import torch
+
+from .. import _lib
+from . import sampling as _S
+
+RELATIONSHIPS = _S.RELATIONSHIPS          # compute_rel's relation order (= the graph builder's predicate indices)
+_IN_ROOM, _ON, _INSIDE, _SURROUND = 0, 15, 5, 6
+_LEFT, _RIGHT, _BEHIND, _FRONT, _LEFT_T, _RIGHT_T, _FRONT_T, _BEHIND_T = 1, 2, 3, 4, 7, 8, 9, 10
+NONE = 16                                 # confusion column of compute_rel returning None
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# vocabulary
+# ------------------------------------------------------------------------------------------------------------------------------
+def room_class(vocab):
+    """index of '__room__' in vocab['object_idx_to_name'] (restore_box and compute_rel test the NAME, test_utils.py:122, utils.py:41)"""
+    return list(vocab["object_idx_to_name"]).index("__room__")
+
+
+def relation_table(vocab):
+    """[16] int32: relation r of compute_rel -> the index of the predicate named RELATIONSHIPS[r] in vocab['pred_idx_to_name'], -1 where
+    the vocabulary lacks the name (such triples never match: test_utils.py:148-151 compares names)."""
+    names = list(vocab["pred_idx_to_name"])
+    tab = []
+    for r in RELATIONSHIPS:
+        hits = [i for i, n in enumerate(names) if n == r]
+        if len(hits) > 1:
+            raise ValueError("pred_idx_to_name names %r more than once" % r)
+        tab.append(hits[0] if hits else -1)
+    return torch.tensor(tab, dtype=torch.int32)
+
+
+def _check_layouts(boxes):
+    if boxes.dim() != 3 or boxes.shape[2] != 6:
+        raise ValueError("layouts must be [S, O, 6] (box_dim 6), got %s" % (tuple(boxes.shape),))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# device entry points
+# ------------------------------------------------------------------------------------------------------------------------------
+def relation_acc(boxes, objs, triples, room_cls, table, good=None, confusion=None):
+    """boxes [S, O, 6] (not modified), objs [O], triples [T, 3] on the device -> good [S] int64 (+= into ``good``) and, when
+    ``confusion`` is True or a [S, 16, 17] int64 tensor, the confusion table (+= into it)."""
+    _check_layouts(boxes)
+    S, O, bd = boxes.shape
+    dev = boxes.device
+    b = boxes.contiguous()
+    objs = objs.to(torch.int64).contiguous()
+    triples = triples.to(torch.int64).reshape(-1, 3).contiguous()
+    if good is None:
+        good = torch.zeros(S, dtype=torch.int64, device=dev)
+    if confusion is True:
+        confusion = torch.zeros(S, 16, 17, dtype=torch.int64, device=dev)
+    elif confusion is False:
+        confusion = None
+    tab = (C.c_int * 16)(*[int(x) for x in table])
+    _lib.check(_lib.lib().sln_layout_relation_acc(_lib.ptr(b), S, O, bd, _lib.ptr(objs), _lib.ptr(triples), triples.shape[0], int(room_cls), tab,
+                                                  _lib.ptr(good), _lib.ptr(confusion), _lib.current_stream_ptr()), "sln_layout_relation_acc")
+    return good, confusion
+
+
+def layout_l1(boxes, gt, out=None):
+    """boxes [S, O, 6], gt [O, 6] -> [S] float64 (+= into ``out``): F.l1_loss(boxes[s], gt)"""
+    _check_layouts(boxes)
+    S, O, bd = boxes.shape
+    b, g = boxes.contiguous(), gt.float().contiguous()
+    if g.shape != (O, 6):
+        raise ValueError("gt must be [O, 6]")
+    out = torch.zeros(S, dtype=torch.float64, device=boxes.device) if out is None else out
+    _lib.check(_lib.lib().sln_layout_l1(_lib.ptr(b), S, O, bd, _lib.ptr(g), _lib.ptr(out), _lib.current_stream_ptr()), "sln_layout_l1")
+    return out
+
+
+def layout_spread(boxes, angle_bins, out=None):
+    """boxes [S, O, 6] (un-restored decodes), angle_bins [S, O] -> [3] float64 (+= into ``out``): mean angle / position / size std"""
+    _check_layouts(boxes)
+    S, O, bd = boxes.shape
+    b, a = boxes.contiguous(), angle_bins.to(torch.int64).contiguous()
+    out = torch.zeros(3, dtype=torch.float64, device=boxes.device) if out is None else out
+    _lib.check(_lib.lib().sln_layout_spread(_lib.ptr(b), _lib.ptr(a), S, O, bd, _lib.ptr(out), _lib.current_stream_ptr()), "sln_layout_spread")
+    return out
+
+
+def baselines(gt, objs, room_cls, uniforms=None, normals=None, key=None, out=None):
+    """gt [O, 6] -> [2, O, 6]: random_scene and the perturbed layout.  Draws: ``uniforms`` / ``normals`` [O, 3] (float32, row-indexed)
+    or ``key`` (int64 [2] on the device; default: two words from torch's device generator)."""
+    if gt.dim() != 2 or gt.shape[1] != 6:
+        raise ValueError("gt must be [O, 6] (box_dim 6)")
+    O = gt.shape[0]
+    dev = gt.device
+    g, o = gt.float().contiguous(), objs.to(torch.int64).contiguous()
+    out = torch.empty(2, O, 6, dtype=torch.float32, device=dev) if out is None else out
+    if uniforms is not None:
+        u, n = uniforms.float().contiguous(), normals.float().contiguous()
+        key = None
+    else:
+        u = n = None
+        if key is None:
+            key = torch.randint(-2 ** 62, 2 ** 62, (2,), dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().sln_layout_baselines(_lib.ptr(g), _lib.ptr(o), O, 6, int(room_cls), _lib.ptr(u), _lib.ptr(n), _lib.ptr(key), _lib.ptr(out),
+                                               _lib.current_stream_ptr()), "sln_layout_baselines")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# torch restatements (CPU tensors)
+# ------------------------------------------------------------------------------------------------------------------------------
+def restore_boxes_torch(boxes, objs, room_cls):
+    """restore_box (test_utils.py:119-132) of [S, O, 6] layouts, out of place"""
+    S, O, _ = boxes.shape
+    is_room = (objs == room_cls)
+    nxt = torch.full((O,), -1, dtype=torch.int64)
+    j = -1
+    for i in range(O - 1, -1, -1):
+        nxt[i] = j if not bool(is_room[i]) else -1
+        if bool(is_room[i]):
+            j = i
+    out = boxes.clone()
+    rows = torch.nonzero(nxt >= 0).flatten()
+    if rows.numel():
+        sc = boxes[:, nxt[rows], 3:6]
+        out[:, rows, 0:3] = boxes[:, rows, 0:3] * sc
+        out[:, rows, 3:6] = boxes[:, rows, 3:6] * sc
+    return out
+
+
+def compute_rel_torch(s, o):
+    """compute_rel (utils.py:36-80) without the room branch for box pairs s, o [..., 6] float32 -> relation index, NONE (16) where
+    the reference returns None.  The atan2 sector test is the comparison form of the device kernel (oracle/graph_build_ref.py)."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    sx0, sy0, sz0, sx1, sy1, sz1 = s.unbind(-1)
+    ox0, oy0, oz0, ox1, oy1, oz1 = o.unbind(-1)
+    c1x, c1y, c1z = (sx0 + sx1) / 2, (sy0 + sy1) / 2, (sz0 + sz1) / 2
+    c2y = (oy0 + oy1) / 2
+    on = (c1x >= ox0) & (c1x <= ox1) & (c1z >= oz0) & (c1z <= oz1) & \
+        (((c1y - c2y) - (sy1 - sy0 + oy1 - oy0) / 2).abs() < f(0.05))
+    dx = c1x - (ox0 + ox1) / 2
+    dz = c1z - (oz0 + oz1) / 2
+    area_s = (sx1 - sx0) * (sz1 - sz0)
+    area_o = (ox1 - ox0) * (oz1 - oz0)
+    zero = torch.zeros_like(dx)
+    area_i = torch.fmax(zero, torch.fmin(sx1, ox1) - torch.fmax(sx0, ox0)) * torch.fmax(zero, torch.fmin(sz1, oz1) - torch.fmax(sz0, oz0))
+    iou = area_i / (area_s + area_o - area_i)
+    touching = (f(0.0001) < iou) & (iou < f(0.5))
+    t = lambda a, b: torch.where(touching, torch.full_like(dx, a, dtype=torch.int64), torch.full_like(dx, b, dtype=torch.int64))
+    rel = t(_FRONT_T, _FRONT)
+    rel = torch.where((dx > 0) & (-dx <= dz) & (dz < dx) | (dx == 0) & (dz == 0), t(_LEFT_T, _RIGHT), rel)
+    rel = torch.where((dz < 0) & (dx.abs() < -dz), t(_BEHIND_T, _BEHIND), rel)
+    rel = torch.where((dx < 0) & (dz.abs() <= -dx), t(_RIGHT_T, _LEFT), rel)
+    rel = torch.where(torch.isnan(dx) | torch.isnan(dz), torch.full_like(rel, NONE), rel)
+    rel = torch.where((sx0 > ox0) & (sx1 < ox1) & (sz0 > oz0) & (sz1 < oz1), torch.full_like(rel, _INSIDE), rel)
+    rel = torch.where((sx0 < ox0) & (sx1 > ox1) & (sz0 < oz0) & (sz1 > oz1), torch.full_like(rel, _SURROUND), rel)
+    return torch.where(on, torch.full_like(rel, _ON), rel)
+
+
+def relation_acc_torch(boxes, objs, triples, room_cls, table):
+    """relation_acc as torch ops: -> (good [S] int64, confusion [S, 16, 17] int64)"""
+    S, O, _ = boxes.shape
+    table = torch.as_tensor(table, dtype=torch.int64)
+    triples = triples.to(torch.int64).reshape(-1, 3)
+    ok = (triples[:, 0] >= 0) & (triples[:, 0] < O) & (triples[:, 2] >= 0) & (triples[:, 2] < O)
+    tr = triples[ok]
+    r = restore_boxes_torch(boxes.float(), objs, room_cls)
+    rel = compute_rel_torch(r[:, tr[:, 0]], r[:, tr[:, 2]])                              # [S, T]
+    rel = torch.where((objs[tr[:, 2]] == room_cls)[None], torch.full_like(rel, _IN_ROOM), rel)
+    pg = tr[:, 1][None]
+    hit = (rel < 16) & (table[rel.clamp(max=15)] >= 0) & (table[rel.clamp(max=15)] == pg)
+    good = hit.sum(1)
+    conf = torch.zeros(S, 16, 17, dtype=torch.int64)
+    match = table[:, None] == tr[:, 1][None]                                             # [16, T]
+    has = match.any(0) & (table[match.int().argmax(0)] >= 0)
+    row = match.int().argmax(0)
+    for s in range(S):
+        idx = (row[has] * 17 + rel[s][has])
+        conf[s].view(-1).scatter_add_(0, idx, torch.ones_like(idx))
+    return good, conf
+
+
+def layout_l1_torch(boxes, gt):
+    """[S] float64: mean over O x 6 of the float32 |a - b| (accumulated in fp64)"""
+    return (boxes.float() - gt.float()[None]).abs().double().flatten(1).sum(1) / (gt.shape[0] * 6)
+
+
+def layout_spread_torch(boxes, angle_bins):
+    """[3] float64: np.mean(np.std(., axis=0)) of the angle bins, centres and sizes (test_acc_mean_std.py:54-66)"""
+    b = boxes.float()
+    pos = b[..., :3] / 2.0 + b[..., 3:] / 2.0
+    size = (b[..., :3] - b[..., 3:]).abs()
+    std = lambda v: v.double().std(0, unbiased=False).mean()
+    return torch.stack([std(angle_bins.double()), std(pos), std(size)])
+
+
+def baselines_torch(gt, objs, room_cls, uniforms, normals):
+    """[2, O, 6]: random_scene (test_utils.py:93-116) and boxes + float32(hstack([off, off])) (test_acc_mean_std.py:109-110)"""
+    g = gt.float()
+    u, n = uniforms.float(), normals.float()
+    h = (g[:, 3:] - g[:, :3]) / 2
+    rnd = torch.cat([u - h, u + h], 1)
+    room = (objs == room_cls)[:, None]
+    rnd = torch.where(room, g, rnd)
+    per = g + torch.cat([n, n], 1)
+    return torch.stack([rnd, per])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the mode
+# ------------------------------------------------------------------------------------------------------------------------------
+def load_mean_cov(path):
+    """the reference's stats file (testing/test_VAE.py:54-61: pickle of [mean_est, cov_est]) -> (mean [E], cov [E, E]) float64"""
+    with open(path, "rb") as f:
+        mean, cov = pickle.load(f)
+    return torch.as_tensor(np.asarray(mean), dtype=torch.float64), torch.as_tensor(np.asarray(cov), dtype=torch.float64)
+
+
+def save_mean_cov(path, mean, cov):
+    """write (mean, cov) as the reference does: a pickled [mean_est, cov_est] of numpy arrays"""
+    m = mean.detach().cpu().double().numpy() if torch.is_tensor(mean) else np.asarray(mean, np.float64)
+    c = cov.detach().cpu().double().numpy() if torch.is_tensor(cov) else np.asarray(cov, np.float64)
+    with open(path, "wb") as f:
+        pickle.dump([m, c], f)
+
+
+def _unpack(batch):
+    """a collated batch: suncg_collate_fn's 8-tuple (ids, objs, boxes, triples, angles, attributes, obj_to_img, triple_to_img) or the
+    5-tuple of sampling.posterior_stats (objs, triples, boxes, angles, attributes) -> (objs, triples, boxes, attributes)"""
+    if len(batch) == 8:
+        _, objs, boxes, triples, _, attributes, _, _ = batch
+    elif len(batch) == 5:
+        objs, triples, boxes, _, attributes = batch
+    else:
+        raise ValueError("a batch is suncg_collate_fn's 8-tuple or (objs, triples, boxes, angles, attributes)")
+    return objs, triples, boxes, attributes
+
+
+def _draw_z(model, objs, triples, attributes, n, mean, cov, gen):
+    """z [n * O, E] ~ N(mean, cov) from the device generator ``gen`` (independent of the engine's Philox stream position)"""
+    E, O = model.embedding_dim, objs.shape[0]
+    eps = torch.randn(n * O, E, generator=gen, device=objs.device, dtype=torch.float32)
+    L, mu = _S._factor(mean, cov, E, objs.device)
+    z = torch.empty_like(eps)
+    _lib.check(_lib.lib().sln_linear_forward(_lib.ptr(eps), eps.shape[0], E, _lib.ptr(L), _lib.ptr(mu), _lib.ptr(z), E, None, -1,
+                                             _lib.current_stream_ptr()), "sln_linear_forward")
+    return z
+
+
+def measure_acc_l1_std(model, batches, mean, cov, vocab, n_std_samples=10, seed=None, draws=None):
+    """testing/test_acc_mean_std.py: get_acc_l1 + get_std over ``batches`` (collated, on the model's device) -> the nine figures the
+    reference prints: {'l1_pred', 'l1_rand', 'l1_pert', 'acc_pred', 'acc_rand', 'acc_pert', 'angle_std', 'position_std', 'size_std'}.
+
+    Per batch: one decode (sampling.sample_layouts), one baselines launch, one relation launch over the three layouts, one L1 launch,
+    ``n_std_samples`` decodes in one engine call and one spread launch; the figures accumulate on the device and are read back once.
+    ``seed``: z and the baseline draws come from a device generator seeded with it (default: the engine's stream / torch's).
+    ``draws``: per batch a dict {'z': [O, E], 'uniforms': [O, 3], 'normals': [O, 3], 'z_std': [n_std_samples, O, E]} replaces
+    every draw (the reference's np.random draws can be replayed)."""
+    dev = next(model.parameters()).device
+    room = room_class(vocab)
+    table = relation_table(vocab)
+    gen = None
+    if seed is not None:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+    good = torch.zeros(3, dtype=torch.int64, device=dev)
+    l1 = torch.zeros(3, dtype=torch.float64, device=dev)
+    spread = torch.zeros(3, dtype=torch.float64, device=dev)
+    n_batches, n_triples = 0, 0
+    draws = list(draws) if draws is not None else None
+    for bi, batch in enumerate(batches):
+        objs, triples, boxes, attributes = _unpack(batch)
+        O = objs.shape[0]
+        if boxes.dim() != 2 or boxes.shape[1] != 6:
+            raise ValueError("measure_acc_l1_std needs 3D boxes [O, 6]")
+        d = draws[bi] if draws is not None else None
+        # --- get_acc_l1: predicted, random, perturbed (test_acc_mean_std.py:104-118) ---
+        if d is not None:
+            z = d["z"].to(dev, torch.float32).reshape(O, -1)
+        elif gen is not None:
+            z = _draw_z(model, objs, triples, attributes, 1, mean, cov, gen)
+        else:
+            z = None
+        bp, _, _ = _S.sample_layouts(model, objs, triples, attributes, n_samples=1, mean=mean, cov=cov, z=z)
+        lay = torch.empty(3, O, 6, dtype=torch.float32, device=dev)
+        lay[0].copy_(bp[0])
+        if d is not None:
+            baselines(boxes, objs, room, uniforms=d["uniforms"].to(dev), normals=d["normals"].to(dev), out=lay[1:])
+        else:
+            key = torch.randint(-2 ** 62, 2 ** 62, (2,), dtype=torch.int64, device=dev, generator=gen)
+            baselines(boxes, objs, room, key=key, out=lay[1:])
+        relation_acc(lay, objs, triples, room, table, good=good)
+        layout_l1(lay, boxes, out=l1)
+        # --- get_std (:39-69) ---
+        if d is not None:
+            z = d["z_std"].to(dev, torch.float32).reshape(n_std_samples * O, -1)
+        elif gen is not None:
+            z = _draw_z(model, objs, triples, attributes, n_std_samples, mean, cov, gen)
+        else:
+            z = None
+        bs, ab, _ = _S.sample_layouts(model, objs, triples, attributes, n_samples=n_std_samples, mean=mean, cov=cov, z=z)
+        layout_spread(bs, ab, out=spread)
+        n_batches += 1
+        n_triples += int(triples.shape[0])            # a host-side shape, no device read
+    if n_batches == 0:
+        raise ValueError("no batches")
+    g, l, s = (t.cpu() for t in (good, l1, spread))   # the one read-back
+    acc = [float(x) / n_triples if n_triples else float("nan") for x in g.tolist()]
+    l = (l / n_batches).tolist()
+    s = (s / n_batches).tolist()
+    return {"l1_pred": l[0], "l1_rand": l[1], "l1_pert": l[2], "acc_pred": acc[0], "acc_rand": acc[1], "acc_pert": acc[2],
+            "angle_std": s[0], "position_std": s[1], "size_std": s[2]}

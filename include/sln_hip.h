@@ -624,6 +624,35 @@ int sln_graph_emit(const SlnRoomTable* tab /* host struct */, const int* room_id
 int sln_graph_draw(const SlnRoomTable* tab /* host struct */, const int* room_idx, int B, const int* offsets, const int64_t* key,
                    int* other, unsigned char* swap, unsigned char* attr_mode, void* stream);
 
+/* Layout evaluation: the --measure_acc_l1_std mode of test.py (testing/test_acc_mean_std.py:10-125: get_std, get_acc_l1) on the
+ * device.  Layouts are [S, O, 6] (box_dim must be 6: anything else is SLN_E_BADARG, nothing launched); objs [O] and triples [T, 3]
+ * are one collated batch (suncg_collate_fn); the layouts are read, never written.
+ *
+ * scene_graph_acc (testing/test_utils.py:135-152) for S layouts in one launch: restore_box (:119-132: every non-room row scaled by
+ * the first '__room__' row at or after it; room rows and rows behind the last room row unscaled), then compute_rel (utils.py:36-80,
+ * '__in_room__' when the object is a room row; None - a NaN centre difference - matches nothing) compared with the triple's
+ * predicate BY NAME: pred_table_host[16] maps compute_rel's relation order (the builder's predicate order) to the vocabulary's
+ * predicate index, -1 where the vocabulary lacks the name.  good[S] (int64) += matches.  confusion [S, 16, 17] (int64, or NULL)
+ * += one count per triple at (relation of the ground-truth name, relation computed | 16 = None); triples whose ground-truth name
+ * is not one of the 16 relations are not entered.  room_cls is the index of '__room__' in object_idx_to_name. */
+int sln_layout_relation_acc(const float* boxes, int S, int O, int box_dim, const int64_t* objs, const int64_t* triples, int T, int room_cls,
+                            const int* pred_table_host, int64_t* good, int64_t* confusion, void* stream);
+/* get_std (testing/test_acc_mean_std.py:39-69) of one batch: S decodes [S, O, 6] (un-restored) + their angle bins [S, O] (int64);
+ * np.std over the samples (ddof 0, two-pass in fp64) of the angle bins, the centres b[:3]/2 + b[3:]/2 and the sizes |b[:3] - b[3:]|
+ * (float32 as numpy forms them), then the mean over the elements of each kind: out[0..2] += (angle, position, size).  Fixed-order
+ * reduction: bit-identical run to run. */
+int sln_layout_spread(const float* boxes, const int64_t* angle_bins, int S, int O, int box_dim, double* out, void* stream);
+/* F.l1_loss(layout, gt) of each of S layouts against gt [O, 6] (testing/test_acc_mean_std.py:111-113): fp64 sum of the float32
+ * |a - b|, fixed order; out[S] += sum / (6 O). */
+int sln_layout_l1(const float* boxes, int S, int O, int box_dim, const float* gt, double* out, void* stream);
+/* The baselines of get_acc_l1 (testing/test_acc_mean_std.py:108-110) from the ground truth gt [O, 6]: out[0] = random_scene
+ * (testing/test_utils.py:93-116: rows of class room_cls copied, every other row re-centred at a uniform (x, y, z) keeping its
+ * extent), out[1] = gt + float32([off, off]) with off ~ N(0, 0.1).  out is [2, O, 6].  Draws: injected (uniforms, normals [O, 3]
+ * float32, row-indexed; the uniforms of room rows are not read) or, with key != NULL, drawn on the device: Philox keyed by
+ * key[0..1] (two 64-bit words in DEVICE memory, as sln_graph_draw), one counter per row. */
+int sln_layout_baselines(const float* gt, const int64_t* objs, int O, int box_dim, int room_cls, const float* uniforms,
+                         const float* normals, const int64_t* key, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
