@@ -189,6 +189,14 @@ SIGNATURES = {
     "sln_spade_modulate_up": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, C.c_int, c_f32p, C.c_int,
                                         c_f32p, C.c_int, C.c_float, c_f32p, C.c_void_p]),
     "sln_layernorm_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, c_f32p, C.c_void_p]),
+    "sln_spade_conv_f16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_float, c_f32p, C.c_void_p]),
+    "sln_spade_conv_sums_f16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_float, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sln_spade_modulate_f16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_int, C.c_int,
+                                         c_f32p, c_f32p, C.c_int, C.c_float, c_f32p, C.c_void_p]),
+    "sln_spade_modulate_up_f16": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_int, C.c_int,
+                                            c_f32p, C.c_int, c_f32p, C.c_int, C.c_float, c_f32p, C.c_void_p]),
     "sln_block_tail": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_f32p, c_f32p, c_f32p,
                                  C.c_int, c_f32p, C.c_void_p, C.c_int, C.c_float, c_f32p, C.c_void_p]),
     "sln_upsample2x": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p]),

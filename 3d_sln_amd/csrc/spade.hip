@@ -752,6 +752,234 @@ int launch_conv(const ConvArgs& a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// fp16-MFMA 3x3 convolution (opt-in precision modes "f16" and "f16x3")
+// ------------------------------------------------------------------------------------------------
+// The same implicit GEMM on v_mfma_f32_32x32x16_f16, K ordered (tap, 16 input channels): one MFMA takes 16 channels of one tap.
+// TERMS = 1: out = sum w_hi x_hi.  TERMS = 3: the fp16 hi / lo split of both operands, out = sum (w_hi x_hi + w_hi x_lo + w_lo x_hi)
+// (the dropped w_lo x_lo is 2^-22 of a product): fp16 products are exact in fp32, so the three-product form is fp32-grade.
+//   * A (weights): packed by the host as fp16 [Cin16 / 16][9][rows_pad][16] (hi, and lo in the 3-term mode), zero padded to
+//     Cin16 = 16 ceil(Cin / 16) channels; lane (li, lk) reads A[row li][k = 8 lk .. 8 lk + 7] as one 16-byte LDS read.
+//   * B (pixels): activations stay fp32 NCHW in HBM; per chunk of 16 channels the reflect-padded halo is loaded through registers
+//     (global_load_lds cannot convert), split into hi = (half)x, lo = (half)(x - hi) (clamped to the finite fp16 range) and
+//     stored channel-last per pixel: [HS][16] halves, so a lane's 8 K values are one 16-byte read too.
+//   * one LDS buffer per chunk (weights + halo, hi and lo); the next chunk is prefetched into registers while the MFMAs of this
+//     one run (the conv_mfma_kernel scheme).  The 32 x 32 D layout does not depend on the input type: conv_epilogue is shared.
+//   * BLK = 1: blocked accumulation (conv_flush after every chunk of 16 channels = 144 products, the fp32 kernels' block);
+//     a.part != nullptr: input-channel split over gridDim.z (the partial sums go through conv_split_finish_kernel).
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // staging registers (an array of HIP's struct uint4 stayed in scratch)
+constexpr int FK = 16;                                   // input channels per chunk (one MFMA K)
+
+template <int BMC, int EPI, int THT, int TERMS, int BLK = 0>
+__global__ __launch_bounds__(256) void conv_f16_kernel(const ConvArgs a, const uint16_t* __restrict__ whi, const uint16_t* __restrict__ wlo) {
+  static_assert(TERMS == 1 || TERMS == 3, "1 or 3 products");
+  constexpr int NT = TERMS == 3 ? 2 : 1;                 // operand parts held: hi (and lo)
+  constexpr int WM = BMC / 64, WN = 4 / WM, TN = THT * TW / WN / 32, TM = 2;
+  constexpr int HS = (THT + 2) * (TW + 2);               // halo pixels
+  constexpr int WQ = 9 * BMC * FK / 8;                   // 16-byte weight words per part and chunk
+  constexpr int NWQ = (WQ + 255) / 256;
+  constexpr int NHI = (2 * HS + 255) / 256;              // halo items (pixel, 8-channel half) per thread and chunk
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  _Float16* wl = reinterpret_cast<_Float16*>(lds);                      // [NT][9][BMC][16]
+  _Float16* xl = wl + NT * 9 * BMC * FK;                                // [NT][HS][16]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + THT - 1) / THT;
+  int bid = blockIdx.x;
+  const int tx = bid % tiles_x; bid /= tiles_x;
+  const int ty = bid % tiles_y; bid /= tiles_y;
+  const int b = bid;
+  const int r0 = blockIdx.y * BMC;
+  const int x0 = tx * TW, y0 = ty * THT;
+  const size_t plane = (size_t)a.H * a.W;
+  const float* xb = a.x + (size_t)b * a.Cin * plane;
+  const int nch = (a.Cin + FK - 1) / FK;
+
+  // halo item e = g * HS + p: pixel p (consecutive lanes, coalesced loads), channels 8 g .. 8 g + 7 of the chunk
+  int h_off[NHI];
+#pragma unroll
+  for (int j = 0; j < NHI; ++j) {
+    const int e = min(tid + 256 * j, 2 * HS - 1), p = e % HS;
+    int gy = reflect_idx(y0 + p / (TW + 2) - 1, a.H), gx = reflect_idx(x0 + p % (TW + 2) - 1, a.W);
+    gy = min(max(gy, 0), a.H - 1); gx = min(max(gx, 0), a.W - 1);
+    h_off[j] = gy * a.W + gx;
+  }
+  float hreg[NHI][8];
+  u32x4 wreg[NT][NWQ];
+  auto gload = [&](int ch) {
+#pragma unroll
+    for (int j = 0; j < NHI; ++j) {
+      const int g = min(tid + 256 * j, 2 * HS - 1) / HS;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int ci = min(ch * FK + 8 * g + k, a.Cin - 1);           // clamped: surplus channels are zeroed at the LDS store
+        hreg[j][k] = xb[(size_t)ci * plane + h_off[j]];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NWQ; ++j) {
+      const int q = min(tid + 256 * j, WQ - 1);
+      const int tap = q / (BMC * FK / 8), rem = q % (BMC * FK / 8);
+      const size_t off = (((size_t)ch * 9 + tap) * a.rows_pad + r0) * FK + (size_t)rem * 8;
+      wreg[0][j] = *reinterpret_cast<const u32x4*>(whi + off);
+      if (TERMS == 3) wreg[NT - 1][j] = *reinterpret_cast<const u32x4*>(wlo + off);
+    }
+  };
+  auto lstore = [&](int ch) {
+#pragma unroll
+    for (int j = 0; j < NHI; ++j) {
+      const int e = tid + 256 * j;
+      if (e < 2 * HS) {
+        const int g = e / HS, p = e % HS;
+        f16x8 hi, lo;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const float x = hreg[j][k];                                   // NaN stays NaN (fmaxf would drop it)
+          const float v = ch * FK + 8 * g + k < a.Cin ? (x != x ? x : fminf(fmaxf(x, -65504.f), 65504.f)) : 0.f;
+          const _Float16 h = (_Float16)v;
+          hi[k] = h;
+          lo[k] = (_Float16)(v - (float)h);
+        }
+        *reinterpret_cast<f16x8*>(xl + p * FK + 8 * g) = hi;
+        if (TERMS == 3) *reinterpret_cast<f16x8*>(xl + (NT - 1) * HS * FK + p * FK + 8 * g) = lo;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NWQ; ++j) {
+      const int q = tid + 256 * j;
+      if (q < WQ) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) *reinterpret_cast<u32x4*>(wl + t * 9 * BMC * FK + q * 8) = wreg[t][j];
+      }
+    }
+  };
+
+  const int wr = (wave / WN) * 64, wp0 = (wave % WN) * (THT * TW / WN);
+  const int li = lane & 31, lk = lane >> 5;
+  f32x16 acc[TM][TN], tot[BLK ? TM : 1][BLK ? TN : 1];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; if (BLK) tot[i][j][r] = 0.f; }
+  int pbase[TN];
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int m = wp0 + 32 * j + li;
+    pbase[j] = (m / TW) * (TW + 2) + (m % TW);
+  }
+
+  int c0 = 0, cend = nch;
+  if (a.part != nullptr) {                               // input-channel split: a whole number of chunks per workgroup
+    const int per = (nch + (int)gridDim.z - 1) / (int)gridDim.z;
+    c0 = min((int)blockIdx.z * per, nch); cend = min(nch, c0 + per);
+  }
+  if (c0 < cend) { gload(c0); lstore(c0); }
+  __syncthreads();
+  for (int ch = c0; ch < cend; ++ch) {
+    if (ch + 1 < cend) gload(ch + 1);
+    auto ld = [&](int tap, f16x8 (&av)[NT][TM], f16x8 (&bv)[NT][TN]) {
+      const int toff = (tap / 3) * (TW + 2) + (tap % 3);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) av[t][i] = *reinterpret_cast<const f16x8*>(wl + ((t * 9 + tap) * BMC + wr + 32 * i + li) * FK + 8 * lk);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) bv[t][j] = *reinterpret_cast<const f16x8*>(xl + (t * HS + pbase[j] + toff) * FK + 8 * lk);
+      }
+    };
+    auto mma = [&](const f16x8 (&av)[NT][TM], const f16x8 (&bv)[NT][TN]) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          if (TERMS == 3) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0][i], bv[NT - 1][j], acc[i][j], 0, 0, 0);     // w_hi x_lo
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[NT - 1][i], bv[0][j], acc[i][j], 0, 0, 0);     // w_lo x_hi
+          }
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0][i], bv[0][j], acc[i][j], 0, 0, 0);             // w_hi x_hi
+        }
+    };
+    // the operands of tap t + 1 are read from LDS before the MFMAs of tap t issue (fenced, as in the fp32 kernels)
+    f16x8 av0[NT][TM], bv0[NT][TN], av1[NT][TM], bv1[NT][TN];
+    ld(0, av0, bv0);
+#pragma unroll
+    for (int tap = 0; tap < 9; tap += 2) {
+      if (tap + 1 < 9) ld(tap + 1, av1, bv1);
+      __builtin_amdgcn_sched_barrier(0);
+      mma(av0, bv0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (tap + 2 < 9) ld(tap + 2, av0, bv0);
+      __builtin_amdgcn_sched_barrier(0);
+      if (tap + 1 < 9) mma(av1, bv1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (BLK > 0) conv_flush(acc, tot, ch + 1 == cend);
+    __syncthreads();                                     // everyone done reading the LDS slab
+    if (ch + 1 < cend) { lstore(ch + 1); __syncthreads(); }
+  }
+  conv_epilogue<BMC, EPI, THT>(a, acc, lds, b, r0, x0, y0);
+}
+
+template <int BMC, int EPI, int THT, int TERMS, int BLK>
+int launch_conv_f16_k(const ConvArgs& a, const uint16_t* whi, const uint16_t* wlo, hipStream_t st, int ksplit = 1) {
+  constexpr int NT = TERMS == 3 ? 2 : 1;
+  size_t smem = sizeof(_Float16) * (size_t)NT * (9 * BMC * FK + (THT + 2) * (TW + 2) * FK);
+  if (a.gap_acc && smem < sizeof(float) * 4 * 64 * 33) smem = sizeof(float) * 4 * 64 * 33;      // the epilogue's row-sum transpose
+  static bool raised = false;
+  if (!raised) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<BMC, EPI, THT, TERMS, BLK>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    raised = true;
+  }
+  const int tiles = sln_cdiv(a.W, TW) * sln_cdiv(a.H, THT) * a.B;
+  hipLaunchKernelGGL((conv_f16_kernel<BMC, EPI, THT, TERMS, BLK>), dim3(tiles, a.rows_pad / BMC, ksplit), dim3(256), smem, st, a, whi, wlo);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+// Routing of the half modes (every 3x3 launch of the generator): blocked accumulation (Cin >= 512) and the input-channel split of
+// launches of fewer than 192 workgroups as in the fp32 path; 16 x 16-pixel workgroups where the image has the rows and the launch
+// gives every CU two of them, else 8 x 16.  -Rpass-analysis=kernel-resource-usage: no spills and no scratch in any variant; 1-3
+// waves per SIMD (three products, 128 rows: 1).
+template <int BMC, int EPI, int TERMS>
+int launch_conv_f16(const ConvArgs& a, const uint16_t* whi, const uint16_t* wlo, hipStream_t st) {
+  if constexpr (EPI == CEPI_BIAS_ACT) {
+    static const int split_max = getenv("SLN_CONV_KSPLIT") ? atoi(getenv("SLN_CONV_KSPLIT")) : 32;      // 1: never
+    const long blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, TH) * a.B * (a.rows_pad / BMC);
+    const int nch = (a.Cin + FK - 1) / FK;
+    const size_t one = (size_t)a.B * a.rows * a.H * a.W;
+    int S = split_max > 1 && blocks < 192 ? (int)std::min<long>(std::min(split_max, nch / 2), (512 + blocks - 1) / blocks) : 1;
+    S = (int)std::min<size_t>((size_t)S, CONV_PART_BYTES / (one * sizeof(float)));
+    if (S > 1) {
+      const int per = (nch + S - 1) / S;
+      S = (nch + per - 1) / per;                          // no workgroup without chunks
+      float* part = nullptr;
+      { const int r = conv_part_scratch(st, &part, true); if (r) return r; }
+      ConvArgs p = a; p.part = part; p.part_stride = (long)one;
+      const int r = a.blocked ? launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 1>(p, whi, wlo, st, S)
+                              : launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 0>(p, whi, wlo, st, S);
+      return r ? r : launch_conv_split_finish(a, part, S, (long)one, st);
+    }
+    if (a.blocked) return launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 1>(a, whi, wlo, st);
+  }
+  // (16 x 16 pixels x 128 rows in the three-product form: 512 registers and still 4 spilled - 8 x 16 there)
+  constexpr bool can_tall = !(TERMS == 3 && BMC == 128);
+  const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / BMC);
+  if (can_tall && a.H >= 16 && tall_blocks >= 512) return launch_conv_f16_k<BMC, EPI, can_tall ? 16 : TH, TERMS, 0>(a, whi, wlo, st);
+  return launch_conv_f16_k<BMC, EPI, TH, TERMS, 0>(a, whi, wlo, st);
+}
+
+template <int EPI>
+int launch_conv_f16_any(const ConvArgs& a, const uint16_t* whi, const uint16_t* wlo, hipStream_t st) {
+  const bool big = a.rows_pad % 128 == 0;
+  if (wlo) return big ? launch_conv_f16<128, EPI, 3>(a, whi, wlo, st) : launch_conv_f16<64, EPI, 3>(a, whi, wlo, st);
+  return big ? launch_conv_f16<128, EPI, 1>(a, whi, wlo, st) : launch_conv_f16<64, EPI, 1>(a, whi, wlo, st);
+}
+
+// ------------------------------------------------------------------------------------------------
 // small kernels
 // ------------------------------------------------------------------------------------------------
 // det (deterministic mode): block k of a sample STORES its sums to slot pair k + 1 of the sample's line (no atomics, at most
@@ -1368,6 +1596,46 @@ int sln_spade_modulate_up(const float* actv, int B, int Cin, int H, int W, const
 int sln_spade_modulate(const float* actv, int B, int Cin, int H, int W, const float* wp, const float* bias, int C, int rows_pad,
                        const float* xin, const float* stats, int act, float slope, float* out, void* stream) {
   return sln_spade_modulate_up(actv, B, Cin, H, W, wp, bias, C, rows_pad, xin, 0, stats, act, slope, out, stream);
+}
+
+// fp16-MFMA forms of the three calls above (conv_f16_kernel): 3x3 only, weights packed fp16 [ceil(Cin / 16)][9][rows_pad][16] as
+// hi (and lo: the three-product mode; NULL: one product).
+int sln_spade_conv_sums_f16(const float* x, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
+                            int rows, int rows_pad, int ksize, int act, float slope, float* y, double* ln_acc, double* gap_acc, void* stream) {
+  if (!x || !wp_hi || !y || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || rows <= 0 || rows_pad % 64 != 0 || rows > rows_pad) return SLN_E_BADARG;
+  if (ksize != 3) return SLN_E_UNSUPPORTED;
+  if (H < 2 || W < 2) return SLN_E_BADARG;
+  if ((int64_t)Cin * H * W >= (int64_t)1 << 31) return SLN_E_UNSUPPORTED;      // 32-bit halo offsets inside a sample
+  hipStream_t st = (hipStream_t)stream;
+  ConvArgs a; a.x = x; a.wp = nullptr; a.bias = bias; a.y = y; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = rows; a.rows_pad = rows_pad;
+  a.act = act; a.slope = slope; a.xin = nullptr; a.stats = nullptr; a.C = 0; a.xin_up = 0; a.ln_acc = ln_acc; a.gap_acc = gap_acc;
+  static const int block_cin = getenv("SLN_CONV_BLOCK_CIN") ? atoi(getenv("SLN_CONV_BLOCK_CIN")) : 512;
+  a.blocked = Cin >= block_cin;
+  a.part = nullptr; a.part_stride = 0;
+  SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * 9 * rows, st);
+  return launch_conv_f16_any<CEPI_BIAS_ACT>(a, wp_hi, wp_lo, st);
+}
+int sln_spade_conv_f16(const float* x, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
+                       int rows, int rows_pad, int ksize, int act, float slope, float* y, void* stream) {
+  return sln_spade_conv_sums_f16(x, B, Cin, H, W, wp_hi, wp_lo, bias, rows, rows_pad, ksize, act, slope, y, nullptr, nullptr, stream);
+}
+int sln_spade_modulate_up_f16(const float* actv, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
+                              int C, int rows_pad, const float* xin, int xin_up, const float* stats, int act, float slope, float* out,
+                              void* stream) {
+  if (xin_up && ((H | W) & 1)) return SLN_E_BADARG;
+  if ((int64_t)C * H * W >= (int64_t)1 << 31 || (int64_t)Cin * H * W >= (int64_t)1 << 31) return SLN_E_UNSUPPORTED;
+  if (!actv || !wp_hi || !bias || !xin || !stats || !out || B <= 0 || Cin <= 0 || C <= 0 || H < 2 || W < 2 || rows_pad % 64 != 0 ||
+      rows_pad < 64 * ((C + 31) / 32))
+    return SLN_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  ConvArgs a; a.x = actv; a.wp = nullptr; a.bias = bias; a.y = out; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = 2 * C; a.rows_pad = rows_pad;
+  a.act = act; a.slope = slope; a.xin = xin; a.stats = stats; a.C = C; a.xin_up = xin_up; a.ln_acc = nullptr; a.gap_acc = nullptr; a.blocked = 0; a.part = nullptr; a.part_stride = 0;
+  SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * 9 * 2 * C, st);
+  return launch_conv_f16_any<CEPI_MODULATE>(a, wp_hi, wp_lo, st);
+}
+int sln_spade_modulate_f16(const float* actv, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
+                           int C, int rows_pad, const float* xin, const float* stats, int act, float slope, float* out, void* stream) {
+  return sln_spade_modulate_up_f16(actv, B, Cin, H, W, wp_hi, wp_lo, bias, C, rows_pad, xin, 0, stats, act, slope, out, stream);
 }
 
 // stats[b] from sums a conv epilogue / block tail accumulated (acc [B][16] doubles: sum, sum of squares over n_acc values,

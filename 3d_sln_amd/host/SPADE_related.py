@@ -93,6 +93,33 @@ def _pack_gamma_beta(wg, bg, wb, bb):
     return w.contiguous(), b.contiguous(), rp
 
 
+CONV_PRECISIONS = ("fp32", "f16x3", "f16")
+
+
+def split_f16(w_packed):
+    """fp16 operands of the half-precision 3x3 convolutions (csrc/spade.hip conv_f16_kernel): the _pack layout [9, Cin, rows_pad]
+    fp32 -> (hi, lo), each fp16 [ceil(Cin / 16), 9, rows_pad, 16] (16 input channels per MFMA K, zero padded), hi = fp16(w),
+    lo = fp16(w - hi); |hi + lo - w| <= max(2^-22 |w|, 2^-25) (2^-25: half of fp16's subnormal step).  Weights are clamped to the
+    finite fp16 range first."""
+    k2, ci, rp = w_packed.shape
+    if k2 != 9:
+        raise ValueError("split_f16 packs 3x3 convolutions only (got %d taps)" % k2)
+    nch = (ci + 15) // 16
+    w = torch.zeros(9, nch * 16, rp, dtype=torch.float32, device=w_packed.device)
+    w[:, :ci] = w_packed.float().clamp(-65504.0, 65504.0)
+    t = w.view(9, nch, 16, rp).permute(1, 0, 3, 2).contiguous()
+    hi = t.half()
+    lo = (t - hi.float()).half()
+    return hi, lo
+
+
+def unpack_f16(hi, lo, cin):
+    """Inverse of split_f16: [ceil(Cin / 16), 9, rows_pad, 16] fp16 hi (+ lo, or None) -> [9, cin, rows_pad] (fp64, exact)."""
+    t = hi.double() if lo is None else hi.double() + lo.double()
+    nch, k2, rp, _ = t.shape
+    return t.permute(1, 0, 3, 2).reshape(k2, nch * 16, rp)[:, :cin].contiguous()
+
+
 class SPADEGenerator4(nn.Module):
     def __init__(self, semantic_nc, target_nc, nz, ngf, norm, crop_size, n_up):
         super().__init__()
@@ -118,6 +145,11 @@ class SPADEGenerator4(nn.Module):
         self.unfused = False          # True: one launch per module (the round-1 schedule; kept for A/B runs and odd sizes)
 
     # ------------------------------------------------------------------ weight packing
+    # Precision of the 3x3 convolutions (conv_0 / conv_1 / mlp_shared / mlp_gamma|beta; conv_img, conv_s, SE, fc and every reduction
+    # stay fp32): "fp32" (v_mfma_f32_32x32x2_f32), "f16x3" (fp16 MFMA, hi / lo split of both operands, three products: fp32-grade),
+    # "f16" (fp16 MFMA, one product: fp16 operands, fp32 accumulation).  Any other value raises.  Switching repacks the weights and
+    # drops the kept gamma|beta planes and the captured batch-1 call.
+    conv_precision = "fp32"
     reuse_map_planes = True          # see forward(): gamma|beta planes of a map kept between consecutive batch-1 calls on it
     _map_repeat = False
     _map_memo = None
@@ -151,7 +183,7 @@ class SPADEGenerator4(nn.Module):
         # (the weights' signature as _pack_all takes it: a captured call has the packed weights' addresses baked in, and a
         #  load_state_dict / optimizer step is only noticed by the NEXT _pack_all - which a replay never reaches)
         wkey = tuple((v.data_ptr(), v._version) for v in self.parameters()) + tuple((v.data_ptr(), v._version) for v in self.buffers())
-        key = (input.data_ptr(), input._version, tuple(input.shape), input.dtype, str(input.device), wkey)
+        key = (input.data_ptr(), input._version, tuple(input.shape), input.dtype, str(input.device), wkey, self.conv_precision)
         ent = getattr(self, "_b1_graph", None)
         if ent is None or ent["key"] != key:
             side = getattr(self, "_b1_stream", None)
@@ -176,6 +208,9 @@ class SPADEGenerator4(nn.Module):
                 with torch.cuda.graph(g, stream=s):
                     ent["out"] = self._eager_forward(input, ent["z"], None)
                 ent["graph"], ent["memo"] = g, self._map_memo   # (the captured launches read the kept planes: they live with the graph)
+                # ... and the packed weights of this capture: a conv_precision round trip (f16 -> fp32 -> f16) repacks twice and
+                # comes back to the same key, so the replay must still find the pack whose addresses it recorded
+                ent["packed"] = self._packed
                 g.replay()
                 out = ent["out"].clone()
         cur.wait_stream(s)
@@ -188,15 +223,28 @@ class SPADEGenerator4(nn.Module):
         st["_map_memo"] = st["_packed"] = st["_packed_key"] = st["_cat_cache"] = st["_b1_graph"] = st["_b1_stream"] = None
         return st
 
+    def _precision(self):
+        p = self.conv_precision
+        if p not in CONV_PRECISIONS:
+            raise ValueError("SPADEGenerator4.conv_precision must be one of %s, not %r" % (", ".join(CONV_PRECISIONS), p))
+        return p
+
     def _pack_all(self):
         # the signature of the weights - (address, version counter) of every parameter and buffer - is taken on every call; walking
         # parameters() / buffers() costs ~0.1 ms where two state_dict() walks with 230 detach().float() copies cost ~1 ms, which at
         # batch 1 was half of the host time of a call (tools/lab/spade_b1_hostprof.py)
-        key = tuple((v.data_ptr(), v._version) for v in self.parameters()) + tuple((v.data_ptr(), v._version) for v in self.buffers())
+        mode = self._precision()
+        key = (mode,) + tuple((v.data_ptr(), v._version) for v in self.parameters()) + tuple((v.data_ptr(), v._version) for v in self.buffers())
         if self._packed is not None and key == self._packed_key:
             return self._packed
         sd = {k: v.detach().float() for k, v in self.state_dict().items()}
-        P = {}
+        P = {"precision": mode}
+
+        def half(w):                     # fp16 packs of a 3x3 weight in the half modes (lo only for the three-product mode)
+            if mode == "fp32":
+                return None
+            hi, lo = split_f16(w)
+            return hi, (lo if mode == "f16x3" else None)
         for name in ("head_0", "G_middle_0", "G_middle_1", "up_0", "up_1", "up_2", "up_3"):
             blk = getattr(self, name)
             e = {}
@@ -204,6 +252,7 @@ class SPADEGenerator4(nn.Module):
                 w, rp = _pack(_fold_sn(sd, "%s.%s.1" % (name, cn)))
                 b = torch.zeros(rp, device=w.device); b[:sd["%s.%s.1.bias" % (name, cn)].numel()] = sd["%s.%s.1.bias" % (name, cn)]
                 e[cn] = (w, b, rp)
+                e[cn + "_h"] = half(w)
             if blk.learned_shortcut:
                 w, rp = _pack(_fold_sn(sd, name + ".conv_s"))
                 e["conv_s"] = (w, None, rp)
@@ -217,7 +266,7 @@ class SPADEGenerator4(nn.Module):
                                                  sd[p + ".mlp_beta.1.weight"], sd[p + ".mlp_beta.1.bias"])
                 e[nn_] = dict(wpd=sd[p + ".mlp_preshared_depth.1.weight"].reshape(NHIDDEN // 8, 9).contiguous(),
                               bpd=sd[p + ".mlp_preshared_depth.1.bias"].contiguous(), wsh=wsh, bsh=bsh, rps=rps,
-                              wgb=wgb, bgb=bgb, rpg=rpg)
+                              wgb=wgb, bgb=bgb, rpg=rpg, wsh_h=half(wsh), wgb_h=half(wgb))
             e["se0"], e["se2"] = sd[name + ".se.fc.0.weight"].contiguous(), sd[name + ".se.fc.2.weight"].contiguous()
             P[name] = e
         self._map_memo = None            # planes computed with the old weights
@@ -242,6 +291,16 @@ class SPADEGenerator4(nn.Module):
                    "sln_layernorm_stats")
         return stats
 
+    def _conv3(self, x, B, Cin, H, W, w, wh, bias, rows, rp, act, y, what):
+        """sln_spade_conv (3x3) of the fp32 pack w, or of its fp16 pack wh = (hi, lo or None) in the half modes."""
+        L = _lib.lib()
+        if wh is None:
+            _lib.check(L.sln_spade_conv(_lib.ptr(x), B, Cin, H, W, _lib.ptr(w), _lib.ptr(bias), rows, rp, 3, act, 0.0, _lib.ptr(y),
+                                        self._st()), "sln_spade_conv(%s)" % what)
+        else:
+            _lib.check(L.sln_spade_conv_f16(_lib.ptr(x), B, Cin, H, W, _lib.ptr(wh[0]), _lib.ptr(wh[1]), _lib.ptr(bias), rows, rp, 3, act,
+                                            0.0, _lib.ptr(y), self._st()), "sln_spade_conv_f16(%s)" % what)
+
     def _spade(self, e, x, stats, seg, leaky, x_up=False):
         """SPADE4.forward (:1438-1454) + the following actvn (:1503-1505) fused into the modulation conv.
         x_up: x is stored at half the resolution of seg and stands for its nearest x2 upsampling (never materialised)."""
@@ -257,12 +316,17 @@ class SPADEGenerator4(nn.Module):
         _lib.check(L.sln_spade_depth_concat(_lib.ptr(seg), B, seg.shape[1], H, W, _lib.ptr(e["wpd"]), _lib.ptr(e["bpd"]), nd,
                                             _lib.ptr(cat), 0, self._st()), "sln_spade_depth_concat")
         actv = torch.empty(B, NHIDDEN, H, W, device=x.device)
-        _lib.check(L.sln_spade_conv(_lib.ptr(cat), B, cat.shape[1], H, W, _lib.ptr(e["wsh"]), _lib.ptr(e["bsh"]), NHIDDEN, e["rps"], 3,
-                                    1, 0.0, _lib.ptr(actv), self._st()), "sln_spade_conv(shared)")
+        self._conv3(cat, B, cat.shape[1], H, W, e["wsh"], e.get("wsh_h"), e["bsh"], NHIDDEN, e["rps"], 1, actv, "shared")
         out = torch.empty(B, C, H, W, device=x.device)
-        _lib.check(L.sln_spade_modulate_up(_lib.ptr(actv), B, NHIDDEN, H, W, _lib.ptr(e["wgb"]), _lib.ptr(e["bgb"]), C, e["rpg"],
-                                           _lib.ptr(x), 1 if x_up else 0, _lib.ptr(stats), 2 if leaky else 0, 0.2, _lib.ptr(out),
-                                           self._st()), "sln_spade_modulate_up")
+        gh = e.get("wgb_h")
+        if gh is None:
+            _lib.check(L.sln_spade_modulate_up(_lib.ptr(actv), B, NHIDDEN, H, W, _lib.ptr(e["wgb"]), _lib.ptr(e["bgb"]), C, e["rpg"],
+                                               _lib.ptr(x), 1 if x_up else 0, _lib.ptr(stats), 2 if leaky else 0, 0.2, _lib.ptr(out),
+                                               self._st()), "sln_spade_modulate_up")
+        else:
+            _lib.check(L.sln_spade_modulate_up_f16(_lib.ptr(actv), B, NHIDDEN, H, W, _lib.ptr(gh[0]), _lib.ptr(gh[1]), _lib.ptr(e["bgb"]), C,
+                                                   e["rpg"], _lib.ptr(x), 1 if x_up else 0, _lib.ptr(stats), 2 if leaky else 0, 0.2,
+                                                   _lib.ptr(out), self._st()), "sln_spade_modulate_up_f16")
         return out
 
     def _cat_buffer(self, seg, nd):
@@ -294,11 +358,9 @@ class SPADEGenerator4(nn.Module):
             _lib.check(L.sln_spade_depth_concat(_lib.ptr(seg), 1, seg.shape[1], H, W, _lib.ptr(e["wpd"]), _lib.ptr(e["bpd"]), nd,
                                                 _lib.ptr(cat), 0, self._st()), "sln_spade_depth_concat")
             actv = torch.empty(1, NHIDDEN, H, W, device=x.device)
-            _lib.check(L.sln_spade_conv(_lib.ptr(cat), 1, cat.shape[1], H, W, _lib.ptr(e["wsh"]), _lib.ptr(e["bsh"]), NHIDDEN, e["rps"], 3,
-                                        1, 0.0, _lib.ptr(actv), self._st()), "sln_spade_conv(shared)")
+            self._conv3(cat, 1, cat.shape[1], H, W, e["wsh"], e.get("wsh_h"), e["bsh"], NHIDDEN, e["rps"], 1, actv, "shared")
             gb = torch.empty(1, e["rpg"], H, W, device=x.device)
-            _lib.check(L.sln_spade_conv(_lib.ptr(actv), 1, NHIDDEN, H, W, _lib.ptr(e["wgb"]), _lib.ptr(e["bgb"]), e["rpg"], e["rpg"], 3,
-                                        0, 0.0, _lib.ptr(gb), self._st()), "sln_spade_conv(gamma|beta)")
+            self._conv3(actv, 1, NHIDDEN, H, W, e["wgb"], e.get("wgb_h"), e["bgb"], e["rpg"], e["rpg"], 0, gb, "gamma|beta")
             if memo is not None:
                 memo[id(e)] = gb
         out = torch.empty(B, C, H, W, device=x.device)
@@ -306,10 +368,16 @@ class SPADEGenerator4(nn.Module):
                                         2 if leaky else 0, 0.2, _lib.ptr(out), self._st()), "sln_spade_apply_up")
         return out
 
-    def _conv(self, x, wbr, cout, ks, ln_acc=None, gap_acc=None):
+    def _conv(self, x, wbr, cout, ks, ln_acc=None, gap_acc=None, wh=None):
         w, b, rp = wbr
         B, _, H, W = x.shape
         y = torch.empty(B, cout, H, W, device=x.device)
+        if wh is not None:                       # half modes: the fp16 pack (hi, lo or None) of this 3x3 weight
+            _lib.check(_lib.lib().sln_spade_conv_sums_f16(_lib.ptr(x), B, x.shape[1], H, W, _lib.ptr(wh[0]), _lib.ptr(wh[1]), _lib.ptr(b), cout,
+                                                          rp, ks, 0, 0.0, _lib.ptr(y), _lib.ptr(ln_acc) if ln_acc is not None else None,
+                                                          _lib.ptr(gap_acc) if gap_acc is not None else None, self._st()),
+                       "sln_spade_conv_sums_f16")
+            return y
         _lib.check(_lib.lib().sln_spade_conv_sums(_lib.ptr(x), B, x.shape[1], H, W, _lib.ptr(w), _lib.ptr(b), cout, rp, ks, 0, 0.0,
                                                   _lib.ptr(y), _lib.ptr(ln_acc) if ln_acc is not None else None,
                                                   _lib.ptr(gap_acc) if gap_acc is not None else None, self._st()), "sln_spade_conv_sums")
@@ -343,14 +411,16 @@ class SPADEGenerator4(nn.Module):
             x_s, xs_up = self._conv(self._spade(e["norm_s"], x, stats_x, seg, False, x_up), e["conv_s"], blk.fout, 1), 0
         else:
             x_s, xs_up = x, 1 if x_up else 0
-        dx = self._conv(self._spade(e["norm_0"], x, stats_x, seg, True, x_up), e["conv_0"], blk.fmiddle, 3, ln_acc=None if det else ln_dx)
+        dx = self._conv(self._spade(e["norm_0"], x, stats_x, seg, True, x_up), e["conv_0"], blk.fmiddle, 3, ln_acc=None if det else ln_dx,
+                        wh=e.get("conv_0_h"))
         if det:
             stats_dx = self._ln_stats(dx)
         else:
             stats_dx = torch.empty(B, 2, device=x.device)
             _lib.check(L.sln_layernorm_finalize(_lib.ptr(ln_dx), B, blk.fmiddle * H * W, 1, 1e-5, _lib.ptr(stats_dx), self._st()),
                        "sln_layernorm_finalize")
-        dx = self._conv(self._spade(e["norm_1"], dx, stats_dx, seg, True), e["conv_1"], blk.fout, 3, gap_acc=None if det else gap)
+        dx = self._conv(self._spade(e["norm_1"], dx, stats_dx, seg, True), e["conv_1"], blk.fout, 3, gap_acc=None if det else gap,
+                        wh=e.get("conv_1_h"))
         gap_p = None if det else _lib.ptr(gap)
         up_mode = 1 if tail == 'bilinear' else -1
         k = 2 if tail == 'bilinear' else 1
@@ -384,8 +454,8 @@ class SPADEGenerator4(nn.Module):
             x_s = self._conv(self._spade(e["norm_s"], x, stats_x, seg, leaky=False), e["conv_s"], blk.fout, 1)
         else:
             x_s = x
-        dx = self._conv(self._spade(e["norm_0"], x, stats_x, seg, leaky=True), e["conv_0"], blk.fmiddle, 3)
-        dx = self._conv(self._spade(e["norm_1"], dx, self._ln_stats(dx), seg, leaky=True), e["conv_1"], blk.fout, 3)
+        dx = self._conv(self._spade(e["norm_0"], x, stats_x, seg, leaky=True), e["conv_0"], blk.fmiddle, 3, wh=e.get("conv_0_h"))
+        dx = self._conv(self._spade(e["norm_1"], dx, self._ln_stats(dx), seg, leaky=True), e["conv_1"], blk.fout, 3, wh=e.get("conv_1_h"))
         B, Cc, H, W = dx.shape
         out = torch.empty_like(dx)
         scratch = torch.empty(2 * B * Cc, device=dx.device)
@@ -409,6 +479,7 @@ class SPADEGenerator4(nn.Module):
 
     def forward(self, input, z=None, taps=None):
         """seg [B, semantic_nc, S, S] (channel 0 depth, 1.. masks), z [B, nz] -> image [B, target_nc, S, S] in (-1, 1)."""
+        self._precision()
         if input.device.type != 'cuda':
             raise _lib.SlnError("SPADEGenerator4 runs on the MI355X only (no CPU fallback)")
         if self._graph_eligible(input, z, taps):

@@ -540,6 +540,20 @@ int sln_spade_modulate_up(const float* actv, int B, int Cin, int H, int W, const
 /* stats[b] = (mean, 1 / (unbiased std + eps)) from accumulated sums: acc [B][16] doubles (sum, sum of squares of n_acc values),
  * every value standing for `rep` elements of the normalised tensor (4 = its nearest x2 upsampling) */
 int sln_layernorm_finalize(const double* acc, int B, int64_t n_acc, int rep, float eps, float* stats, void* stream);
+/* fp16-MFMA forms of sln_spade_conv / _conv_sums / _modulate / _modulate_up (opt-in precision modes): same sizes,
+ * same epilogues, ksize must be 3 (SLN_E_UNSUPPORTED otherwise, nothing launched).  Weights are packed fp16 (IEEE binary16 bits)
+ * [ceil(Cin / 16)][9][rows_pad][16] (input channels zero padded to a multiple of 16): wp_hi = fp16(w), wp_lo = fp16(w - wp_hi).
+ * wp_lo != NULL: three products per term (w_hi x_hi + w_hi x_lo + w_lo x_hi, the activations split the same way on the fly),
+ * fp32-grade; wp_lo == NULL: one product (w_hi x_hi), fp16 operands with fp32 accumulation. */
+int sln_spade_conv_f16(const float* x, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
+                       int rows, int rows_pad, int ksize, int act, float slope, float* y, void* stream);
+int sln_spade_conv_sums_f16(const float* x, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
+                            int rows, int rows_pad, int ksize, int act, float slope, float* y, double* ln_acc, double* gap_acc, void* stream);
+int sln_spade_modulate_f16(const float* actv, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
+                           int C, int rows_pad, const float* xin, const float* stats, int act, float slope, float* out, void* stream);
+int sln_spade_modulate_up_f16(const float* actv, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
+                              int C, int rows_pad, const float* xin, int xin_up, const float* stats, int act, float slope, float* out,
+                              void* stream);
 /* Tail of SPADEResnetBlock4.forward (:1492-1493) and the nn.Upsample after it (:1585-1600) in one pass:
  *   out = up(xs + dx * sigmoid(W2 relu(W0 GAP(dx)))),  stats = LayerNorm2D statistics of the next block's input.
  * xs [B,C,H,W] (xs_up = 1: [B,C,H/2,W/2] read through nearest x2); gap_sums = the gap_acc of sln_spade_conv_sums or NULL;
