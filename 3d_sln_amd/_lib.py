@@ -211,6 +211,11 @@ SIGNATURES = {
     "sln_layout_spread": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sln_layout_l1": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, C.c_void_p]),
     "sln_layout_baselines": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_i64p, c_f32p, C.c_void_p]),
+    "sln_layout_cuboid_iou": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f32p,
+                                        C.c_void_p, C.c_void_p]),
+    "sln_layout_overlap": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, c_i64p, C.c_void_p]),
+    "sln_refine_report": (C.c_int, [C.POINTER(SlnRefineLoss), c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p]),
+    "sln_refine_report_scratch_doubles": (C.c_int, [C.c_int]),
     "sln_scene_live_channels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sln_scene_backward": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_float, C.c_void_p, c_f32p, c_f32p, C.c_void_p]),

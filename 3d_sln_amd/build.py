@@ -21,7 +21,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
          "-I" + os.path.join(os.path.dirname(HERE), "include")] + os.environ.get("SLN_HIPCC_EXTRA", "").split()   # lab: -DSLN_NT_SCHED=0 ...
 # raster kernels: bit-exact agreement with the CPU restatement needs contraction off (see raster.hip)
 # placement: the torch expression it replaces rounds after every elementwise op
-PER_FILE = {"raster.hip": ["-ffp-contract=off"], "graph_build.hip": ["-ffp-contract=off"], "placement.hip": ["-ffp-contract=off"]}
+# layout_iou: the cuboid corners as torch forms them; a cross product of a point with itself must be exactly 0
+PER_FILE = {"raster.hip": ["-ffp-contract=off"], "graph_build.hip": ["-ffp-contract=off"], "placement.hip": ["-ffp-contract=off"],
+            "layout_iou.hip": ["-ffp-contract=off"]}
 
 
 def sources():

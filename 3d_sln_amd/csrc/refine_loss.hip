@@ -260,6 +260,57 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float2* __rest
   }
 }
 
+// The refinement report (testing/test_render_refine.py:369-374, what the reference pickles into bbox_rot_0.pkl): per room
+//   depth_l1 = L1Loss(iter[:, 41:], target[:, 41:]) at full resolution, the iterate after the null fill (:332), the target as rendered
+//   ce_last  = the cross-entropy of the last pooling scale, without the / 800
+// report_depth_kernel: REPORT_BLOCKS workgroups per room, each over a run of pixels of all n_dep planes (dead planes enter as the
+// constants they are, unread); report_finalize_kernel sums a room's partials and the last scale's blocks of loss_kernel's partials
+// (a block of loss_kernel lies inside one (room, scale) when P * P is a multiple of 128) in a fixed order.
+constexpr int REPORT_BLOCKS = 64;
+__global__ __launch_bounds__(256) void report_depth_kernel(const float* __restrict__ img, const float* __restrict__ tgt, const unsigned char* __restrict__ null,
+                                                           const unsigned char* __restrict__ live, RefineDims d, double* __restrict__ scratch) {
+  __shared__ double red[4];
+  const int b = blockIdx.y;
+  const long plane = (long)d.S * d.S, per = (plane + REPORT_BLOCKS - 1) / REPORT_BLOCKS;
+  const long p0 = (long)blockIdx.x * per, p1 = p0 + per < plane ? p0 + per : plane;
+  const float* src = img + ((long)b * d.C + d.dep0) * plane;
+  const float* tg = tgt + (long)b * d.n_dep * plane;
+  const unsigned char* nm = null + (long)b * plane;
+  double acc = 0.0;
+  for (int c = 0; c < d.n_dep; ++c) {
+    const int lv = live != nullptr ? live[b * d.C + d.dep0 + c] : 3;
+    const bool last = c == d.n_dep - 1;
+    const float cst = (lv & 1) ? 1.f : 0.f;
+    float a = 0.f;
+    for (long p = p0 + threadIdx.x; p < p1; p += 256) {
+      float v = lv == 3 ? src[c * plane + p] : cst;
+      if (last && nm[p]) v = 1.f;
+      a += fabsf(v - tg[c * plane + p]);
+    }
+    acc += (double)a;
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) scratch[b * REPORT_BLOCKS + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(64) void report_finalize_kernel(const double* __restrict__ scratch, const float2* __restrict__ partial, RefineDims d,
+                                                             double* __restrict__ iou_mean, float* __restrict__ report) {
+  const int b = blockIdx.x, bps = d.P * d.P / 128;                      // blocks of loss_kernel per (room, scale)
+  double a = scratch[b * REPORT_BLOCKS + threadIdx.x], c = 0.0;
+  const float2* ps = partial + (long)(b * d.n_scales + d.n_scales - 1) * bps;      // part row 0 (the semantic part), the last scale
+  for (int i = threadIdx.x; i < bps; i += 64) c += (double)ps[i].y;
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); c += __shfl_down(c, o, 64); }
+  if (threadIdx.x == 0) {
+    float iou = __builtin_nanf("");
+    if (iou_mean != nullptr) { iou = (float)iou_mean[b]; iou_mean[b] = 0.0; }
+    report[3 * b + 0] = iou;
+    report[3 * b + 1] = (float)(a / ((double)d.n_dep * d.S * d.S));
+    report[3 * b + 2] = (float)(c * 800.0);
+  }
+}
+
 // d loss / d image[b][c][y][x] = gscale * sum_s sum_{(oy, wy) in col_s(y)} sum_{(ox, wx) in col_s(x)} wy wx dpooled[b][s][c][oy][ox]
 __global__ __launch_bounds__(256) void refine_bwd_kernel(const float* __restrict__ dpooled, const unsigned char* __restrict__ null, RefineDims d,
                                                          const int* __restrict__ col_ptr, const int* __restrict__ col_out,
@@ -667,5 +718,25 @@ int sln_refine_loss_backward(const SlnRefineLoss* L, const void* workspace, cons
   SLN_CHECK_LAUNCH();
   return 0;
 }
+
+int sln_refine_report(const SlnRefineLoss* L, const float* image, const float* target_depth, const void* workspace, double* scratch,
+                      double* iou_mean, float* report_out, void* stream) {
+  int r = check(L);
+  if (r) return r;
+  if (!image || !target_depth || !workspace || !scratch || !report_out) return SLN_E_BADARG;
+  const RefineDims d = dims_of(L);
+  if ((d.P * d.P) % 128 != 0 || (!d.per_room && d.B != 1)) return SLN_E_UNSUPPORTED;
+  float* pooled; unsigned char* mask; float2* partial;
+  carve(L, const_cast<void*>(workspace), &pooled, &mask, &partial);
+  const unsigned char* live = live_of(L, d);
+  if (live != nullptr && L->null_mask != nullptr) mask = const_cast<unsigned char*>(L->null_mask);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(report_depth_kernel, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch);
+  hipLaunchKernelGGL(report_finalize_kernel, dim3(d.B), dim3(64), 0, st, scratch, partial, d, iou_mean, report_out);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_refine_report_scratch_doubles(int B) { return B > 0 ? B * REPORT_BLOCKS : 0; }
 
 }  // extern "C"

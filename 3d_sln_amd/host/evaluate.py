@@ -6,7 +6,10 @@
   * ``layout_l1``     - F.l1_loss of S layouts against the ground truth (sln_layout_l1);
   * ``layout_spread`` - the get_std figures of one batch from its Nsample decodes (sln_layout_spread);
   * ``baselines``     - the random and perturbed layouts of get_acc_l1 (sln_layout_baselines), draws injected or drawn on the device;
-  * ``measure_acc_l1_std`` - the whole mode: the nine figures the reference prints, read back once at the end.
+  * ``measure_acc_l1_std`` - the whole mode: the nine figures the reference prints, read back once at the end;
+  * ``cuboid_iou``    - the rotated-cuboid 3-D IoU of S layouts against the ground truth (testing/test_render_refine.py:78-116,360-368,
+    testing/test_utils.py:7-40) with per-room means (sln_layout_cuboid_iou) - the figure of the refinement table;
+  * ``layout_overlap`` - how much of a layout's furniture interpenetrates: intersection volume and pair count (sln_layout_overlap).
 
 The ``*_torch`` functions restate each kernel in torch ops for CPU tensors (the host-side tests), as ``sampling.layout_heatmap``
 does for the heat-map kernel.
@@ -119,9 +122,193 @@ def baselines(gt, objs, room_cls, uniforms=None, normals=None, key=None, out=Non
     return out
 
 
+DO_NOT_VIS = ("wall", "ceiling", "floor", "person", "door", "window", "curtain", "blinds")      # testing/test_render_refine.py:16
+MAX_ROOM_ROWS = 1024                      # rows of one room sln_layout_overlap stages at once
+
+
+def visible_rows(objs, vocab_names):
+    """[O] bool: the rows get_boxes keeps (test_render_refine.py:87-89: the class name is not in do_not_vis) - room rows included"""
+    names = list(vocab_names)
+    keep = torch.tensor([n not in DO_NOT_VIS for n in names], dtype=torch.bool, device=objs.device)
+    return keep[objs.to(torch.int64)]
+
+
+def room_rows(objs, room_cls):
+    """[O] int32: for every row the index of its room row - the first row of class ``room_cls`` at or behind it, the last row of its
+    room (restore_box, test_utils.py:119-132; get_boxes' ``input_boxes[-1]`` for a single room); -1 behind the last room row"""
+    is_room = (objs.to(torch.int64) == int(room_cls)).cpu().tolist()
+    out, j = [], -1
+    for i in range(len(is_room) - 1, -1, -1):
+        if is_room[i]:
+            j = i
+        out.append(j)
+    return torch.tensor(out[::-1], dtype=torch.int32, device=objs.device)
+
+
+def _room_ids(room_of_row):
+    """[O] int32 ordinal of every row's room, and the number of rooms (host side: one read of the table)"""
+    r = room_of_row.cpu().to(torch.int64)
+    uniq, inv = torch.unique(r, sorted=True, return_inverse=True)
+    return inv.to(torch.int32).to(room_of_row.device), int(uniq.numel())
+
+
+def _check_rooms(room_of_row, O):
+    r = room_of_row.cpu().to(torch.int64)
+    if r.shape != (O,) or bool((r < torch.arange(O)).any()) or bool((r >= O).any()) or bool((r[1:] < r[:-1]).any()) or bool((r[r] != r).any()):
+        raise ValueError("room_of_row must be [O]: for every row the index of the last row of its room (rows of a room consecutive)")
+    return r
+
+
+def cuboid_iou(boxes, angles, gt_boxes, gt_angles, room_of_row, visible, room_id=None, n_rooms=None, want_rows=True, mean=None):
+    """boxes [S, O, 6], angles [S, O] (float bins) against gt_boxes [O, 6], gt_angles [O] -> (iou [S, O] float32 or None,
+    mean [S, n_rooms] float64, += into ``mean``): get_iou_cuboid of every row, averaged over the visible rows of every room."""
+    _check_layouts(boxes)
+    S, O, _ = boxes.shape
+    dev = boxes.device
+    if angles.shape != (S, O) or gt_boxes.shape != (O, 6) or gt_angles.shape != (O,) or visible.shape != (O,):
+        raise ValueError("angles must be [S, O], gt_boxes [O, 6], gt_angles and visible [O]")
+    _check_rooms(room_of_row, O)
+    if room_id is None:
+        room_id, n_rooms = _room_ids(room_of_row)
+    b, a = boxes.float().contiguous(), angles.float().contiguous()
+    g, ga = gt_boxes.float().contiguous(), gt_angles.float().contiguous()
+    rr, vis, rid = room_of_row.to(torch.int32).contiguous(), visible.to(torch.uint8).contiguous(), room_id.to(torch.int32).contiguous()
+    iou = torch.empty(S, O, dtype=torch.float32, device=dev) if want_rows else None
+    mean = torch.zeros(S, int(n_rooms), dtype=torch.float64, device=dev) if mean is None else mean
+    if mean.shape != (S, int(n_rooms)) or mean.dtype != torch.float64:
+        raise ValueError("mean must be [S, n_rooms] float64")
+    for s0 in range(0, S, 65535):                       # (the layout index is a grid axis)
+        n = min(65535, S - s0)
+        _lib.check(_lib.lib().sln_layout_cuboid_iou(_lib.ptr(b[s0:]), _lib.ptr(a[s0:]), _lib.ptr(g), _lib.ptr(ga), _lib.ptr(rr), _lib.ptr(vis), _lib.ptr(rid),
+                                                    int(n_rooms), n, O, _lib.ptr(iou[s0:]) if want_rows else None, _lib.ptr(mean[s0:]),
+                                                    _lib.current_stream_ptr()), "sln_layout_cuboid_iou")
+    return iou, mean
+
+
+def layout_overlap(boxes, angles, room_of_row, visible, thresh=0.0, vol=None, pairs=None):
+    """boxes [S, O, 6], angles [S, O] -> (vol [S] float64, pairs [S] int64), both +=: over the pairs of visible rows of the same room,
+    the summed intersection volume and the number of pairs whose IoU exceeds ``thresh``"""
+    _check_layouts(boxes)
+    S, O, _ = boxes.shape
+    dev = boxes.device
+    if angles.shape != (S, O) or visible.shape != (O,):
+        raise ValueError("angles must be [S, O], visible [O]")
+    r = _check_rooms(room_of_row, O)
+    if O and int(torch.bincount(r).max()) > MAX_ROOM_ROWS:
+        raise ValueError("a room of more than %d rows" % MAX_ROOM_ROWS)
+    b, a = boxes.float().contiguous(), angles.float().contiguous()
+    rr, vis = room_of_row.to(torch.int32).contiguous(), visible.to(torch.uint8).contiguous()
+    vol = torch.zeros(S, dtype=torch.float64, device=dev) if vol is None else vol
+    pairs = torch.zeros(S, dtype=torch.int64, device=dev) if pairs is None else pairs
+    _lib.check(_lib.lib().sln_layout_overlap(_lib.ptr(b), _lib.ptr(a), _lib.ptr(rr), _lib.ptr(vis), S, O, float(thresh), _lib.ptr(vol), _lib.ptr(pairs),
+                                             _lib.current_stream_ptr()), "sln_layout_overlap")
+    return vol, pairs
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # torch restatements (CPU tensors)
 # ------------------------------------------------------------------------------------------------------------------------------
+def _shoelace(q):
+    """signed area of rings q [..., n, 2]"""
+    x, y = q[..., 0], q[..., 1]
+    return 0.5 * (x * torch.roll(y, -1, -1) - torch.roll(x, -1, -1) * y).sum(-1)
+
+
+def quad_intersection_area_torch(a, b):
+    """area of quad a ^ quad b, [..., 4, 2] each (convex, any winding): Sutherland-Hodgman of a against the edges of b on masks -
+    the device function of csrc/layout_iou.hip, statement for statement"""
+    a, b = torch.broadcast_tensors(a, b)
+    flip = lambda q: torch.where((_shoelace(q) < 0)[..., None, None], q[..., [0, 3, 2, 1], :], q)
+    a, b = flip(a), flip(b)
+    shape = a.shape[:-2]
+    P = torch.zeros(shape + (8, 2), dtype=a.dtype)
+    P[..., :4, :] = a
+    n = torch.full(shape, 4, dtype=torch.int64)
+    slots = torch.arange(8)
+    for e in range(4):
+        b0, ed = b[..., e, :], b[..., (e + 1) % 4, :] - b[..., e, :]
+        d = ed[..., None, 0] * (P[..., 1] - b0[..., None, 1]) - ed[..., None, 1] * (P[..., 0] - b0[..., None, 0])
+        out = torch.zeros_like(P)
+        m = torch.zeros_like(n)
+        for k in range(8):
+            wrap = (k + 1) >= n
+            kn = (k + 1) % 8
+            nxt = torch.where(wrap[..., None], P[..., 0, :], P[..., kn, :])
+            dn = torch.where(wrap, d[..., 0], d[..., kn])
+            cur, dc = P[..., k, :], d[..., k]
+            live = k < n
+            in_c, in_n = dc >= 0, dn >= 0
+            put_c = live & in_c
+            put_x = live & (in_c != in_n) & ~torch.isnan(dc) & ~torch.isnan(dn)
+            t = dc / (dc - dn)
+            ip = cur + t[..., None] * (nxt - cur)
+            w = (put_c[..., None] & (slots == m[..., None]))[..., None]
+            out = torch.where(w, cur[..., None, :], out)
+            m = m + put_c.long()
+            w = (put_x[..., None] & (slots == m[..., None]))[..., None]
+            out = torch.where(w, ip[..., None, :], out)
+            m = m + put_x.long()
+        n, P = m.clamp(max=8), out
+    k = slots.expand(shape + (8,))
+    nxt_i = torch.where(k + 1 >= n[..., None], torch.zeros_like(k), (k + 1) % 8)
+    Pn = torch.gather(P, -2, nxt_i[..., None].expand(shape + (8, 2)))
+    term = P[..., 0] * Pn[..., 1] - Pn[..., 0] * P[..., 1]
+    return (0.5 * torch.where(k < n[..., None], term, torch.zeros_like(term)).sum(-1)).abs()
+
+
+def cuboids_torch(boxes, angles, room_of_row, dtype=torch.float64):
+    """get_boxes (test_render_refine.py:90-110) of boxes [..., O, 6] / angles [..., O] -> (ring [..., O, 4, 2] in (x, z), h0, h1)"""
+    b, ang = boxes.to(dtype), angles.to(dtype)
+    rr = room_of_row.to(torch.int64).clamp(min=0)
+    ext = b[..., rr, 3:6]
+    mn, mx = b[..., 0:3] * ext, b[..., 3:6] * ext
+    ctr = (mx + mn) / 2
+    mn, mx = mn - ctr, mx - ctr
+    theta = -ang * float(np.float32(2.0 * float(np.pi) / 24.0))
+    c, s = torch.cos(theta), torch.sin(theta)
+    xs = torch.stack([mn[..., 0], mn[..., 0], mx[..., 0], mx[..., 0]], -1)
+    zs = torch.stack([mn[..., 2], mx[..., 2], mx[..., 2], mn[..., 2]], -1)
+    ring = torch.stack([c[..., None] * xs + s[..., None] * zs + ctr[..., None, 0], -s[..., None] * xs + c[..., None] * zs + ctr[..., None, 2]], -1)
+    return ring, mn[..., 1] + ctr[..., 1], mx[..., 1] + ctr[..., 1]
+
+
+def _pair_iou(ra, h0a, h1a, rb, h0b, h1b):
+    inter = quad_intersection_area_torch(ra, rb) * (torch.minimum(h1a, h1b) - torch.maximum(h0a, h0b)).clamp(min=0)
+    va, vb = _shoelace(ra).abs() * (h1a - h0a), _shoelace(rb).abs() * (h1b - h0b)
+    return inter / (va + vb - inter + 1e-5), inter
+
+
+def cuboid_iou_torch(boxes, angles, gt_boxes, gt_angles, room_of_row, visible=None, room_id=None, n_rooms=None, dtype=torch.float64):
+    """cuboid_iou as torch ops in ``dtype`` -> (iou [S, O], mean [S, n_rooms]; NaN for a room without a visible row)"""
+    S, O, _ = boxes.shape
+    rp, p0, p1 = cuboids_torch(boxes, angles, room_of_row, dtype)
+    rg, g0, g1 = cuboids_torch(gt_boxes, gt_angles, room_of_row, dtype)
+    iou, _ = _pair_iou(rg[None], g0[None], g1[None], rp, p0, p1)
+    if visible is None:
+        visible = torch.ones(O, dtype=torch.bool)
+    if room_id is None:
+        room_id, n_rooms = _room_ids(room_of_row)
+    mean = torch.full((S, int(n_rooms)), float("nan"), dtype=dtype)
+    for r in range(int(n_rooms)):
+        rows = torch.nonzero((room_id == r) & visible.bool()).flatten()
+        if rows.numel():
+            mean[:, r] = iou[:, rows].sum(1) / rows.numel()
+    return iou, mean
+
+
+def layout_overlap_torch(boxes, angles, room_of_row, visible, thresh=0.0, dtype=torch.float64):
+    """layout_overlap as torch ops -> (vol [S], pairs [S] int64, iou of every counted pair [S, n_pairs])"""
+    S, O, _ = boxes.shape
+    ring, h0, h1 = cuboids_torch(boxes, angles, room_of_row, dtype)
+    vis = visible.bool()
+    i, j = torch.triu_indices(O, O, 1)
+    ok = (room_of_row[i] == room_of_row[j]) & vis[i] & vis[j]
+    i, j = i[ok], j[ok]
+    iou, inter = _pair_iou(ring[:, i], h0[:, i], h1[:, i], ring[:, j], h0[:, j], h1[:, j])
+    return inter.sum(1), (iou > thresh).sum(1), iou
+
+
+# (the restatements of the --measure_acc_l1_std kernels)
 def restore_boxes_torch(boxes, objs, room_cls):
     """restore_box (test_utils.py:119-132) of [S, O, 6] layouts, out of place"""
     S, O, _ = boxes.shape
@@ -260,7 +447,7 @@ def _draw_z(model, objs, triples, attributes, n, mean, cov, gen):
     return z
 
 
-def measure_acc_l1_std(model, batches, mean, cov, vocab, n_std_samples=10, seed=None, draws=None):
+def measure_acc_l1_std(model, batches, mean, cov, vocab, n_std_samples=10, seed=None, draws=None, overlap=False):
     """testing/test_acc_mean_std.py: get_acc_l1 + get_std over ``batches`` (collated, on the model's device) -> the nine figures the
     reference prints: {'l1_pred', 'l1_rand', 'l1_pert', 'acc_pred', 'acc_rand', 'acc_pert', 'angle_std', 'position_std', 'size_std'}.
 
@@ -268,7 +455,10 @@ def measure_acc_l1_std(model, batches, mean, cov, vocab, n_std_samples=10, seed=
     ``n_std_samples`` decodes in one engine call and one spread launch; the figures accumulate on the device and are read back once.
     ``seed``: z and the baseline draws come from a device generator seeded with it (default: the engine's stream / torch's).
     ``draws``: per batch a dict {'z': [O, E], 'uniforms': [O, 3], 'normals': [O, 3], 'z_std': [n_std_samples, O, E]} replaces
-    every draw (the reference's np.random draws can be replayed)."""
+    every draw (the reference's np.random draws can be replayed).
+    ``overlap``: the dict gains 'overlap_pred' / 'overlap_rand' / 'overlap_pert' - the mean intersecting volume of a layout's
+    furniture (``layout_overlap`` of the three layouts: the decoded angle bins, the ground-truth bins for the two baselines), one
+    more launch per batch; it needs the batches' angles (the 8- or 5-tuple carries them)."""
     dev = next(model.parameters()).device
     room = room_class(vocab)
     table = relation_table(vocab)
@@ -279,6 +469,9 @@ def measure_acc_l1_std(model, batches, mean, cov, vocab, n_std_samples=10, seed=
     good = torch.zeros(3, dtype=torch.int64, device=dev)
     l1 = torch.zeros(3, dtype=torch.float64, device=dev)
     spread = torch.zeros(3, dtype=torch.float64, device=dev)
+    ov_vol = torch.zeros(3, dtype=torch.float64, device=dev) if overlap else None
+    ov_pairs = torch.zeros(3, dtype=torch.int64, device=dev) if overlap else None
+    names = list(vocab["object_idx_to_name"])
     n_batches, n_triples = 0, 0
     draws = list(draws) if draws is not None else None
     for bi, batch in enumerate(batches):
@@ -294,7 +487,7 @@ def measure_acc_l1_std(model, batches, mean, cov, vocab, n_std_samples=10, seed=
             z = _draw_z(model, objs, triples, attributes, 1, mean, cov, gen)
         else:
             z = None
-        bp, _, _ = _S.sample_layouts(model, objs, triples, attributes, n_samples=1, mean=mean, cov=cov, z=z)
+        bp, ap, _ = _S.sample_layouts(model, objs, triples, attributes, n_samples=1, mean=mean, cov=cov, z=z)
         lay = torch.empty(3, O, 6, dtype=torch.float32, device=dev)
         lay[0].copy_(bp[0])
         if d is not None:
@@ -304,6 +497,10 @@ def measure_acc_l1_std(model, batches, mean, cov, vocab, n_std_samples=10, seed=
             baselines(boxes, objs, room, key=key, out=lay[1:])
         relation_acc(lay, objs, triples, room, table, good=good)
         layout_l1(lay, boxes, out=l1)
+        if overlap:
+            gt_ang = (batch[4] if len(batch) == 8 else batch[3]).to(dev, torch.float32)
+            ang = torch.stack([ap[0].to(torch.float32), gt_ang, gt_ang])
+            layout_overlap(lay, ang, room_rows(objs, room), visible_rows(objs, names), vol=ov_vol, pairs=ov_pairs)
         # --- get_std (:39-69) ---
         if d is not None:
             z = d["z_std"].to(dev, torch.float32).reshape(n_std_samples * O, -1)
@@ -321,5 +518,9 @@ def measure_acc_l1_std(model, batches, mean, cov, vocab, n_std_samples=10, seed=
     acc = [float(x) / n_triples if n_triples else float("nan") for x in g.tolist()]
     l = (l / n_batches).tolist()
     s = (s / n_batches).tolist()
-    return {"l1_pred": l[0], "l1_rand": l[1], "l1_pert": l[2], "acc_pred": acc[0], "acc_rand": acc[1], "acc_pert": acc[2],
-            "angle_std": s[0], "position_std": s[1], "size_std": s[2]}
+    res = {"l1_pred": l[0], "l1_rand": l[1], "l1_pert": l[2], "acc_pred": acc[0], "acc_rand": acc[1], "acc_pert": acc[2],
+           "angle_std": s[0], "position_std": s[1], "size_std": s[2]}
+    if overlap:
+        v = (ov_vol.cpu() / n_batches).tolist()
+        res.update(overlap_pred=v[0], overlap_rand=v[1], overlap_pert=v[2])
+    return res

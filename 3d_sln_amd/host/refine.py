@@ -711,9 +711,16 @@ class RefineBatch:
     ``class_names``.  Every room starts from ``model``'s parameters (the checkpoint), encoded with ``model`` in eval mode.
     A room's numbers do not depend on the other rooms of the batch: the kernels are the single-room ones over a (room) grid axis.
     After ``run(iters)``: ``losses`` [iters, R], ``boxes`` / ``idx`` (row-concatenated, ``row0`` / ``rows`` per room), ``params``
-    [R, n_flat] the fine-tuned copies, ``z`` the refined latents."""
+    [R, n_flat] the fine-tuned copies, ``z`` the refined latents.
 
-    def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60):
+    ``report``: None (default: nothing below exists, the launches are those above), "ends" (iterations 0 and the last: what the
+    reference dumps, test_render_refine.py:369), "all", or an iterable of iteration numbers.  A reported iteration issues two more
+    calls - sln_layout_cuboid_iou over all rooms' rows after the head (boxes / idx of the iterate against the ground truth, :360-368)
+    and sln_refine_report after the loss forward - and fills ``report[k]`` [R, 3] = (mean IoU of the room's visible rows,
+    depth_l1 at full resolution, cross-entropy of the last scale; :371-372); rows of unreported iterations stay NaN.  Nothing is
+    read back and nothing allocated inside an iteration."""
+
+    def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None):
         L = _lib.lib()
         self.model, self.R, self.iters, self.lr = model, len(rooms), int(iters), float(learning_rate)
         R = self.R
@@ -760,6 +767,27 @@ class RefineBatch:
             box_last[r] = rm["boxes"][-1].detach().float(); angle_last[r] = rm["angles"][-1].detach().float()
         self.z, self.scenes = z, scenes
         tick("encoder, z, scenes, targets")
+        self._report_all = report == "all"
+        if report is None:
+            self._report_at = None
+        else:
+            last = max(self.iters - 1, 0)
+            at = range(self.iters) if report == "all" else ((0, last) if report == "ends" else [int(k) for k in report])
+            if isinstance(report, str) and report not in ("all", "ends"):
+                raise ValueError("report is None, 'ends', 'all' or an iterable of iteration numbers")
+            self._report_at = frozenset(at)
+            if any(k < 0 or k >= max(self.iters, 1) for k in self._report_at):
+                raise ValueError("report names an iteration outside [0, %d)" % self.iters)
+            # the ground truth of the IoU (all rooms' rows), the full-resolution depth-hot planes of the targets (not null-filled, :332)
+            self._gt_boxes = torch.cat([rm["boxes"].detach().float() for rm in rooms]).to(dev).contiguous()
+            self._gt_angles = torch.cat([rm["angles"].detach().float() for rm in rooms]).to(dev).contiguous()
+            self._visible = torch.tensor([nm not in DO_NOT_VIS for rm in rooms for nm in rm["class_names"]], dtype=torch.uint8, device=dev)
+            if self._visible.numel() != N:
+                raise ValueError("class_names must name every row of a room")
+            self._target_depth = torch.cat([t[:, 41:] for t in targets], 0).contiguous()
+            self._iou_mean = torch.zeros(R, dtype=torch.float64, device=dev)
+            self._report_ws = torch.empty(int(L.sln_refine_report_scratch_doubles(R)), dtype=torch.float64, device=dev)
+            self.report = torch.full((max(self.iters, 1), R, 3), float("nan"), **f32)
         self.noise_all = noise.to(dev)
         self.box_last, self.angle_last = box_last, angle_last
         # ---- the loss of all rooms: one descriptor, per-room normalisation ----
@@ -807,6 +835,8 @@ class RefineBatch:
         # ---- head / placement tables ----
         self.room_of_row = torch.cat([torch.full((n,), r, dtype=torch.int32) for r, n in enumerate(self.rows)]).to(dev)
         self.last_row = torch.tensor([a + n - 1 for a, n in zip(self.row0, self.rows)], dtype=torch.int32, device=dev)
+        if self._report_at is not None:
+            self._room_row = self.last_row[self.room_of_row.long()].contiguous()         # [N]: every row's room row
         self.boxes, self.idx = torch.empty(N, 6, **f32), torch.empty(N, **f32)
         self.g_boxes, self.g_idx = torch.empty(N, 6, **f32), torch.empty(N, **f32)
         self.F2 = 2 * max(sc.desc.F for sc in scenes)
@@ -923,8 +953,9 @@ class RefineBatch:
         _lib.check(_lib.lib().sln_vae_group_launches(self._group, C.byref(f), C.byref(b), C.byref(s1)), "sln_vae_group_launches")
         return dict(decoder_forward=f.value, decoder_backward=b.value, single_room_fallbacks=s1.value)
 
-    def _iteration(self, noise, out):
-        """one iteration of every room on the current stream; ``noise`` [N], ``out`` [R] receives the rooms' losses"""
+    def _iteration(self, noise, out, report_out=None):
+        """one iteration of every room on the current stream; ``noise`` [N], ``out`` [R] receives the rooms' losses, ``report_out``
+        [R, 3] (a reported iteration) the report"""
         L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
         N, R, na, S = self.N, self.R, self.model.Nangle, self.S
         _lib.check(L.sln_vae_group_decoder(self._group, st), "sln_vae_group_decoder")
@@ -933,6 +964,9 @@ class RefineBatch:
                                                        P(self.box_last), P(self.angle_last), 2.0, P(self.boxes), P(self.idx), st),
                        "sln_refine_head_forward_rooms")
         _lib.check(L.sln_place_forward_rooms(P(self._place_tab), R, self.F2 // 2, st), "sln_place_forward_rooms")
+        if report_out is not None:      # (the fused head lives in the placement launch: boxes / idx of this iterate exist from here on)
+            _lib.check(L.sln_layout_cuboid_iou(P(self.boxes), P(self.idx), P(self._gt_boxes), P(self._gt_angles), P(self._room_row), P(self._visible),
+                                               P(self.room_of_row), R, 1, N, None, P(self._iou_mean), st), "sln_layout_cuboid_iou")
         rl = self.loss
         if rl.desc.live_planes:
             _lib.check(L.sln_scene_forward_live(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 0.1, 0.001, 100.0,
@@ -943,6 +977,9 @@ class RefineBatch:
         _lib.check(L.sln_refine_loss_forward(rl.desc, P(self.image), P(rl.target_depth), P(rl.labels), P(rl.inv_count), P(rl.ws), P(self.loss_out), st),
                    "sln_refine_loss_forward")
         torch.add(self.loss_out[:, 0], self.size_loss, alpha=2.0, out=out)
+        if report_out is not None:      # reads the image and the loss forward's partial sums, consumes (and re-arms) the IoU means
+            _lib.check(L.sln_refine_report(rl.desc, P(self.image), P(self._target_depth), P(rl.ws), P(self._report_ws), P(self._iou_mean), P(report_out),
+                                           st), "sln_refine_report")
         _lib.check(L.sln_refine_loss_backward(rl.desc, P(rl.ws), P(self.one), P(self.g_image), st), "sln_refine_loss_backward")
         _lib.check(L.sln_scene_backward(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 1e-3, P(self.scene_ws),
                                         P(self.g_image), P(self.g_faces), st), "sln_scene_backward")
@@ -963,11 +1000,15 @@ class RefineBatch:
         n = (self.iters - self.k) if iters is None else int(iters)
         if self.k + n > self.iters:
             raise ValueError("RefineBatch was built for %d iterations (the noise of every iteration is drawn at construction)" % self.iters)
+        if capture and self._report_at is not None and not self._report_all:
+            raise ValueError("run(capture=True) replays one graph for every iteration: report must be 'all' or None")
         scratch = self.loss_out.new_empty(self.R)
+        rep_scratch = self.loss_out.new_empty(self.R, 3) if capture and self._report_all and self._graph is None else None
         if n > 0 and self.k == 0:
             self._first_iterate_sizes()
         for _ in range(n):
             k = self.k
+            rep = self.report[k] if self._report_at is not None and k in self._report_at else None
             if capture:
                 if not self._fused_head:
                     self.noise.copy_(self.noise_all[k])
@@ -975,17 +1016,19 @@ class RefineBatch:
                     side = torch.cuda.Stream()
                     side.wait_stream(torch.cuda.current_stream())
                     with torch.cuda.stream(side):                  # warm-up outside the capture (lazy kernel attributes)
-                        self._iteration(self.noise, self.losses[k])
+                        self._iteration(self.noise, self.losses[k], rep)
                     torch.cuda.current_stream().wait_stream(side)
                     self._graph = torch.cuda.CUDAGraph()
-                    self._graph_out = scratch
+                    self._graph_out, self._graph_report = scratch, rep_scratch
                     with torch.cuda.graph(self._graph):
-                        self._iteration(self.noise, self._graph_out)
+                        self._iteration(self.noise, self._graph_out, self._graph_report)
                 else:
                     self._graph.replay()
                     self.losses[k].copy_(self._graph_out)
+                    if rep is not None:
+                        rep.copy_(self._graph_report)
             else:
-                self._iteration(self.noise_all[k], self.losses[k])
+                self._iteration(self.noise_all[k], self.losses[k], rep)
             self.k += 1
         return self.losses[:self.k]
 
@@ -1010,16 +1053,18 @@ class RefineBatch:
             pass
 
 
-def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False):
+def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
-    noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room])."""
-    rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters)
+    noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
+    ``report`` is given, the report [iters, R, 3] as a third element."""
+    rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report)
     try:
         losses = rb.run(capture=capture).clone()
         res = [(b.clone(), i.clone()) for b, i in rb.results()]
+        rep = rb.report.clone() if report is not None else None
     finally:
         rb.close()
-    return losses, res
+    return (losses, res) if report is None else (losses, res, rep)
 
 
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,

@@ -667,6 +667,42 @@ int sln_layout_l1(const float* boxes, int S, int O, int box_dim, const float* gt
 int sln_layout_baselines(const float* gt, const int64_t* objs, int O, int box_dim, int room_cls, const float* uniforms,
                          const float* normals, const int64_t* key, float* out, void* stream);
 
+/* Rotated-cuboid IoU of S layouts against the ground truth - the figure of the reference's refinement table (get_boxes
+ * testing/test_render_refine.py:78-116, get_eight_coors_bbox_new / get_iou_cuboid testing/test_utils.py:7-40, the print_iou block
+ * :360-368).  boxes [S, O, 6] and angles [S, O] (float angle bins, fractional allowed), gt_boxes [O, 6], gt_angles [O].  Row i is
+ * scaled by the [3:6] of ITS layout's room row room_of_row[i] (int32 [O]: the row index of the last row of the row's room, >= i; the
+ * rows of a room are consecutive, as suncg_collate_fn lays them out), centred, rotated about y by -angle * (2 pi / 24) and moved back
+ * (:90-110); iou = inter2d * max(0, min(h1) - max(h0)) / (vol_a + vol_b - inter + 1e-5) with the unsigned areas of shapely (the
+ * winding of a ring does not matter, zero-width boxes have area 0) and the SIGNED height of the reference.  NaN input gives NaN.
+ * iou_out [S, O] (float, or NULL) receives every row's IoU (NaN for a row whose room_of_row entry is not a row at or behind it).
+ * mean_out (float64, or NULL; one of the two is needed) is PER ROOM: [S, n_rooms], mean_out[s][room_id[room row]] += the mean over the
+ * room's rows with visible[row] != 0 (uint8 [O]), NaN for a room without a visible row (np.mean([])); room_id is int32 [O] with
+ * values in [0, n_rooms), distinct per room (one room: all zeros, n_rooms 1).  Fixed summation order: bit-identical run to run.
+ * One lane per (layout, row); S <= 65535 per call. */
+int sln_layout_cuboid_iou(const float* boxes, const float* angles, const float* gt_boxes, const float* gt_angles,
+                          const int32_t* room_of_row, const unsigned char* visible, const int32_t* room_id, int n_rooms, int S, int O,
+                          float* iou_out, double* mean_out, void* stream);
+/* How much of a layout's furniture interpenetrates: over the unordered pairs (i < j) of visible rows of the same room (cuboids as
+ * above), vol_out[s] (float64) += the sum of the intersection volumes and pairs_out[s] (int64) += the number of pairs whose IoU
+ * exceeds thresh.  One workgroup per layout (several layouts per workgroup when O <= 128), the cuboids staged once in LDS in tiles
+ * of whole rooms; a room of more than 1024 rows (or a room_of_row table that is not as described above) gives vol_out = NaN. */
+int sln_layout_overlap(const float* boxes, const float* angles, const int32_t* room_of_row, const unsigned char* visible, int S, int O,
+                       float thresh, double* vol_out, int64_t* pairs_out, void* stream);
+/* The refinement report of testing/test_render_refine.py:369-374 (what the reference pickles into bbox_rot_0.pkl) for the rooms of a
+ * per_room descriptor (or the single image of a B = 1 one), after sln_refine_loss_forward on `image` with the same descriptor and
+ * workspace and before the next one: report_out [B, 3] (float) = (iou, depth_l1, ce_last).
+ *   depth_l1 = L1Loss(iter[:, 41:], target[:, 41:]) at full resolution: the iterate after the null fill of its last depth channel
+ *              (:332), target_depth [B, n_dep, S, S] the target's depth-hot planes as rendered (not filled).  Planes of `image` that
+ *              live_planes flags dead are not read (zeros, respectively the constant 1).
+ *   ce_last  = the cross-entropy of the last pooling scale without the / 800, from the partial sums the loss forward left in the
+ *              workspace (needs pooled_size^2 % 128 == 0: SLN_E_UNSUPPORTED otherwise).
+ *   iou      = iou_mean[b] (float64 [B], e.g. the mean_out of sln_layout_cuboid_iou), which is then RESET to 0 for the next
+ *              accumulation; NaN when iou_mean is NULL.
+ * scratch: sln_refine_report_scratch_doubles(B) float64.  Fixed summation order. */
+int sln_refine_report(const SlnRefineLoss* L, const float* image, const float* target_depth, const void* workspace, double* scratch,
+                      double* iou_mean, float* report_out, void* stream);
+int sln_refine_report_scratch_doubles(int B);
+
 #ifdef __cplusplus
 }
 #endif
