@@ -9,9 +9,11 @@
 //     result then has lanes = 32 consecutive pixels, i.e. coalesced NCHW stores and epilogue loads;
 //   * a workgroup owns a (16 x 16)- or (8 x 16)-pixel patch x 128 (or 64) channels; per chunk of 4 or 8 input channels the
 //     reflect-padded halo is staged once in LDS and reused for all 9 taps (9x fewer global loads than im2col) together with
-//     the [9][chunk][channels] weight slab.  Two kernels share the K loop and the epilogue: conv_glds_kernel DMAs the next
-//     chunk straight into a second LDS buffer (global_load_lds) while the MFMAs of the current one run; conv_mfma_kernel
-//     (64-row blocks on small grids, 1x1 convs, tiny images, Cin % 8 != 0) prefetches it into registers;
+//     the [9][chunk][channels] weight slab.  Three kernels differ in how the operands reach LDS and share everything else
+//     (ConvTile: the workgroup's and the lane's place; conv_k_ladder: the pipelined K steps; conv_epilogue): conv_glds_kernel
+//     DMAs the next chunk straight into a second LDS buffer (global_load_lds) while the MFMAs of the current one run;
+//     conv_mfma_kernel (64-row blocks on small grids, 1x1 convs, tiny images, Cin % 8 != 0) prefetches it into registers;
+//     conv_f16_kernel (opt-in half modes) does the same with fp16 hi / lo operands on v_mfma_f32_32x32x16_f16;
 //   * epilogues: bias + {none, ReLU, LeakyReLU(s)}; or the SPADE modulation - the gamma and beta channels
 //     of one feature land in the same lane/register of two accumulators (weights are packed [32 gamma | 32
 //     beta] per 64 rows), so out = (x - mu_b) * inv_b * (1 + gamma) + beta [-> LeakyReLU(0.2)] is computed in
@@ -31,7 +33,6 @@ namespace {
 
 constexpr int CK = 8;                  // input channels per LDS chunk
 constexpr int TH = 8, TW = 16;         // pixel patch per workgroup (128 pixels)
-constexpr int HALO = (TH + 2) * (TW + 2);
 
 enum { CEPI_BIAS_ACT = 0, CEPI_MODULATE = 1 };
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_LEAKY = 2 };
@@ -233,6 +234,119 @@ __device__ __forceinline__ void conv_flush(f32x16 (&acc)[TM][TN], f32x16 (&tot)[
         acc[i][j][r] = last ? t : 0.f;
       }
 }
+template <int TM, int TN>
+__device__ __forceinline__ void conv_zero(f32x16 (&v)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) v[i][j][r] = 0.f;
+}
+
+// Where a workgroup stands, the same in every conv kernel: blockIdx.x = (tile x, tile y, sample) over THT x 16-pixel patches,
+// blockIdx.y = block of BMC packed rows; 4 waves, WM x WN over (rows, pixels), each 64 rows = TM = 2 tiles x TN pixel tiles of 32.
+template <int BMC, int THT>
+struct ConvTile {
+  static constexpr int WM = BMC / 64, WN = 4 / WM, TN = THT * TW / WN / 32, TM = 2;
+  static constexpr int halo(int KS) { return KS == 3 ? (THT + 2) * (TW + 2) : THT * TW; }     // floats per channel in the LDS patch
+  int b, r0, x0, y0;       // sample, first packed row, first pixel of the patch
+  size_t plane;
+  const float* xb;         // the sample's input
+  __device__ __forceinline__ ConvTile(const ConvArgs& a) {
+    const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + THT - 1) / THT;
+    int bid = blockIdx.x;
+    const int tx = bid % tiles_x; bid /= tiles_x;
+    const int ty = bid % tiles_y; bid /= tiles_y;
+    b = bid;
+    r0 = blockIdx.y * BMC;
+    x0 = tx * TW; y0 = ty * THT;
+    plane = (size_t)a.H * a.W;
+    xb = a.x + (size_t)b * a.Cin * plane;
+  }
+  // offset inside a channel plane of patch position p: reflect-padded halo (KS 3) or the patch itself, clamped into the image
+  // (positions past the image edge load a valid address; what they produce is never stored)
+  __device__ __forceinline__ size_t source(const ConvArgs& a, int p, int KS) const {
+    int gy, gx;
+    if (KS == 3) { gy = reflect_idx(y0 + p / (TW + 2) - 1, a.H); gx = reflect_idx(x0 + p % (TW + 2) - 1, a.W); }
+    else { gy = y0 + p / TW; gx = x0 + p % TW; }
+    gy = min(max(gy, 0), a.H - 1); gx = min(max(gx, 0), a.W - 1);
+    return (size_t)gy * a.W + gx;
+  }
+  // input-channel split (a.part): workgroup z of gridDim.z takes the chunks [c0, cend) of its share, a multiple of `quantum`
+  // chunks (the accumulation block of the fp32 kernels) per share
+  __device__ __forceinline__ void range(const ConvArgs& a, int nchunks, int quantum, int& c0, int& cend) const {
+    c0 = 0; cend = nchunks;
+    if (a.part != nullptr) {
+      const int per = ((nchunks + (int)gridDim.z - 1) / (int)gridDim.z + quantum - 1) / quantum * quantum;
+      c0 = min((int)blockIdx.z * per, nchunks); cend = min(nchunks, c0 + per);
+    }
+  }
+};
+
+// Where a wave and a lane stand inside the workgroup's tile (built after the kernel's operand movement, in front of the K loop:
+// built earlier, the staged kernels' register counts move).  `wave` is the caller's: conv_glds_kernel keeps it scalar (readfirstlane).
+template <int BMC, int THT>
+struct ConvLane {
+  int wr, wp0, li, lk;     // wave: first row inside the block, first pixel inside the patch; lane: MFMA column, K half
+  __device__ __forceinline__ ConvLane(int wave) {
+    constexpr int WN = ConvTile<BMC, THT>::WN;
+    const int lane = threadIdx.x & 63;
+    wr = (wave / WN) * 64; wp0 = (wave % WN) * (THT * TW / WN);
+    li = lane & 31; lk = lane >> 5;
+  }
+  // LDS patch position of this lane's pixel of pixel tile j: m = wp0 + 32 j + li -> (py, px)
+  __device__ __forceinline__ int pbase(int j, int KS) const {
+    const int m = wp0 + 32 * j + li;
+    return KS == 3 ? (m / TW) * (TW + 2) + (m % TW) : m;
+  }
+};
+
+// NS steps of a chunk, software-pipelined: the operands of step s + 1 are read from LDS before the MFMAs of step s issue (hipcc
+// on its own sinks each step's ds_reads to right in front of its first MFMA: the scheduler is fenced).  All steps unrolled:
+// rolled per tap, the 25 scalar / address instructions at the loop end outlast the tap's last MFMA and the K loop alone drops
+// from 154 to 139 TFLOP/s (tools/lab/mfma_peak modes 6 / 4); the two-way bank conflict of the two-row pixel tile costs nothing
+// once unrolled (modes 6 / 7), a conflict-free 48-float row stride measured 0.7 % slower (larger LDS image).
+template <int NS, class Ops, class LD, class MMA>
+__device__ __forceinline__ void conv_k_ladder(const LD& ld, const MMA& mma) {
+  Ops o0, o1;
+  ld(0, o0);
+#pragma unroll
+  for (int s = 0; s < NS; s += 2) {
+    if (s + 1 < NS) ld(s + 1, o1);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(o0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (s + 2 < NS) ld(s + 2, o0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (s + 1 < NS) mma(o1);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// One chunk of CKC input channels of an fp32 kernel from its LDS image (wl [TAPS][CKC][BMC], xl [CKC][halo]): TAPS * CKC / 2
+// (tap, channel pair) steps of TM x TN v_mfma_f32_32x32x2_f32.
+template <int KS, int CKC, int BMC, int THT, int TN>
+__device__ __forceinline__ void conv_f32_chunk(const ConvLane<BMC, THT>& l, const float* wl, const float* xl, const int (&pbase)[TN],
+                                               f32x16 (&acc)[2][TN]) {
+  constexpr int TM = 2, HS = ConvTile<BMC, THT>::halo(KS), SPT = CKC / 2, NS = KS * KS * SPT;      // channel-pair steps per tap, steps per chunk
+  struct Ops { float a[TM], b[TN]; };
+  auto ld = [&](int st, Ops& o) {
+    const int tap = st / SPT, kk = (st % SPT) * 2;
+    const int toff = KS == 3 ? (tap / 3) * (TW + 2) + (tap % 3) : 0;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) o.a[i] = wl[(tap * CKC + kk + l.lk) * BMC + l.wr + 32 * i + l.li];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) o.b[j] = xl[(kk + l.lk) * HS + pbase[j] + toff];
+  };
+  auto mma = [&](const Ops& o) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.a[i], o.b[j], acc[i][j], 0, 0, 0);
+  };
+  conv_k_ladder<NS, Ops>(ld, mma);
+}
 
 // BMC: channels (rows) per block (64 or 128); KS: 1 or 3.  4 waves: WM x WN over (rows, pixels).
 //
@@ -246,12 +360,8 @@ __device__ __forceinline__ void conv_flush(f32x16 (&acc)[TM][TN], f32x16 (&tot)[
 // Cin >= 512 (tools/spade_error_budget.py section 4: 15 % of the MACs).
 template <int BMC, int KS, int EPI, int BLK = 0>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
-  constexpr int TAPS = KS * KS;
-  constexpr int WM = BMC / 64;                 // waves along rows (each wave: 64 rows = 2 tiles)
-  constexpr int WN = 4 / WM;                   // waves along pixels
-  constexpr int TN = 128 / WN / 32;            // pixel tiles per wave (128 pixels per block)
-  constexpr int TM = 2;
-  constexpr int HS = KS == 3 ? HALO : TH * TW; // floats per channel in the LDS patch
+  using Tile = ConvTile<BMC, TH>;
+  constexpr int TAPS = KS * KS, TM = Tile::TM, TN = Tile::TN, HS = Tile::halo(KS);
   constexpr int WSLAB = TAPS * CK * BMC;
   constexpr int NW4 = (WSLAB / 4 + 255) / 256; // float4 weight loads per thread per chunk (tail slots clamped)
   constexpr int NH = (CK * HS + 255) / 256;    // scalar patch loads per thread per chunk
@@ -259,28 +369,18 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
   float* wl = lds;                             // [TAPS][CK][BMC]
   float* xl = lds + WSLAB;                     // [CK][HS]
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;
-  int bid = blockIdx.x;
-  const int tx = bid % tiles_x; bid /= tiles_x;
-  const int ty = bid % tiles_y; bid /= tiles_y;
-  const int b = bid;
-  const int r0 = blockIdx.y * BMC;             // first packed row of this block
-  const int x0 = tx * TW, y0 = ty * TH;
-  const size_t plane = (size_t)a.H * a.W;
-  const float* xb = a.x + (size_t)b * a.Cin * plane;
+  const int tid = threadIdx.x;
+  const Tile t(a);
+  const size_t plane = t.plane;
+  const float* xb = t.xb;
+  const int r0 = t.r0;
 
   // per-thread patch positions (constant over chunks): element e -> (channel-in-chunk, pos) -> global offset
   int h_off[NH], h_lds[NH];
 #pragma unroll
   for (int j = 0; j < NH; ++j) {
     const int e = tid + 256 * j;
-    const int c = e / HS, p = e % HS;
-    int gy, gx;
-    if (KS == 3) { gy = reflect_idx(y0 + p / (TW + 2) - 1, a.H); gx = reflect_idx(x0 + p % (TW + 2) - 1, a.W); }
-    else { gy = min(y0 + p / TW, a.H - 1); gx = min(x0 + p % TW, a.W - 1); }
-    gy = min(max(gy, 0), a.H - 1); gx = min(max(gx, 0), a.W - 1);
-    h_off[j] = e < CK * HS ? (int)(c * plane + (size_t)gy * a.W + gx) : 0;     // tail slots load a valid address, never stored
+    h_off[j] = e < CK * HS ? (int)(e / HS * plane + t.source(a, e % HS, KS)) : 0;     // tail slots load a valid address, never stored
     h_lds[j] = e;
   }
   float hreg[NH];
@@ -322,44 +422,29 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
     }
   };
 
-  const int wr = (wave / WN) * 64;                 // wave's first row inside the block
-  const int wp0 = (wave % WN) * (128 / WN);        // wave's first pixel inside the patch
-  const int li = lane & 31, lk = lane >> 5;
+  const ConvLane<BMC, TH> l(tid >> 6);
   f32x16 acc[TM][TN], tot[BLK ? TM : 1][BLK ? TN : 1];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; if (BLK) tot[i][j][r] = 0.f; }
-  // pixel of this lane for pixel-tile j: m = wp0 + 32 j + li -> (py, px)
+  conv_zero(acc); conv_zero(tot);
   int pbase[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int m = wp0 + 32 * j + li;
-    pbase[j] = KS == 3 ? (m / TW) * (TW + 2) + (m % TW) : m;
-  }
+  for (int j = 0; j < TN; ++j) pbase[j] = l.pbase(j, KS);
 
   gload(0);
   lstore(0);
   __syncthreads();
   for (int ch = 0; ch < nchunks; ++ch) {
     if (ch + 1 < nchunks) gload(ch + 1);
-    // 36 (tap, channel pair) steps of 4 MFMAs; the operands of step s + 1 are read from LDS before the MFMAs of step s issue
-    // (hipcc on its own sinks each step's ds_reads to right in front of its first MFMA: the scheduler is fenced)
-    // 36 (tap, channel pair) steps of 4 MFMAs; the operands of step s + 1 are read from LDS before the MFMAs of step s issue
-    // (hipcc on its own sinks each step's ds_reads to right in front of its first MFMA: the scheduler is fenced).  All 36 steps
-    // unrolled: rolled per tap, the 25 scalar / address instructions at the loop end outlast the tap's last MFMA and the K loop
-    // alone drops from 154 to 139 TFLOP/s (tools/lab/mfma_peak modes 6 / 4); the two-way bank conflict of the two-row pixel tile
-    // costs nothing once unrolled (modes 6 / 7), a conflict-free 48-float row stride measured 0.7 % slower (larger LDS image).
-    constexpr int NS = TAPS * (CK / 2);
+    // conv_f32_chunk, written out: through the shared ladder the 128-row forms of this kernel allocate 184 / 308 registers
+    // instead of 204 / 325 and the modulating 64-row form 128 instead of 132 (a fourth wave per SIMD); the refactor that
+    // introduced the ladder was not to move occupancy, so this loop stays as it was
+    constexpr int SPT = CK / 2, NS = TAPS * SPT;
     auto ld = [&](int st, float (&av)[TM], float (&bv)[TN]) {
-      const int tap = st / (CK / 2), kk = (st % (CK / 2)) * 2;
+      const int tap = st / SPT, kk = (st % SPT) * 2;
       const int toff = KS == 3 ? (tap / 3) * (TW + 2) + (tap % 3) : 0;
 #pragma unroll
-      for (int i = 0; i < TM; ++i) av[i] = wl[(tap * CK + kk + lk) * BMC + wr + 32 * i + li];
+      for (int i = 0; i < TM; ++i) av[i] = wl[(tap * CK + kk + l.lk) * BMC + l.wr + 32 * i + l.li];
 #pragma unroll
-      for (int j = 0; j < TN; ++j) bv[j] = xl[(kk + lk) * HS + pbase[j] + toff];
+      for (int j = 0; j < TN; ++j) bv[j] = xl[(kk + l.lk) * HS + pbase[j] + toff];
     };
     auto mma = [&](const float (&av)[TM], const float (&bv)[TN]) {
 #pragma unroll
@@ -385,7 +470,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
     if (ch + 1 < nchunks) { lstore(ch + 1); __syncthreads(); }
   }
 
-  conv_epilogue<BMC, EPI>(a, acc, lds, b, r0, x0, y0);
+  conv_epilogue<BMC, EPI>(a, acc, lds, t.b, t.r0, t.x0, t.y0);
 }
 
 // The same convolution with its operands DMA'd straight into LDS (global_load_lds; Cin % GK == 0): no staging registers and no
@@ -397,39 +482,26 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
 // channels at 256 x 256, 9.8 ms): 8.84 ms without its per-chunk load / ds_write / second barrier; this kernel: 9.06 ms.
 template <int BMC, int KS, int EPI, int THT, int GK, int BLK = 0>      // GK input channels per LDS buffer (4 or 8); BLK: see conv_mfma_kernel
 __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs a) {
-  constexpr int TAPS = KS * KS;
-  constexpr int WM = BMC / 64, WN = 4 / WM, TN = THT * TW / WN / 32, TM = 2;   // THT x 16 pixels per workgroup (THT = 8 or 16)
-  constexpr int HS = KS == 3 ? (THT + 2) * (TW + 2) : THT * TW;
+  using Tile = ConvTile<BMC, THT>;                  // THT x 16 pixels per workgroup (THT = 8 or 16)
+  constexpr int TAPS = KS * KS, TM = Tile::TM, TN = Tile::TN, HS = Tile::halo(KS);
   constexpr int WSLAB = TAPS * GK * BMC;            // floats; WSLAB / 4 float4 is a multiple of 64: whole waves per round
   constexpr int NWR = (WSLAB / 4 + 255) / 256;      // rounds of 256 x 16 B
   constexpr int NHR = (GK * HS + 255) / 256;        // rounds of 256 x 4 B (the last one runs past the patch into padding)
   constexpr int BUF = WSLAB + NHR * 256;
   static_assert((WSLAB / 4) % 64 == 0, "weight slab is a whole number of wave-wide 16-byte loads");
+  static_assert(TAPS * GK / 2 % 2 == 0, "steps are issued in pairs");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   typedef __attribute__((address_space(3))) void* lds_ptr;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + THT - 1) / THT;
-  int bid = blockIdx.x;
-  const int tx = bid % tiles_x; bid /= tiles_x;
-  const int ty = bid % tiles_y; bid /= tiles_y;
-  const int b = bid;
-  const int r0 = blockIdx.y * BMC;
-  const int x0 = tx * TW, y0 = ty * THT;
-  const size_t plane = (size_t)a.H * a.W;
-  const float* xb = a.x + (size_t)b * a.Cin * plane;
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const Tile t(a);
 
   // per-lane source offsets inside a chunk (constant over chunks)
   unsigned h_off[NHR], w_off[NWR];
 #pragma unroll
   for (int j = 0; j < NHR; ++j) {
     const int e = tid + 256 * j;
-    const int c = e / HS, p = e % HS;
-    int gy, gx;
-    if (KS == 3) { gy = reflect_idx(y0 + p / (TW + 2) - 1, a.H); gx = reflect_idx(x0 + p % (TW + 2) - 1, a.W); }
-    else { gy = y0 + p / TW; gx = x0 + p % TW; }
-    gy = min(max(gy, 0), a.H - 1); gx = min(max(gx, 0), a.W - 1);
-    h_off[j] = e < GK * HS ? (unsigned)(c * plane + (size_t)gy * a.W + gx) : 0u;     // padding lanes fetch a valid word
+    h_off[j] = e < GK * HS ? (unsigned)(e / HS * t.plane + t.source(a, e % HS, KS)) : 0u;     // padding lanes fetch a valid word
   }
 #pragma unroll
   for (int j = 0; j < NWR; ++j) {
@@ -440,8 +512,8 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs a) {
   auto issue = [&](int ch, int buf) {
 #if defined(__HIP_DEVICE_COMPILE__)      // the DMA builtin exists in the device pass only (the host pass must still emit the launch stub)
     float* wb = lds + buf * BUF;
-    const float* ws = a.wp + (size_t)ch * GK * a.rows_pad + r0;
-    const float* xs = xb + (size_t)ch * GK * plane;
+    const float* ws = a.wp + (size_t)ch * GK * a.rows_pad + t.r0;
+    const float* xs = t.xb + (size_t)ch * GK * t.plane;
 #pragma unroll
     for (int j = 0; j < NWR; ++j)
       if (256 * (j + 1) <= WSLAB / 4 || 256 * j + 64 * wave < WSLAB / 4)
@@ -452,87 +524,54 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs a) {
 #endif
   };
 
-  const int wr = (wave / WN) * 64, wp0 = (wave % WN) * (THT * TW / WN);
-  const int li = lane & 31, lk = lane >> 5;
+  const ConvLane<BMC, THT> l(wave);
   f32x16 acc[TM][TN], tot[BLK ? TM : 1][BLK ? TN : 1];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; if (BLK) tot[i][j][r] = 0.f; }
+  conv_zero(acc); conv_zero(tot);
   int pbase[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int m = wp0 + 32 * j + li;
-    pbase[j] = KS == 3 ? (m / TW) * (TW + 2) + (m % TW) : m;
-  }
+  for (int j = 0; j < TN; ++j) pbase[j] = l.pbase(j, KS);
 
-  // input-channel split (a.part): workgroup z of gridDim.z takes the chunks [c0, nchunks) of its share, a whole number of
-  // accumulation blocks each
-  int c0 = 0, nchunks = a.Cin / GK;
-  if (a.part != nullptr) {
-    constexpr int Q = BLK > 0 ? BLK : 1;
-    const int per = ((nchunks + (int)gridDim.z - 1) / (int)gridDim.z + Q - 1) / Q * Q;
-    c0 = min((int)blockIdx.z * per, nchunks); nchunks = min(nchunks, c0 + per);
-  }
+  int c0, nchunks;                   // a share of a split is a whole number of accumulation blocks
+  t.range(a, a.Cin / GK, BLK > 0 ? BLK : 1, c0, nchunks);
   if (c0 < nchunks) issue(c0, c0 & 1);
   for (int ch = c0; ch < nchunks; ++ch) {
     __syncthreads();                 // chunk ch has landed (the barrier drains the DMA queue); nobody reads the other buffer any more
     if (ch + 1 < nchunks) issue(ch + 1, (ch + 1) & 1);
     const float* wl = lds + (ch & 1) * BUF;
-    const float* xl = wl + WSLAB;
-    auto ld = [&](int tap, int kk, float (&av)[TM], float (&bv)[TN]) {
-      const int toff = KS == 3 ? (tap / 3) * (TW + 2) + (tap % 3) : 0;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) av[i] = wl[(tap * GK + kk + lk) * BMC + wr + 32 * i + li];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bv[j] = xl[(kk + lk) * HS + pbase[j] + toff];
-    };
-    auto mma = [&](const float (&av)[TM], const float (&bv)[TN]) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-    };
-    constexpr int SPT = GK / 2, NS = TAPS * SPT;       // channel-pair steps per tap, steps per chunk (even)
-    static_assert(NS % 2 == 0, "steps are issued in pairs");
-    float av0[TM], bv0[TN], av1[TM], bv1[TN];
-    ld(0, 0, av0, bv0);
-#pragma unroll
-    for (int st = 0; st < NS; st += 2) {             // operands of the next step read before the MFMAs of this one (fenced, see above)
-      ld((st + 1) / SPT, ((st + 1) % SPT) * 2, av1, bv1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(av0, bv0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (st + 2 < NS) ld((st + 2) / SPT, ((st + 2) % SPT) * 2, av0, bv0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(av1, bv1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    conv_f32_chunk<KS, GK>(l, wl, wl + WSLAB, pbase, acc);
     if constexpr (BLK > 0) { if ((ch + 1 - c0) % BLK == 0 || ch + 1 == nchunks) conv_flush(acc, tot, ch + 1 == nchunks); }
   }
   __syncthreads();                   // the epilogue's reductions reuse the buffers
-  conv_epilogue<BMC, EPI, THT>(a, acc, lds, b, r0, x0, y0);
+  conv_epilogue<BMC, EPI, THT>(a, acc, lds, t.b, t.r0, t.x0, t.y0);
+}
+
+// The launch every conv kernel shares.  lds_bytes: what the kernel's K loop needs; bmc x (tile_h x 16 pixels): its workgroup;
+// extra: kernel arguments behind ConvArgs.  The dynamic-LDS limit is raised once per kernel instantiation and process.
+template <auto Kernel, class... Extra>
+int launch_conv_kernel(size_t lds_bytes, int bmc, int tile_h, const ConvArgs& a, hipStream_t st, int ksplit, Extra... extra) {
+  if (a.gap_acc) lds_bytes = std::max(lds_bytes, sizeof(float) * 4 * 64 * 33);      // the epilogue's row-sum transpose
+  static bool raised = false;
+  if (!raised) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
+    raised = true;
+  }
+  const int tiles = sln_cdiv(a.W, TW) * sln_cdiv(a.H, tile_h) * a.B;
+  hipLaunchKernelGGL(Kernel, dim3(tiles, a.rows_pad / bmc, ksplit), dim3(256), lds_bytes, st, a, extra...);
+  SLN_CHECK_LAUNCH();
+  return 0;
 }
 
 template <int BMC, int KS, int EPI, int THT, int GK, int BLK = 0>
 int launch_conv_dma(const ConvArgs& a, hipStream_t st, int ksplit = 1) {
-  constexpr int TAPS = KS * KS;
-  constexpr int HS = KS == 3 ? (THT + 2) * (TW + 2) : THT * TW;
-  size_t smem = sizeof(float) * 2 * (size_t)(TAPS * GK * BMC + ((GK * HS + 255) / 256) * 256);
-  if (a.gap_acc && smem < sizeof(float) * 4 * 64 * 33) smem = sizeof(float) * 4 * 64 * 33;      // the epilogue's row-sum transpose
-  static bool raised = false;
-  if (!raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_glds_kernel<BMC, KS, EPI, THT, GK, BLK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    raised = true;
-  }
-  const int tiles = sln_cdiv(a.W, TW) * sln_cdiv(a.H, THT) * a.B;
-  hipLaunchKernelGGL((conv_glds_kernel<BMC, KS, EPI, THT, GK, BLK>), dim3(tiles, a.rows_pad / BMC, ksplit), dim3(256), smem, st, a);
-  SLN_CHECK_LAUNCH();
-  return 0;
+  constexpr int HS = ConvTile<BMC, THT>::halo(KS);
+  return launch_conv_kernel<&conv_glds_kernel<BMC, KS, EPI, THT, GK, BLK>>(
+      sizeof(float) * 2 * (size_t)(KS * KS * GK * BMC + ((GK * HS + 255) / 256) * 256), BMC, THT, a, st, ksplit);
+}
+template <int BMC, int KS, int EPI, int BLK = 0>
+int launch_conv_staged(const ConvArgs& a, hipStream_t st) {
+  return launch_conv_kernel<&conv_mfma_kernel<BMC, KS, EPI, BLK>>(
+      sizeof(float) * (size_t)(KS * KS * CK * BMC + CK * ConvTile<BMC, TH>::halo(KS)), BMC, TH, a, st, 1);
 }
 
 // Second half of an input-channel split: y = act(sum_z part[z] + bias), the partial sums added in z order (a fixed order: the
@@ -656,99 +695,94 @@ static int conv_part_release(hipStream_t st, int flags) {
 // Batch-1 calls (test_SPADE_shade.py:77-79: one call per z).  The 1 024 / 512-channel layers at 8 x 8 .. 64 x 64 pixels are 8 .. 64
 // workgroups that each walk all input channels: 375-760 us per launch on 3-25 % of the CUs - 6 of the 7.7 ms of a call - and the
 // 256 / 128-channel layers behind them 64-128 workgroups.  Launches of fewer than 192 workgroups split the input channels over
-// gridDim.z workgroups (>= 8 chunks = 32 channels each, ~512 workgroups in all: the 8 x 16-pixel DMA kernel, BLK = accumulation
-// block of the blocked form or 0) and conv_split_finish_kernel adds the partial sums in order.  *done: the launch was taken.
-template <int BMC, int KS, int BLK>
-int launch_conv_split(const ConvArgs& a, hipStream_t st, bool* done) {
-  static const int split_max = getenv("SLN_CONV_KSPLIT") ? atoi(getenv("SLN_CONV_KSPLIT")) : 32;      // 1: never
+// gridDim.z workgroups (~512 workgroups in all, the 8 x 16-pixel kernels) and conv_split_finish_kernel adds the partial sums in
+// order.  One policy for the fp32 and the half kernels:
+constexpr long CONV_SPLIT_BELOW = 192;      // unsplit launches of fewer workgroups are split ...
+constexpr long CONV_SPLIT_TARGET = 512;     // ... into about this many
+constexpr int CONV_SPLIT_MAX = 32;          // shares at most; SLN_CONV_KSPLIT sets another bound (1: never)
+// shares of a launch of `blocks` workgroups over `chunks` chunks of input channels, at least `least_chunks` each, whose partial
+// images of part_bytes each fit the scratch slot; <= 1: no split
+static int conv_split_shares(long blocks, int chunks, int least_chunks, size_t part_bytes) {
+  static const int split_max = getenv("SLN_CONV_KSPLIT") ? atoi(getenv("SLN_CONV_KSPLIT")) : CONV_SPLIT_MAX;
+  if (split_max <= 1 || blocks >= CONV_SPLIT_BELOW) return 1;
+  const int S = (int)std::min<long>(std::min(split_max, chunks / least_chunks), (CONV_SPLIT_TARGET + blocks - 1) / blocks);
+  return (int)std::min<size_t>((size_t)S, CONV_PART_BYTES / part_bytes);
+}
+// where the two operand types differ
+struct ConvSplitKind {
+  int chunk_cin;          // input channels per chunk of the kernel that runs the shares
+  int least_chunks;       // per share
+  bool whole_chunks;      // Cin % chunk_cin == 0 required (the DMA kernel has no channel tail), else no split
+  bool no_idle_share;     // fewer shares of the same ceil(chunks / S) chunks, so that no workgroup is left without a chunk
+};
+constexpr ConvSplitKind CONV_SPLIT_F32{4, 8, true, false};
+// bmc: rows per workgroup; launch(args with part / part_stride set, S) runs the shares.  *done: the launch was taken.
+template <class Launch>
+int launch_conv_split(const ConvArgs& a, hipStream_t st, int bmc, const ConvSplitKind& k, bool* done, Launch launch) {
   *done = false;
-  if (split_max <= 1 || a.Cin % 4 != 0) return 0;
-  const long blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, TH) * a.B * (a.rows_pad / BMC);
-  static const int few = getenv("SLN_CONV_KSPLIT_BLOCKS") ? atoi(getenv("SLN_CONV_KSPLIT_BLOCKS")) : 192;      // lab
-  static const int target = getenv("SLN_CONV_KSPLIT_TARGET") ? atoi(getenv("SLN_CONV_KSPLIT_TARGET")) : 512;
-  if (blocks >= few) return 0;
-  const int nch = a.Cin / 4;
+  if (k.whole_chunks && a.Cin % k.chunk_cin != 0) return 0;
+  const long blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, TH) * a.B * (a.rows_pad / bmc);
+  const int chunks = sln_cdiv(a.Cin, k.chunk_cin);
   const size_t one = (size_t)a.B * a.rows * a.H * a.W;
-  int S = (int)std::min<long>(std::min(split_max, nch / 8), (target + blocks - 1) / blocks);
-  S = (int)std::min<size_t>((size_t)S, CONV_PART_BYTES / (one * sizeof(float)));
+  int S = conv_split_shares(blocks, chunks, k.least_chunks, one * sizeof(float));
   if (S <= 1) return 0;
+  if (k.no_idle_share) S = sln_cdiv(chunks, sln_cdiv(chunks, S));
   float* part = nullptr;
   *done = true;                                            // from here on the launch is the split one - or an error, never another kernel
   { const int r = conv_part_scratch(st, &part, true); if (r) return r; }
   ConvArgs p = a; p.part = part; p.part_stride = (long)one;
-  const int r = launch_conv_dma<BMC, KS, CEPI_BIAS_ACT, TH, 4, BLK>(p, st, S);
+  const int r = launch(p, S);
   return r ? r : launch_conv_split_finish(a, part, S, (long)one, st);
+}
+
+static bool conv_staged_only() {      // SLN_CONV_STAGED: A/B runs and tests, the Cin >= 512 convolutions included
+  static const bool v = getenv("SLN_CONV_STAGED") != nullptr;
+  return v;
 }
 
 // Blocked accumulation (see conv_mfma_kernel): variants with 64 accumulators per lane.  Blocks of 16 input channels (144
 // products): 2 buffers of 8 channels / 4 buffers of 4 / 2 staged chunks of 8.
 template <int BMC>
 int launch_conv_blocked(const ConvArgs& a, hipStream_t st) {
-  static const int variant = getenv("SLN_CONV_BLOCK_VARIANT") ? atoi(getenv("SLN_CONV_BLOCK_VARIANT")) : 0;   // lab: 1 = 8 x 16 x BMC rows, 2 = staged
-  static const bool staged_only = getenv("SLN_CONV_STAGED") != nullptr;      // the A/B switch of launch_conv covers the Cin >= 512 convolutions too
-  if (a.Cin % 8 == 0 && variant != 2 && !staged_only) {
-    // 64-row workgroups of 16 x 16 pixels (the halo is DMA'd once per 64 rows instead of once per 128: 1.2x the operand traffic
-    // of the 128-row workgroups; 8 x 16 x 128 rows re-reads the weights per 128 pixels: 1.8x)
-    const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / 64);
-    if (variant == 0 && a.H >= 16 && tall_blocks >= 512) return launch_conv_dma<64, 3, CEPI_BIAS_ACT, 16, 8, 2>(a, st);
-    { bool done = false; const int r = launch_conv_split<BMC, 3, 4>(a, st, &done); if (done) return r; }
-    return launch_conv_dma<BMC, 3, CEPI_BIAS_ACT, TH, 4, 4>(a, st);
-  }
-  constexpr int HS = HALO;
-  size_t smem = sizeof(float) * (size_t)(9 * CK * BMC + CK * HS);
-  if (a.gap_acc && smem < sizeof(float) * 4 * 64 * 33) smem = sizeof(float) * 4 * 64 * 33;
-  static bool raised = false;
-  if (!raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<BMC, 3, CEPI_BIAS_ACT, 2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    raised = true;
-  }
-  const int tiles = sln_cdiv(a.W, TW) * sln_cdiv(a.H, TH) * a.B;
-  hipLaunchKernelGGL((conv_mfma_kernel<BMC, 3, CEPI_BIAS_ACT, 2>), dim3(tiles, a.rows_pad / BMC), dim3(256), smem, st, a);
-  SLN_CHECK_LAUNCH();
-  return 0;
+  if (a.Cin % 8 != 0 || conv_staged_only()) return launch_conv_staged<BMC, 3, CEPI_BIAS_ACT, 2>(a, st);
+  // 64-row workgroups of 16 x 16 pixels (the halo is DMA'd once per 64 rows instead of once per 128: 1.2x the operand traffic
+  // of the 128-row workgroups; 8 x 16 x 128 rows re-reads the weights per 128 pixels: 1.8x)
+  const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / 64);
+  if (a.H >= 16 && tall_blocks >= 512) return launch_conv_dma<64, 3, CEPI_BIAS_ACT, 16, 8, 2>(a, st);
+  auto launch = [&](const ConvArgs& p, int S) { return launch_conv_dma<BMC, 3, CEPI_BIAS_ACT, TH, 4, 4>(p, st, S); };
+  bool done = false;
+  const int r = launch_conv_split(a, st, BMC, CONV_SPLIT_F32, &done, launch);
+  return done ? r : launch(a, 1);
 }
 
 template <int BMC, int KS, int EPI>
 int launch_conv(const ConvArgs& a, hipStream_t st) {
-  constexpr int TAPS = KS * KS;
-  constexpr int HS = KS == 3 ? HALO : TH * TW;
-  static const bool staged_only = getenv("SLN_CONV_STAGED") != nullptr;      // A/B runs and tests
   // measured per shape (tools/lab/conv_lab.py, same box): with 8 x 16 pixels per workgroup the DMA kernel wins 2 % on the modulation
   // convs and loses 2-6 % on the bias/activation convs (twice the barriers of the staged kernel); with 16 x 16 pixels it wins on
   // every 128-row conv (modulation 9.8 -> 9.15 ms, 1 024 -> 512 channels at 32 x 32 2.34 -> 2.26 ms)
   static const bool dma_all = getenv("SLN_CONV_DMA") != nullptr;
-  static const bool tall = getenv("SLN_CONV_NO_TALL") == nullptr;
+  const bool staged_only = conv_staged_only();
   if constexpr (KS == 3 && EPI == CEPI_BIAS_ACT) { if (a.blocked) return launch_conv_blocked<BMC>(a, st); }
   if constexpr (EPI == CEPI_BIAS_ACT) {
-    if (!staged_only) { bool done = false; const int r = launch_conv_split<BMC, KS, 0>(a, st, &done); if (done) return r; }
+    if (!staged_only) {
+      bool done = false;
+      const int r = launch_conv_split(a, st, BMC, CONV_SPLIT_F32, &done,
+                                      [&](const ConvArgs& p, int S) { return launch_conv_dma<BMC, KS, CEPI_BIAS_ACT, TH, 4>(p, st, S); });
+      if (done) return r;
+    }
   }
   if (a.Cin % 8 == 0 && !staged_only) {
-    // 16 x 16 pixels per workgroup where the image has the rows (half the weight DMA per MFMA, twice the MFMAs per barrier)
-    // (not for launches too small to give every CU two of the tall workgroups: batch-1 convs of the one-map-many-z path)
-    const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / BMC);
-    if (BMC == 128 && KS == 3 && tall && a.H >= 16 && tall_blocks >= 512)
-      return launch_conv_dma<BMC, KS, EPI, (BMC == 128 && KS == 3 ? 16 : TH), 4>(a, st);
-    // 64-row blocks: buffers of 8 channels (the same 144 MFMAs per wave and barrier; 2 % over the staged kernel at 256 x 256).
-    // 8-channel buffers for the 128-row blocks leave room for one workgroup per CU only: 10.1 ms against 9.06 ms.
-    if (BMC == 64 && KS == 3 && tall && a.H >= 16 && tall_blocks >= 512)
-      return launch_conv_dma<BMC, KS, EPI, (BMC == 64 && KS == 3 ? 16 : TH), 8>(a, st);
+    if constexpr (KS == 3) {
+      // 16 x 16 pixels per workgroup where the image has the rows (half the weight DMA per MFMA, twice the MFMAs per barrier)
+      // (not for launches too small to give every CU two of the tall workgroups: batch-1 convs of the one-map-many-z path).
+      // 64-row blocks: buffers of 8 channels (the same 144 MFMAs per wave and barrier; 2 % over the staged kernel at 256 x 256).
+      // 8-channel buffers for the 128-row blocks leave room for one workgroup per CU only: 10.1 ms against 9.06 ms.
+      const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / BMC);
+      if (a.H >= 16 && tall_blocks >= 512) return launch_conv_dma<BMC, 3, EPI, 16, BMC == 128 ? 4 : 8>(a, st);
+    }
     if (EPI == CEPI_MODULATE || dma_all) return launch_conv_dma<BMC, KS, EPI, TH, 4>(a, st);
   }
-  size_t smem = sizeof(float) * (size_t)(TAPS * CK * BMC + CK * HS);
-  if (a.gap_acc && smem < sizeof(float) * 4 * 64 * 33) smem = sizeof(float) * 4 * 64 * 33;      // the epilogue's row-sum transpose
-  static bool raised = false;
-  if (!raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<BMC, KS, EPI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    raised = true;
-  }
-  const int tiles = sln_cdiv(a.W, TW) * sln_cdiv(a.H, TH) * a.B;
-  hipLaunchKernelGGL((conv_mfma_kernel<BMC, KS, EPI>), dim3(tiles, a.rows_pad / BMC), dim3(256), smem, st, a);
-  SLN_CHECK_LAUNCH();
-  return 0;
+  return launch_conv_staged<BMC, KS, EPI>(a, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -773,9 +807,9 @@ constexpr int FK = 16;                                   // input channels per c
 template <int BMC, int EPI, int THT, int TERMS, int BLK = 0>
 __global__ __launch_bounds__(256) void conv_f16_kernel(const ConvArgs a, const uint16_t* __restrict__ whi, const uint16_t* __restrict__ wlo) {
   static_assert(TERMS == 1 || TERMS == 3, "1 or 3 products");
+  using Tile = ConvTile<BMC, THT>;
   constexpr int NT = TERMS == 3 ? 2 : 1;                 // operand parts held: hi (and lo)
-  constexpr int WM = BMC / 64, WN = 4 / WM, TN = THT * TW / WN / 32, TM = 2;
-  constexpr int HS = (THT + 2) * (TW + 2);               // halo pixels
+  constexpr int TM = Tile::TM, TN = Tile::TN, HS = Tile::halo(3);      // HS: halo pixels
   constexpr int WQ = 9 * BMC * FK / 8;                   // 16-byte weight words per part and chunk
   constexpr int NWQ = (WQ + 255) / 256;
   constexpr int NHI = (2 * HS + 255) / 256;              // halo items (pixel, 8-channel half) per thread and chunk
@@ -783,27 +817,16 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(const ConvArgs a, const u
   _Float16* wl = reinterpret_cast<_Float16*>(lds);                      // [NT][9][BMC][16]
   _Float16* xl = wl + NT * 9 * BMC * FK;                                // [NT][HS][16]
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + THT - 1) / THT;
-  int bid = blockIdx.x;
-  const int tx = bid % tiles_x; bid /= tiles_x;
-  const int ty = bid % tiles_y; bid /= tiles_y;
-  const int b = bid;
-  const int r0 = blockIdx.y * BMC;
-  const int x0 = tx * TW, y0 = ty * THT;
-  const size_t plane = (size_t)a.H * a.W;
-  const float* xb = a.x + (size_t)b * a.Cin * plane;
-  const int nch = (a.Cin + FK - 1) / FK;
+  const int tid = threadIdx.x;
+  const Tile t(a);
+  const size_t plane = t.plane;
+  const float* xb = t.xb;
+  const int r0 = t.r0;
 
   // halo item e = g * HS + p: pixel p (consecutive lanes, coalesced loads), channels 8 g .. 8 g + 7 of the chunk
   int h_off[NHI];
 #pragma unroll
-  for (int j = 0; j < NHI; ++j) {
-    const int e = min(tid + 256 * j, 2 * HS - 1), p = e % HS;
-    int gy = reflect_idx(y0 + p / (TW + 2) - 1, a.H), gx = reflect_idx(x0 + p % (TW + 2) - 1, a.W);
-    gy = min(max(gy, 0), a.H - 1); gx = min(max(gx, 0), a.W - 1);
-    h_off[j] = gy * a.W + gx;
-  }
+  for (int j = 0; j < NHI; ++j) h_off[j] = (int)t.source(a, min(tid + 256 * j, 2 * HS - 1) % HS, 3);
   float hreg[NHI][8];
   u32x4 wreg[NT][NWQ];
   auto gload = [&](int ch) {
@@ -849,126 +872,84 @@ __global__ __launch_bounds__(256) void conv_f16_kernel(const ConvArgs a, const u
       const int q = tid + 256 * j;
       if (q < WQ) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) *reinterpret_cast<u32x4*>(wl + t * 9 * BMC * FK + q * 8) = wreg[t][j];
+        for (int h = 0; h < NT; ++h) *reinterpret_cast<u32x4*>(wl + h * 9 * BMC * FK + q * 8) = wreg[h][j];
       }
     }
   };
 
-  const int wr = (wave / WN) * 64, wp0 = (wave % WN) * (THT * TW / WN);
-  const int li = lane & 31, lk = lane >> 5;
+  const ConvLane<BMC, THT> l(tid >> 6);
   f32x16 acc[TM][TN], tot[BLK ? TM : 1][BLK ? TN : 1];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; if (BLK) tot[i][j][r] = 0.f; }
+  conv_zero(acc); conv_zero(tot);
   int pbase[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int m = wp0 + 32 * j + li;
-    pbase[j] = (m / TW) * (TW + 2) + (m % TW);
-  }
+  for (int j = 0; j < TN; ++j) pbase[j] = l.pbase(j, 3);
 
-  int c0 = 0, cend = nch;
-  if (a.part != nullptr) {                               // input-channel split: a whole number of chunks per workgroup
-    const int per = (nch + (int)gridDim.z - 1) / (int)gridDim.z;
-    c0 = min((int)blockIdx.z * per, nch); cend = min(nch, c0 + per);
-  }
+  int c0, cend;                                          // a share of a split is a whole number of chunks
+  t.range(a, (a.Cin + FK - 1) / FK, 1, c0, cend);
   if (c0 < cend) { gload(c0); lstore(c0); }
   __syncthreads();
   for (int ch = c0; ch < cend; ++ch) {
     if (ch + 1 < cend) gload(ch + 1);
-    auto ld = [&](int tap, f16x8 (&av)[NT][TM], f16x8 (&bv)[NT][TN]) {
+    struct Ops { f16x8 a[NT][TM], b[NT][TN]; };
+    auto ld = [&](int tap, Ops& o) {
       const int toff = (tap / 3) * (TW + 2) + (tap % 3);
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
+      for (int h = 0; h < NT; ++h) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) av[t][i] = *reinterpret_cast<const f16x8*>(wl + ((t * 9 + tap) * BMC + wr + 32 * i + li) * FK + 8 * lk);
+        for (int i = 0; i < TM; ++i) o.a[h][i] = *reinterpret_cast<const f16x8*>(wl + ((h * 9 + tap) * BMC + l.wr + 32 * i + l.li) * FK + 8 * l.lk);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) bv[t][j] = *reinterpret_cast<const f16x8*>(xl + (t * HS + pbase[j] + toff) * FK + 8 * lk);
+        for (int j = 0; j < TN; ++j) o.b[h][j] = *reinterpret_cast<const f16x8*>(xl + (h * HS + pbase[j] + toff) * FK + 8 * l.lk);
       }
     };
-    auto mma = [&](const f16x8 (&av)[NT][TM], const f16x8 (&bv)[NT][TN]) {
+    auto mma = [&](const Ops& o) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
           if (TERMS == 3) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0][i], bv[NT - 1][j], acc[i][j], 0, 0, 0);     // w_hi x_lo
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[NT - 1][i], bv[0][j], acc[i][j], 0, 0, 0);     // w_lo x_hi
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(o.a[0][i], o.b[NT - 1][j], acc[i][j], 0, 0, 0);     // w_hi x_lo
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(o.a[NT - 1][i], o.b[0][j], acc[i][j], 0, 0, 0);     // w_lo x_hi
           }
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[0][i], bv[0][j], acc[i][j], 0, 0, 0);             // w_hi x_hi
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(o.a[0][i], o.b[0][j], acc[i][j], 0, 0, 0);             // w_hi x_hi
         }
     };
-    // the operands of tap t + 1 are read from LDS before the MFMAs of tap t issue (fenced, as in the fp32 kernels)
-    f16x8 av0[NT][TM], bv0[NT][TN], av1[NT][TM], bv1[NT][TN];
-    ld(0, av0, bv0);
-#pragma unroll
-    for (int tap = 0; tap < 9; tap += 2) {
-      if (tap + 1 < 9) ld(tap + 1, av1, bv1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(av0, bv0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (tap + 2 < 9) ld(tap + 2, av0, bv0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (tap + 1 < 9) mma(av1, bv1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    conv_k_ladder<9, Ops>(ld, mma);                      // one step per tap
     if constexpr (BLK > 0) conv_flush(acc, tot, ch + 1 == cend);
     __syncthreads();                                     // everyone done reading the LDS slab
     if (ch + 1 < cend) { lstore(ch + 1); __syncthreads(); }
   }
-  conv_epilogue<BMC, EPI, THT>(a, acc, lds, b, r0, x0, y0);
+  conv_epilogue<BMC, EPI, THT>(a, acc, lds, t.b, t.r0, t.x0, t.y0);
 }
 
 template <int BMC, int EPI, int THT, int TERMS, int BLK>
 int launch_conv_f16_k(const ConvArgs& a, const uint16_t* whi, const uint16_t* wlo, hipStream_t st, int ksplit = 1) {
   constexpr int NT = TERMS == 3 ? 2 : 1;
-  size_t smem = sizeof(_Float16) * (size_t)NT * (9 * BMC * FK + (THT + 2) * (TW + 2) * FK);
-  if (a.gap_acc && smem < sizeof(float) * 4 * 64 * 33) smem = sizeof(float) * 4 * 64 * 33;      // the epilogue's row-sum transpose
-  static bool raised = false;
-  if (!raised) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<BMC, EPI, THT, TERMS, BLK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    raised = true;
-  }
-  const int tiles = sln_cdiv(a.W, TW) * sln_cdiv(a.H, THT) * a.B;
-  hipLaunchKernelGGL((conv_f16_kernel<BMC, EPI, THT, TERMS, BLK>), dim3(tiles, a.rows_pad / BMC, ksplit), dim3(256), smem, st, a, whi, wlo);
-  SLN_CHECK_LAUNCH();
-  return 0;
+  return launch_conv_kernel<&conv_f16_kernel<BMC, EPI, THT, TERMS, BLK>>(
+      sizeof(_Float16) * (size_t)NT * (9 * BMC * FK + ConvTile<BMC, THT>::halo(3) * FK), BMC, THT, a, st, ksplit, whi, wlo);
 }
 
 // Routing of the half modes (every 3x3 launch of the generator): blocked accumulation (Cin >= 512) and the input-channel split of
 // launches of fewer than 192 workgroups as in the fp32 path; 16 x 16-pixel workgroups where the image has the rows and the launch
 // gives every CU two of them, else 8 x 16.  -Rpass-analysis=kernel-resource-usage: no spills and no scratch in any variant; 1-3
 // waves per SIMD (three products, 128 rows: 1).
+constexpr ConvSplitKind CONV_SPLIT_F16{FK, 2, false, true};      // the channel tail is zero padded; a share without a chunk would be a wasted workgroup
 template <int BMC, int EPI, int TERMS>
 int launch_conv_f16(const ConvArgs& a, const uint16_t* whi, const uint16_t* wlo, hipStream_t st) {
   if constexpr (EPI == CEPI_BIAS_ACT) {
-    static const int split_max = getenv("SLN_CONV_KSPLIT") ? atoi(getenv("SLN_CONV_KSPLIT")) : 32;      // 1: never
-    const long blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, TH) * a.B * (a.rows_pad / BMC);
-    const int nch = (a.Cin + FK - 1) / FK;
-    const size_t one = (size_t)a.B * a.rows * a.H * a.W;
-    int S = split_max > 1 && blocks < 192 ? (int)std::min<long>(std::min(split_max, nch / 2), (512 + blocks - 1) / blocks) : 1;
-    S = (int)std::min<size_t>((size_t)S, CONV_PART_BYTES / (one * sizeof(float)));
-    if (S > 1) {
-      const int per = (nch + S - 1) / S;
-      S = (nch + per - 1) / per;                          // no workgroup without chunks
-      float* part = nullptr;
-      { const int r = conv_part_scratch(st, &part, true); if (r) return r; }
-      ConvArgs p = a; p.part = part; p.part_stride = (long)one;
-      const int r = a.blocked ? launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 1>(p, whi, wlo, st, S)
-                              : launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 0>(p, whi, wlo, st, S);
-      return r ? r : launch_conv_split_finish(a, part, S, (long)one, st);
-    }
-    if (a.blocked) return launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 1>(a, whi, wlo, st);
+    auto launch = [&](const ConvArgs& p, int S) {
+      return a.blocked ? launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 1>(p, whi, wlo, st, S)
+                       : launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 0>(p, whi, wlo, st, S);
+    };
+    bool done = false;
+    const int r = launch_conv_split(a, st, BMC, CONV_SPLIT_F16, &done, launch);
+    if (done) return r;
+    if (a.blocked) return launch(a, 1);
   }
   // (16 x 16 pixels x 128 rows in the three-product form: 512 registers and still 4 spilled - 8 x 16 there)
-  constexpr bool can_tall = !(TERMS == 3 && BMC == 128);
-  const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / BMC);
-  if (can_tall && a.H >= 16 && tall_blocks >= 512) return launch_conv_f16_k<BMC, EPI, can_tall ? 16 : TH, TERMS, 0>(a, whi, wlo, st);
+  if constexpr (!(TERMS == 3 && BMC == 128)) {
+    const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / BMC);
+    if (a.H >= 16 && tall_blocks >= 512) return launch_conv_f16_k<BMC, EPI, 16, TERMS, 0>(a, whi, wlo, st);
+  }
   return launch_conv_f16_k<BMC, EPI, TH, TERMS, 0>(a, whi, wlo, st);
 }
 
@@ -977,6 +958,41 @@ int launch_conv_f16_any(const ConvArgs& a, const uint16_t* whi, const uint16_t* 
   const bool big = a.rows_pad % 128 == 0;
   if (wlo) return big ? launch_conv_f16<128, EPI, 3>(a, whi, wlo, st) : launch_conv_f16<64, EPI, 3>(a, whi, wlo, st);
   return big ? launch_conv_f16<128, EPI, 1>(a, whi, wlo, st) : launch_conv_f16<64, EPI, 1>(a, whi, wlo, st);
+}
+
+// The two call shapes of the C entry points, fp32 and half alike (half: wp = the fp16 hi pack for the checks, nullptr in ConvArgs -
+// the packs are kernel arguments of their own - and two more terms in the checks, at the place they had).
+constexpr int CONV_BLOCK_CIN = 512;      // blocked accumulation for the long chains (K = 9 Cin >= 4 608), see conv_mfma_kernel
+int conv_sums_check(const void* x, const void* wp, const void* y, int B, int Cin, int H, int W, int rows, int rows_pad, int ksize, bool half) {
+  if (!x || !wp || !y || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || rows <= 0 || rows_pad % 64 != 0 || rows > rows_pad) return SLN_E_BADARG;
+  if (ksize != 3 && (half || ksize != 1)) return SLN_E_UNSUPPORTED;
+  if (ksize == 3 && (H < 2 || W < 2)) return SLN_E_BADARG;
+  if (half && (int64_t)Cin * H * W >= (int64_t)1 << 31) return SLN_E_UNSUPPORTED;      // 32-bit halo offsets inside a sample
+  return 0;
+}
+ConvArgs conv_sums_args(const float* x, int B, int Cin, int H, int W, const float* wp, const float* bias, int rows, int rows_pad, int ksize,
+                        int act, float slope, float* y, double* ln_acc, double* gap_acc) {
+  ConvArgs a{};
+  a.x = x; a.wp = wp; a.bias = bias; a.y = y; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = rows; a.rows_pad = rows_pad;
+  a.act = act; a.slope = slope; a.ln_acc = ln_acc; a.gap_acc = gap_acc;
+  a.blocked = ksize == 3 && Cin >= CONV_BLOCK_CIN;
+  return a;
+}
+int conv_modulate_check(const void* actv, const void* wp, const void* bias, const void* xin, const void* stats, const void* out, int B, int Cin,
+                        int H, int W, int C, int rows_pad, int xin_up, bool half) {
+  if (xin_up && ((H | W) & 1)) return SLN_E_BADARG;
+  if ((int64_t)C * H * W >= (int64_t)1 << 31 || (half && (int64_t)Cin * H * W >= (int64_t)1 << 31)) return SLN_E_UNSUPPORTED;   // 32-bit offsets inside a sample
+  if (!actv || !wp || !bias || !xin || !stats || !out || B <= 0 || C <= 0 || rows_pad % 64 != 0 || rows_pad < 64 * ((C + 31) / 32) ||
+      (half && (Cin <= 0 || H < 2 || W < 2)))
+    return SLN_E_BADARG;
+  return 0;
+}
+ConvArgs conv_modulate_args(const float* actv, int B, int Cin, int H, int W, const float* wp, const float* bias, int C, int rows_pad,
+                            const float* xin, int xin_up, const float* stats, int act, float slope, float* out) {
+  ConvArgs a{};
+  a.x = actv; a.wp = wp; a.bias = bias; a.y = out; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = 2 * C; a.rows_pad = rows_pad;
+  a.act = act; a.slope = slope; a.xin = xin; a.stats = stats; a.C = C; a.xin_up = xin_up;
+  return a;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1551,16 +1567,9 @@ int sln_spade_apply(const float* x, const float* gb, int B, int C, int H, int W,
 // conv KSxKS (KS = 3 reflect pad 1, KS = 1) with packed weights wp[KS*KS][Cin][rows_pad]; rows_pad % 64 == 0.
 int sln_spade_conv_sums(const float* x, int B, int Cin, int H, int W, const float* wp, const float* bias, int rows, int rows_pad,
                         int ksize, int act, float slope, float* y, double* ln_acc, double* gap_acc, void* stream) {
-  if (!x || !wp || !y || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || rows <= 0 || rows_pad % 64 != 0 || rows > rows_pad) return SLN_E_BADARG;
-  if (ksize != 1 && ksize != 3) return SLN_E_UNSUPPORTED;
-  if (ksize == 3 && (H < 2 || W < 2)) return SLN_E_BADARG;
+  if (const int r = conv_sums_check(x, wp, y, B, Cin, H, W, rows, rows_pad, ksize, false)) return r;
   hipStream_t st = (hipStream_t)stream;
-  ConvArgs a; a.x = x; a.wp = wp; a.bias = bias; a.y = y; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = rows; a.rows_pad = rows_pad;
-  a.act = act; a.slope = slope; a.xin = nullptr; a.stats = nullptr; a.C = 0; a.xin_up = 0; a.ln_acc = ln_acc; a.gap_acc = gap_acc;
-  // blocked accumulation for the long chains (K = 9 Cin >= 4 608), see conv_mfma_kernel; SLN_CONV_BLOCK_CIN moves the threshold (lab)
-  static const int block_cin = getenv("SLN_CONV_BLOCK_CIN") ? atoi(getenv("SLN_CONV_BLOCK_CIN")) : 512;
-  a.blocked = ksize == 3 && Cin >= block_cin;
-  a.part = nullptr; a.part_stride = 0;
+  const ConvArgs a = conv_sums_args(x, B, Cin, H, W, wp, bias, rows, rows_pad, ksize, act, slope, y, ln_acc, gap_acc);
   SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * ksize * ksize * rows, st);
   const bool big = rows_pad % 128 == 0;
   if (ksize == 3) return big ? launch_conv<128, 3, CEPI_BIAS_ACT>(a, st) : launch_conv<64, 3, CEPI_BIAS_ACT>(a, st);
@@ -1583,13 +1592,9 @@ int sln_spade_conv(const float* x, int B, int Cin, int H, int W, const float* wp
 // weights packed [32 gamma | 32 beta] per 64 rows (rows_pad = 64 * ceil(C / 32)).
 int sln_spade_modulate_up(const float* actv, int B, int Cin, int H, int W, const float* wp, const float* bias, int C, int rows_pad,
                           const float* xin, int xin_up, const float* stats, int act, float slope, float* out, void* stream) {
-  if (xin_up && ((H | W) & 1)) return SLN_E_BADARG;
-  if ((int64_t)C * H * W >= (int64_t)1 << 31) return SLN_E_UNSUPPORTED;      // 32-bit offsets inside a sample
-  if (!actv || !wp || !bias || !xin || !stats || !out || B <= 0 || C <= 0 || rows_pad % 64 != 0 || rows_pad < 64 * ((C + 31) / 32))
-    return SLN_E_BADARG;
+  if (const int r = conv_modulate_check(actv, wp, bias, xin, stats, out, B, Cin, H, W, C, rows_pad, xin_up, false)) return r;
   hipStream_t st = (hipStream_t)stream;
-  ConvArgs a; a.x = actv; a.wp = wp; a.bias = bias; a.y = out; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = 2 * C; a.rows_pad = rows_pad;
-  a.act = act; a.slope = slope; a.xin = xin; a.stats = stats; a.C = C; a.xin_up = xin_up; a.ln_acc = nullptr; a.gap_acc = nullptr; a.blocked = 0; a.part = nullptr; a.part_stride = 0;
+  const ConvArgs a = conv_modulate_args(actv, B, Cin, H, W, wp, bias, C, rows_pad, xin, xin_up, stats, act, slope, out);
   SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * 9 * 2 * C, st);
   return rows_pad % 128 == 0 ? launch_conv<128, 3, CEPI_MODULATE>(a, st) : launch_conv<64, 3, CEPI_MODULATE>(a, st);
 }
@@ -1602,16 +1607,9 @@ int sln_spade_modulate(const float* actv, int B, int Cin, int H, int W, const fl
 // hi (and lo: the three-product mode; NULL: one product).
 int sln_spade_conv_sums_f16(const float* x, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
                             int rows, int rows_pad, int ksize, int act, float slope, float* y, double* ln_acc, double* gap_acc, void* stream) {
-  if (!x || !wp_hi || !y || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || rows <= 0 || rows_pad % 64 != 0 || rows > rows_pad) return SLN_E_BADARG;
-  if (ksize != 3) return SLN_E_UNSUPPORTED;
-  if (H < 2 || W < 2) return SLN_E_BADARG;
-  if ((int64_t)Cin * H * W >= (int64_t)1 << 31) return SLN_E_UNSUPPORTED;      // 32-bit halo offsets inside a sample
+  if (const int r = conv_sums_check(x, wp_hi, y, B, Cin, H, W, rows, rows_pad, ksize, true)) return r;
   hipStream_t st = (hipStream_t)stream;
-  ConvArgs a; a.x = x; a.wp = nullptr; a.bias = bias; a.y = y; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = rows; a.rows_pad = rows_pad;
-  a.act = act; a.slope = slope; a.xin = nullptr; a.stats = nullptr; a.C = 0; a.xin_up = 0; a.ln_acc = ln_acc; a.gap_acc = gap_acc;
-  static const int block_cin = getenv("SLN_CONV_BLOCK_CIN") ? atoi(getenv("SLN_CONV_BLOCK_CIN")) : 512;
-  a.blocked = Cin >= block_cin;
-  a.part = nullptr; a.part_stride = 0;
+  const ConvArgs a = conv_sums_args(x, B, Cin, H, W, nullptr, bias, rows, rows_pad, ksize, act, slope, y, ln_acc, gap_acc);
   SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * 9 * rows, st);
   return launch_conv_f16_any<CEPI_BIAS_ACT>(a, wp_hi, wp_lo, st);
 }
@@ -1622,14 +1620,9 @@ int sln_spade_conv_f16(const float* x, int B, int Cin, int H, int W, const uint1
 int sln_spade_modulate_up_f16(const float* actv, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
                               int C, int rows_pad, const float* xin, int xin_up, const float* stats, int act, float slope, float* out,
                               void* stream) {
-  if (xin_up && ((H | W) & 1)) return SLN_E_BADARG;
-  if ((int64_t)C * H * W >= (int64_t)1 << 31 || (int64_t)Cin * H * W >= (int64_t)1 << 31) return SLN_E_UNSUPPORTED;
-  if (!actv || !wp_hi || !bias || !xin || !stats || !out || B <= 0 || Cin <= 0 || C <= 0 || H < 2 || W < 2 || rows_pad % 64 != 0 ||
-      rows_pad < 64 * ((C + 31) / 32))
-    return SLN_E_BADARG;
+  if (const int r = conv_modulate_check(actv, wp_hi, bias, xin, stats, out, B, Cin, H, W, C, rows_pad, xin_up, true)) return r;
   hipStream_t st = (hipStream_t)stream;
-  ConvArgs a; a.x = actv; a.wp = nullptr; a.bias = bias; a.y = out; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = 2 * C; a.rows_pad = rows_pad;
-  a.act = act; a.slope = slope; a.xin = xin; a.stats = stats; a.C = C; a.xin_up = xin_up; a.ln_acc = nullptr; a.gap_acc = nullptr; a.blocked = 0; a.part = nullptr; a.part_stride = 0;
+  const ConvArgs a = conv_modulate_args(actv, B, Cin, H, W, nullptr, bias, C, rows_pad, xin, xin_up, stats, act, slope, out);
   SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * 9 * 2 * C, st);
   return launch_conv_f16_any<CEPI_MODULATE>(a, wp_hi, wp_lo, st);
 }
@@ -1756,8 +1749,7 @@ int sln_conv_img_tanh(const float* x, int B, int Cin, int H, int W, const float*
   if (!x || !w || !bias || !y || Cout > 4 || Cout <= 0) return SLN_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   SlnProfScope prof(SLN_FAM_OTHER, 4.0 * B * H * W * (Cin + Cout), st);
-  static const bool no_small = getenv("SLN_CONV_IMG_NO_SMALL") != nullptr;      // lab
-  if (!no_small && (long)sln_cdiv(W, IT) * sln_cdiv(H, IT) * B < 512) {      // a few hundred 16 x 16 tiles: 8 x 8 tiles, channels over the wavefronts
+  if ((long)sln_cdiv(W, IT) * sln_cdiv(H, IT) * B < 512) {      // a few hundred 16 x 16 tiles: 8 x 8 tiles, channels over the wavefronts
     const dim3 g2(sln_cdiv(W, IT2) * sln_cdiv(H, IT2), B);
     switch (Cout) {
       case 1: hipLaunchKernelGGL(conv_img_small_kernel<1>, g2, dim3(256), 0, st, x, Cin, H, W, w, bias, y); break;

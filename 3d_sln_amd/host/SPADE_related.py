@@ -291,15 +291,29 @@ class SPADEGenerator4(nn.Module):
                    "sln_layernorm_stats")
         return stats
 
-    def _conv3(self, x, B, Cin, H, W, w, wh, bias, rows, rp, act, y, what):
-        """sln_spade_conv (3x3) of the fp32 pack w, or of its fp16 pack wh = (hi, lo or None) in the half modes."""
-        L = _lib.lib()
+    @staticmethod
+    def _weights(name, w, wh):
+        """Symbol and weight arguments of a C call family: the fp32 pack w, or its fp16 pack wh = (hi, lo or None) in the half modes."""
         if wh is None:
-            _lib.check(L.sln_spade_conv(_lib.ptr(x), B, Cin, H, W, _lib.ptr(w), _lib.ptr(bias), rows, rp, 3, act, 0.0, _lib.ptr(y),
-                                        self._st()), "sln_spade_conv(%s)" % what)
-        else:
-            _lib.check(L.sln_spade_conv_f16(_lib.ptr(x), B, Cin, H, W, _lib.ptr(wh[0]), _lib.ptr(wh[1]), _lib.ptr(bias), rows, rp, 3, act,
-                                            0.0, _lib.ptr(y), self._st()), "sln_spade_conv_f16(%s)" % what)
+            return name, (_lib.ptr(w),)
+        return name + "_f16", (_lib.ptr(wh[0]), _lib.ptr(wh[1]))
+
+    def _conv_sums(self, x, B, Cin, H, W, w, wh, bias, rows, rp, ks, act, y, ln_acc=None, gap_acc=None, what=""):
+        """sln_spade_conv_sums[_f16]; without accumulators it is sln_spade_conv[_f16]."""
+        name, wargs = self._weights("sln_spade_conv_sums", w, wh)
+        _lib.check(getattr(_lib.lib(), name)(_lib.ptr(x), B, Cin, H, W, *wargs, _lib.ptr(bias), rows, rp, ks, act, 0.0, _lib.ptr(y),
+                                             _lib.ptr(ln_acc) if ln_acc is not None else None,
+                                             _lib.ptr(gap_acc) if gap_acc is not None else None, self._st()), name + what)
+
+    def _modulate_up(self, actv, B, Cin, H, W, w, wh, bias, C, rp, x, x_up, stats, leaky, out):
+        """sln_spade_modulate_up[_f16]"""
+        name, wargs = self._weights("sln_spade_modulate_up", w, wh)
+        _lib.check(getattr(_lib.lib(), name)(_lib.ptr(actv), B, Cin, H, W, *wargs, _lib.ptr(bias), C, rp, _lib.ptr(x), 1 if x_up else 0,
+                                             _lib.ptr(stats), 2 if leaky else 0, 0.2, _lib.ptr(out), self._st()), name)
+
+    def _conv3(self, x, B, Cin, H, W, w, wh, bias, rows, rp, act, y, what):
+        """3x3 convolution of the fp32 pack w, or of its fp16 pack wh in the half modes."""
+        self._conv_sums(x, B, Cin, H, W, w, wh, bias, rows, rp, 3, act, y, what="(%s)" % what)
 
     def _spade(self, e, x, stats, seg, leaky, x_up=False):
         """SPADE4.forward (:1438-1454) + the following actvn (:1503-1505) fused into the modulation conv.
@@ -318,15 +332,7 @@ class SPADEGenerator4(nn.Module):
         actv = torch.empty(B, NHIDDEN, H, W, device=x.device)
         self._conv3(cat, B, cat.shape[1], H, W, e["wsh"], e.get("wsh_h"), e["bsh"], NHIDDEN, e["rps"], 1, actv, "shared")
         out = torch.empty(B, C, H, W, device=x.device)
-        gh = e.get("wgb_h")
-        if gh is None:
-            _lib.check(L.sln_spade_modulate_up(_lib.ptr(actv), B, NHIDDEN, H, W, _lib.ptr(e["wgb"]), _lib.ptr(e["bgb"]), C, e["rpg"],
-                                               _lib.ptr(x), 1 if x_up else 0, _lib.ptr(stats), 2 if leaky else 0, 0.2, _lib.ptr(out),
-                                               self._st()), "sln_spade_modulate_up")
-        else:
-            _lib.check(L.sln_spade_modulate_up_f16(_lib.ptr(actv), B, NHIDDEN, H, W, _lib.ptr(gh[0]), _lib.ptr(gh[1]), _lib.ptr(e["bgb"]), C,
-                                                   e["rpg"], _lib.ptr(x), 1 if x_up else 0, _lib.ptr(stats), 2 if leaky else 0, 0.2,
-                                                   _lib.ptr(out), self._st()), "sln_spade_modulate_up_f16")
+        self._modulate_up(actv, B, NHIDDEN, H, W, e["wgb"], e.get("wgb_h"), e["bgb"], C, e["rpg"], x, x_up, stats, leaky, out)
         return out
 
     def _cat_buffer(self, seg, nd):
@@ -372,15 +378,7 @@ class SPADEGenerator4(nn.Module):
         w, b, rp = wbr
         B, _, H, W = x.shape
         y = torch.empty(B, cout, H, W, device=x.device)
-        if wh is not None:                       # half modes: the fp16 pack (hi, lo or None) of this 3x3 weight
-            _lib.check(_lib.lib().sln_spade_conv_sums_f16(_lib.ptr(x), B, x.shape[1], H, W, _lib.ptr(wh[0]), _lib.ptr(wh[1]), _lib.ptr(b), cout,
-                                                          rp, ks, 0, 0.0, _lib.ptr(y), _lib.ptr(ln_acc) if ln_acc is not None else None,
-                                                          _lib.ptr(gap_acc) if gap_acc is not None else None, self._st()),
-                       "sln_spade_conv_sums_f16")
-            return y
-        _lib.check(_lib.lib().sln_spade_conv_sums(_lib.ptr(x), B, x.shape[1], H, W, _lib.ptr(w), _lib.ptr(b), cout, rp, ks, 0, 0.0,
-                                                  _lib.ptr(y), _lib.ptr(ln_acc) if ln_acc is not None else None,
-                                                  _lib.ptr(gap_acc) if gap_acc is not None else None, self._st()), "sln_spade_conv_sums")
+        self._conv_sums(x, B, x.shape[1], H, W, w, wh, b, cout, rp, ks, 0, y, ln_acc, gap_acc)      # wh: the fp16 pack of this 3x3 weight
         return y
 
     def _block(self, name, x, x_up, stats_x, seg, tail, want_stats=True, tap=None):
