@@ -238,6 +238,9 @@ SIGNATURES = {
     "sln_refine_pool": (C.c_int, [C.POINTER(SlnRefineLoss), c_f32p, C.c_int, C.c_void_p, c_f32p, C.c_void_p]),
     "sln_refine_loss_forward": (C.c_int, [C.POINTER(SlnRefineLoss), c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_void_p, c_f32p, C.c_void_p]),
     "sln_refine_loss_backward": (C.c_int, [C.POINTER(SlnRefineLoss), C.c_void_p, c_f32p, c_f32p, C.c_void_p]),
+    "sln_spade_input_workspace_bytes": (C.c_int64, [C.c_int]),
+    "sln_spade_input_forward": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -10,12 +10,19 @@ generator consumes and the many-z colourisation of one room.
     and is tested against scipy.ndimage itself.
   * ``colorize``     - ``num_z`` images of one map in ONE generator call (gamma/beta shared, SPADEGenerator4.forward with a
     single-row ``seg``) instead of ``num_z`` batch-1 calls (:74-79); ``to_uint8`` is ``save_color``'s conversion (:16-27).
+  * ``InputBuilder`` - the same tensor from csrc/spade_input.hip: depth statistics, normalisation, thresholding (or the one-hot
+    expansion of a class-index image) and the resize in three launches that read the depth and one byte per pixel of every mask that
+    is present, apply the resize from a banded table (``band_table``) and never form the full-resolution stack.  ``build_inputs`` is its
+    convenience form, ``colorize_rooms`` shades a list of rooms with it.  ``build_input`` stays as the ATen restatement the tests hold
+    the kernels to.
 File reading (.exr / .png through imageio, :45-58) stays with the caller.
 """
 import functools
 
 import numpy as np
 import torch
+
+from .. import _lib as L
 
 NYU40 = ['wall', 'floor', 'cabinet', 'bed', 'chair', 'sofa', 'table', 'door', 'window', 'bookshelf', 'picture',
          'counter', 'blinds', 'desk', 'shelves', 'curtain', 'dresser', 'pillow', 'mirror', 'floor_mat',
@@ -103,3 +110,154 @@ def to_uint8(images):
     """save_color's conversion (:16-27): [N,3,S,S] in [-1,1] -> uint8 [N,S,S,3]"""
     a = (images.detach().float() + 1.0) / 2.0
     return (a.permute(0, 2, 3, 1) * 255.0).to(torch.uint8)
+
+
+@functools.lru_cache(maxsize=8)
+def band_table(n_in, n_out, eps=1e-12):
+    """``resize_matrix(n_in, n_out)`` as a band: (first [n_out] int32, weights [n_out, width] float64) with
+    ``R[o, first[o] + k] ~ weights[o, k]``.  ``width`` is the longest run, over the rows, from the first to the last entry with
+    ``|R| > eps``; a row whose own run is shorter (or would end behind ``n_in``) is filled with its true neighbouring entries, so
+    every entry left out is ``<= eps`` in magnitude."""
+    R = resize_matrix(n_in, n_out)
+    big = np.abs(R) > eps
+    lo = big.argmax(1)
+    hi = n_in - 1 - big[:, ::-1].argmax(1)
+    width = int((hi - lo + 1).max())
+    first = np.minimum(lo, n_in - width).astype(np.int32)
+    weights = np.ascontiguousarray(R[np.arange(n_out)[:, None], first[:, None] + np.arange(width)[None, :]])
+    return first, weights
+
+
+def masks_from_labels(labels):
+    """class-index image [H,W] (0: no class, 1 + c: NYU class c) -> {class name: uint8 mask [H,W] of 0 / 255} of the classes present"""
+    labels = torch.as_tensor(labels)
+    return {NYU40[c - 1]: (labels == c).to(torch.uint8) * 255 for c in torch.unique(labels).tolist() if c > 0}
+
+
+def labels_from_masks(masks, shape=None):
+    """{class name: mask [H,W] 0..255} of DISJOINT masks (> 120 is inside) -> uint8 class-index image; the inverse of
+    ``masks_from_labels``"""
+    masks = {k: torch.as_tensor(v) for k, v in masks.items()}
+    first = next(iter(masks.values())) if masks else None
+    labels = torch.zeros(tuple(shape) if first is None else first.shape, dtype=torch.uint8, device=None if first is None else first.device)
+    for name, m in masks.items():
+        inside = m > 120
+        if bool((labels[inside] != 0).any()):
+            raise ValueError("masks overlap at class %r: a class-index image holds one class per pixel" % name)
+        labels[inside] = 1 + NYU40.index(name)
+    return labels
+
+
+class InputBuilder:
+    """[B,41,size,size] float32 from ``B`` rooms of [H,W] file arrays, on the device (csrc/spade_input.hip).
+
+        builder = InputBuilder(1024, 1024, device="cuda")
+        total = builder(depth, masks=planes, channels=["bed", "wall"])      # planes [2,H,W] uint8 (a PNG's bytes) or float32
+        total = builder(depth, labels=class_index_image)                    # uint8 [H,W]: 0 no class, 1 + c NYU class c
+
+    With ``batch`` > 1 the arrays carry a leading room axis (depth [B,H,W], masks [B,n,H,W], labels [B,H,W]) and ``channels`` is one
+    list of names per room; a room with fewer masks pads its list with ``None`` (the plane is not read).  ``channels`` may also be an
+    int32 device tensor [B,n] of NYU class indices (< 0: padding), which costs no host work - the form to use under a graph capture.
+    The result is the builder's static output buffer: the next call overwrites it.  The call allocates nothing, reads nothing back
+    and runs on the current stream.
+
+    If no depth value of a room lies below ``min + 20`` the reference raises (``np.max`` of an empty selection).  The kernel leaves 1
+    in that room's word of ``status`` (int32 [B], device).  ``validate=True`` reads it after every call - one synchronisation - and
+    raises ``ValueError``; the default does not read it, and such a room's depth channel is NaN."""
+
+    def __init__(self, H, W, size=256, batch=1, device="cuda", validate=False):
+        self.H, self.W, self.size, self.batch, self.validate = int(H), int(W), int(size), int(batch), validate
+        self.device = torch.device(device)
+        fh, wh = band_table(self.H, self.size)
+        fw, ww = band_table(self.W, self.size)
+        self.width_h, self.width_w = wh.shape[1], ww.shape[1]
+        self._first_h, self._w_h = torch.from_numpy(fh).to(self.device), torch.from_numpy(wh).to(self.device)
+        self._first_w = torch.from_numpy(fw).to(self.device)
+        self._w_w = torch.from_numpy(np.ascontiguousarray(ww.T)).to(self.device)          # [width, size]: see sln_hip.h
+        nbytes = L.lib().sln_spade_input_workspace_bytes(self.batch)
+        if nbytes < 0:
+            L.check(nbytes, "sln_spade_input_workspace_bytes")
+        self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
+        self.out = torch.empty(self.batch, 41, self.size, self.size, dtype=torch.float32, device=self.device)
+        self.status = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+        self._channels = {}
+
+    def _channel_table(self, channels, n):
+        if torch.is_tensor(channels):
+            if channels.dtype != torch.int32 or channels.numel() != self.batch * n or channels.device != self.out.device:
+                raise ValueError("channels: int32 [%d, %d] on %s expected" % (self.batch, n, self.out.device))
+            return channels.contiguous()
+        rows = [list(channels)] if self.batch == 1 and (len(channels) == 0 or channels[0] is None or isinstance(channels[0], str)) \
+            else [list(c) for c in channels]
+        if len(rows) != self.batch or any(len(r) != n for r in rows):
+            raise ValueError("channels: %d list(s) of %d class names expected" % (self.batch, n))
+        key = tuple(tuple(r) for r in rows)
+        if key not in self._channels:
+            idx = [[-1 if nm is None else NYU40.index(nm) for nm in r] for r in rows]
+            for r in idx:
+                live = [c for c in r if c >= 0]
+                if len(set(live)) != len(live):
+                    raise ValueError("channels: a class is named twice in one room")
+            self._channels[key] = torch.tensor(idx, dtype=torch.int32).reshape(self.batch, n).to(self.device)
+        return self._channels[key]
+
+    def _room_array(self, t, what, dtypes, planes=False):
+        if not torch.is_tensor(t) or t.device != self.out.device or t.dtype not in dtypes:
+            raise ValueError("%s: a %s tensor on %s expected" % (what, " / ".join(str(d) for d in dtypes), self.out.device))
+        tail = (self.H, self.W)
+        if tuple(t.shape[-2:]) != tail or t.numel() % (self.batch * self.H * self.W) or (not planes and t.numel() != self.batch * self.H * self.W):
+            raise ValueError("%s: shape %s does not hold %d room(s) of %d x %d" % (what, tuple(t.shape), self.batch, self.H, self.W))
+        return t.contiguous()
+
+    def __call__(self, depth, masks=None, channels=None, labels=None):
+        depth = self._room_array(depth, "depth", (torch.float32,))
+        chan, n_live = None, 0
+        if labels is not None:
+            if masks is not None or channels is not None:
+                raise ValueError("give masks and channels, or labels")
+            planes, mode = self._room_array(labels, "labels", (torch.uint8,)), 2
+        elif masks is not None and masks.numel():
+            planes = self._room_array(masks, "masks", (torch.uint8, torch.float32), planes=True)
+            mode = 0 if planes.dtype == torch.uint8 else 1
+            n_live = planes.numel() // (self.batch * self.H * self.W)
+            if n_live > 40 or channels is None:
+                raise ValueError("masks: at most 40 planes per room, with the class of each in `channels`")
+            chan = self._channel_table(channels, n_live)
+        else:
+            planes, mode = None, 0
+        L.check(L.lib().sln_spade_input_forward(L.ptr(depth), L.ptr(planes), mode, L.ptr(chan), n_live, self.batch, self.H, self.W, self.size,
+                                                L.ptr(self._first_h), L.ptr(self._w_h), self.width_h, L.ptr(self._first_w), L.ptr(self._w_w),
+                                                self.width_w, L.ptr(self._ws), L.ptr(self.out), L.ptr(self.status), L.current_stream_ptr()),
+                "sln_spade_input_forward")
+        torch.autograd.graph.increment_version(self.out)       # written through its pointer: SPADEGenerator4 keeps a map's planes by version
+        if self.validate:
+            bad = self.status.cpu().nonzero().flatten().tolist()
+            if bad:
+                raise ValueError("no depth value below min + 20 in room(s) %s: the reference's np.max of an empty selection" % bad)
+        return self.out
+
+
+def build_inputs(depths, masks_list, size=256):
+    """depths: B tensors [H,W] on the device, masks_list: B dicts {class name: [H,W] mask, uint8 or float32} -> [B,41,size,size]"""
+    B = len(depths)
+    H, W = depths[0].shape
+    dev = depths[0].device
+    n = max([len(m) for m in masks_list] + [1])
+    dtype = torch.uint8 if all(v.dtype == torch.uint8 for m in masks_list for v in m.values()) else torch.float32
+    planes = torch.zeros(B, n, H, W, dtype=dtype, device=dev)
+    names = []
+    for b, m in enumerate(masks_list):
+        for j, (name, v) in enumerate(m.items()):
+            planes[b, j] = v.to(dev)
+        names.append(list(m) + [None] * (n - len(m)))
+    builder = InputBuilder(H, W, size=size, batch=B, device=dev)
+    return builder(torch.stack([d.to(dev).float() for d in depths]), masks=planes, channels=names)
+
+
+def colorize_rooms(model, builder, rooms, num_z, generator=None):
+    """rooms: keyword dicts of ``builder`` (batch 1), e.g. {"depth": d, "masks": planes, "channels": names} or {"depth": d,
+    "labels": l}, device tensors.  For each room: the input on the device and ONE ``colorize`` call.  -> uint8 [R, num_z, S, S, 3];
+    nothing is read back in between."""
+    if builder.batch != 1:
+        raise ValueError("colorize_rooms shades one room per generator call: a batch-1 builder expected")
+    return torch.stack([to_uint8(colorize(model, builder(**room), num_z, generator)) for room in rooms])

@@ -703,6 +703,25 @@ int sln_refine_report(const SlnRefineLoss* L, const float* image, const float* t
                       double* iou_mean, float* report_out, void* stream);
 int sln_refine_report_scratch_doubles(int B);
 
+/* The [B, 41, size, size] float32 tensor SPADEGenerator4 consumes, from the file arrays of colorize_with_spade
+ * (testing/test_SPADE_shade.py:50-76): channel 0 = ((clip(d - min d, 0, dmax) / dmax) - 0.5) * 2 with dmax = max{d - min d < 20} per
+ * room (float32, the reference's operation order), channel 1 + c = the mask of NYU class c (< 120 -> 0, > 120 -> 1, exactly 120 stays),
+ * every channel resized by Rh . X . Rw^T in float64.  depth [B, H, W] float32.  `planes` by mode:
+ *   SLN_SPADE_INPUT_MASKS_U8 / _F32   [B, n_live, H, W] uint8 / float32 masks; channels [B, n_live] int32 = the NYU class (0..39) each
+ *                                     plane fills, < 0 for a padding plane (not read); n_live 0..40
+ *   SLN_SPADE_INPUT_LABELS            [B, H, W] uint8 class-index image: 0 no class, 1 + c NYU class c (channels, n_live unused)
+ * A channel no plane fills is written as exact 0.0.  The resize operators are banded tables: first_h [size] int32 and w_h
+ * [size, width_h] float64 with Rh[o, first_h[o] + k] = w_h[o, k] (first_h[o] + width_h <= H), first_w [size] and w_w TRANSPOSED
+ * [width_w, size] for Rw.  status [B] int32: 1 when no depth value of the room lies below min + 20 (the reference raises there; the
+ * room's depth channel is NaN), else 0.  Three launches on `stream`; no allocation, no synchronisation, no host read, no atomics:
+ * legal inside a stream capture and bit-identical from call to call.  workspace: sln_spade_input_workspace_bytes(B) bytes, 8-byte
+ * aligned.  SLN_E_UNSUPPORTED when a [4, W] float64 row tile does not fit 64 KiB of LDS (W above about 1 900). */
+enum { SLN_SPADE_INPUT_MASKS_U8 = 0, SLN_SPADE_INPUT_MASKS_F32 = 1, SLN_SPADE_INPUT_LABELS = 2 };
+int64_t sln_spade_input_workspace_bytes(int B);
+int sln_spade_input_forward(const float* depth, const void* planes, int mode, const int32_t* channels, int n_live, int B, int H, int W,
+                            int size, const int32_t* first_h, const double* w_h, int width_h, const int32_t* first_w, const double* w_w,
+                            int width_w, void* workspace, float* out, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
