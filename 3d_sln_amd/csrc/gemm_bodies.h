@@ -1,4 +1,4 @@
-// Templates shared by the GEMM translation units (gemm_f32.hip: single / dual launches, gemm_group.hip: grouped launches).
+// Templates shared by the GEMM translation units (gemm_f32.hip: single-problem and table-driven launches, gemm_group.hip: grouped launches).
 // Everything lives in an anonymous namespace: each translation unit gets its own instantiations.
 #pragma once
 #include "sln_common.h"

@@ -132,20 +132,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmTNArgs a) {
   gemm_tn_body<BM, BN, WM, WN, G_X2, XG>(a, blockIdx.x, blockIdx.y, smem);
 }
 
-// One launch for the two GEMMs that consume the same output gradient G of a Linear: the dgrad (NT, 64x64 tiles, blocks
-// [0, nt_blocks)) and the wgrad (TN, the remaining tn_gx * tn_gy blocks).  At batch 64 either one fills less than half of
-// the chip and a launch costs about as much as its work, so the pair shares one dispatch.
-template <int AMODE, int EPI, bool XG>
-__global__ __launch_bounds__(256) void gemm_dual_kernel(const GemmNTArgs a, const GemmTNArgs b, const int nt_blocks, const int tn_gx) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  if ((int)blockIdx.x < nt_blocks) {
-    gemm_nt_body<64, 64, 2, 2, AMODE, EPI, 0>(a, blockIdx.x, nt_blocks, smem);
-  } else {
-    const int id = blockIdx.x - nt_blocks;
-    gemm_tn_body<64, 64, 2, 2, AMODE == 1, XG>(b, id % tn_gx, id / tn_gx, smem);
-  }
-}
-
 // Every wgrad of a backward pass in one grid: workgroup b runs entry b of the item table (problem, output tile, row chunk; see
 // TnMultiMeta for the XCD-aware layout) on that problem's description in device memory (uniform address: scalar loads).
 template <bool G_X2, bool XG>
@@ -154,20 +140,6 @@ __global__ __launch_bounds__(256) void gemm_tn_multi_kernel(const GemmTNArgs* __
   const TnMultiItem it = meta->item[blockIdx.x];
   if (it.prob < 0) return;
   gemm_tn_body<64, 64, 2, 2, G_X2, XG>(probs[it.prob], it.tile, it.chunk, smem);
-}
-
-
-template <int AMODE, int EPI>
-int launch_dual(const GemmNTArgs& a, const GemmTNArgs& b, hipStream_t st) {
-  const size_t s1 = nt_smem_bytes(a.K, 64, 64, 2), s2 = tn_smem_bytes(64, 64);
-  const size_t smem = s1 > s2 ? s1 : s2;
-  const int nt_blocks = sln_cdiv(a.M, 64) * sln_cdiv(a.N, 64);
-  const int gx = sln_cdiv(b.Nout, 64) * sln_cdiv(b.Kin, 64), gy = sln_cdiv(b.R, b.rows_per_block);
-  if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
-  if (tn_gathers(b)) hipLaunchKernelGGL((gemm_dual_kernel<AMODE, EPI, true>), dim3(nt_blocks + gx * gy), dim3(256), smem, st, a, b, nt_blocks, gx);
-  else hipLaunchKernelGGL((gemm_dual_kernel<AMODE, EPI, false>), dim3(nt_blocks + gx * gy), dim3(256), smem, st, a, b, nt_blocks, gx);
-  SLN_CHECK_LAUNCH();
-  return 0;
 }
 
 template <int BM, int BN, int WM, int WN, bool G_X2>
@@ -240,14 +212,6 @@ int sln_gemm_init() {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   SLN_SET_TNM(true, true) SLN_SET_TNM(true, false) SLN_SET_TNM(false, true) SLN_SET_TNM(false, false)
 #undef SLN_SET_TNM
-#define SLN_SET_DUAL(AM, EPI)                                                                                     \
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dual_kernel<AM, EPI, false>),         \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dual_kernel<AM, EPI, true>),          \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  SLN_SET_DUAL(0, EPI_PLAIN) SLN_SET_DUAL(0, EPI_MASK) SLN_SET_DUAL(1, EPI_PLAIN) SLN_SET_DUAL(1, EPI_MASK)
-  SLN_SET_DUAL(2, EPI_PLAIN) SLN_SET_DUAL(2, EPI_MASK)
-#undef SLN_SET_DUAL
   if (!r) r = sln_gemm_group_init();
   done = r == 0;
   return r;
@@ -263,8 +227,9 @@ int sln_launch_gemm_nt(const GemmNTArgs& a, int epi, int tile, hipStream_t st) {
   // SLN_NT_LOG=1: one line per launch on stderr (tools/lab/nt_by_shape.sh joins them, in order, with a kernel trace)
   static const bool nt_log = std::getenv("SLN_NT_LOG") != nullptr;
   if (nt_log) std::fprintf(stderr, "NTLOG M=%d N=%d K=%d amode=%d epi=%d nseg=%d\n", a.M, a.N, a.K, amode, epi, a.A.nseg);
-  // stand-alone launches only: inside a dual launch (dgrad blocks next to wgrad blocks on every CU) the small body measured
-  // slower than the 64 x 64 one (pairs 28.8 -> 30.3 us on average): its 4x more workgroups pay 4x the prologues on a busy chip
+  // stand-alone launches only: a grouped launch (gemm_group.hip) keeps the 64 x 64 body.  Sharing a grid with another problem's
+  // blocks, the small body's 4x more workgroups pay 4x the prologues on a busy chip (measured with a wgrad's blocks next to a
+  // dgrad's on every CU: 28.8 -> 30.3 us on average)
   if (tile < 0 && !no_small && nt_wants_small(a)) {
 #define SLN_DISPATCH_S(AM)                                                            \
     if (amode == AM) {                                                                \
@@ -378,30 +343,12 @@ int sln_launch_gemm_nt_small_multi(const GemmNTArgs* tab, const int* tiles_dev, 
   return -1;
 }
 
-int sln_launch_gemm_tn(const GemmTNArgs& a0, int tile, hipStream_t st) {
+int sln_launch_gemm_tn(const GemmTNArgs& a0, hipStream_t st) {
   SlnProfScope prof(SLN_FAM_GEMM_TN, 2.0 * a0.R * a0.Nout * a0.Kin, st);
   GemmTNArgs a = a0;
   const bool x2 = tn_prepare(a);
-  (void)tile;
   if (x2) return launch_tn<64, 64, 2, 2, true>(a, st);
   return launch_tn<64, 64, 2, 2, false>(a, st);
-}
-
-int sln_launch_gemm_dual(const GemmNTArgs& a, int epi, const GemmTNArgs& b0, hipStream_t st) {
-  GemmTNArgs b = b0;
-  const bool x2 = tn_prepare(b);
-  const int amode = nt_amode(a);
-  const bool nonempty = a.M > 0 && a.N > 0 && b.R > 0 && b.Nout > 0 && b.Kin > 0;
-  if (!nonempty || nt_big_shape(a) || epi == EPI_STATS || x2 != (amode == 1) || a.A.nseg > 1 || !tn_supported(b)) {   // big or odd shapes: separate launches
-    int r = sln_launch_gemm_tn(b0, -1, st);
-    return r ? r : sln_launch_gemm_nt(a, epi, -1, st);
-  }
-  SlnProfScope prof(SLN_FAM_GEMM_DUAL, 2.0 * a.M * a.N * a.K + 2.0 * b.R * b.Nout * b.Kin, st);
-#define SLN_DISPATCH(AM)                                                              \
-  if (amode == AM) return epi == EPI_MASK ? launch_dual<AM, EPI_MASK>(a, b, st) : launch_dual<AM, EPI_PLAIN>(a, b, st);
-  SLN_DISPATCH(0) SLN_DISPATCH(1) SLN_DISPATCH(2)
-#undef SLN_DISPATCH
-  return -1;
 }
 
 int sln_tn_multi_plan(GemmTNArgs* probs, int n, TnMultiMeta* meta, int* blocks, bool* x2, bool* xg, double* flops) {

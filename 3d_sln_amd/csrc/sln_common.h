@@ -318,9 +318,8 @@ static inline int sln_zero_async(void* p, size_t bytes, hipStream_t st) {
   } while (0)
 
 // A pooled stream that overlaps with `main` (streams.hip: two streams on one hardware queue do not; probed once per caller stream);
-// nullptr when none can be had right now (first use inside a stream capture).  Plain engine side streams: sln_side_stream_create.
+// nullptr when none can be had right now (first use inside a stream capture).
 hipStream_t sln_overlapping_stream(hipStream_t main);
-inline hipError_t sln_side_stream_create(hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
 inline bool sln_capturing(hipStream_t st) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;

@@ -41,15 +41,13 @@ struct GemmTNArgs {
 
 // epi: EPI_*; tile: -1 = heuristic, 0 = 64x64, 1 = 128x64, 2 = 128x128
 int sln_launch_gemm_nt(const GemmNTArgs& a, int epi, int tile, hipStream_t st);
-int sln_launch_gemm_tn(const GemmTNArgs& a, int tile, hipStream_t st);
-// dgrad (NT) and wgrad (TN) of the same Linear in one launch when both are small; falls back to two launches otherwise
-int sln_launch_gemm_dual(const GemmNTArgs& nt, int epi, const GemmTNArgs& tn, hipStream_t st);
-// up to two independent NT problems + up to two independent TN problems in one launch (gemm_group.hip); returns 1 without
-// launching anything when the problems cannot share a kernel - the caller launches them separately then
-int sln_launch_gemm_group(const GemmNTArgs* nt, const int* epi, int n_nt, const GemmTNArgs* tn, int n_tn, hipStream_t st);
-// ---- every wgrad of a backward pass as ONE launch (round 3) --------------------------------------------------------------
-// A wgrad has no consumer before the optimizer, so the engine no longer pairs it with the next dgrad: it records the problems
-// and launches them together when the pass is over.  The problem table lives in device memory (a hipGraph replays the launch
+int sln_launch_gemm_tn(const GemmTNArgs& a, hipStream_t st);
+// up to two independent NT problems in one launch (gemm_group.hip); returns 1 without launching anything when the problems
+// cannot share a kernel - the caller launches them separately then
+int sln_launch_gemm_group(const GemmNTArgs* nt, const int* epi, int n_nt, hipStream_t st);
+// ---- every wgrad of a backward pass as ONE launch --------------------------------------------------------------------------
+// A wgrad has no consumer before the optimizer, so the engine does not run it next to the dgrad of its Linear: it records the
+// problems and launches them together when the pass is over.  The problem table lives in device memory (a hipGraph replays the launch
 // with the same pointers); each block finds its problem from the prefix of block counts.
 enum { SLN_TN_MULTI_MAX = 64, SLN_TN_MULTI_ITEMS = 4096 };
 // One entry per workgroup of the launch: problem, output tile, row chunk.  The table is laid out for the hardware's round-robin

@@ -128,35 +128,11 @@ struct SlnVae {
   bool draw_eps = false;          // the iteration draws its own N(0,1) (no eps from the caller)
   unsigned long long host_seed[2] = {0, 0};
 
-  // wgrad GEMMs run on a side stream, concurrent with the dgrad chain (both only half-fill the chip at
-  // batch 64); fork after the producer of the wgrad's gradient operand, join before that buffer is reused.
-  hipStream_t side = nullptr;
-  std::vector<hipEvent_t> events; size_t ev_next = 0; bool use_side = true; bool side_busy = false;
-  hipEvent_t next_event() {
-    if (ev_next == events.size()) { hipEvent_t e = nullptr; (void)hipEventCreateWithFlags(&e, hipEventDisableTiming); events.push_back(e); }
-    return events[ev_next++];
-  }
-  int fork_side(hipStream_t st) {
-    hipEvent_t e = next_event();
-    hipError_t r = hipEventRecord(e, st);
-    if (r == hipSuccess) r = hipStreamWaitEvent(side, e, 0);
-    side_busy = true;
-    return (int)r;
-  }
-  // Pairing: a wgrad is held back and shares the launch of the next dgrad (sln_launch_gemm_dual); this replaced the
-  // side stream as the default (SLN_NO_DUAL=1 goes back to it) - one dispatch instead of two, and no event edges.
-  bool use_dual = true;
-  std::vector<GemmTNArgs> pending;
-  int flush_pending(hipStream_t st) {
-    for (const GemmTNArgs& t : pending) { int r = sln_launch_gemm_tn(t, -1, st); if (r) { pending.clear(); return r; } }
-    pending.clear();
-    return 0;
-  }
-  // Round 3: deferral.  A wgrad has no consumer before the optimizer, so nothing forces it to run next to the dgrad of the same
+  // Deferral: a wgrad has no consumer before the optimizer, so nothing forces it to run next to the dgrad of the same
   // Linear.  The problems of a backward pass are recorded and run as ONE launch per pass (two when some gather their X rows)
   // through sln_launch_gemm_tn_multi: chunks of ~1 k rows instead of 256 (the prologue, the first-tile latency and the 64 x 64
-  // atomics of a block are paid a quarter as often), no launch boundary per wgrad, and the dgrad chain - now alone in its
-  // launches - gets the chip to itself.  SLN_NO_DEFER=1 restores the pairing.
+  // atomics of a block are paid a quarter as often), no launch boundary per wgrad, and the dgrad chain - alone in its
+  // launches - gets the chip to itself.
   // The problem tables live in device memory.  Set 0 belongs to the captured iterations (filled after the capture ends, before
   // the graph is launched: a capture records, nothing runs), set 1 to eager calls; [which] 0 = decoder pass, 1 = encoder pass;
   // [k] 0 = plain rows, 1 = gathered X rows.
@@ -170,10 +146,9 @@ struct SlnVae {
   // layer; a launch that finds none runs its problems one by one)
   int tn_slots = 32;
   std::vector<GemmTNArgs> tn_kind_scratch;
-  bool defer = true, capturing = false, tn_upload_pending = false;
+  bool capturing = false, tn_upload_pending = false;
   int det_seen = 0;                              // g_sln_deterministic the captured iterations were recorded with
   bool tn_per_layer = false;                     // flush after every GraphTripleConv instead of once per pass
-  bool tn_side = false, tn_side_busy = false;    // run the wgrad launches on the side stream, next to the dgrad chain
   int tn_slot_next[3] = {0, 0, 0};
   std::vector<GemmTNArgs> deferred;
   TnGroup* tn_groups_store = nullptr;            // [2 sets][TN_SLOTS][2], heap (a TnGroup is 50 KB)
@@ -230,17 +205,6 @@ struct SlnVae {
     tn_upload_pending = false;
     return 0;
   }
-  // the wgrad launches may run on the side stream: fork behind the producer of their operands, join before anything reads the
-  // parameter gradients (end of an iteration / of an eager backward call)
-  hipStream_t tn_side_stream = nullptr;          // the stream the current iteration's wgrad launches went to (join_tn_side)
-  int join_tn_side(hipStream_t st) {
-    if (!tn_side_busy) return 0;
-    hipEvent_t e = next_event();
-    hipError_t r = hipEventRecord(e, tn_side_stream ? tn_side_stream : side);
-    if (r == hipSuccess) r = hipStreamWaitEvent(st, e, 0);
-    tn_side_busy = false;
-    return (int)r;
-  }
   hipStream_t tn_eager_stream = nullptr;         // the stream whose launches read the eager table set (set 1) last
   int flush_deferred(int which, hipStream_t st) {
     if (rec) { rec_push(SK_TN_FLUSH); return 0; }
@@ -258,18 +222,6 @@ struct SlnVae {
           (void)hipStreamSynchronize(tn_eager_stream);
         tn_eager_stream = st;
       }
-    }
-    hipStream_t lst = st;
-    if (tn_side && side) {
-      // (lab, SLN_TN_SIDE=1) eager launches: a pooled stream that is PROBED to overlap with the caller's (csrc/streams.hip: the engine's
-      // own side stream may share the caller's hardware queue); captures keep the engine's stream
-      hipStream_t sd = sln_capturing(st) ? side : sln_overlapping_stream(st);
-      if (sd == nullptr) sd = side;
-      hipEvent_t e = next_event();
-      hipError_t r = hipEventRecord(e, st);
-      if (r == hipSuccess) r = hipStreamWaitEvent(sd, e, 0);
-      if (r != hipSuccess) { deferred.clear(); return (int)r; }
-      lst = sd; tn_side_stream = sd; tn_side_busy = true;
     }
     static thread_local TnGroup tmp;
     // two kinds of problems (X rows gathered: every net1.0; plain rows: the rest).  A launch group is closed by problem count
@@ -304,7 +256,7 @@ struct SlnVae {
         if (r != 0) {                 // one problem, launched on its own (2-D grid: no table)
           GemmTNArgs one = kind[next++];
           if (g_sln_deterministic) one.rows_per_block = sln_cdiv(one.R, 32) * 32;         // one add per dW element, as in the planned launches
-          r = sln_launch_gemm_tn(one, -1, lst);
+          r = sln_launch_gemm_tn(one, st);
           if (r) { deferred.clear(); return r; }
           continue;
         }
@@ -319,33 +271,17 @@ struct SlnVae {
         }
         if (g.dirty) {
           if (capturing) tn_upload_pending = true;
-          else if (lst == st) {       // eager call with a new problem set (new shape, other BatchNorm mode): stream-ordered upload
+          else {                      // eager call with a new problem set (new shape, other BatchNorm mode): stream-ordered upload
             r = upload_group_async(g, st);
-            if (r) { deferred.clear(); return r; }
-          } else {                    // wgrads on the side stream (SLN_TN_SIDE=1): blocking, as before
-            hipError_t e = hipStreamSynchronize(st);          // an earlier launch may still read the old table
-            if (e == hipSuccess && side) e = hipStreamSynchronize(side);
-            if (e == hipSuccess && lst != side) e = hipStreamSynchronize(lst);
-            if (e != hipSuccess) { deferred.clear(); return (int)e; }
-            r = upload_group(g);
             if (r) { deferred.clear(); return r; }
           }
         }
-        r = sln_launch_gemm_tn_multi(g.dev_probs, g.dev_meta, g.blocks, g.x2, g.xg, g.flops, lst);
+        r = sln_launch_gemm_tn_multi(g.dev_probs, g.dev_meta, g.blocks, g.x2, g.xg, g.flops, st);
         if (r) { deferred.clear(); return r; }
       }
     }
     deferred.clear();
     return 0;
-  }
-  int join_side(hipStream_t st) {
-    { int r = flush_pending(st); if (r) return r; }
-    if (!side_busy) return 0;
-    hipEvent_t e = next_event();
-    hipError_t r = hipEventRecord(e, side);
-    if (r == hipSuccess) r = hipStreamWaitEvent(st, e, 0);
-    side_busy = false;
-    return (int)r;
   }
 
   // hipGraph of one training iteration
@@ -358,7 +294,8 @@ struct SlnVae {
   bool it_zero_in_prologue = false;   // ... and that launch also clears the iteration's accumulators
   bool it_prologue = false;       // enc_assemble + both predicate gathers (+ the N(0,1) draw) already issued as ONE launch
   bool it_fused_loss = false;     // log_softmax is taken inside the loss kernel
-  bool it_one_flush = false;      // full iterations: the decoder pass's wgrads ride with the encoder pass's launches (SLN_TN_ONE_FLUSH=0: off)
+  bool it_one_flush = false;      // full iterations: the decoder pass's wgrads ride with the encoder pass's launches
+  bool one_flush = true;          // SLN_TN_ONE_FLUSH=0 at creation: off, every pass flushes its own
   bool it_merge_bn = false;       // ONE running-statistics launch per iteration (after the decoder) and ONE parameter-gradient launch
   bool no_merge = false;          // SLN_NO_MERGE=1 at creation: none of the three
   bool gconv_only = false;        // a bare GraphTripleConvNet (sln_gconv_net_*): units = the modules' four Linears, one net, no heads
@@ -435,13 +372,11 @@ struct SlnVae {
   // Group mode: between begin_group() and end_group() the Linear launches are recorded instead of issued; end_group()
   // issues them two at a time through sln_launch_gemm_group (the recorded problems must be independent of each other:
   // the two posterior heads of the encoder, box_net / angle_net of the decoder).
-  struct GroupItem { GemmNTArgs nt; int epi; bool has_tn; GemmTNArgs tn; };
+  struct GroupItem { GemmNTArgs nt; int epi; };
   bool grouping = false, use_group = true;
   std::vector<GroupItem> group_items;
   void begin_group() { grouping = use_group; group_items.clear(); }
-  int launch_item(const GroupItem& it, hipStream_t st) {
-    return it.has_tn ? sln_launch_gemm_dual(it.nt, it.epi, it.tn, st) : sln_launch_gemm_nt(it.nt, it.epi, -1, st);
-  }
+  int launch_item(const GroupItem& it, hipStream_t st) { return sln_launch_gemm_nt(it.nt, it.epi, -1, st); }
   int end_group(hipStream_t st) {
     grouping = false;
     for (size_t i = 0; i < group_items.size(); i += 2) {
@@ -449,10 +384,7 @@ struct SlnVae {
       if (i + 1 == group_items.size()) { int r = launch_item(a, st); if (r) return r; break; }
       const GroupItem& b2 = group_items[i + 1];
       GemmNTArgs nt[2] = {a.nt, b2.nt}; int epi[2] = {a.epi, b2.epi};
-      GemmTNArgs tn[2]; int ntn = 0;
-      if (a.has_tn) tn[ntn++] = a.tn;
-      if (b2.has_tn) tn[ntn++] = b2.tn;
-      int r = sln_launch_gemm_group(nt, epi, 2, tn, ntn, st);
+      int r = sln_launch_gemm_group(nt, epi, 2, st);
       if (r == 1) { r = launch_item(a, st); if (!r) r = launch_item(b2, st); }
       if (r) return r;
     }
@@ -468,7 +400,7 @@ struct SlnVae {
     int epi = EPI_PLAIN;
     if (inst >= 0 && bn_mode(bns[inst], training) == SLN_BN_TRAIN) { epi = EPI_STATS; a.osums = bns[inst].sums; a.ocstride = bns[inst].C; }
     if (rec) { RecStep& r = rec_push(SK_NT); r.nt = a; r.epi = epi; return 0; }
-    if (grouping) { GroupItem it; it.nt = a; it.epi = epi; it.has_tn = false; group_items.push_back(it); return 0; }
+    if (grouping) { group_items.push_back(GroupItem{a, epi}); return 0; }
     return sln_launch_gemm_nt(a, epi, -1, st);
   }
   // dIn[M, in] = G[M, out] * W ; optional relu/BN mask of the producing stage (xprev, inst) and addend
@@ -486,33 +418,17 @@ struct SlnVae {
       if (a.obn.mode != SLN_BN_NONE) { a.ogsums = bns[mask_inst].gsums; a.ocstride = bns[mask_inst].C; }
     }
     if (rec) { RecStep& r = rec_push(SK_NT); r.nt = a; r.epi = epi; return 0; }
-    if (grouping) {
-      GroupItem it; it.nt = a; it.epi = epi; it.has_tn = !pending.empty();
-      if (it.has_tn) { it.tn = pending.front(); pending.erase(pending.begin()); }
-      group_items.push_back(it);
-      return 0;
-    }
-    if (!pending.empty()) {
-      const GemmTNArgs t = pending.front();
-      pending.erase(pending.begin());
-      return sln_launch_gemm_dual(a, epi, t, st);
-    }
+    if (grouping) { group_items.push_back(GroupItem{a, epi}); return 0; }
     return sln_launch_gemm_nt(a, epi, -1, st);
   }
-  int linear_wgrad(const Operand& G, const Operand& X, int ui, int R, hipStream_t st) {
+  int linear_wgrad(const Operand& G, const Operand& X, int ui, int R) {
     const Unit& u = units[ui];
     GemmTNArgs a; std::memset(&a, 0, sizeof(a));
     a.G = G; a.X = X; a.dW = u.p.d_weight; a.db = u.p.d_bias; a.lddw = u.in;
     a.R = R; a.Nout = u.out; a.Kin = u.in; a.rows_per_block = 0;
-    if (rec) { rec_push(SK_TN).tn = a; return 0; }
-    if (defer) { deferred.push_back(a); return 0; }
-    if (use_dual) { pending.push_back(a); return 0; }
-    if (use_side && side) {
-      int r = fork_side(st);
-      if (r) return r;
-      return sln_launch_gemm_tn(a, -1, side);
-    }
-    return sln_launch_gemm_tn(a, -1, st);
+    if (rec) rec_push(SK_TN).tn = a;
+    else deferred.push_back(a);              // launched by flush_deferred
+    return 0;
   }
 
   // ---- launch sites of the decoder path: launch, or record (see Recorder) ----
@@ -729,11 +645,11 @@ int SlnVae::gconv_backward(int gi, const float* dP, int lddp, int dpcol0, int sl
   // net2.1 : h3 -> A4
   float *g1 = ly.g1, *g2 = ly.g2, *g3 = ly.g3, *g4 = ly.g4;
   Operand G4 = op1(seg_bwd(g4, Do, ly.A4, Do, Do, ly.bn[3], tr), O);
-  RET_IF(linear_wgrad(G4, op1(seg_act(ly.A3, H, 0, H, ly.bn[2], 0, tr), O), ly.u0 + 3, O, st));
+  RET_IF(linear_wgrad(G4, op1(seg_act(ly.A3, H, 0, H, ly.bn[2], 0, tr), O), ly.u0 + 3, O));
   RET_IF(linear_dgrad(G4, ly.u0 + 3, g3, H, O, ly.A3, H, ly.bn[2], true, nullptr, 0, tr, st));
   // net2.0 : pooled -> A3
   Operand G3 = op1(seg_bwd(g3, H, ly.A3, H, H, ly.bn[2], tr), O);
-  RET_IF(linear_wgrad(G3, op1(seg_ident(ly.M, H, 0, H, 0), O), ly.u0 + 2, O, st));
+  RET_IF(linear_wgrad(G3, op1(seg_ident(ly.M, H, 0, H, 0), O), ly.u0 + 2, O));
   RET_IF(linear_dgrad(G3, ly.u0 + 2, dM, H, O, nullptr, 0, -1, false, nullptr, 0, tr, st));
   // avg-pool backward (a gather) + relu/BN mask of A2
   BnView v2 = view(ly.bn[1], 0, tr);
@@ -741,13 +657,12 @@ int SlnVae::gconv_backward(int gi, const float* dP, int lddp, int dpcol0, int sl
                        v2.mode != SLN_BN_NONE ? bns[ly.bn[1]].gsums : nullptr, C2, st));
   // net1.1 : h1 -> A2
   Operand G2 = op1(seg_bwd(g2, C2, ly.A2, C2, C2, ly.bn[1], tr), T);
-  RET_IF(linear_wgrad(G2, op1(seg_act(ly.A1, H, 0, H, ly.bn[0], 0, tr), T), ly.u0 + 1, T, st));
+  RET_IF(linear_wgrad(G2, op1(seg_act(ly.A1, H, 0, H, ly.bn[0], 0, tr), T), ly.u0 + 1, T));
   RET_IF(linear_dgrad(G2, ly.u0 + 1, g1, H, T, ly.A1, H, ly.bn[0], true, nullptr, 0, tr, st));
   // net1.0 : gathered concat -> A1
   Operand G1 = op1(seg_bwd(g1, H, ly.A1, H, H, ly.bn[0], tr), T);
-  RET_IF(linear_wgrad(G1, layer_input(gi, tr), ly.u0 + 0, T, st));
+  RET_IF(linear_wgrad(G1, layer_input(gi, tr), ly.u0 + 0, T));
   RET_IF(linear_dgrad(G1, ly.u0 + 0, dG[slot], 3 * D, T, nullptr, 0, -1, false, nullptr, 0, tr, st));
-  RET_IF(join_side(st));      // (pairing / side-stream modes: their wgrads are launched before the next layer starts)
   // deterministic mode with shared (recurrent) weights: the layers' wgrads add into the SAME dW, so they run as separate
   // launches in stream order instead of side by side in one
   if (tn_per_layer || (g_sln_deterministic && cfg.recurrent) || rec) RET_IF(flush_deferred(ly.net == 0 ? 1 : 0, st));     // (a group runs a layer's wgrads on its side stream, next to the following layers' dgrad chain)
@@ -846,7 +761,6 @@ int SlnVae::loss(const float* bp, const float* ap, const float* mu_, const float
 // Backward of decoder(): expects dbp (padded) and dlogits filled.
 int SlnVae::decoder_backward(hipStream_t st) {
   const bool tr = dec_training;
-  ev_next = 0;
   tn_slot_next[0] = 0;
   const size_t dec_doubles = stats_doubles - enc_stats_doubles;
   if (dec_doubles && !bulk_zeroed && !rec) RET_IF(sln_zero_async(gstats_base + enc_stats_doubles, dec_doubles * sizeof(double), st));
@@ -861,22 +775,21 @@ int SlnVae::decoder_backward(hipStream_t st) {
   begin_group();
   {
     Operand Gw = Gb; Gw.seg[0].len = cfg.box_dim; Gw.cols = cfg.box_dim;   // wgrad masks the padded columns itself
-    RET_IF(linear_wgrad(Gw, op1(seg_act(bnA1, H, 0, H, bn_head[4], 0, tr), O), unit_boxnet(1), O, st));
+    RET_IF(linear_wgrad(Gw, op1(seg_act(bnA1, H, 0, H, bn_head[4], 0, tr), O), unit_boxnet(1), O));
   }
   RET_IF(linear_dgrad(Gb, unit_boxnet(1), g_bn, H, O, bnA1, H, bn_head[4], true, nullptr, 0, tr, st));
-  RET_IF(linear_wgrad(Ga, op1(seg_act(anA1, H, 0, H, bn_head[5], 0, tr), O), unit_anglenet(1), O, st));
+  RET_IF(linear_wgrad(Ga, op1(seg_act(anA1, H, 0, H, bn_head[5], 0, tr), O), unit_anglenet(1), O));
   RET_IF(linear_dgrad(Ga, unit_anglenet(1), g_an, H, O, anA1, H, bn_head[5], true, nullptr, 0, tr, st));
   RET_IF(end_group(st));
   Operand G0 = op1(seg_bwd(g_bn, H, bnA1, H, H, bn_head[4], tr), O);
   const Operand XA = head_input(true, tr);
   Operand Ga0 = op1(seg_bwd(g_an, H, anA1, H, H, bn_head[5], tr), O);
   begin_group();
-  RET_IF(linear_wgrad(G0, XA, unit_boxnet(0), O, st));
+  RET_IF(linear_wgrad(G0, XA, unit_boxnet(0), O));
   RET_IF(linear_dgrad(G0, unit_boxnet(0), d_bx, WA, O, nullptr, 0, -1, false, nullptr, 0, tr, st));
-  RET_IF(linear_wgrad(Ga0, head_input(false, tr), unit_anglenet(0), O, st));
+  RET_IF(linear_wgrad(Ga0, head_input(false, tr), unit_anglenet(0), O));
   RET_IF(linear_dgrad(Ga0, unit_anglenet(0), d_ax, Wh, O, nullptr, 0, -1, false, nullptr, 0, tr, st));
   RET_IF(end_group(st));
-  RET_IF(join_side(st));      // g_bn / g_an / dbp / dlogits consumers done before g4 is produced
   // junction: obj_vecs feeds box_net (first W columns of d_bx) and angle_net
   {
     BnView v = view(ll.bn[3], 0, tr);
@@ -924,7 +837,6 @@ int SlnVae::decoder_backward(hipStream_t st) {
 // Backward of encoder(): expects dmu / dlv filled.
 int SlnVae::encoder_backward(hipStream_t st) {
   const bool tr = enc_training;
-  if (ev_next > 4096) ev_next = 0;
   tn_slot_next[1] = tn_slot_next[2] = 0;
   if (enc_stats_doubles && !bulk_zeroed) RET_IF(sln_zero_async(gstats_base, enc_stats_doubles * sizeof(double), st));
   RET_IF(refresh_transposes(st));
@@ -941,7 +853,7 @@ int SlnVae::encoder_backward(hipStream_t st) {
   for (int br = 0; br < 2; ++br) {
     const Operand Hh = op1(seg_act(hA2v[br], W, 0, W, bn_head[br * 2 + 1], 0, tr), O);
     Operand Gm = op1(seg_ident(dmu, E, c0v[br], nv[br], 0), O);
-    RET_IF(linear_wgrad(Gm, Hh, br * 4 + 2, O, st));
+    RET_IF(linear_wgrad(Gm, Hh, br * 4 + 2, O));
     RET_IF(linear_dgrad(Gm, br * 4 + 2, tmpv[br], W, O, nullptr, 0, -1, false, nullptr, 0, tr, st));
   }
   RET_IF(end_group(st));
@@ -950,7 +862,7 @@ int SlnVae::encoder_backward(hipStream_t st) {
     const int b1 = bn_head[br * 2 + 1];
     const Operand Hh = op1(seg_act(hA2v[br], W, 0, W, b1, 0, tr), O);
     Operand Gv = op1(seg_ident(dlv, E, c0v[br], nv[br], 0), O);
-    RET_IF(linear_wgrad(Gv, Hh, br * 4 + 3, O, st));
+    RET_IF(linear_wgrad(Gv, Hh, br * 4 + 3, O));
     RET_IF(linear_dgrad(Gv, br * 4 + 3, gh2v[br], W, O, hA2v[br], W, b1, true, tmpv[br], W, tr, st));
   }
   RET_IF(end_group(st));
@@ -958,7 +870,7 @@ int SlnVae::encoder_backward(hipStream_t st) {
   for (int br = 0; br < 2; ++br) {
     const int b0 = bn_head[br * 2], b1 = bn_head[br * 2 + 1];
     Operand G2 = op1(seg_bwd(gh2v[br], W, hA2v[br], W, W, b1, tr), O);
-    RET_IF(linear_wgrad(G2, op1(seg_act(hA1v[br], H, 0, H, b0, 0, tr), O), br * 4 + 1, O, st));
+    RET_IF(linear_wgrad(G2, op1(seg_act(hA1v[br], H, 0, H, b0, 0, tr), O), br * 4 + 1, O));
     RET_IF(linear_dgrad(G2, br * 4 + 1, gh1v[br], H, O, hA1v[br], H, b0, true, nullptr, 0, tr, st));
   }
   RET_IF(end_group(st));
@@ -966,11 +878,10 @@ int SlnVae::encoder_backward(hipStream_t st) {
   for (int br = 0; br < 2; ++br) {
     const int b0 = bn_head[br * 2];
     Operand G1 = op1(seg_bwd(gh1v[br], H, hA1v[br], H, H, b0, tr), O);
-    RET_IF(linear_wgrad(G1, XL, br * 4 + 0, O, st));
+    RET_IF(linear_wgrad(G1, XL, br * 4 + 0, O));
     RET_IF(linear_dgrad(G1, br * 4 + 0, d_x[br], W, O, nullptr, 0, -1, false, nullptr, 0, tr, st));
   }
   RET_IF(end_group(st));
-  RET_IF(join_side(st));
   {
     BnView v = view(ll.bn[3], 0, tr);
     RET_IF(sln_launch_mask_gstats(d_xb, W, d_xa, W, ll.A4, W, v, O, W, ll.g4, W,
@@ -1026,7 +937,7 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
     if (!it_zero_in_prologue) HIP_RET(hipMemsetAsync(zero_begin, 0, zero_bytes, st));
     bulk_zeroed = true;
     it_merge_bn = !no_merge && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);    // the two-half form hands the decoder's gradients out early
-    { static const bool one = !(std::getenv("SLN_TN_ONE_FLUSH") && std::getenv("SLN_TN_ONE_FLUSH")[0] == '0'); it_one_flush = one && defer && !tn_per_layer && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL); }
+    it_one_flush = one_flush && !tn_per_layer && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);
     if (!it_prologue && draw_eps) r = sln_launch_randn(eps_buf, (long)O * E, scalars, st);       // Sg2ScVAE_model.py:182
     if (!r) r = encoder_forward(step_training, st);
     if (!r) r = decoder_forward(nullptr, eps, step_training, st);
@@ -1045,7 +956,6 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
   bulk_zeroed = false;
   it_prologue = it_fused_loss = it_merge_bn = it_zero_in_prologue = it_one_flush = false;
   RET_IF(r);
-  RET_IF(join_tn_side(st));            // the parameter gradients are complete behind this point (all-reduce, optimizer)
   if (mode == TRAIN_FULL) {
     RET_IF(sln_launch_adam(t.flat_params, t.flat_grads, t.adam_m, t.adam_v, (long)t.n_flat, scalars, losses + 3, st));
     wt_fresh = false;                  // transposed copies are rebuilt at the start of the next backward
@@ -1082,6 +992,18 @@ int sln_vae_num_units(const SlnVaeConfig* c) {
   if (cfg_check(c) != 0) return cfg_check(c);
   const int nmod = c->recurrent ? 1 : c->gconv_num_layers;
   return 8 + 2 * nmod * 4 + 4;
+}
+
+// The schedule switches of an engine, read once at creation (h->L set), and its wgrad table store.
+static int read_engine_options(SlnVae* h) {
+  auto is = [](const char* name, char c) { const char* v = std::getenv(name); return v && v[0] == c; };
+  h->use_group = !is("SLN_NO_GROUP", '1');
+  h->no_merge = is("SLN_NO_MERGE", '1');
+  h->tn_per_layer = is("SLN_TN_PER_LAYER", '1');
+  h->one_flush = !is("SLN_TN_ONE_FLUSH", '0');
+  h->tn_slots = 3 * (2 * h->L + 8 > 16 ? 2 * h->L + 8 : 16);
+  h->tn_groups_store = new (std::nothrow) SlnVae::TnGroup[2 * (size_t)h->tn_slots * 2];
+  return h->tn_groups_store ? 0 : SLN_E_BADARG;
 }
 
 int sln_vae_create(const SlnVaeConfig* c, SlnVae** out) {
@@ -1130,24 +1052,7 @@ int sln_vae_create(const SlnVaeConfig* c, SlnVae** out) {
     else { head(4, h->unit_boxnet(0), H); head(5, h->unit_anglenet(0), H); }
   }
   if (!c->batch_norm) h->n_bn_enc = 0;
-  {
-    const char* ns = std::getenv("SLN_NO_SIDE_STREAM");
-    const char* nd = std::getenv("SLN_NO_DUAL");
-    h->use_dual = !(nd && nd[0] == '1');
-    const char* nf = std::getenv("SLN_NO_DEFER");
-    h->defer = !(nf && nf[0] == '1');
-    { const char* v = std::getenv("SLN_NO_MERGE"); h->no_merge = v && v[0] == '1'; }
-    h->tn_slots = 3 * (2 * h->L + 8 > 16 ? 2 * h->L + 8 : 16);
-    h->tn_groups_store = new (std::nothrow) SlnVae::TnGroup[2 * (size_t)h->tn_slots * 2];
-    if (!h->tn_groups_store) { delete h; return SLN_E_BADARG; }
-    { const char* v = std::getenv("SLN_TN_PER_LAYER"); h->tn_per_layer = v && v[0] == '1'; }
-    { const char* v = std::getenv("SLN_TN_SIDE"); h->tn_side = h->defer && v && v[0] == '1'; }
-    if (h->tn_side && !h->side && sln_side_stream_create(&h->side) != hipSuccess) { h->side = nullptr; h->tn_side = false; }
-    const char* ng = std::getenv("SLN_NO_GROUP");
-    h->use_group = h->use_dual && !(ng && ng[0] == '1');
-    h->use_side = !h->use_dual && !(ns && ns[0] == '1');
-    if (h->use_side && sln_side_stream_create(&h->side) != hipSuccess) { h->side = nullptr; h->use_side = false; }
-  }
+  if (read_engine_options(h) != 0) { delete h; return SLN_E_BADARG; }
   *out = h;
   return 0;
 }
@@ -1155,8 +1060,6 @@ int sln_vae_create(const SlnVaeConfig* c, SlnVae** out) {
 void sln_vae_destroy(SlnVae* h) {
   if (!h) return;
   h->drop_graphs();
-  for (auto e : h->events) (void)hipEventDestroy(e);
-  if (h->side) (void)hipStreamDestroy(h->side);
   delete[] h->tn_groups_store;
   for (auto& sl : h->tn_stage) {
     if (sl.done) { (void)hipEventSynchronize(sl.done); (void)hipEventDestroy(sl.done); }
@@ -1357,7 +1260,6 @@ int sln_vae_decoder_backward(SlnVae* h, const float* d_boxes_pred, const float* 
   if (d_angles_pred) RET_IF(sln_launch_log_softmax_bwd(h->angles_pred, d_angles_pred, h->dlogits, h->O, h->cfg.n_angle, st));
   else RET_IF(sln_zero_async(h->dlogits, sizeof(float) * (size_t)h->O * h->cfg.n_angle, st));
   RET_IF(h->decoder_backward(st));
-  RET_IF(h->join_tn_side(st));
   RET_IF(copy_out(dz, h->dz, (size_t)h->O * h->E, st));
   return 0;
 }
@@ -1369,7 +1271,6 @@ int sln_vae_encoder_backward(SlnVae* h, const float* d_mu, const float* d_logvar
   if (d_mu) RET_IF(copy_out(h->dmu, d_mu, n, st)); else RET_IF(sln_zero_async(h->dmu, n * sizeof(float), st));
   if (d_logvar) RET_IF(copy_out(h->dlv, d_logvar, n, st)); else RET_IF(sln_zero_async(h->dlv, n * sizeof(float), st));
   RET_IF(h->encoder_backward(st));
-  RET_IF(h->join_tn_side(st));
   return 0;
 }
 
@@ -1380,7 +1281,6 @@ int sln_vae_backward(SlnVae* h, void* stream) {
   RET_IF(sln_launch_latent_bwd(h->mu, h->logvar, h->eps_buf, h->dz, &h->scalars->kl_weight, h->O, h->E, h->cfg.use_ae,
                                h->dmu, h->dlv, st));
   RET_IF(h->encoder_backward(st));
-  RET_IF(h->join_tn_side(st));
   return 0;
 }
 
@@ -1539,18 +1439,8 @@ int sln_gconv_net_create(int D, int H, int Dout, int num_layers, int recurrent, 
     }
   }
   h->n_bn_enc = (int)h->bns.size();
-  h->use_dual = true; h->use_group = false; h->use_side = false;
-  {
-    const char* nf = std::getenv("SLN_NO_DEFER");
-    h->defer = !(nf && nf[0] == '1');
-    { const char* v = std::getenv("SLN_NO_MERGE"); h->no_merge = v && v[0] == '1'; }
-    h->tn_slots = 3 * (2 * h->L + 8 > 16 ? 2 * h->L + 8 : 16);
-    h->tn_groups_store = new (std::nothrow) SlnVae::TnGroup[2 * (size_t)h->tn_slots * 2];
-    if (!h->tn_groups_store) { delete h; return SLN_E_BADARG; }
-    { const char* v = std::getenv("SLN_TN_PER_LAYER"); h->tn_per_layer = v && v[0] == '1'; }
-    { const char* v = std::getenv("SLN_TN_SIDE"); h->tn_side = h->defer && v && v[0] == '1'; }
-    if (h->tn_side && !h->side && sln_side_stream_create(&h->side) != hipSuccess) { h->side = nullptr; h->tn_side = false; }
-  }
+  if (read_engine_options(h) != 0) { delete h; return SLN_E_BADARG; }
+  h->use_group = false;                       // no twin heads in a bare net
   *out = h;
   return 0;
 }
@@ -1611,7 +1501,6 @@ int sln_gconv_net_backward(SlnVae* h, const float* d_new_obj, const float* d_new
   hipStream_t st = (hipStream_t)stream;
   const int D = h->Dec, L = h->L;
   const bool tr = h->enc_training;
-  h->ev_next = 0;
   h->tn_slot_next[0] = h->tn_slot_next[1] = h->tn_slot_next[2] = 0;
   if (h->stats_doubles) RET_IF(sln_zero_async(h->gstats_base, h->stats_doubles * sizeof(double), st));
   h->wt_fresh = false;                      // the caller's optimizer owns the parameters: rebuild W^T every backward
@@ -1647,7 +1536,6 @@ int sln_gconv_net_backward(SlnVae* h, const float* d_new_obj, const float* d_new
     RET_IF(sln_launch_bn_param_grads(h->bn_table_dev, (int)h->bns.size(), maxc, h->cfg.recurrent ? 0 : 1, st));
   }
   RET_IF(h->flush_deferred(1, st));
-  RET_IF(h->join_tn_side(st));
   return 0;
 }
 
@@ -1938,7 +1826,7 @@ struct SlnVaeGroup {
           break;
         case L_NT: r = sln_launch_gemm_nt_small_multi(static_cast<const GemmNTArgs*>(l.tab), l.tiles, l.count, l.variant, l.gx, l.maxK, l.flops, st); break;
         case L_TN_MULTI: r = sln_launch_gemm_tn_multi(l.tn_probs, l.tn_meta, l.blocks, l.x2, l.xg, l.flops, st); break;
-        case L_TN_SINGLE: r = sln_launch_gemm_tn(singles[l.single].tn, -1, st); break;
+        case L_TN_SINGLE: r = sln_launch_gemm_tn(singles[l.single].tn, st); break;
         case L_SINGLE_STEP: r = run_single(singles[l.single], st); break;
         case SK_SCATTER_FWD: r = sln_launch_scatter_avg_fwd_multi(static_cast<const MScatterFwd*>(l.tab), l.count, l.variant, l.gx, l.gy, st); break;
         case SK_SCATTER_BWD: r = sln_launch_scatter_avg_bwd_multi(static_cast<const MScatterBwd*>(l.tab), l.count, l.variant, l.gx, l.gy, st); break;
@@ -2196,7 +2084,7 @@ int sln_linear_wgrad(const float* gq, const float* x, int R, int N, int K, float
   a.G.seg[0] = sg; a.G.nseg = 1; a.G.rows = R; a.G.cols = N;
   a.X.seg[0] = sx; a.X.nseg = 1; a.X.rows = R; a.X.cols = K;
   a.dW = dW; a.db = db; a.lddw = K; a.R = R; a.Nout = N; a.Kin = K;
-  return sln_launch_gemm_tn(a, -1, (hipStream_t)stream);
+  return sln_launch_gemm_tn(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

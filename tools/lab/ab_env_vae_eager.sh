@@ -1,5 +1,5 @@
 #!/bin/bash
-# same-box A/B of environment settings on the VAE leg, bench flags after "--":  tools/lab/ab_env_vae_eager.sh "SLN_TN_SIDE=1" ... -- --no-graph
+# same-box A/B of environment settings on the VAE leg, bench flags after "--":  tools/lab/ab_env_vae_eager.sh "SLN_TN_PER_LAYER=1" ... -- --no-graph
 envs=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
 for v in "${envs[@]}"; do
   env $v timeout 300 python bench.py --full --no-render --no-spade --no-graph-build --no-refine --no-sampling --no-dropin --no-cpu --large-batches= --steps 200 --warmup 20 --prof-steps 0 "$@" 2>/dev/null | python -c "
