@@ -90,6 +90,38 @@ class SlnVaeGroupIO(C.Structure):
                [(n, C.c_void_p) for n in ("z", "boxes_pred", "angles_pred", "d_boxes_pred", "d_angles_pred", "dz", "sgd_step")]
 
 
+# Descriptions of the GEMM test hooks (sln_debug_gemm_*): mirrors of SlnDbg* in include/sln_hip.h, checked against
+# sln_debug_gemm_sizes by tests/test_gemm_ref_host.py
+class SlnDbgBn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("sums", "gsums", "gamma", "beta", "rmean", "rvar")] + \
+               [("cstride", C.c_int), ("mode", C.c_int), ("n_rows", C.c_float), ("eps", C.c_float)]
+
+
+class SlnDbgSeg(C.Structure):
+    _fields_ = [("x1", C.c_void_p), ("x2", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("ld1", "ld2", "c1", "c2", "len", "which", "coef", "pad_")] + [("bn", SlnDbgBn)]
+
+
+class SlnDbgOperand(C.Structure):
+    _fields_ = [("seg", SlnDbgSeg * 3), ("idx_a", C.c_void_p), ("idx_b", C.c_void_p), ("nseg", C.c_int), ("pad_", C.c_int)]
+
+
+class SlnDbgGemmNT(C.Structure):
+    _fields_ = [("A", SlnDbgOperand)] + [(n, C.c_void_p) for n in ("W", "bias", "Y", "addend", "xprev", "osums", "ogsums")] + \
+               [("obn", SlnDbgBn)] + \
+               [(n, C.c_int) for n in ("M", "N", "K", "ldw", "ldy", "ycol0", "ldadd", "addcol0", "ocstride", "ldx", "xcol0", "epi", "tile",
+                                       "pad_")]
+
+
+class SlnDbgGemmTN(C.Structure):
+    _fields_ = [("G", SlnDbgOperand), ("X", SlnDbgOperand), ("dW", C.c_void_p), ("db", C.c_void_p), ("sgd_step", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("lddw", "R", "Nout", "Kin", "rows_per_block", "pad_")]
+
+
+class SlnDbgNTRoute(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("body", "multi", "amode", "threads")]
+
+
 # name -> (restype, argtypes); every symbol include/sln_hip.h declares must be listed here
 # (tests/test_abi.py checks the header against this table and against the built library).
 SIGNATURES = {
@@ -148,6 +180,10 @@ SIGNATURES = {
     "sln_linear_forward": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int, C.c_void_p,
                                      C.c_int, C.c_void_p]),
     "sln_linear_wgrad": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_void_p]),
+    "sln_debug_gemm_nt": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "sln_debug_gemm_tn": (C.c_int, [C.POINTER(SlnDbgGemmTN), C.c_int, C.c_int, C.c_void_p]),
+    "sln_debug_gemm_nt_route": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.POINTER(SlnDbgNTRoute)]),
+    "sln_debug_gemm_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "sln_project_faces": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p]),
     "sln_project_faces_backward": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p,
                                              c_f32p, C.c_void_p]),

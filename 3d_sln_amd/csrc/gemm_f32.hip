@@ -29,8 +29,9 @@
 #include "vae_multi.h"
 namespace {
 // 64 x 64 tiles with a BatchNorm operand or a masked epilogue run with four helper wavefronts (512 threads, see gemm_nt_body)
+constexpr bool nt_coef_helpers(int amode, int epi) { return amode != 2 || epi == EPI_MASK; }      // there is a coefficient table to build
 template <int BM, int BN, int AMODE, int EPI>
-constexpr bool nt_helpers() { return BM == 64 && BN == 64 && (AMODE != 2 || EPI == EPI_MASK); }
+constexpr bool nt_helpers() { return BM == 64 && BN == 64 && nt_coef_helpers(AMODE, EPI); }
 template <int BM, int BN, int WM, int WN, int AMODE, int EPI, int MULTI>
 __global__ __launch_bounds__((nt_helpers<BM, BN, AMODE, EPI>() ? 512 : 256)) void gemm_nt_kernel(const GemmNTArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -40,7 +41,7 @@ __global__ __launch_bounds__((nt_helpers<BM, BN, AMODE, EPI>() ? 512 : 256)) voi
 }
 
 template <int AMODE, int EPI>
-constexpr bool nt_helpers2() { return AMODE != 2 || EPI == EPI_MASK; }      // there is a coefficient table to build
+constexpr bool nt_helpers2() { return nt_coef_helpers(AMODE, EPI); }
 template <int J, int AMODE, int EPI>
 __global__ __launch_bounds__((nt_helpers2<AMODE, EPI>() ? 512 : 256)) void gemm_nt16_kernel(const GemmNTArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -76,8 +77,14 @@ __global__ __launch_bounds__((nt_helpers<64, 64, AMODE, EPI>() ? 512 : 256)) voi
 int sln_gemm_init();
 namespace {
 
+// Which kernel an NT launch runs: decided in ONE place (nt_route), carried out by the launchers below.  A launcher whose compiled
+// workgroup size differs from the route's refuses to launch, so what sln_debug_gemm_nt_route reports is what runs.
+enum { NT_BODY_64 = 0, NT_BODY_128x64 = 1, NT_BODY_128 = 2, NT_BODY_16J3 = 3, NT_BODY_16J5 = 4, NT_BODY_SMALL = 5, NT_BODY_SMALL3 = 6 };
+struct NtRoute { int body, multi, amode, threads; };      // multi: 0 one segment, 1 boundaries on k-tiles, 2 a boundary inside a k-tile
+
 template <int AMODE, int EPI, int NSEG = 1>
-int launch_nt_small(const GemmNTArgs& a, hipStream_t st) {
+int launch_nt_small(const GemmNTArgs& a, const NtRoute& rt, hipStream_t st) {
+  if (rt.threads != (nt_helpers2<AMODE, EPI>() ? 512 : 256)) return -3;
   const size_t smem = nt_small_smem_bytes(a.K);
   const int grid = sln_cdiv(a.M, 32) * sln_cdiv(a.N, 32);
   if (grid <= 0) return 0;
@@ -89,7 +96,8 @@ int launch_nt_small(const GemmNTArgs& a, hipStream_t st) {
 }
 
 template <int J, int AMODE, int EPI>
-int launch_nt16(const GemmNTArgs& a, hipStream_t st) {
+int launch_nt16(const GemmNTArgs& a, const NtRoute& rt, hipStream_t st) {
+  if (rt.threads != (nt_helpers2<AMODE, EPI>() ? 512 : 256)) return -3;
   const size_t smem = nt16_smem_bytes(a.K, J);
   const int grid = sln_cdiv(a.M, 64) * sln_cdiv(a.N, 32 * J);
   if (grid <= 0) return 0;
@@ -100,30 +108,64 @@ int launch_nt16(const GemmNTArgs& a, hipStream_t st) {
 }
 
 template <int BM, int BN, int WM, int WN, int AMODE, int EPI>
-int launch_nt(const GemmNTArgs& a, hipStream_t st) {
-  const int kpad = (a.K + 31) & ~31;
+int launch_nt(const GemmNTArgs& a, const NtRoute& rt, hipStream_t st) {
   const size_t smem = nt_smem_bytes(a.K, BM, BN, WM);
   const int grid = sln_cdiv(a.M, BM) * sln_cdiv(a.N, BN);
   if (grid <= 0) return 0;
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
   constexpr int NTHR = nt_helpers<BM, BN, AMODE, EPI>() ? 512 : 256;
-  if (a.A.nseg > 1 && nt_unaligned(a)) {
+  if (rt.threads != NTHR) return -3;
+  if (rt.multi == 2) {
     if constexpr (BM == 64 && BN == 64) hipLaunchKernelGGL((gemm_nt_kernel<64, 64, WM, WN, AMODE, EPI, 2>), dim3(grid), dim3(NTHR), smem, st, a);
-    else return -2;   // SLN_E_UNSUPPORTED (sln_launch_gemm_nt forces tile 0 for such operands)
+    else return -2;   // SLN_E_UNSUPPORTED (nt_route forces the 64 x 64 tile for such operands)
   }
-  else if (a.A.nseg > 1) hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, AMODE, EPI, 1>), dim3(grid), dim3(NTHR), smem, st, a);
+  else if (rt.multi == 1) hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, AMODE, EPI, 1>), dim3(grid), dim3(NTHR), smem, st, a);
   else hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, AMODE, EPI, 0>), dim3(grid), dim3(NTHR), smem, st, a);
   SLN_CHECK_LAUNCH();
   return 0;
 }
 
 template <int AMODE, int EPI>
-int dispatch_nt_tile(const GemmNTArgs& a, hipStream_t st, int tile) {
-  switch (tile) {
-    case 1: return launch_nt<128, 64, 2, 2, AMODE, EPI>(a, st);
-    case 2: return launch_nt<128, 128, 2, 2, AMODE, EPI>(a, st);
-    default: return launch_nt<64, 64, 2, 2, AMODE, EPI>(a, st);
+int launch_nt_route(const GemmNTArgs& a, const NtRoute& rt, hipStream_t st) {
+  switch (rt.body) {
+    case NT_BODY_SMALL: return launch_nt_small<AMODE, EPI>(a, rt, st);
+    case NT_BODY_SMALL3: return launch_nt_small<AMODE, EPI, 3>(a, rt, st);
+    case NT_BODY_16J3: return launch_nt16<3, AMODE, EPI>(a, rt, st);
+    case NT_BODY_16J5: return launch_nt16<5, AMODE, EPI>(a, rt, st);
+    case NT_BODY_128x64: return launch_nt<128, 64, 2, 2, AMODE, EPI>(a, rt, st);
+    case NT_BODY_128: return launch_nt<128, 128, 2, 2, AMODE, EPI>(a, rt, st);
+    case NT_BODY_64: return launch_nt<64, 64, 2, 2, AMODE, EPI>(a, rt, st);
+    default: return -1;
   }
+}
+
+// The dispatcher's decision.  tile: -1 = choose, 0 / 1 / 2 = the 64 x 64 / 128 x 64 / 128 x 128 body.
+NtRoute nt_route(const GemmNTArgs& a, int epi, int tile) {
+  static const bool no_small = std::getenv("SLN_NO_SMALL_NT") != nullptr;
+  NtRoute r;
+  r.amode = nt_amode(a); r.multi = 0;
+  // stand-alone launches only: a grouped launch (gemm_group.hip) keeps the 64 x 64 body.  Sharing a grid with another problem's
+  // blocks, the small body's 4x more workgroups pay 4x the prologues on a busy chip (measured with a wgrad's blocks next to a
+  // dgrad's on every CU: 28.8 -> 30.3 us on average)
+  if (tile < 0 && !no_small && nt_wants_small(a)) r.body = NT_BODY_SMALL;
+  else if (tile < 0 && !no_small && nt_wants_small3(a)) { r.body = NT_BODY_SMALL3; r.multi = 1; }      // the gathered concat of a graph of a few rows
+  else {
+    // widths that leave 64 x 64 tiles with a ragged last round (N = 640: 2.5 tiles per CU at 64 graphs, N = 384: 1.5) run on
+    // 64 x 160 / 64 x 96 tiles of 16 x 16 MFMAs - one workgroup per CU, see gemm_nt_body16
+    const int J16 = tile < 0 ? nt16_pick(a) : 0;
+    if (J16 == 3) r.body = NT_BODY_16J3;
+    else if (J16 == 5) r.body = NT_BODY_16J5;
+    else {
+      if (tile < 0) tile = nt_heuristic_tile(a);
+      const bool unaligned = a.A.nseg > 1 && nt_unaligned(a);
+      if (unaligned) tile = 0;        // the per-thread segment choice exists for the 64x64 tile only
+      r.body = tile == 1 ? NT_BODY_128x64 : (tile == 2 ? NT_BODY_128 : NT_BODY_64);
+      r.multi = a.A.nseg > 1 ? (unaligned ? 2 : 1) : 0;
+    }
+  }
+  const bool big = r.body == NT_BODY_128x64 || r.body == NT_BODY_128;      // no helper wavefronts (nt_helpers)
+  r.threads = !big && nt_coef_helpers(r.amode, epi) ? 512 : 256;
+  return r;
 }
 
 template <int BM, int BN, int WM, int WN, bool G_X2, bool XG>
@@ -222,54 +264,15 @@ int sln_gemm_init() {
 
 int sln_launch_gemm_nt(const GemmNTArgs& a, int epi, int tile, hipStream_t st) {
   SlnProfScope prof(SLN_FAM_GEMM_NT, 2.0 * a.M * a.N * a.K, st);
-  static const bool no_small = std::getenv("SLN_NO_SMALL_NT") != nullptr;
-  const int amode = nt_amode(a);
+  const NtRoute rt = nt_route(a, epi, tile);
   // SLN_NT_LOG=1: one line per launch on stderr (tools/lab/nt_by_shape.sh joins them, in order, with a kernel trace)
   static const bool nt_log = std::getenv("SLN_NT_LOG") != nullptr;
-  if (nt_log) std::fprintf(stderr, "NTLOG M=%d N=%d K=%d amode=%d epi=%d nseg=%d\n", a.M, a.N, a.K, amode, epi, a.A.nseg);
-  // stand-alone launches only: a grouped launch (gemm_group.hip) keeps the 64 x 64 body.  Sharing a grid with another problem's
-  // blocks, the small body's 4x more workgroups pay 4x the prologues on a busy chip (measured with a wgrad's blocks next to a
-  // dgrad's on every CU: 28.8 -> 30.3 us on average)
-  if (tile < 0 && !no_small && nt_wants_small(a)) {
-#define SLN_DISPATCH_S(AM)                                                            \
-    if (amode == AM) {                                                                \
-      if (epi == EPI_MASK) return launch_nt_small<AM, EPI_MASK>(a, st);               \
-      if (epi == EPI_STATS) return launch_nt_small<AM, EPI_STATS>(a, st);             \
-      return launch_nt_small<AM, EPI_PLAIN>(a, st);                                   \
-    }
-    SLN_DISPATCH_S(0) SLN_DISPATCH_S(1) SLN_DISPATCH_S(2)
-#undef SLN_DISPATCH_S
-  }
-  if (tile < 0 && !no_small && nt_wants_small3(a)) {          // the gathered concat of a graph of a few rows
-#define SLN_DISPATCH_S3(AM)                                                           \
-    if (amode == AM) {                                                                \
-      if (epi == EPI_MASK) return launch_nt_small<AM, EPI_MASK, 3>(a, st);            \
-      if (epi == EPI_STATS) return launch_nt_small<AM, EPI_STATS, 3>(a, st);          \
-      return launch_nt_small<AM, EPI_PLAIN, 3>(a, st);                                \
-    }
-    SLN_DISPATCH_S3(0) SLN_DISPATCH_S3(1) SLN_DISPATCH_S3(2)
-#undef SLN_DISPATCH_S3
-  }
-  if (tile < 0) {
-    // widths that leave 64 x 64 tiles with a ragged last round (N = 640: 2.5 tiles per CU at 64 graphs, N = 384: 1.5) run on
-    // 64 x 160 / 64 x 96 tiles of 16 x 16 MFMAs - one workgroup per CU, see gemm_nt_body16
-    const int J16 = nt16_pick(a);
-#define SLN_DISPATCH_16(J, AM)                                                        \
-    if (J16 == J && amode == AM) {                                                    \
-      if (epi == EPI_MASK) return launch_nt16<J, AM, EPI_MASK>(a, st);                \
-      if (epi == EPI_STATS) return launch_nt16<J, AM, EPI_STATS>(a, st);              \
-      return launch_nt16<J, AM, EPI_PLAIN>(a, st);                                    \
-    }
-    SLN_DISPATCH_16(3, 0) SLN_DISPATCH_16(3, 1) SLN_DISPATCH_16(3, 2) SLN_DISPATCH_16(5, 0) SLN_DISPATCH_16(5, 1) SLN_DISPATCH_16(5, 2)
-#undef SLN_DISPATCH_16
-  }
-  if (tile < 0) tile = nt_heuristic_tile(a);
-  if (a.A.nseg > 1 && nt_unaligned(a)) tile = 0;        // the per-thread segment choice exists for the 64x64 tile only
+  if (nt_log) std::fprintf(stderr, "NTLOG M=%d N=%d K=%d amode=%d epi=%d nseg=%d\n", a.M, a.N, a.K, rt.amode, epi, a.A.nseg);
 #define SLN_DISPATCH(AM)                                                              \
-  if (amode == AM) {                                                                  \
-    if (epi == EPI_MASK) return dispatch_nt_tile<AM, EPI_MASK>(a, st, tile);          \
-    if (epi == EPI_STATS) return dispatch_nt_tile<AM, EPI_STATS>(a, st, tile);        \
-    return dispatch_nt_tile<AM, EPI_PLAIN>(a, st, tile);                              \
+  if (rt.amode == AM) {                                                               \
+    if (epi == EPI_MASK) return launch_nt_route<AM, EPI_MASK>(a, rt, st);             \
+    if (epi == EPI_STATS) return launch_nt_route<AM, EPI_STATS>(a, rt, st);           \
+    return launch_nt_route<AM, EPI_PLAIN>(a, rt, st);                                 \
   }
   SLN_DISPATCH(0) SLN_DISPATCH(1) SLN_DISPATCH(2)
 #undef SLN_DISPATCH
@@ -458,4 +461,127 @@ extern "C" int sln_debug_tn_plan(const int* R, const int* Nout, const int* Kin, 
     items[3 * b] = it.prob < 0 ? -1 : probs[it.prob].lddw; items[3 * b + 1] = it.tile; items[3 * b + 2] = it.chunk;
   }
   return blocks;
+}
+
+// ---- test hooks: an arbitrary operand through the dispatchers above (include/sln_hip.h) ----------------------------------------
+#include "sln_hip.h"
+namespace {
+
+// what a BatchNorm view must carry for the coefficients `coef` reads out of it
+bool dbg_bn(const SlnDbgBn& d, int coef, BnView& v) {
+  std::memset(&v, 0, sizeof(v));
+  v.sums = d.sums; v.gsums = d.gsums; v.gamma = d.gamma; v.beta = d.beta; v.rmean = d.rmean; v.rvar = d.rvar;
+  v.cstride = d.cstride; v.mode = d.mode; v.n_rows = d.n_rows; v.eps = d.eps;
+  v.rn = 1.0 / (double)(d.n_rows > 0.f ? d.n_rows : 1.f);          // on the host, as the engine does
+  if (coef == SLN_COEF_IDENT || d.mode == SLN_BN_NONE) return d.mode >= SLN_BN_NONE && d.mode <= SLN_BN_EVAL;
+  const bool bwd = coef == SLN_COEF_BWD;
+  if (d.mode == SLN_BN_TRAIN) return d.gamma && d.sums && d.cstride > 0 && d.n_rows >= 1.f && (bwd ? d.gsums != nullptr : d.beta != nullptr);
+  if (d.mode == SLN_BN_EVAL) return d.gamma && d.rvar && (bwd || (d.beta && d.rmean));
+  return false;
+}
+
+// gather_ok: whether segments may be row-gathered; x2_ok: whether a second source is read at all
+bool dbg_operand(const SlnDbgOperand& d, int rows, int cols, bool gather_ok, bool x2_ok, Operand& op) {
+  std::memset(&op, 0, sizeof(op));
+  if (d.nseg < 1 || d.nseg > 3 || rows <= 0) return false;
+  int tot = 0;
+  for (int s = 0; s < d.nseg; ++s) {
+    const SlnDbgSeg& g = d.seg[s];
+    Seg& o = op.seg[s];
+    if (!g.x1 || g.len <= 0 || (g.len & 3)) return false;      // (a boundary inside a k-tile: the MULTI = 2 form, nt_route)
+    if ((g.ld1 & 3) || (g.c1 & 3) || g.c1 < 0 || g.ld1 < g.c1 + g.len) return false;
+    if (g.coef < SLN_COEF_IDENT || g.coef > SLN_COEF_BWD || g.which < 0 || g.which > 2) return false;
+    if (g.which && (!gather_ok || !(g.which == 1 ? d.idx_a : d.idx_b))) return false;
+    if (g.x2) {
+      if (!x2_ok || g.coef != SLN_COEF_BWD || (g.ld2 & 3) || (g.c2 & 3) || g.c2 < 0 || g.ld2 < g.c2 + g.len) return false;
+    } else if (g.coef == SLN_COEF_BWD && g.bn.mode == SLN_BN_TRAIN) return false;      // p1 multiplies the pre-activation
+    if (g.coef == SLN_COEF_BWD && !x2_ok) return false;
+    o.x1 = g.x1; o.x2 = g.x2; o.ld1 = g.ld1; o.ld2 = g.ld2; o.c1 = g.c1; o.c2 = g.c2; o.len = g.len; o.which = g.which; o.coef = g.coef;
+    if (!dbg_bn(g.bn, g.coef, o.bn)) return false;
+    tot += g.len;
+  }
+  if (tot != cols) return false;
+  op.idx_a = d.idx_a; op.idx_b = d.idx_b; op.nseg = d.nseg; op.rows = rows; op.cols = cols;
+  return true;
+}
+
+bool dbg_nt(const SlnDbgGemmNT& d, GemmNTArgs& a) {
+  std::memset(&a, 0, sizeof(a));
+  if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.epi < EPI_PLAIN || d.epi > EPI_MASK || d.tile < -1 || d.tile > 2) return false;
+  if (!dbg_operand(d.A, d.M, d.K, true, true, a.A)) return false;
+  if (!d.W || !d.Y || (d.ldw & 3) || d.ldw < d.K || d.ycol0 < 0 || d.ldy < d.ycol0 + d.N) return false;
+  if (d.addend && (d.addcol0 < 0 || d.ldadd < d.addcol0 + d.N)) return false;
+  if ((d.epi == EPI_STATS && d.osums) || (d.epi == EPI_MASK && d.ogsums)) { if (d.ocstride < d.N) return false; }
+  if (d.epi == EPI_MASK) {
+    if (!d.xprev || d.xcol0 < 0 || d.ldx < d.xcol0 + d.N || !dbg_bn(d.obn, SLN_COEF_FWD, a.obn)) return false;
+  } else if (!dbg_bn(d.obn, SLN_COEF_IDENT, a.obn)) return false;
+  a.W = d.W; a.bias = d.bias; a.Y = d.Y; a.ldy = d.ldy; a.ycol0 = d.ycol0; a.M = d.M; a.N = d.N; a.K = d.K; a.ldw = d.ldw;
+  a.addend = d.addend; a.ldadd = d.ldadd; a.addcol0 = d.addcol0; a.osums = d.osums; a.ocstride = d.ocstride;
+  a.ldx = d.ldx; a.xcol0 = d.xcol0; a.xprev = d.xprev; a.ogsums = d.ogsums;
+  return true;
+}
+
+bool dbg_tn(const SlnDbgGemmTN& d, GemmTNArgs& a) {
+  std::memset(&a, 0, sizeof(a));
+  if (d.R <= 0 || d.Nout <= 0 || d.Kin <= 0 || !d.dW || d.lddw < d.Kin) return false;
+  if (!dbg_operand(d.G, d.R, d.Nout, false, true, a.G)) return false;       // the gradient operand is addressed by plain rows
+  if (!dbg_operand(d.X, d.R, d.Kin, true, false, a.X)) return false;        // the input operand has one source
+  a.dW = d.dW; a.db = d.db; a.lddw = d.lddw; a.R = d.R; a.Nout = d.Nout; a.Kin = d.Kin;
+  a.rows_per_block = d.rows_per_block; a.sgd_step = d.sgd_step;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int sln_debug_gemm_sizes(int* out, int max) {
+  const int sz[6] = {(int)sizeof(SlnDbgBn), (int)sizeof(SlnDbgSeg), (int)sizeof(SlnDbgOperand), (int)sizeof(SlnDbgGemmNT),
+                     (int)sizeof(SlnDbgGemmTN), (int)sizeof(SlnDbgNTRoute)};
+  for (int i = 0; out && i < 6 && i < max; ++i) out[i] = sz[i];
+  return 6;
+}
+
+extern "C" int sln_debug_gemm_nt_route(const SlnDbgGemmNT* desc, SlnDbgNTRoute* out) {
+  GemmNTArgs a;
+  if (!desc || !out || !dbg_nt(*desc, a)) return SLN_E_BADARG;
+  const NtRoute rt = nt_route(a, desc->epi, desc->tile);
+  out->body = rt.body; out->multi = rt.multi; out->amode = rt.amode; out->threads = rt.threads;
+  return 0;
+}
+
+extern "C" int sln_debug_gemm_nt(const SlnDbgGemmNT* desc, int n, int* grouped, void* stream) {
+  if (!desc || n < 1 || n > 2) return SLN_E_BADARG;
+  GemmNTArgs nt[2]; int epi[2] = {0, 0};
+  for (int i = 0; i < n; ++i) { if (!dbg_nt(desc[i], nt[i])) return SLN_E_BADARG; epi[i] = desc[i].epi; }
+  hipStream_t st = (hipStream_t)stream;
+  if (grouped) *grouped = 0;
+  if (n == 2) {
+    const int r = sln_launch_gemm_group(nt, epi, 2, st);
+    if (r != 1) { if (grouped && !r) *grouped = 1; return r; }
+  }
+  for (int i = 0; i < n; ++i) { const int r = sln_launch_gemm_nt(nt[i], epi[i], desc[i].tile, st); if (r) return r; }
+  return 0;
+}
+
+extern "C" int sln_debug_gemm_tn(const SlnDbgGemmTN* desc, int n, int multi, void* stream) {
+  if (!desc || n < 1 || n > SLN_TN_MULTI_MAX || (!multi && n != 1)) return SLN_E_BADARG;
+  std::vector<GemmTNArgs> probs((size_t)n);
+  for (int i = 0; i < n; ++i) if (!dbg_tn(desc[i], probs[(size_t)i])) return SLN_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (!multi) return sln_launch_gemm_tn(probs[0], st);
+  if (sln_capturing(st)) return SLN_E_CAPTURE;
+  std::vector<TnMultiMeta> meta(1);
+  int blocks = 0; bool x2 = false, xg = false; double flops = 0.0;
+  if (sln_tn_multi_plan(probs.data(), n, meta.data(), &blocks, &x2, &xg, &flops)) return SLN_E_BADARG;
+  GemmTNArgs* dprobs = nullptr; TnMultiMeta* dmeta = nullptr;
+  const size_t pbytes = sizeof(GemmTNArgs) * (size_t)n;
+  int r = (int)hipMalloc((void**)&dprobs, pbytes);
+  if (!r) r = (int)hipMalloc((void**)&dmeta, sizeof(TnMultiMeta));
+  if (!r) r = (int)hipMemcpy(dprobs, probs.data(), pbytes, hipMemcpyHostToDevice);
+  if (!r) r = (int)hipMemcpy(dmeta, meta.data(), sizeof(TnMultiMeta), hipMemcpyHostToDevice);
+  if (!r) r = sln_launch_gemm_tn_multi(dprobs, dmeta, blocks, x2, xg, flops, st);
+  const int rs = (int)hipStreamSynchronize(st);         // the table must outlive the launch
+  if (!r) r = rs;
+  if (dprobs) (void)hipFree(dprobs);
+  if (dmeta) (void)hipFree(dmeta);
+  return r;
 }

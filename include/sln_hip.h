@@ -297,6 +297,80 @@ int sln_linear_forward(const float* x, int M, int K, const float* W, const float
 /*   dW[N,K] += g[R,N]^T x[R,K];  db[N] += colsum(g) */
 int sln_linear_wgrad(const float* g, const float* x, int R, int N, int K, float* dW, float* db, void* stream);
 
+/* Test hooks of the fused GEMM family (csrc/gemm_f32.hip, gemm_group.hip): an ARBITRARY operand through the engine's own
+ * dispatcher.  The descriptions are plain-C mirrors of the argument blocks in csrc/sln_gemm.h / sln_common.h; all pointers are
+ * device pointers.  Operand value of logical column c of a segment, row r:
+ *     v = max(c0 * x1[r', c1 + c] + c1coef * x2[r', c2 + c] + c2coef, floor),   r' = r | idx_a[r] | idx_b[r]  (which = 0 | 1 | 2)
+ * with the coefficients of `coef` (0 identity, 1 BatchNorm forward + ReLU, 2 BatchNorm forward, 3 BatchNorm backward
+ * dX = p0 g + p1 x + p2 with g = x1 and x = x2) taken from the segment's BatchNorm view.  The hooks check what the engine
+ * guarantees by construction and return SLN_E_BADARG without launching otherwise: 1..3 segments, every len > 0 and a multiple of 4
+ * (a segment but the last that is no multiple of 32 puts a boundary inside a k-tile: box_net's form, which only the 64x64 body
+ * takes - the dispatcher sends it there), the lens adding up to K (NT) / Nout, Kin (TN), ld / first columns multiples of 4 (rows
+ * are read as float4), pointers present where a mode reads them, G never gathered.  1 / n_rows is taken on the host. */
+typedef struct SlnDbgBn {
+  const double* sums;   /* [2][cstride]: sum x, sum x^2 over n_rows rows (mode 1) */
+  const double* gsums;  /* [2][cstride]: sum g, sum g * xhat (coef 3, mode 1) */
+  const float* gamma;
+  const float* beta;
+  const float* rmean;   /* mode 2 */
+  const float* rvar;
+  int cstride;
+  int mode;             /* 0 none, 1 train (statistics from sums), 2 eval (running statistics) */
+  float n_rows;
+  float eps;
+} SlnDbgBn;
+typedef struct SlnDbgSeg {
+  const float* x1;
+  const float* x2;
+  int ld1, ld2, c1, c2, len, which, coef, pad_;
+  SlnDbgBn bn;          /* aligned with the segment's first column */
+} SlnDbgSeg;
+typedef struct SlnDbgOperand {
+  SlnDbgSeg seg[3];
+  const int* idx_a;
+  const int* idx_b;
+  int nseg, pad_;
+} SlnDbgOperand;
+/* Y[:, ycol0 .. ycol0 + N) = op(A) W^T + bias + addend[:, addcol0 ..); epi 1: osums[2][ocstride] += column sums of y, y^2;
+ * epi 2: y *= [scale * xprev[:, xcol0 + col] + shift > 0] (obn's forward coefficients, aligned with output column 0) and
+ * ogsums[2][ocstride] += column sums of y, y * xhat.  tile: -1 the dispatcher's choice, 0 / 1 / 2 = 64x64 / 128x64 / 128x128. */
+typedef struct SlnDbgGemmNT {
+  SlnDbgOperand A;
+  const float* W;
+  const float* bias;
+  float* Y;
+  const float* addend;
+  const float* xprev;
+  double* osums;
+  double* ogsums;
+  SlnDbgBn obn;
+  int M, N, K, ldw, ldy, ycol0, ldadd, addcol0, ocstride, ldx, xcol0, epi, tile, pad_;
+} SlnDbgGemmNT;
+/* dW[Nout, Kin] += op(G)^T op(X), db += colsum(op(G)); with sgd_step (device pointer to the step) dW / db are the PARAMETERS and
+ * receive -step * (the gradient).  rows_per_block <= 0: the launcher's choice. */
+typedef struct SlnDbgGemmTN {
+  SlnDbgOperand G, X;
+  float* dW;
+  float* db;
+  const float* sgd_step;
+  int lddw, R, Nout, Kin, rows_per_block, pad_;
+} SlnDbgGemmTN;
+/* body: 0 64x64, 1 128x64, 2 128x128, 3 16x16-MFMA J = 3, 4 16x16-MFMA J = 5, 5 32x32 split-K one segment, 6 32x32 split-K
+ * three segments; multi: 0 one segment, 1 boundaries on k-tiles, 2 a boundary inside a k-tile; amode: 0 per-column affine,
+ * 1 two sources, 2 identity; threads: workgroup size (512 with helper wavefronts). */
+typedef struct SlnDbgNTRoute { int body, multi, amode, threads; } SlnDbgNTRoute;
+/* n = 1: sln_launch_gemm_nt.  n = 2: the grouped launch, and two separate launches when the pair cannot share a kernel - as the
+ * engine does; *grouped (may be NULL) then says which happened. */
+int sln_debug_gemm_nt(const SlnDbgGemmNT* desc, int n, int* grouped, void* stream);
+/* multi == 0 (n must be 1): sln_launch_gemm_tn.  multi != 0 (1 <= n <= 64): the planner and the one-launch-per-pass kernel; the
+ * problem table lives in device memory the hook owns and frees after synchronising the stream. */
+int sln_debug_gemm_tn(const SlnDbgGemmTN* desc, int n, int multi, void* stream);
+/* Host only: the kernel sln_launch_gemm_nt would run for this description (the launcher's own decision function). */
+int sln_debug_gemm_nt_route(const SlnDbgGemmNT* desc, SlnDbgNTRoute* out);
+/* sizeof of the description structs, in the order SlnDbgBn, SlnDbgSeg, SlnDbgOperand, SlnDbgGemmNT, SlnDbgGemmTN, SlnDbgNTRoute;
+ * returns how many there are (fills at most max). */
+int sln_debug_gemm_sizes(int* out, int max);
+
 
 /* =============================================================================================
  * B. Differentiable rasterizer  (third-party `neural_renderer`, un-vendored; reference call sites
