@@ -122,6 +122,48 @@ class SlnDbgNTRoute(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("body", "multi", "amode", "threads")]
 
 
+# Descriptions of the VAE kernel test hooks (sln_debug_vae_*), checked against sln_debug_vae_sizes by tests/test_vae_ref_host.py
+class SlnDbgCsr(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("s", "p", "o", "deg", "invdeg", "rowptr", "cursor", "ent")] + [("T", C.c_int), ("O", C.c_int)]
+
+
+class SlnDbgEdge(C.Structure):
+    _fields_ = [("g", SlnDbgCsr), ("bn", SlnDbgBn)] + [(n, C.c_void_p) for n in ("a", "b", "c", "out", "gsums")] + \
+               [(n, C.c_int) for n in ("kind", "lda", "ldb", "ldc", "ldo", "H", "D", "rows", "cols", "col0", "cstride", "masked")]
+
+
+class SlnDbgLoss(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("boxes", "boxes_pred", "angles", "logits", "angles_pred", "mu", "logvar", "eps", "dz", "d_logprob",
+                                          "kl_weight", "acc", "losses", "d_boxes_pred", "d_logits", "dmu", "dlogvar")] + \
+               [(n, C.c_int) for n in ("kind", "O", "box_dim", "n_angle", "n_z", "use_ae", "ld_dbp", "acc_prezeroed", "from_logits", "pad_")]
+
+
+class SlnDbgBnEntry(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("sums", "gsums", "rmean", "rvar", "nbt", "dgamma", "dbeta")] + \
+               [(n, C.c_int) for n in ("cstride", "C", "rows", "pad_")]
+
+
+class SlnDbgTranspose(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(n, C.c_int) for n in ("rows", "cols", "dst_ld", "pad_")]
+
+
+class SlnDbgEmbed(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("objs", "attrs", "angles", "boxes", "obj_emb", "attr_emb", "angle_emb", "wb", "bb", "mu", "logvar", "eps",
+                                          "z_in", "z", "x0", "dx0", "d_obj_emb", "d_attr_emb", "d_angle_emb", "d_wb", "d_bb", "dz", "idx", "src",
+                                          "dst", "src2", "dst2", "st_objs", "st_attrs", "st_angles", "st_boxes", "attrs32", "deg", "err",
+                                          "zero_ptr")] + [("zero_bytes", C.c_int64)] + \
+               [(n, C.c_int) for n in ("kind", "O", "n_obj", "n_attr", "n_box", "n_angle", "box_dim", "n_z", "use_ae", "z_in_x0", "rows_obj",
+                                       "rows_attr", "rows_angle", "ld", "col0", "n", "table_rows", "T", "n2", "pad_")]
+
+
+class SlnDbgOpt(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("params", "grads", "m", "v", "total_loss")] + [("pro", C.POINTER(SlnDbgEmbed))] + \
+               [("n", C.c_int64), ("step", C.c_int64), ("seed", C.c_uint64), ("offset", C.c_uint64)] + \
+               [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps")] + [("kind", C.c_int), ("calls", C.c_int)] + \
+               [("out_step", C.c_int64), ("out_offset", C.c_uint64), ("out_bc1", C.c_float), ("out_bc2", C.c_float), ("out_skip", C.c_int),
+                ("pad_", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/sln_hip.h declares must be listed here
 # (tests/test_abi.py checks the header against this table and against the built library).
 SIGNATURES = {
@@ -184,6 +226,13 @@ SIGNATURES = {
     "sln_debug_gemm_tn": (C.c_int, [C.POINTER(SlnDbgGemmTN), C.c_int, C.c_int, C.c_void_p]),
     "sln_debug_gemm_nt_route": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.POINTER(SlnDbgNTRoute)]),
     "sln_debug_gemm_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "sln_debug_vae_csr": (C.c_int, [c_i64p, C.c_int, C.c_int, C.c_int, C.POINTER(SlnDbgCsr), C.c_void_p, C.c_void_p]),
+    "sln_debug_vae_edge": (C.c_int, [C.POINTER(SlnDbgEdge), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "sln_debug_vae_loss": (C.c_int, [C.POINTER(SlnDbgLoss), C.c_void_p]),
+    "sln_debug_vae_tables": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sln_debug_vae_embed": (C.c_int, [C.POINTER(SlnDbgEmbed), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "sln_debug_vae_opt": (C.c_int, [C.POINTER(SlnDbgOpt), C.c_void_p]),
+    "sln_debug_vae_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "sln_project_faces": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p]),
     "sln_project_faces_backward": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p,
                                              c_f32p, C.c_void_p]),

@@ -464,11 +464,10 @@ extern "C" int sln_debug_tn_plan(const int* R, const int* Nout, const int* Kin, 
 }
 
 // ---- test hooks: an arbitrary operand through the dispatchers above (include/sln_hip.h) ----------------------------------------
-#include "sln_hip.h"
-namespace {
+#include "sln_debug.h"
 
-// what a BatchNorm view must carry for the coefficients `coef` reads out of it
-bool dbg_bn(const SlnDbgBn& d, int coef, BnView& v) {
+// what a BatchNorm view must carry for the coefficients `coef` reads out of it (shared with vae_debug.hip)
+bool sln_dbg_bn(const SlnDbgBn& d, int coef, BnView& v) {
   std::memset(&v, 0, sizeof(v));
   v.sums = d.sums; v.gsums = d.gsums; v.gamma = d.gamma; v.beta = d.beta; v.rmean = d.rmean; v.rvar = d.rvar;
   v.cstride = d.cstride; v.mode = d.mode; v.n_rows = d.n_rows; v.eps = d.eps;
@@ -479,6 +478,8 @@ bool dbg_bn(const SlnDbgBn& d, int coef, BnView& v) {
   if (d.mode == SLN_BN_EVAL) return d.gamma && d.rvar && (bwd || (d.beta && d.rmean));
   return false;
 }
+
+namespace {
 
 // gather_ok: whether segments may be row-gathered; x2_ok: whether a second source is read at all
 bool dbg_operand(const SlnDbgOperand& d, int rows, int cols, bool gather_ok, bool x2_ok, Operand& op) {
@@ -497,7 +498,7 @@ bool dbg_operand(const SlnDbgOperand& d, int rows, int cols, bool gather_ok, boo
     } else if (g.coef == SLN_COEF_BWD && g.bn.mode == SLN_BN_TRAIN) return false;      // p1 multiplies the pre-activation
     if (g.coef == SLN_COEF_BWD && !x2_ok) return false;
     o.x1 = g.x1; o.x2 = g.x2; o.ld1 = g.ld1; o.ld2 = g.ld2; o.c1 = g.c1; o.c2 = g.c2; o.len = g.len; o.which = g.which; o.coef = g.coef;
-    if (!dbg_bn(g.bn, g.coef, o.bn)) return false;
+    if (!sln_dbg_bn(g.bn, g.coef, o.bn)) return false;
     tot += g.len;
   }
   if (tot != cols) return false;
@@ -513,8 +514,8 @@ bool dbg_nt(const SlnDbgGemmNT& d, GemmNTArgs& a) {
   if (d.addend && (d.addcol0 < 0 || d.ldadd < d.addcol0 + d.N)) return false;
   if ((d.epi == EPI_STATS && d.osums) || (d.epi == EPI_MASK && d.ogsums)) { if (d.ocstride < d.N) return false; }
   if (d.epi == EPI_MASK) {
-    if (!d.xprev || d.xcol0 < 0 || d.ldx < d.xcol0 + d.N || !dbg_bn(d.obn, SLN_COEF_FWD, a.obn)) return false;
-  } else if (!dbg_bn(d.obn, SLN_COEF_IDENT, a.obn)) return false;
+    if (!d.xprev || d.xcol0 < 0 || d.ldx < d.xcol0 + d.N || !sln_dbg_bn(d.obn, SLN_COEF_FWD, a.obn)) return false;
+  } else if (!sln_dbg_bn(d.obn, SLN_COEF_IDENT, a.obn)) return false;
   a.W = d.W; a.bias = d.bias; a.Y = d.Y; a.ldy = d.ldy; a.ycol0 = d.ycol0; a.M = d.M; a.N = d.N; a.K = d.K; a.ldw = d.ldw;
   a.addend = d.addend; a.ldadd = d.ldadd; a.addcol0 = d.addcol0; a.osums = d.osums; a.ocstride = d.ocstride;
   a.ldx = d.ldx; a.xcol0 = d.xcol0; a.xprev = d.xprev; a.ogsums = d.ogsums;

@@ -371,6 +371,103 @@ int sln_debug_gemm_nt_route(const SlnDbgGemmNT* desc, SlnDbgNTRoute* out);
  * returns how many there are (fills at most max). */
 int sln_debug_gemm_sizes(int* out, int max);
 
+/* Test hooks of the VAE path's non-GEMM kernels (csrc/vae_kernels.hip) through their own launchers (csrc/vae_debug.hip).  All
+ * pointers are device pointers the caller allocates.  The hooks return SLN_E_BADARG without launching for what the launchers
+ * assume by construction (pointers present where a form reads them, positive widths, strides that hold the logical width,
+ * statistics strides that hold the columns); a misaligned edge argument is passed on and comes back as the launcher's own -2. */
+typedef struct SlnDbgCsr {   /* GraphCsr: s, p, o [T]; deg, invdeg, cursor [O]; rowptr [O + 1]; ent [2 T] */
+  int* s; int* p; int* o; int* deg; float* invdeg; int* rowptr; int* cursor; int* ent;
+  int T, O;
+} SlnDbgCsr;
+/* sln_launch_graph_prep: triples [T, 3] int64 (s, p, o), or edges [T, 2] (s, o) with edges_only; deg_is_zero: the caller has
+ * cleared deg.  *err (may be NULL) receives bit 1 for an id out of range. */
+int sln_debug_vae_csr(const int64_t* triples, int num_preds, int edges_only, int deg_is_zero, const SlnDbgCsr* g, int* err, void* stream);
+/* kind 0 scatter_avg_fwd: out[O = rows, H] from a = A2 (lda), bn, g
+ *      1 scatter_avg_bwd: out = g2 [T = rows, ldc] from a = dM [O, H], b = dP (ldb, first column col0; may be NULL), c = A2 (ldc)
+ *      2 gather_bwd:      out (ldo) [O = rows, D] from a = dG (lda), b = add1 (ldb; may be NULL), c = xprev (ldc), masked
+ *      3 mask_gstats:     out (ldo) [rows, cols] from a = d1 (lda), b = d2 (ldb; may be NULL), c = xprev (ldc)
+ *      4 bn_relu_apply:   out (ldo) [rows, cols] = relu(bn(a[:, col0 + c]))
+ *      5 add2:            out (ldo) [rows, cols] = a + b
+ * gsums [2][cstride] (may be NULL) receives += the column sums of the result and of result * xhat (kinds 1, 2 masked, 3). */
+typedef struct SlnDbgEdge {
+  SlnDbgCsr g;
+  SlnDbgBn bn;
+  const float* a; const float* b; const float* c;
+  float* out;
+  double* gsums;
+  int kind, lda, ldb, ldc, ldo, H, D, rows, cols, col0, cstride, masked;
+} SlnDbgEdge;
+/* multi == 0 (n must be 1): the single-room launcher.  multi != 0 (kinds 0, 1, 2, 3, 5; 1 <= n <= 64 rooms of one kind): the
+ * planner per room and ONE *_multi launch off a room table in device memory the hook owns and frees after synchronising the
+ * stream; rooms whose planners disagree on the variant are refused with SLN_E_UNSUPPORTED (the engine splits such a step).
+ * *variant (may be NULL): what the planner chose, -1 for the single-room launch. */
+int sln_debug_vae_edge(const SlnDbgEdge* desc, int n, int multi, int* variant, void* stream);
+/* kind 0 loss (LossArgs); 1 log_softmax: angles_pred = log_softmax(logits); 2 log_softmax_bwd: d_logits from angles_pred and
+ * d_logprob; 3 latent_bwd: dmu, dlogvar from mu, logvar, eps, dz, kl_weight */
+typedef struct SlnDbgLoss {
+  const float* boxes; const float* boxes_pred; const int64_t* angles; const float* logits; float* angles_pred;
+  const float* mu; const float* logvar; const float* eps; const float* dz; const float* d_logprob; const float* kl_weight;
+  double* acc; float* losses; float* d_boxes_pred; float* d_logits; float* dmu; float* dlogvar;
+  int kind, O, box_dim, n_angle, n_z, use_ae, ld_dbp, acc_prezeroed, from_logits, pad_;
+} SlnDbgLoss;
+int sln_debug_vae_loss(const SlnDbgLoss* desc, void* stream);
+typedef struct SlnDbgBnEntry {   /* BnTableEntry; rows -1 / -2: rows_t / rows_o of the call */
+  const double* sums; const double* gsums; float* rmean; float* rvar; int64_t* nbt; float* dgamma; float* dbeta;
+  int cstride, C, rows, pad_;
+} SlnDbgBnEntry;
+typedef struct SlnDbgTranspose { const float* src; float* dst; int rows, cols, dst_ld, pad_; } SlnDbgTranspose;   /* dst[c * dst_ld + r] = src[r * cols + c] */
+/* kind 0 bn_running_update, 1 bn_param_grads (entries: SlnDbgBnEntry [n], width: the largest C), 2 transpose_table (entries:
+ * SlnDbgTranspose [n], width: max_tiles).  `entries` is a HOST array; the hook uploads the table and frees it after synchronising. */
+int sln_debug_vae_tables(int kind, const void* entries_host, int n, int width, float momentum, int independent, int rows_t, int rows_o,
+                         void* stream);
+/* The embedding group.  kind 0 enc_assemble:     x0 [O, n_obj + n_attr + n_box + n_angle] (n_attr == 0: no attribute columns)
+ *      1 enc_assemble_bwd: the three tables, d_wb [n_box, box_dim] and d_bb [n_box] += from dx0; rows_* are the tables' row counts
+ *                          (all > 0 and at most 10 240 floats of tables: accumulated in LDS first; 0: plain atomics)
+ *      2 dec_assemble:     z [O, n_z] (may be NULL) = z_in, or mu (use_ae), or eps * exp(logvar / 2) + mu; x0 = [obj | attr | z]
+ *                          (z_in_x0 == 0: x0 = [obj | attr])
+ *      3 dec_assemble_bwd: the two tables += from dx0, dz [O, n_z] (may be NULL) = its z columns when z_in_x0
+ *      4 embed_gather_i32: dst [O, n] = src[idx[r], :]               (idx int32 [O])
+ *      5 embed_bwd_i32, 6 embed_bwd_i64: dst[idx[r], :] += src[r, col0 : col0 + n] (row stride ld); table_rows > 0 allows the
+ *                          LDS form (table_rows * n <= 8 192) and the deterministic one (sln_set_deterministic)
+ *      7 i64_to_i32:       dst int32 [O] = idx int64 [O]
+ *      8 stage_batch:      st_* = copies of objs / attrs / angles / boxes, attrs32, deg = 0, *err |= 2 / 4 / 8 for an object class /
+ *                          attribute / angle bin outside rows_obj / rows_attr / rows_angle (rows_attr == 0: attributes not looked at)
+ *      9 validate_ids:     *err as above (angles may be NULL)
+ * The index VALUES are the caller's to keep inside the tables: the hooks cannot see them.  T, src2, dst2, n2, zero_ptr and
+ * zero_bytes belong to the step prologue (sln_debug_vae_opt, kind 2) only. */
+typedef struct SlnDbgEmbed {
+  const int64_t* objs; const int64_t* attrs; const int64_t* angles; const float* boxes;
+  const float* obj_emb; const float* attr_emb; const float* angle_emb; const float* wb; const float* bb;
+  const float* mu; const float* logvar; const float* eps; const float* z_in; float* z;
+  float* x0; const float* dx0;
+  float* d_obj_emb; float* d_attr_emb; float* d_angle_emb; float* d_wb; float* d_bb; float* dz;
+  const void* idx; const float* src; void* dst; const float* src2; void* dst2;
+  int64_t* st_objs; int64_t* st_attrs; int64_t* st_angles; float* st_boxes; int* attrs32; int* deg; int* err;
+  void* zero_ptr; int64_t zero_bytes;
+  int kind, O, n_obj, n_attr, n_box, n_angle, box_dim, n_z, use_ae, z_in_x0, rows_obj, rows_attr, rows_angle, ld, col0, n, table_rows,
+      T, n2, pad_;
+} SlnDbgEmbed;
+/* multi as in sln_debug_vae_edge (kinds 2 - 6): the planner per room, one *_multi launch.  *variant: MV_ASM_BWD_* (kind 3),
+ * MV_EMBED_* (+ 4 for int64 indices; kinds 5, 6), 0 (kinds 2, 4); a planner that has no multi form for a room (deterministic mode or
+ * more than 8 192 rows in kind 3) and rooms of different variants are refused with SLN_E_UNSUPPORTED. */
+int sln_debug_vae_embed(const SlnDbgEmbed* desc, int n, int multi, int* variant, void* stream);
+/* kind 0 adam (params, grads, m, v [n]; total_loss may be NULL), 1 randn (params = the output [n]), 2 step_prologue (params = eps [n],
+ * may be NULL: no draw; pro = the encoder assembly as in kind 0 of SlnDbgEmbed, plus p0e [T, n] = src[idx] and p0d [T, n2] =
+ * src2[idx] into dst / dst2 (idx int32 [T]; T may be 0) and zero_bytes (a multiple of 16) cleared at zero_ptr (16-byte aligned; may be
+ * NULL)).  The hook owns a device AdamScalars filled from step .. offset, makes `calls` launches in a row on it and reports its
+ * contents afterwards. */
+typedef struct SlnDbgOpt {
+  float* params; const float* grads; float* m; float* v; const float* total_loss; const SlnDbgEmbed* pro;
+  int64_t n, step;
+  uint64_t seed, offset;
+  float lr, beta1, beta2, eps;
+  int kind, calls;
+  int64_t out_step; uint64_t out_offset; float out_bc1, out_bc2; int out_skip, pad_;
+} SlnDbgOpt;
+int sln_debug_vae_opt(SlnDbgOpt* desc, void* stream);
+/* sizeof of SlnDbgCsr, SlnDbgEdge, SlnDbgLoss, SlnDbgBnEntry, SlnDbgTranspose, SlnDbgOpt, SlnDbgEmbed; returns how many there are. */
+int sln_debug_vae_sizes(int* out, int max);
+
 
 /* =============================================================================================
  * B. Differentiable rasterizer  (third-party `neural_renderer`, un-vendored; reference call sites
