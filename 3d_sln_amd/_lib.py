@@ -299,6 +299,9 @@ SIGNATURES = {
     "sln_layout_cuboid_iou": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f32p,
                                         C.c_void_p, C.c_void_p]),
     "sln_layout_overlap": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, c_i64p, C.c_void_p]),
+    "sln_layout_plot": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "sln_layout_footprint_counts": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sln_refine_report": (C.c_int, [C.POINTER(SlnRefineLoss), c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p]),
     "sln_refine_report_scratch_doubles": (C.c_int, [C.c_int]),
     "sln_scene_live_channels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

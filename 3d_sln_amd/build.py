@@ -23,8 +23,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # placement: the torch expression it replaces rounds after every elementwise op
 # layout_iou: the cuboid corners as torch forms them; a cross product of a point with itself must be exactly 0
 # spade_input: the depth normalisation rounds after every float32 operation, as numpy does
+# layout_plot: the rings of layout_iou (csrc/layout_geom.h), bit for bit; edge functions that round after every operation
 PER_FILE = {"raster.hip": ["-ffp-contract=off"], "graph_build.hip": ["-ffp-contract=off"], "placement.hip": ["-ffp-contract=off"],
-            "layout_iou.hip": ["-ffp-contract=off"], "spade_input.hip": ["-ffp-contract=off"]}
+            "layout_iou.hip": ["-ffp-contract=off"], "spade_input.hip": ["-ffp-contract=off"], "layout_plot.hip": ["-ffp-contract=off"]}
 
 
 def sources():

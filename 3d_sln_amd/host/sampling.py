@@ -173,3 +173,29 @@ def heatmap_from_words(model, objs_in_scene, rels_in_scene, mean, cov, num_iter=
         counts = layout_counts(bp, container_size, True, out=counts)
         done += n
     return counts / counts.sum((1, 2), keepdim=True).clamp(min=1.0)
+
+
+def footprints_from_words(model, objs_in_scene, rels_in_scene, mean, cov, num_iter=20000, chunk=None, size=100, generator=None):
+    """``heatmap_from_words`` with footprints instead of centres: ``num_iter`` posterior samples of the scene are decoded in chunks and
+    every object's rotated footprint (the ring testing/test_plot2d.py:88-110 draws, with the decoded angle bin) is accumulated on the
+    device (``plot2d.layout_footprints``) -> counts [n + 1, size, size] int32: per object row and pixel the number of samples that
+    cover it.  The planes of rows that plot2d does not draw (the room row, do_not_vis classes) stay 0."""
+    from . import plot2d as _P
+    dev = next(model.parameters()).device
+    gkey = (tuple(objs_in_scene), tuple(rels_in_scene), str(dev))
+    if gkey not in _WORD_GRAPHS:
+        if len(_WORD_GRAPHS) > 8:
+            _WORD_GRAPHS.clear()
+        _WORD_GRAPHS[gkey] = scene_graph_from_words(objs_in_scene, rels_in_scene, device=dev)
+    objs, triples, attrs = _WORD_GRAPHS[gkey]
+    O = objs.shape[0]
+    rank, _ = _P.plot_tables(objs, VALID_CLASSES)
+    rr = torch.full((O,), O - 1, dtype=torch.int32, device=dev)
+    chunk = num_iter if chunk is None else chunk
+    counts, done = None, 0
+    while done < num_iter:
+        n = min(chunk, num_iter - done)
+        bp, ab, _ = sample_layouts(model, objs, triples, attrs, n_samples=n, mean=mean, cov=cov, generator=generator)
+        counts = _P.layout_footprints(bp, ab, rr, rank, size=size, counts=counts)
+        done += n
+    return counts

@@ -859,6 +859,27 @@ int sln_layout_cuboid_iou(const float* boxes, const float* angles, const float* 
  * of whole rooms; a room of more than 1024 rows (or a room_of_row table that is not as described above) gives vol_out = NaN. */
 int sln_layout_overlap(const float* boxes, const float* angles, const int32_t* room_of_row, const unsigned char* visible, int S, int O,
                        float thresh, double* vol_out, int64_t* pairs_out, void* stream);
+/* The top-down picture of testing/test_plot2d.py:9-141 (plot2d) for S layouts x n_rooms rooms in one launch.  boxes [S, O, 6], angles
+ * [S, O], room_of_row and room_id (int32 [O]) as in sln_layout_cuboid_iou.  A row's ring is the (x, z) corners of the cuboid above
+ * (:88-110 are the statements of get_boxes).  rank (int32 [O]) is the class's index in nyu_class_order (:25-29, at most 127), < 0 for
+ * a row that is not drawn (do_not_vis :74,86, room rows); rgb (uint32 [O]) is mapped_colors[nyu_class_orig.index(name)] (:30-71,122)
+ * packed r | g << 8 | b << 16 - both tables are the caller's, the kernel knows no vocabulary.  The image of a room is N x N over
+ * [0, 1]^2, the pixel of row r, column c centred at x = (c + 0.5) / N, z = (r + 0.5) / N (row 0 at z ~ 0: what `1 - z` :124 under
+ * matplotlib's y-up axes shows).  A pixel is covered by a ring q when the four edge functions (q[k+1].x - q[k].x)(z - q[k].z) -
+ * (q[k+1].z - q[k].z)(x - q[k].x) are all >= 0 or all <= 0 (either winding, edges inclusive, float32, contraction off); a ring whose
+ * shoelace sum is exactly 0 and a ring with a NaN coordinate cover nothing.  Among the drawn rows of the room that cover a pixel
+ * the greatest (rank, row) wins - the order sorted(zip(current_types, iter_idx)) paints in (:118-126).  winner (int32
+ * [S, n_rooms, N, N], or NULL) receives the winning row, -1 where nothing covers; image (uint8 [S, n_rooms, N, N, 3], or NULL; one of
+ * the two is needed, image needs rgb) its colour, the floor's (152, 223, 138) (:115-117) where nothing covers.  Rooms are staged
+ * 256 rows at a time, of any length.  1 <= N <= 1024, S <= 65535 per call, n_rooms <= 65535, O <= 2^24. */
+int sln_layout_plot(const float* boxes, const float* angles, const int32_t* room_of_row, const int32_t* room_id, const int32_t* rank,
+                    const uint32_t* rgb, int n_rooms, int S, int O, int N, int32_t* winner, unsigned char* image, void* stream);
+/* Footprint heat map: counts[o][r][c] (int32 [O, N, N]) += the number of the S layouts whose ring of row o covers pixel (r, c) (ring,
+ * pixel and coverage as above), for the rows with rank[o] >= 0; the planes of the other rows are not touched.  Where
+ * sln_layout_heatmap (testing/test_heatmap.py:80-99) counts an object's centre, this counts everywhere the object is.  Integer
+ * atomics only: exact, and the same from run to run.  1 <= N <= 1024, O <= 65535. */
+int sln_layout_footprint_counts(const float* boxes, const float* angles, const int32_t* room_of_row, const int32_t* rank, int S, int O,
+                                int N, int32_t* counts, void* stream);
 /* The refinement report of testing/test_render_refine.py:369-374 (what the reference pickles into bbox_rot_0.pkl) for the rooms of a
  * per_room descriptor (or the single image of a B = 1 one), after sln_refine_loss_forward on `image` with the same descriptor and
  * workspace and before the next one: report_out [B, 3] (float) = (iou, depth_l1, ce_last).
