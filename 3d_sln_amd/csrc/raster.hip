@@ -20,6 +20,7 @@
 #include <mutex>
 
 #include "../../include/sln_hip.h"
+#include "pmb_stamp.h"
 #include "sln_common.h"
 #include "sln_prof.h"
 
@@ -244,9 +245,12 @@ __global__ __launch_bounds__(256) void raster_tile_kernel(const FaceRec* __restr
     }
   }
   if (TEX && st_out != nullptr) {
-    // ... and scene_stats_kernel's (per-class depth sums in exact fixed point, visible-face marks, the wall's maximum depth): the
-    // tile's sums in LDS, one set of device atomics per tile.  Exact integer / power-of-two arithmetic: the statistics are the
-    // same bits as the separate pass gave, whatever the order of the tiles.
+    // ... and the per-image statistics of the class pass: the owner mark of the winning face (FaceRec::pad_[1], cleared by the prep
+    // kernel: see pixel_map_backward_kernel), the visible-class marks, and over the pixels inside a class's 0.1 mask the depth sum, the
+    // pixel count and the wall's maximum depth (models/diff_render.py:408-411).  Depth sums in 64-bit FIXED POINT (2^-32): depths are
+    // fp32 values below 16, i.e. multiples of 2^-30 down to 2^-7 - the integer sum is exact and does not depend on the order the lanes
+    // arrive in; as a double it is a multiple of 2^-32 below 2^21, so the cross-tile fp64 atomics are exact too.  The tile's sums in
+    // LDS, one set of device atomics per tile: the statistics are the same bits whatever the order of the tiles.
     __shared__ unsigned long long ssum[64]; __shared__ int scnt[64]; __shared__ int svis[64];
     __shared__ int s_wkey, s_wany;
     if (tid < 64) { ssum[tid] = 0ull; scnt[tid] = 0; svis[tid] = 0; }
@@ -377,7 +381,7 @@ __global__ __launch_bounds__(64) void depth_backward_face_kernel(const float* __
   // Block order (round 6).  xcd_images = B >= 8 (grid.x = 8 * ceil(B / 8) * F, depth_bwd_grid_x): consecutive workgroups go to
   // consecutive XCDs, XCD x walks the images x, x + 8, ... only (their maps stay in one L2) and face f of its images side by side, so
   // that every image's large faces are dispatched at the same point of the launch instead of the last image's starting when the
-  // others are done: 77.2 -> 59.7 us for 16 rooms.  xcd_images = 0: image-major, grid.x = B * F.  SLN_DEPTH_BWD_ORDER=0 (lab).
+  // others are done: 77.2 -> 59.7 us for 16 rooms.  xcd_images = 0: image-major, grid.x = B * F.
   const int lane = threadIdx.x;
   int b, fn;
   if (xcd_images > 0) {
@@ -445,17 +449,11 @@ __global__ __launch_bounds__(64) void depth_backward_face_kernel(const float* __
   }
 }
 
-// raster_tile_kernel's grid and its xcd_images argument (see the kernel): SLN_TILE_ORDER=0 (lab) keeps the (tiles, images) grid
-inline bool raster_tile_xcd(int B) {
-  static const bool off = [] { const char* e = std::getenv("SLN_TILE_ORDER"); return e != nullptr && e[0] == '0'; }();
-  return !off && B >= 8;
-}
+// raster_tile_kernel's grid and its xcd_images argument (see the kernel)
+inline bool raster_tile_xcd(int B) { return B >= 8; }
 inline dim3 raster_tile_grid(int tiles, int B) { return raster_tile_xcd(B) ? dim3((unsigned)((B + 7) / 8 * 8 * tiles)) : dim3(tiles, B); }
 inline int raster_tile_arg(int B) { return raster_tile_xcd(B) ? B : 0; }
-inline int depth_bwd_xcd(int B) {
-  static const bool off = [] { const char* e = std::getenv("SLN_DEPTH_BWD_ORDER"); return e != nullptr && e[0] == '0'; }();
-  return !off && B >= 8 ? B : 0;
-}
+inline int depth_bwd_xcd(int B) { return B >= 8 ? B : 0; }
 inline unsigned depth_bwd_grid_x(int B, int F) { return (unsigned)((long)(depth_bwd_xcd(B) ? (B + 7) / 8 * 8 : B) * F); }
 // Few (image, face) pairs leave the chip idle while the largest faces are walked: split their walks (see the two kernels).
 inline int small_batch_split(long units, int max_split, long budget = 32768) {
@@ -469,9 +467,9 @@ inline int small_batch_split(long units, int max_split, long budget = 32768) {
 // `budget` wavefronts (16 refinement rooms, 22 k faces: 247 -> us with the split of 8 the face count alone denied)
 // ... but only for images of FEW faces (<= 2 048: few faces over a fixed image area are big faces): the 16 x 4 000-face batch of
 // BASELINE config c3 went 0.596 -> 0.643 ms per batch with the split everywhere, 16 refinement rooms (1 400 faces each) 247 -> 130 us
+constexpr int DEPTH_SPLIT_FEW_FACES = 2048;
 inline int depth_bwd_split(long units, int F) {
-  static const int few = std::getenv("SLN_DEPTH_SPLIT_FACES") ? std::atoi(std::getenv("SLN_DEPTH_SPLIT_FACES")) : 2048;
-  return F <= few ? small_batch_split(units, 8, 1L << 20) : small_batch_split(units, 8);
+  return F <= DEPTH_SPLIT_FEW_FACES ? small_batch_split(units, 8, 1L << 20) : small_batch_split(units, 8);
 }
 inline unsigned pixel_map_grid_x(int B, int F);
 inline bool pixel_map_grid_ok(int B, int F) { return (long)(B >= 8 ? (B + 7) / 8 * 8 : B) * F * 6 < (1L << 31); }   // 32-bit workgroup ids in the kernel
@@ -662,22 +660,13 @@ __device__ __forceinline__ float pix_scale(float x, int is, bool pow2, float s2)
 // small faces had finished - the kernel ran as long as its largest face.  Units outside the edge's d0 range exit at
 // once; each unit adds its two partial sums to the face gradient with two atomics.
 constexpr int PMB_DC = 64;
-#ifndef PMB_ILP
-#define PMB_ILP 2            // windows of a row in flight per pass of phase 2a (same-box A/B of 1 / 2 / 3 / 4 / 8: 0.590 / 0.549 / 0.556 / 0.571 / 0.688 ms per 16-room batch)
-#endif
-#ifndef PMB_LONG
-#define PMB_LONG 64          // rows of at least this many pixels are scanned row by row (phase 2a); 0: every row flattened (16 / 32 / 48 / 64: 0.586 / 0.571 / 0.548 / 0.546 ms with two windows per pass)
-#endif
+constexpr int PMB_ILP = 2;   // windows of a row in flight per pass of phase 2a (same-box A/B of 1 / 2 / 3 / 4 / 8: 0.590 / 0.549 / 0.556 / 0.571 / 0.688 ms per 16-room batch)
+constexpr int PMB_LONG = 64; // rows of at least this many pixels are scanned row by row (phase 2a); 0: every row flattened (16 / 32 / 48 / 64: 0.586 / 0.571 / 0.548 / 0.546 ms with two windows per pass)
 // diff / dist of a contributing scan pixel: v_rcp_f32 (1 ulp) and a multiplication instead of the ~12-instruction IEEE division
 // sequence, twice per contributing pixel in a kernel bound by instruction issue (0.774 -> 0.750 ms per 16 rooms forward + backward).
 // The face gradient is a sum of thousands of such terms whose order already differs from the restatement's (lane partial sums,
-// atomics): the relative change is ~1e-7, three orders below the 1e-4 tolerance of the parity tests (which pass in both builds).
-// -DPMB_EXACT_DIV restores the division.
-#ifdef PMB_EXACT_DIV
-#define PMB_DIV(a, b) ((a) / (b))
-#else
-#define PMB_DIV(a, b) ((a) * __builtin_amdgcn_rcpf(b))
-#endif
+// atomics): the relative change is ~1e-7, three orders below the 1e-4 tolerance of the parity tests (which passed with the division too).
+__device__ __forceinline__ float PMB_DIV(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
 // Inside a unit the serial form of the edge walk (for each d0: load the face index under the edge, then scan) is a
 // chain of three dependent memory round trips per edge step.  Here the walk is flattened:
@@ -716,13 +705,6 @@ static bool pmb_wave64() {
 // (B * F, 6, scan split)
 inline unsigned pixel_map_grid_x(int B, int F) { return (unsigned)((long)(B >= 8 ? (B + 7) / 8 * 8 * 6 : B) * F); }
 inline unsigned pixel_map_grid_y(int B) { return B >= 8 ? 1u : 6u; }
-#ifdef PMB_STAMP
-// lab build only: per-workgroup clock sums (prologue, phase 1, phase 2a load waits / evaluation / passes / rows, phase 2b), one slot per
-// workgroup, read back by sln_lab_pmb_stamps
-constexpr int PMB_STAMP_SLOTS = 1 << 19;
-__device__ unsigned long long g_pmb_stamp[PMB_STAMP_SLOTS][10];      // [8], [9]: wall clock (100 MHz) at the start and the end
-#define PMB_T() ((unsigned long long)clock64())
-#endif
 template <typename PIX, bool POW2>
 __global__ __launch_bounds__(64) void pixel_map_backward_kernel(const float* __restrict__ faces, const FaceRec* __restrict__ vis,
                                                                 float* __restrict__ gfaces, int B, int F, int is, float eps, PIX pix) {
@@ -742,10 +724,8 @@ __global__ __launch_bounds__(64) void pixel_map_backward_kernel(const float* __r
   // (32-bit arithmetic: the first version did this mapping with 64-bit integers - four software divisions, ~600 scalar
   // instructions in front of every one of the 370 k workgroups of a 16-room batch, as many as all their scan windows issue)
   const int lane = threadIdx.x;
-#ifdef PMB_STAMP
-  const unsigned long long T_start = PMB_T(), W_start = (unsigned long long)wall_clock64();
-  unsigned long long T_p1 = 0, T_wait = 0, T_eval = 0, T_2b = 0, N_pass = 0, N_rows = 0, T_pro = 0;
-#endif
+  PmbStamp stamp;                               // clock stamps of the lab build (pmb_stamp.h): empty, and every call a no-op, otherwise
+  stamp.begin();
   unsigned bu, fnu; int ea;
   if (B >= 8) {
     // Order inside an XCD's share (round 6): its images one after the other, FACE-MAJOR - the six (edge, axis) units of a face side by
@@ -818,15 +798,11 @@ __global__ __launch_bounds__(64) void pixel_map_backward_kernel(const float* __r
   const int wfirst = 64 * (int)blockIdx.z, wstep = 64 * (int)gridDim.z;
   // an edge longer than PMB_DC steps takes several rounds (chunks) in the same wavefront: one workgroup per chunk filled the
   // grid with empty workgroups (three out of four), whose dispatch alone cost ~0.25 ms per batch of 16 rooms
-#ifdef PMB_STAMP
-  T_pro = PMB_T() - T_start;
-#endif
+  stamp.prologue_done();
   for (int c_from = d0_from; c_from <= d0_to; c_from += PMB_DC) {
   const int c_to = min(d0_to, c_from + PMB_DC - 1);
   PMB_SYNC();                                   // the LDS tables of the previous round are no longer read
-#ifdef PMB_STAMP
-  const unsigned long long T_c0 = PMB_T();
-#endif
+  stamp.round_start();
 
   // ---- phase 1: one edge step per lane ----
   const int d0 = c_from + lane;
@@ -876,9 +852,7 @@ __global__ __launch_bounds__(64) void pixel_map_backward_kernel(const float* __r
   s_ratio[lane] = make_float2(r0, r1);
   PMB_SYNC();
   const int W = s_pre[64];
-#ifdef PMB_STAMP
-  T_p1 += PMB_T() - T_c0;
-#endif
+  stamp.phase1_done();
 
   // ---- phase 2a: one row per pass of the wavefront (round 6) ----
   // Everything that describes the row - its step's crossing, ratios, reference record, first pixel, length - is wavefront-uniform
@@ -920,14 +894,10 @@ __global__ __launch_bounds__(64) void pixel_map_backward_kernel(const float* __r
         const float e0 = (((m_pos0 >> l) & 1ull) != 0ull) == (dir > 0) ? eps : -eps;
         const float e1 = (((m_pos1 >> l) & 1ull) != 0ull) == (dir > 0) ? eps : -eps;
         const float qs0 = q0 * s2, qs1 = q1 * s2;
-#ifdef PMB_STAMP
-        ++N_rows;
-#endif
+        stamp.row();
         for (int k = 0; k < len; k += 64 * PMB_ILP, ++widx) {
           if (gz > 1 && widx % gz != zme) continue;
-#ifdef PMB_STAMP
-          const unsigned long long T_a = PMB_T();
-#endif
+          stamp.pass_start();
           typename View::Loaded ld[PMB_ILP];
 #pragma unroll
           for (int u = 0; u < PMB_ILP; ++u) {
@@ -936,10 +906,7 @@ __global__ __launch_bounds__(64) void pixel_map_backward_kernel(const float* __r
           }
 #pragma unroll
           for (int u = 0; u < PMB_ILP; ++u) View::pin(ld[u]);
-#ifdef PMB_STAMP
-          const unsigned long long T_b = PMB_T();
-          T_wait += T_b - T_a; ++N_pass;
-#endif
+          stamp.loads_landed();
 #pragma unroll
           for (int u = 0; u < PMB_ILP; ++u) {
             const int t = k + 64 * u + lane;
@@ -968,17 +935,12 @@ __global__ __launch_bounds__(64) void pixel_map_backward_kernel(const float* __r
               }
             }
           }
-#ifdef PMB_STAMP
-          asm volatile("" : "+v"(acc0), "+v"(acc1));
-          T_eval += PMB_T() - T_b;
-#endif
+          stamp.eval_done(acc0, acc1);
         }
       }
     }
   }
-#ifdef PMB_STAMP
-  const unsigned long long T_2b0 = PMB_T();
-#endif
+  stamp.phase2b_start();
 
   // ---- phase 2b: the scan pixels of the remaining (short) rows of all steps, flattened ----
   // Few images (gridDim.z > 1, pixel_map_scan_split): the launch lasts as long as the longest walk - a wall edge is 64 steps
@@ -1016,21 +978,14 @@ __global__ __launch_bounds__(64) void pixel_map_backward_kernel(const float* __r
       }
     }
   }
-#ifdef PMB_STAMP
-  asm volatile("" : "+v"(acc0), "+v"(acc1));
-  T_2b += PMB_T() - T_2b0;
-#endif
+  stamp.phase2b_done(acc0, acc1);
   }   // rounds
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) { acc0 += __shfl_xor(acc0, off, 64); acc1 += __shfl_xor(acc1, off, 64); }
   if (lane == 0) {
     if (acc0 != 0.f) atomicAdd(gfaces + 9 * i + pi[0] * 3 + (1 - axis), acc0);
     if (acc1 != 0.f) atomicAdd(gfaces + 9 * i + pi[1] * 3 + (1 - axis), acc1);
-#ifdef PMB_STAMP
-    unsigned long long* o = g_pmb_stamp[((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) & (PMB_STAMP_SLOTS - 1)];
-    o[0] = PMB_T() - T_start; o[1] = T_pro; o[2] = T_p1; o[3] = T_wait; o[4] = T_eval; o[5] = N_pass; o[6] = T_2b; o[7] = N_rows;
-    o[8] = W_start; o[9] = (unsigned long long)wall_clock64();
-#endif
+    stamp.flush();
   }
 }
 
@@ -1156,12 +1111,6 @@ __global__ __launch_bounds__(64) void project_faces_bwd_det_kernel(const float* 
 }
 
 }  // namespace
-#ifdef PMB_STAMP
-extern "C" int sln_lab_pmb_stamps(unsigned long long* host, int clear) {
-  if (clear) { void* p = nullptr; if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_pmb_stamp)) != hipSuccess) return -1; return (int)hipMemset(p, 0, sizeof(g_pmb_stamp)); }
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_pmb_stamp), sizeof(g_pmb_stamp));
-}
-#endif
 
 // ====================================================================================================
 // C ABI
@@ -1354,51 +1303,6 @@ SceneSide* scene_side() {
     per_dev[dev] = s;
   }
   return per_dev[dev];
-}
-
-__global__ void scene_stats_kernel(const int32_t* __restrict__ fi_b, const float* __restrict__ val, const float* __restrict__ d_a,
-                                   const int32_t* __restrict__ cls, int F, int is, int NC, SceneStats* __restrict__ st,
-                                   FaceRec* __restrict__ rec) {
-  const int b = blockIdx.y;
-  const long plane = (long)is * is;
-  // Per-class depth sums in 64-bit FIXED POINT (2^-32): depths are fp32 values below 16, i.e. multiples of 2^-30 down to 2^-7 - the
-  // integer sum is exact and does not depend on the order the lanes arrive in (the LDS float atomics of rounds 1-2 did, at ulp level,
-  // and carried the rounding of a 65 536-term fp32 sum); as a double it is a multiple of 2^-32 below 2^21: the cross-block fp64
-  // atomics are exact too.  The statistics of the forward pass are order-independent in every mode.
-  __shared__ unsigned long long ssum[64]; __shared__ int scnt[64]; __shared__ int svis[64];
-  __shared__ int s_wkey, s_wany;        // the block's wall maximum: ONE pair of device atomics per block (every wall pixel - a third
-                                        // of a room image - used to issue its own pair on the same two words)
-  if (threadIdx.x < 64) { ssum[threadIdx.x] = 0ull; scnt[threadIdx.x] = 0; svis[threadIdx.x] = 0; }
-  if (threadIdx.x == 0) { s_wkey = (int)0x80000000; s_wany = 0; }
-  __syncthreads();
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < plane; p += (long)gridDim.x * blockDim.x) {
-    const long q = b * plane + p;
-    // the three streams of a pixel in one round trip (pinned: hipcc sinks each load behind the test that precedes its use)
-    int f = fi_b[q]; float v = val[3 * q]; float d = d_a[q];
-    asm volatile("" : "+v"(f), "+v"(v), "+v"(d));
-    if (f < 0) continue;
-    rec[(long)b * F + f].pad_[1] = 1;       // the face owns a pixel of the class pass (raster_prep_kernel cleared the flag): see pixel_map_backward_kernel
-    const int c = cls[(long)b * F + f];
-    if (c < 0 || c >= NC) continue;
-    svis[c] = 1;
-    if (!(class_image_value(v) > 0.1f)) continue;
-    const float dd = depth_value(d);
-    atomicAdd(&ssum[c], (unsigned long long)(long long)rint((double)dd * 4294967296.0)); atomicAdd(&scnt[c], 1);
-    if (c == 0) {                       // wall_max = max depth over the wall mask (models/diff_render.py:408-411)
-      s_wany = 1;
-      atomicMax(&s_wkey, fkey(dd));
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < NC && scnt[threadIdx.x] > 0) {
-    atomicAdd(&st[b].sum[threadIdx.x], (double)(long long)ssum[threadIdx.x] * (1.0 / 4294967296.0));
-    atomicAdd(&st[b].cnt[threadIdx.x], (double)scnt[threadIdx.x]);
-  }
-  if (threadIdx.x < NC && svis[threadIdx.x]) st[b].vis[threadIdx.x] = 1;
-  if (threadIdx.x == 0 && s_wany) {
-    atomicMax(&st[b].wall_any, 1);
-    atomicMax(&st[b].wall_key, s_wkey);
-  }
 }
 
 struct ComposeTabs { int chan[64]; int dch[64]; int owner[32]; float fill[32]; float wall; unsigned char live[72]; };
@@ -1658,9 +1562,7 @@ __device__ __forceinline__ void scene_bwd_grad_planes_body(const int bc, const i
     if (x < is && y < is) gT[(long)bc * plane + (long)x * is + y] = t[tx][r];
   }
 }
-#ifndef TABLES_TPB
-#define TABLES_TPB 2         // 32 x 32 tiles per workgroup of scene_bwd_tables_kernel (same-box, 16-room batch, 1 / 2 / 4 / 8: 0.4925 / 0.4855 / 0.4859 / 0.4949 ms)
-#endif
+constexpr int TABLES_TPB = 2;  // 32 x 32 tiles per workgroup of scene_bwd_tables_kernel (same-box, 16-room batch, 1 / 2 / 4 / 8: 0.4925 / 0.4855 / 0.4859 / 0.4949 ms)
 // Both tables the edge scans read - the per-pixel records and the class-gradient planes, each with its transpose - in ONE launch
 // (blockIdx.z < B: records of image z; above: plane (b, c) = z - B).  Round 5: they were two launches on two streams with an event
 // between them and the scan kernel; the scan kernel (the longest of the pass, on the critical path) started ~40 us after the
@@ -1773,19 +1675,8 @@ static int scene_forward_impl(const float* faces, const int32_t* face_class, int
     hipLaunchKernelGGL(scene_prep_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, faces, n, is, w.rec, w.bbox, w.ones, w.st, B);
   }
   const int tiles = sln_cdiv(is, TS) * sln_cdiv(is, TS);
-  static const bool tex_apart = std::getenv("SLN_SCENE_TEX_APART") != nullptr;       // lab: the texture sample as its own launch
-  if (tex_apart) {
-    hipLaunchKernelGGL((raster_tile_kernel<true>), raster_tile_grid(tiles, B), dim3(256), 0, st, w.rec, w.bbox, F, is, near_depth, near_rgb, far,
-                       w.fiA, w.wA, w.dA, w.fiB, w.wB, w.dB, (const float*)nullptr, (const float*)nullptr, 0, 0.f, (float*)nullptr,
-                       (const int32_t*)nullptr, 0, (SceneStats*)nullptr, raster_tile_arg(B));
-    hipLaunchKernelGGL(texture_sample_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, faces, w.ones, w.fiB, w.wB,
-                       w.dB, F, is, 2, tex_eps, npix, w.val);
-    // wall_max starts at -inf surrogate
-    hipLaunchKernelGGL(scene_stats_kernel, dim3(64, B), dim3(256), 0, st, w.fiB, w.val, w.dA, face_class, F, is, num_classes, w.st, w.rec);
-  } else {
-    hipLaunchKernelGGL((raster_tile_kernel<true, true>), raster_tile_grid(tiles, B), dim3(256), 0, st, w.rec, w.bbox, F, is, near_depth, near_rgb, far,
-                       w.fiA, w.wA, w.dA, w.fiB, w.wB, w.dB, faces, (const float*)w.ones, 2, tex_eps, w.val, face_class, num_classes, w.st, raster_tile_arg(B));
-  }
+  hipLaunchKernelGGL((raster_tile_kernel<true, true>), raster_tile_grid(tiles, B), dim3(256), 0, st, w.rec, w.bbox, F, is, near_depth, near_rgb, far,
+                     w.fiA, w.wA, w.dA, w.fiB, w.wB, w.dB, faces, (const float*)w.ones, 2, tex_eps, w.val, face_class, num_classes, w.st, raster_tile_arg(B));
   hipLaunchKernelGGL(scene_compose_kernel, dim3((unsigned)((plane + 255) / 256), B), dim3(256), 0, st, w.fiB, w.val, w.dA,
                      face_class, class_channel, class_depth_channel, F, is, num_classes, 70, w.st, final_out, live, null_mask);
   SLN_CHECK_LAUNCH();
@@ -1879,17 +1770,10 @@ int sln_scene_backward(const float* faces, const int32_t* face_class, int B, int
   // four small kernels run NEXT TO the tables launch and its per-face walk next to the start of the scans.  (Round 5 forked behind the
   // tables launch.  With the scan kernel in its round-5 dispatch order that was equal - 0.540 vs 0.538 ms per 16-room batch: the scans
   // ended in a 40 us tail of low occupancy that absorbed the depth chain wherever it started.  With the face-major order the tail is
-  // gone and the late fork costs: 0.549 vs 0.520 ms, same box.  SLN_SCENE_FORK_LATE=1 restores it.)
-  const int t32 = sln_cdiv(is, 32);
-  static const bool fork_late = std::getenv("SLN_SCENE_FORK_LATE") != nullptr;      // lab
-  auto tables = [&]() {
-    hipLaunchKernelGGL(scene_bwd_tables_kernel, dim3(sln_cdiv(t32, TABLES_TPB), t32, B + B * num_classes), dim3(256), 0, st, w.fiB, w.val, face_class, class_channel,
-                       grad_final, B, F, is, num_classes, 70, w.st, w.prec, w.precT, w.g, w.gT);
-  };
+  // gone and the late fork costs: 0.549 vs 0.520 ms, same box.)
   {
     const int e = sln_zero_async(grad_faces, sizeof(float) * 9 * (size_t)n, st);
     if (e != hipSuccess) return (int)e;
-    if (fork_late) tables();
   }
   hipStream_t sd_st = st;
   if (sd != nullptr) {
@@ -1898,7 +1782,9 @@ int sln_scene_backward(const float* faces, const int32_t* face_class, int B, int
     if (sd->stream != nullptr && hipEventRecord(sd->fork, st) == hipSuccess && hipStreamWaitEvent(sd->stream, sd->fork, 0) == hipSuccess) sd_st = sd->stream;
     else { sd = nullptr; side_lock.unlock(); }
   }
-  if (!fork_late) tables();
+  const int t32 = sln_cdiv(is, 32);
+  hipLaunchKernelGGL(scene_bwd_tables_kernel, dim3(sln_cdiv(t32, TABLES_TPB), t32, B + B * num_classes), dim3(256), 0, st, w.fiB, w.val, face_class, class_channel,
+                     grad_final, B, F, is, num_classes, 70, w.st, w.prec, w.precT, w.g, w.gT);
   struct Join {
     SceneSide* sd; hipStream_t st; hipError_t err;
     void run() {

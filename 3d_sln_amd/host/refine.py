@@ -19,7 +19,6 @@ What is replaced
 import ctypes as C
 import math
 import os
-import time
 
 import numpy as np
 import torch
@@ -724,15 +723,6 @@ class RefineBatch:
         L = _lib.lib()
         self.model, self.R, self.iters, self.lr = model, len(rooms), int(iters), float(learning_rate)
         R = self.R
-        _log = os.environ.get("SLN_REFINE_SETUP_LOG")
-        _t = [time.perf_counter()]
-
-        def tick(what):                              # lab: where the set-up time of a batch goes (synchronises: only with the switch)
-            if _log:
-                torch.cuda.synchronize()
-                now = time.perf_counter()
-                print("RefineBatch set-up: %-28s %7.2f ms" % (what, (now - _t[0]) * 1e3), flush=True)
-                _t[0] = now
         if R < 1:
             raise ValueError("RefineBatch needs at least one room")
         dev = model.flat_params.device
@@ -766,7 +756,6 @@ class RefineBatch:
             scenes.append(sc); targets.append(tgt); size_targets.append(sizes.detach().clone().contiguous())
             box_last[r] = rm["boxes"][-1].detach().float(); angle_last[r] = rm["angles"][-1].detach().float()
         self.z, self.scenes = z, scenes
-        tick("encoder, z, scenes, targets")
         self._report_all = report == "all"
         if report is None:
             self._report_at = None
@@ -793,14 +782,11 @@ class RefineBatch:
         # ---- the loss of all rooms: one descriptor, per-room normalisation ----
         self.loss = RefineLoss(torch.cat(targets, 0), per_room=True)
         del targets
-        tick("RefineLoss")
         # ---- R parameter copies, R engines, one launch program ----
         nflat = model.flat_params.numel()
         self.params = model.flat_params.detach().unsqueeze(0).repeat(R, 1).contiguous()
         self.grads = torch.zeros(R, nflat, **f32)
-        tick("parameter copies")
         self._engines = model.room_engines(self.params, self.grads, max(self.rows), max(int(rm["triples"].shape[0]) for rm in rooms))
-        tick("room engines (create + bind)")
         st = _lib.current_stream_ptr()
         self._keep = []
         for (h, _ws, _arr), rm in zip(self._engines, rooms):
@@ -831,7 +817,6 @@ class RefineBatch:
         torch.cuda.current_stream(dev).synchronize()          # the tables of the program are uploaded with blocking copies
         _lib.check(L.sln_vae_group_create(harr, R, C.byref(io), C.byref(g)), "sln_vae_group_create")
         self._group = g
-        tick("set_batch + group create")
         # ---- head / placement tables ----
         self.room_of_row = torch.cat([torch.full((n,), r, dtype=torch.int32) for r, n in enumerate(self.rows)]).to(dev)
         self.last_row = torch.tensor([a + n - 1 for a, n in zip(self.row0, self.rows)], dtype=torch.int32, device=dev)
@@ -887,12 +872,10 @@ class RefineBatch:
         #  the sparse scene pass leaves unwritten)
         if not os.environ.get("SLN_REFINE_ALL_PLANES") and L.sln_refine_loss_live_ok(C.byref(self.loss.desc)):
             self.loss.desc.live_planes = self.live.data_ptr()
-            if not os.environ.get("SLN_REFINE_NULL_MASK_APART"):       # (lab switch: the loss computes the null mask itself)
-                self.null_mask = torch.zeros(R, S, S, dtype=torch.uint8, device=dev)
-                self.loss.desc.null_mask = self.null_mask.data_ptr()
-            if not os.environ.get("SLN_REFINE_POOL_ONES"):             # (lab switch: pool the constant planes per room)
-                self._pooled_ones = self.loss.pooled_ones()
-                self.loss.desc.pooled_ones = self._pooled_ones.data_ptr()
+            self.null_mask = torch.zeros(R, S, S, dtype=torch.uint8, device=dev)
+            self.loss.desc.null_mask = self.null_mask.data_ptr()
+            self._pooled_ones = self.loss.pooled_ones()
+            self.loss.desc.pooled_ones = self._pooled_ones.data_ptr()
         self.one = torch.ones(1, **f32)
         self.losses = torch.zeros(max(self.iters, 1), R, **f32)
         rg = model.decoder_param_ranges()
@@ -928,7 +911,6 @@ class RefineBatch:
         # synchronises that stream: here, at set-up, not inside the first iteration's asynchronous calls (csrc/streams.hip)
         if not torch.cuda.is_current_stream_capturing():
             L.sln_side_stream_prepare(st)
-        tick("tables, buffers")
 
     def _first_iterate_sizes(self):
         """The size penalty holds every object to the size of the FIRST iterate (testing/test_render_refine.py:319-327: ``size_infos`` is

@@ -237,11 +237,8 @@ def test_fast_finetune_loop_matches_the_reference_shaped_loop_and_its_graph_repl
     assert len(set(runs["graph"][0].tolist())) > 1
 
 
-@pytest.mark.parametrize("image_size,batch", [(256, 1), (96, 1), (96, 2)])
-def test_fused_refinement_loss_matches_the_torch_ops(image_size, batch):
-    """csrc/refine_loss.hip (null-fill, PSP pooling, L1, cross-entropy; backward through the transposed resampling) against
-    the reference's own formulation - F.interpolate / l1_loss / cross_entropy (test_render_refine.py:192-215,328-356) -
-    evaluated on the CPU in fp64 and fp32 on the same two images."""
+def _target_and_iterate(image_size, batch):
+    """Two renders of the same room, the second with its objects moved and turned: (target, iterate) of the loss tests"""
     R = pkg("host.refine"); DR = pkg("host.diff_render")
     boxes, angles = _inputs("cuda")
     bank = R.MeshBank([n for n in NAMES if n not in R.DO_NOT_VIS and n != "__room__"], "cuda", seed=3)
@@ -254,12 +251,11 @@ def test_fused_refinement_loss_matches_the_torch_ops(image_size, batch):
         img = DR.scene_render(v, f, ranges, room, image_size=image_size)
         if batch == 2:                                            # second sample: the roles swapped (cross_entropy / l1 average over the batch)
             target, img = torch.cat([target, img]), torch.cat([img, target])
-    rl = R.RefineLoss(target)
-    x = img.clone().requires_grad_(True)
-    out = rl(x)
-    (out[0] * 1.5).backward()                                     # a non-trivial incoming gradient
-    got = [float(t) for t in out.detach().cpu()]
-    g = x.grad.cpu().numpy() / 1.5
+    return target, img
+
+
+def _torch_loss_and_gradient(rl, target, img):
+    """The oracle of the loss tests - the reference's torch calls on the CPU, in fp64 and in fp32: {dtype: ([loss, depth, sem], gradient)}"""
     # labels: the product derives them from its own resampling of the target; torch's resampling must agree on them
     lab_t = torch.cat(refine_ref.target_labels(target.cpu()), 1)
     assert (lab_t != rl.labels.cpu().long()).float().mean() < 2e-3
@@ -270,6 +266,23 @@ def test_fused_refinement_loss_matches_the_torch_ops(image_size, batch):
         loss, dl, sl = refine_ref.refinement_loss(xi, target.cpu().to(dt), labels, torch.zeros((), dtype=dt))     # the oracle: the reference's torch calls
         loss.backward()
         ref[dt] = ([float(loss.detach()), float(dl.detach()), float(sl.detach())], xi.grad.numpy())
+    return ref
+
+
+@pytest.mark.parametrize("image_size,batch", [(256, 1), (96, 1), (96, 2)])
+def test_fused_refinement_loss_matches_the_torch_ops(image_size, batch):
+    """csrc/refine_loss.hip (null-fill, PSP pooling, L1, cross-entropy; backward through the transposed resampling) against
+    the reference's own formulation - F.interpolate / l1_loss / cross_entropy (test_render_refine.py:192-215,328-356) -
+    evaluated on the CPU in fp64 and fp32 on the same two images."""
+    R = pkg("host.refine")
+    target, img = _target_and_iterate(image_size, batch)
+    rl = R.RefineLoss(target)
+    x = img.clone().requires_grad_(True)
+    out = rl(x)
+    (out[0] * 1.5).backward()                                     # a non-trivial incoming gradient
+    got = [float(t) for t in out.detach().cpu()]
+    g = x.grad.cpu().numpy() / 1.5
+    ref = _torch_loss_and_gradient(rl, target, img)
     r64, r32 = ref[torch.float64], ref[torch.float32]
     for a, b, nm in zip(got, r64[0], ("total", "depth", "semantic")):
         assert abs(a - b) <= 1e-4 * abs(b) + 1e-7, (nm, a, b)
@@ -289,6 +302,60 @@ def test_fused_refinement_loss_matches_the_torch_ops(image_size, batch):
     null = (target[:, 41:].sum(1) < 0.5)
     assert float(y.grad[:, 41:-1].abs().max()) == 0.0
     assert float(y.grad[:, -1][null].abs().max() if null.any() else 0.0) == 0.0 and torch.isfinite(filled)
+
+
+def test_fused_refinement_loss_with_plane_flags_and_neither_optional_table():
+    """SlnRefineLoss::live_planes WITHOUT null_mask and pooled_ones (the rooms-in-flight loop always hands over all three): the loss
+    then computes the null mask itself, through the flags, and pools a plane flagged "the constant 1" from 1.f.  The flags are read off
+    the iterate (a plane of zeros: 0, a depth-hot plane of ones: 1, else 3), so the image they describe is the image itself and the
+    torch expressions of the test above apply, at its tolerances; planes whose gradient nobody reads keep what the buffer held."""
+    import ctypes as C
+    R = pkg("host.refine"); _lib = pkg("_lib")
+    target, img = _target_and_iterate(96, 2)
+    img = img.clone()
+    # a window without depth-hot values: null pixels in sample 1; in sample 0 one depth-hot plane is the constant 1 throughout, which
+    # alone keeps the window's sums at 1 - not null, but only for a mask that counts the flagged plane
+    flat = [c for c in range(41, 69) if float(img[0, c].min()) == float(img[0, c].max())]      # planes of classes the room does not show
+    assert flat, "no constant depth-hot plane in sample 0"
+    img[:, 41:, 10:40, 20:70] = 0.0
+    img[0, flat[0]] = 1.0
+    live = torch.full(img.shape[:2], 3, dtype=torch.uint8)
+    for b in range(img.shape[0]):
+        for c in range(1, 69):
+            plane = img[b, c]
+            if not bool(plane.any()):
+                live[b, c] = 0
+            elif c >= 41 and bool((plane == 1.0).all()):
+                live[b, c] = 1
+    assert (live[:, 1:41] == 0).any() and (live[:, 1:41] == 3).any() and (live[0, 41:] == 1).any() and (live[:, 41:69] == 3).any()
+    null = img[:, 41:].sum(1) < 0.5
+    assert not bool(null[0].any()) and bool(null[1, 10:40, 20:70].all())
+    live_dev = live.cuda()
+    rl = R.RefineLoss(target)
+    assert _lib.lib().sln_refine_loss_live_ok(C.byref(rl.desc)) == 1
+    rl.desc.live_planes = live_dev.data_ptr()
+    assert not rl.desc.null_mask and not rl.desc.pooled_ones
+    with torch.no_grad():
+        out = rl(img)
+    got = [float(t) for t in out.cpu()]
+    sentinel = 7.0
+    g_dev, g_scale = torch.full(img.shape, sentinel, device="cuda"), torch.full((1,), 1.5, device="cuda")
+    _lib.check(_lib.lib().sln_refine_loss_backward(rl.desc, _lib.ptr(rl.ws), _lib.ptr(g_scale), _lib.ptr(g_dev),
+                                                   _lib.current_stream_ptr()), "sln_refine_loss_backward")
+    g = g_dev.cpu().numpy()
+    ref = _torch_loss_and_gradient(rl, target, img)
+    r64, r32 = ref[torch.float64], ref[torch.float32]
+    for a, b, nm in zip(got, r64[0], ("total", "depth", "semantic")):
+        assert abs(a - b) <= 1e-4 * abs(b) + 1e-7, (nm, a, b)
+    read = ((live.numpy() & 2) != 0)                               # [B, C]: planes whose gradient is written
+    assert (g[~read] == sentinel).all()
+    g, g64, g32 = g[read] / 1.5, r64[1][read], r32[1][read]
+    scale = np.abs(r64[1]).max()
+    bad = np.abs(g - g64) > 1e-4 * scale
+    bad32 = np.abs(g32 - g64) > 1e-4 * scale
+    assert scale > 0 and bool((g_dev[:, 0] == 0).all()) and bool((g_dev[1, -1][null[1]] == 0).all())
+    assert bad.mean() <= max(4.0 * bad32.mean(), 1e-5), (bad.mean(), bad32.mean())
+    assert np.abs(g - g64).max() <= 1e-4 * scale + 4.0 * np.abs(g32 - g64).max()
 
 
 def test_room_without_visible_objects():
