@@ -16,6 +16,7 @@ What is replaced
   * the 33 raster passes per call: one fused HIP pass (diff_render.scene_render semantics).
 ``render_fn`` is injectable so that the tests can run the very same loss graph on the CPU oracle.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -25,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import diff_render as DR
+from . import scene_pictures as SP
 from . import synthetic
 from .. import _lib
 
@@ -696,6 +698,9 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
     return losses, (state["boxes"], state["idx"])
 
 
+PictureSet = collections.namedtuple("PictureSet", "depth8 labels rgb status iterations")
+
+
 class RefineBatch:
     """R rooms in flight: one refinement iteration of R independent rooms (testing/test_render_refine.py:250-263 runs its trials
     one after the other; each reloads the checkpoint, ``model.eval()``, and :279-359 steps ``z`` AND its own copy of the parameters)
@@ -717,9 +722,16 @@ class RefineBatch:
     calls - sln_layout_cuboid_iou over all rooms' rows after the head (boxes / idx of the iterate against the ground truth, :360-368)
     and sln_refine_report after the loss forward - and fills ``report[k]`` [R, 3] = (mean IoU of the room's visible rows,
     depth_l1 at full resolution, cross-entropy of the last scale; :371-372); rows of unreported iterations stay NaN.  Nothing is
-    read back and nothing allocated inside an iteration."""
+    read back and nothing allocated inside an iteration.
 
-    def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None):
+    ``pictures``: None (default: nothing below exists, the launches are those above), "ends" (:369), "all", or an iterable of iteration
+    numbers - what the reference's ``save_images`` calls show (:320, :377; host/scene_pictures.py).  A pictured iteration issues
+    sln_scene_pictures (three launches) on ``image`` with ``live`` after the loss forward and fills slot j of ``pictures.depth8`` /
+    ``labels`` [n_pictured, R, S, S], ``rgb`` [n_pictured, R, S, S, 3] and ``status`` [n_pictured, R]; ``pictures.iterations[j]`` names the
+    iteration.  ``target_pictures`` (``scene_pictures.Pictures``, [R, S, S(, 3)]) is filled once at set-up from the target renders.
+    Needs image_size % 4 == 0."""
+
+    def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None):
         L = _lib.lib()
         self.model, self.R, self.iters, self.lr = model, len(rooms), int(iters), float(learning_rate)
         R = self.R
@@ -777,6 +789,25 @@ class RefineBatch:
             self._iou_mean = torch.zeros(R, dtype=torch.float64, device=dev)
             self._report_ws = torch.empty(int(L.sln_refine_report_scratch_doubles(R)), dtype=torch.float64, device=dev)
             self.report = torch.full((max(self.iters, 1), R, 3), float("nan"), **f32)
+        self._pictures_all = isinstance(pictures, str) and pictures == "all"
+        if pictures is None:
+            self._pictures_at = None
+        else:
+            if isinstance(pictures, str) and pictures not in ("all", "ends"):
+                raise ValueError("pictures is None, 'ends', 'all' or an iterable of iteration numbers")
+            last = max(self.iters - 1, 0)
+            at = range(max(self.iters, 1)) if pictures == "all" else ((0, last) if pictures == "ends" else [int(k) for k in pictures])
+            at = sorted(set(at))
+            if any(k < 0 or k >= max(self.iters, 1) for k in at):
+                raise ValueError("pictures names an iteration outside [0, %d)" % self.iters)
+            self._pictures_at = {k: j for j, k in enumerate(at)}
+            self._pics = SP.ScenePictures(S, batch=R, channels=DR.N_SCENE_CHANNELS, device=dev)
+            u8 = dict(dtype=torch.uint8, device=dev)
+            n_pic = len(at)
+            self.pictures = PictureSet(torch.zeros(n_pic, R, S, S, **u8), torch.zeros(n_pic, R, S, S, **u8), torch.zeros(n_pic, R, S, S, 3, **u8),
+                                       torch.zeros(n_pic, R, dtype=torch.int32, device=dev), tuple(at))
+            t = self._pics(torch.cat(targets, 0).contiguous())                     # (:320: the target as rendered, every plane written)
+            self.target_pictures = SP.Pictures(t.depth8.clone(), t.labels.clone(), t.rgb.clone(), None, t.status.clone())
         self.noise_all = noise.to(dev)
         self.box_last, self.angle_last = box_last, angle_last
         # ---- the loss of all rooms: one descriptor, per-room normalisation ----
@@ -935,9 +966,9 @@ class RefineBatch:
         _lib.check(_lib.lib().sln_vae_group_launches(self._group, C.byref(f), C.byref(b), C.byref(s1)), "sln_vae_group_launches")
         return dict(decoder_forward=f.value, decoder_backward=b.value, single_room_fallbacks=s1.value)
 
-    def _iteration(self, noise, out, report_out=None):
+    def _iteration(self, noise, out, report_out=None, pictures_out=None):
         """one iteration of every room on the current stream; ``noise`` [N], ``out`` [R] receives the rooms' losses, ``report_out``
-        [R, 3] (a reported iteration) the report"""
+        [R, 3] (a reported iteration) the report, ``pictures_out`` (a pictured iteration) = (depth8, labels, rgb, status) of one slot"""
         L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
         N, R, na, S = self.N, self.R, self.model.Nangle, self.S
         _lib.check(L.sln_vae_group_decoder(self._group, st), "sln_vae_group_decoder")
@@ -962,6 +993,9 @@ class RefineBatch:
         if report_out is not None:      # reads the image and the loss forward's partial sums, consumes (and re-arms) the IoU means
             _lib.check(L.sln_refine_report(rl.desc, P(self.image), P(self._target_depth), P(rl.ws), P(self._report_ws), P(self._iou_mean), P(report_out),
                                            st), "sln_refine_report")
+        if pictures_out is not None:    # the iterate as the loss saw it: the planes `live` flags dead are not read
+            d8, lab, rgb, stat = pictures_out
+            self._pics.into(self.image, self.live, d8, lab, rgb, None, stat)
         _lib.check(L.sln_refine_loss_backward(rl.desc, P(rl.ws), P(self.one), P(self.g_image), st), "sln_refine_loss_backward")
         _lib.check(L.sln_scene_backward(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 1e-3, P(self.scene_ws),
                                         P(self.g_image), P(self.g_faces), st), "sln_scene_backward")
@@ -984,13 +1018,21 @@ class RefineBatch:
             raise ValueError("RefineBatch was built for %d iterations (the noise of every iteration is drawn at construction)" % self.iters)
         if capture and self._report_at is not None and not self._report_all:
             raise ValueError("run(capture=True) replays one graph for every iteration: report must be 'all' or None")
+        if capture and self._pictures_at is not None and not self._pictures_all:
+            raise ValueError("run(capture=True) replays one graph for every iteration: pictures must be 'all' or None")
         scratch = self.loss_out.new_empty(self.R)
         rep_scratch = self.loss_out.new_empty(self.R, 3) if capture and self._report_all and self._graph is None else None
+        pic_scratch = None
+        if capture and self._pictures_all and self._graph is None:                # the graph's slot: copied to the iteration's after a replay
+            pic_scratch = tuple(torch.empty_like(t[0]) for t in self.pictures[:4])
         if n > 0 and self.k == 0:
             self._first_iterate_sizes()
         for _ in range(n):
             k = self.k
             rep = self.report[k] if self._report_at is not None and k in self._report_at else None
+            pic = None
+            if self._pictures_at is not None and k in self._pictures_at:
+                pic = tuple(t[self._pictures_at[k]] for t in self.pictures[:4])
             if capture:
                 if not self._fused_head:
                     self.noise.copy_(self.noise_all[k])
@@ -998,19 +1040,22 @@ class RefineBatch:
                     side = torch.cuda.Stream()
                     side.wait_stream(torch.cuda.current_stream())
                     with torch.cuda.stream(side):                  # warm-up outside the capture (lazy kernel attributes)
-                        self._iteration(self.noise, self.losses[k], rep)
+                        self._iteration(self.noise, self.losses[k], rep, pic)
                     torch.cuda.current_stream().wait_stream(side)
                     self._graph = torch.cuda.CUDAGraph()
-                    self._graph_out, self._graph_report = scratch, rep_scratch
+                    self._graph_out, self._graph_report, self._graph_pictures = scratch, rep_scratch, pic_scratch
                     with torch.cuda.graph(self._graph):
-                        self._iteration(self.noise, self._graph_out, self._graph_report)
+                        self._iteration(self.noise, self._graph_out, self._graph_report, self._graph_pictures)
                 else:
                     self._graph.replay()
                     self.losses[k].copy_(self._graph_out)
                     if rep is not None:
                         rep.copy_(self._graph_report)
+                    if pic is not None:
+                        for dst, src in zip(pic, self._graph_pictures):
+                            dst.copy_(src)
             else:
-                self._iteration(self.noise_all[k], self.losses[k], rep)
+                self._iteration(self.noise_all[k], self.losses[k], rep, pic)
             self.k += 1
         return self.losses[:self.k]
 
@@ -1035,18 +1080,23 @@ class RefineBatch:
             pass
 
 
-def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None):
+def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None,
+                            pictures=None):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
     noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
-    ``report`` is given, the report [iters, R, 3] as a third element."""
-    rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report)
+    ``report`` is given, the report [iters, R, 3] as a further element; only when ``pictures`` is given, the pair
+    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one."""
+    rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report,
+                     pictures=pictures)
     try:
-        losses = rb.run(capture=capture).clone()
-        res = [(b.clone(), i.clone()) for b, i in rb.results()]
-        rep = rb.report.clone() if report is not None else None
+        out = (rb.run(capture=capture).clone(), [(b.clone(), i.clone()) for b, i in rb.results()])
+        if report is not None:
+            out += (rb.report.clone(),)
+        if pictures is not None:
+            out += ((rb.pictures, rb.target_pictures),)             # (buffers of their own: nothing of the batch's is referenced)
     finally:
         rb.close()
-    return (losses, res) if report is None else (losses, res, rep)
+    return out
 
 
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,

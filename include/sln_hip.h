@@ -914,6 +914,28 @@ int sln_spade_input_forward(const float* depth, const void* planes, int mode, co
                             int size, const int32_t* first_h, const double* w_h, int width_h, const int32_t* first_w, const double* w_w,
                             int width_w, void* workspace, float* out, int32_t* status, void* stream);
 
+/* The pictures of the refinement loop (testing/test_render_refine.py: save_images :144-163, save_label_depth :118-142 and the label
+ * statements :343-344) from a scene tensor image [B, channels, S, S] float32 on the device; channels is 70, or 41 (depth plus the 40
+ * semantic planes: target[:, :41]).  Per room, all float32, in this order of operations:
+ *   depth8 [B, S, S]       d = x - min x over channel 0; m = max{d : d < 10}; every d > 10 becomes m; byte = trunc((d / m) * 255) with a
+ *                          correctly rounded division.  A d of exactly 10 is outside the reference's defined behaviour (its uint8 cast
+ *                          overflows): the byte saturates at 255.
+ *   labels [B, S, S]       0 where the sum of channels 1..40 (channel order) is < 0.5, else 1 + argmax over them (the first maximum wins):
+ *                          the class-index image of sln_spade_input_forward's SLN_SPADE_INPUT_LABELS.  NULL: not computed.
+ *   rgb    [B, S, S, 3]    palette[labels]; palette [41] (device) = r | g << 8 | b << 16, entry 0 = no class.  NULL: not computed.
+ *   masks8 [B, 40, S, S]   trunc(255 * plane) of channels 1..40 for planes in [0, 1] (saturated outside).  NULL: not computed.
+ *   status [B] int32       bit 0: no d < 10 exists (the reference's np.max raises), bit 1: m == 0 (the reference divides by zero); the
+ *                          room's depth bytes are 0 in both cases.
+ * live_planes [B, channels] (or NULL: every plane is read) are the flags of SlnRefineLoss::live_planes: a plane with bit 0 clear is
+ * all zeros, a plane with the value 1 the constant 1; neither is read.  At most three launches on `stream`; no allocation, no
+ * synchronisation, no host read, no atomics: legal inside a stream capture and bit-identical from call to call.  workspace:
+ * sln_scene_pictures_workspace_bytes(B, S) bytes; image 16-byte, every other buffer 4-byte aligned (SLN_E_BADARG otherwise).
+ * SLN_E_UNSUPPORTED, nothing launched: S % 4 != 0, S * S > 2^30, B < 1 or > 65535, channels not 41 or 70. */
+int64_t sln_scene_pictures_workspace_bytes(int B, int S);
+int sln_scene_pictures(const float* image, int B, int channels, int S, const unsigned char* live_planes, const uint32_t* palette,
+                       void* workspace, unsigned char* depth8, unsigned char* labels, unsigned char* rgb, unsigned char* masks8,
+                       int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
