@@ -233,6 +233,7 @@ SIGNATURES = {
     "sln_debug_vae_embed": (C.c_int, [C.POINTER(SlnDbgEmbed), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "sln_debug_vae_opt": (C.c_int, [C.POINTER(SlnDbgOpt), C.c_void_p]),
     "sln_debug_vae_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "sln_debug_vae_leaf_launches": (C.c_int64, [C.c_void_p]),
     "sln_project_faces": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p]),
     "sln_project_faces_backward": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p,
                                              c_f32p, C.c_void_p]),

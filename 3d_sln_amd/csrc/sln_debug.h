@@ -5,3 +5,5 @@
 
 // fills v from the plain-C description; false when the view lacks what the coefficients `coef` (SLN_COEF_*) read out of it
 bool sln_dbg_bn(const SlnDbgBn& d, int coef, BnView& v);
+// leaf launches an engine issued so far (vae_engine.hip; read by sln_debug_vae_leaf_launches)
+long sln_vae_engine_leaf_launches(const SlnVae* h);

@@ -389,3 +389,5 @@ extern "C" int sln_debug_vae_opt(SlnDbgOpt* d, void* stream) {
   if (h[0].adam_done != 0 || h[0].rng_done != 0) return SLN_E_STATE;        // an arrival ticket that did not reset
   return 0;
 }
+
+extern "C" int64_t sln_debug_vae_leaf_launches(const SlnVae* h) { return h ? (int64_t)sln_vae_engine_leaf_launches(h) : (int64_t)SLN_E_BADARG; }

@@ -2,9 +2,9 @@
 // models/Sg2ScVAE_model.py:115-188, models/graph.py:57-143, utils.py:12-33, train.py:62-84) and
 // exposes it through the C ABI of include/sln_hip.h.  One engine per process/GPU; every call
 // enqueues kernels on the caller's stream.  A whole training iteration (zero_grad, forward, loss,
-// backward, Adam) is 145 launches at train.py's defaults (one per forward Linear / dgrad, 30 edge
-// launches, FOUR wgrad launches - every wgrad of a pass runs in one multi-problem grid, see
-// flush_deferred -, a dozen bookkeeping launches), captured once into a hipGraph and replayed.
+// backward, Adam) is 136 launches at train.py's defaults (one per forward Linear / dgrad, 30 edge
+// launches, two wgrad launches - every wgrad of the iteration runs in one multi-problem grid per kind, see
+// flush_deferred -, half a dozen bookkeeping launches), captured once into a hipGraph and replayed.
 #include <cstddef>
 #include <new>
 #include <type_traits>
@@ -113,7 +113,7 @@ struct SlnVae {
   float *bnA1 = nullptr, *anA1 = nullptr, *boxes_pred = nullptr, *logits = nullptr, *angles_pred = nullptr;
   // backward temporaries
   float *dbp = nullptr, *dlogits = nullptr, *g_bn = nullptr, *g_an = nullptr, *d_bx = nullptr, *d_ax = nullptr;
-  float *dM = nullptr, *dG[2] = {nullptr, nullptr};
+  float *dM = nullptr, *dG[3] = {nullptr, nullptr, nullptr};   // [2]: the decoder's layer 0 when its predicate-table job waits for the leaf launch
   float *dX0 = nullptr, *dz = nullptr, *dmu = nullptr, *dlv = nullptr;
   float *g_h2 = nullptr, *g_h1 = nullptr, *d_xb = nullptr, *d_xa = nullptr, *tmp_d = nullptr;
   float *g_h2b = nullptr, *g_h1b = nullptr, *tmp_db = nullptr;     // the angle branch's copies (both branches run grouped)
@@ -298,6 +298,14 @@ struct SlnVae {
   bool one_flush = true;          // SLN_TN_ONE_FLUSH=0 at creation: off, every pass flushes its own
   bool it_merge_bn = false;       // ONE running-statistics launch per iteration (after the decoder) and ONE parameter-gradient launch
   bool no_merge = false;          // SLN_NO_MERGE=1 at creation: none of the three
+  // Round 7: the leaves of a full iteration - what nothing reads before the optimizer: three embedding-table gradients, the encoder's
+  // assembly tables, the box embedding's Linear, the BatchNorm parameter gradients and running statistics - leave the dependent
+  // chain and run side by side in ONE launch at the end of encoder_backward (sln_launch_vae_leaf); W^T of the iteration's dgrads is
+  // rebuilt by the prologue launch (the weights are final since the last update).
+  bool it_leaf = false;           // this iteration defers its leaves
+  bool it_wt_prologue = false;    // this iteration's prologue rebuilds the transposed weights when they are stale
+  bool leaf_merge = true;         // SLN_LEAF_MERGE=0 at creation: neither, the per-kernel sequence
+  long leaf_launches = 0;         // leaf launches issued by this engine (sln_vae_leaf_launches)
   bool gconv_only = false;        // a bare GraphTripleConvNet (sln_gconv_net_*): units = the modules' four Linears, one net, no heads
   int unit_of(int net, int l, int k) const { return (gconv_only ? 0 : 8) + (net * nmod + (cfg.recurrent ? 0 : l)) * 4 + k; }
   int unit_boxnet(int k) const { return 8 + 2 * nmod * 4 + k; }
@@ -518,6 +526,7 @@ struct SlnVae {
   int encoder_backward(hipStream_t st);
   int loss(const float* bp, const float* ap, const float* mu_, const float* lv_, bool with_grads, hipStream_t st);
   int run_bn_updates(int first, int count, hipStream_t st);
+  VaeLeaf leaf_args() const;
   enum { TRAIN_BACKWARD = 0, TRAIN_FULL = 1, TRAIN_UPTO_DECODER = 2, TRAIN_ENCODER_BWD = 3 };   // = SLN_TRAIN_* of sln_hip.h
   int train_iteration(const float* eps, int mode, hipStream_t st);
   // input of box_net (with_attr) / angle_net: [obj_vecs | attr_vecs] resp. obj_vecs, where obj_vecs is the decoder gconv
@@ -600,6 +609,10 @@ size_t SlnVae::carve(void* base, int mo, int mt) {
         }
       }
   dG[0] = b.take<float>(Tm * 3 * Dm); dG[1] = b.take<float>(Tm * 3 * Dm);
+  // the encoder's backward pass reuses both slots: the decoder's layer-0 dG, whose predicate columns the leaf launch reads at the
+  // end of the iteration, gets a slice of its own - only in engines that can take the leaf launch at all (the whole [T, 3 Ddc]
+  // block: the layer's dgrad writes it in one piece and its gather reads the outer thirds; 6.3 MB at 64 graphs, 403 MB at 4 096)
+  dG[2] = (gconv_only || !leaf_merge || no_merge || n_attr_e == 0 || !cfg.decoder_cat) ? nullptr : b.take<float>(Tm * 3 * (size_t)Ddc);
   dX0 = b.take<float>(Om * Dm); dz = b.take<float>(Om * E); dmu = b.take<float>(Om * E); dlv = b.take<float>(Om * E);
   g_h2 = b.take<float>(Om * W); g_h1 = b.take<float>(Om * H); d_xb = b.take<float>(Om * W); d_xa = b.take<float>(Om * W);
   tmp_d = b.take<float>(Om * W);
@@ -612,6 +625,29 @@ int SlnVae::refresh_transposes(hipStream_t st) {
   RET_IF(sln_launch_transpose_table(tr_table_dev, n_tr, tr_max_tiles, st));
   wt_fresh = true;
   return 0;
+}
+
+// Operands of the leaf launch.  Each outlives the passes behind its producer: d_bx and dG[2] are written by the decoder's backward
+// pass only, the encoder's dG[0] and dX0 by the last launches of encoder_backward, and the statistics arenas are cleared by the
+// next iteration's first launch only.
+VaeLeaf SlnVae::leaf_args() const {
+  VaeLeaf v; std::memset(&v, 0, sizeof(v));
+  EncAssembleBwd& eb = v.enc;
+  eb.objs = batch.objs; eb.attrs = batch.attributes; eb.angles = batch.angles; eb.boxes = batch.boxes; eb.dx0 = dX0;
+  eb.O = O; eb.n_obj = n_obj_e; eb.n_attr = n_attr_e; eb.n_box = n_box_e; eb.n_angle = n_angle_e; eb.box_dim = cfg.box_dim;
+  eb.d_obj_emb = t.d_obj_emb_ec; eb.d_attr_emb = t.d_attr_emb_ec; eb.d_angle_emb = t.d_angle_emb;
+  eb.d_wb = t.d_box_emb_w; eb.d_bb = t.d_box_emb_b;
+  eb.rows_obj = cfg.num_objs; eb.rows_attr = cfg.num_attrs; eb.rows_angle = cfg.n_angle;
+  v.pidx = g.p; v.pred_rows = T; v.pred_table_rows = cfg.num_preds;
+  v.d_pdc = dG[2]; v.ld_pdc = 3 * Ddc; v.col0_pdc = Ddc; v.n_pdc = Ddc; v.d_pred_dc = t.d_pred_emb_dc;
+  v.d_pec = dG[0]; v.ld_pec = 3 * Dec; v.col0_pec = Dec; v.n_pec = Dec; v.d_pred_ec = t.d_pred_emb_ec;
+  v.attr_idx = batch.attributes; v.d_attr = d_bx; v.ld_attr = 2 * E + n_attr_e; v.col0_attr = 2 * E; v.n_attr_dc = n_attr_e;
+  v.attr_table_rows = cfg.num_attrs; v.d_attr_dc = t.d_attr_emb_dc;
+  int maxc = 0;
+  for (auto& bi : bns) maxc = bi.C > maxc ? bi.C : maxc;
+  v.bn_tab = bn_table_dev; v.bn_n = (int)bns.size(); v.bn_max_c = maxc; v.bn_independent = cfg.recurrent ? 0 : 1;
+  v.bn_update = step_training ? 1 : 0; v.bn_momentum = kBnMomentum;
+  return v;
 }
 
 int SlnVae::run_bn_updates(int first, int count, hipStream_t st) {
@@ -683,7 +719,9 @@ int SlnVae::encoder_forward(bool training, hipStream_t st) {
     sp.pemb_ec = t.pred_emb_ec; sp.n_ec = Dec; sp.p0e = P0e;
     sp.pemb_dc = t.pred_emb_dc; sp.n_dc = Ddc; sp.p0d = P0d;
     if (it_zero_in_prologue) { sp.zero_ptr = zero_begin; sp.zero_bytes = (long)zero_bytes; }
+    if (it_wt_prologue && !wt_fresh) { sp.tr_tab = tr_table_dev; sp.n_tr = n_tr; sp.tr_max_tiles = tr_max_tiles; }
     RET_IF(sln_launch_step_prologue(sp, st));
+    if (sp.tr_tab) wt_fresh = true;           // refresh_transposes launches nothing in this iteration's backward passes
   } else {
     RET_IF(sln_launch_enc_assemble(ea, st));
     RET_IF(sln_launch_embed_gather_i32(g.p, t.pred_emb_ec, T, Dec, P0e, st));
@@ -737,7 +775,7 @@ int SlnVae::decoder_forward(const float* z_ext, const float* eps, bool training,
                     training, st));
   RET_IF(end_group(st));
   if (!it_fused_loss && !rec) RET_IF(sln_launch_log_softmax(logits, angles_pred, O, cfg.n_angle, st));     // (a group takes it over all rooms' rows at once)
-  if (training) {
+  if (training && !it_leaf) {               // (it_leaf: the update rides in the leaf launch, the forward sums stay until the next prologue)
     if (it_merge_bn) RET_IF(run_bn_updates(0, (int)bns.size(), st));      // encoder's and decoder's tables: one launch, application order
     else RET_IF(run_bn_updates(n_bn_enc, (int)bns.size() - n_bn_enc, st));
   }
@@ -798,11 +836,11 @@ int SlnVae::decoder_backward(hipStream_t st) {
   }
   // decoder_cat off: z entered behind the gconv net, its gradient is the sum of the two heads' (Sg2ScVAE_model.py:164)
   if (!cfg.decoder_cat) RET_IF(k_add2(d_bx + W, WA, d_ax + W, Wh, O, E, dz, E, st));
-  if (n_attr_e > 0) RET_IF(k_embed_bwd(batch.attributes, 1, d_bx, WA, Wh, O, n_attr_e, cfg.num_attrs, t.d_attr_emb_dc, st));
+  if (n_attr_e > 0 && !it_leaf) RET_IF(k_embed_bwd(batch.attributes, 1, d_bx, WA, Wh, O, n_attr_e, cfg.num_attrs, t.d_attr_emb_dc, st));
   // gconv layers, last to first
   for (int l = L - 1; l >= 0; --l) {
-    const int gi = L + l, slot = l & 1;
-    const float* dP = (l == L - 1) ? nullptr : dG[slot ^ 1];
+    const int gi = L + l, slot = (it_leaf && l == 0) ? 2 : (l & 1);
+    const float* dP = (l == L - 1) ? nullptr : dG[(l & 1) ^ 1];
     RET_IF(gconv_backward(gi, dP, 3 * W, W, slot, tr, st));
     if (l > 0) {
       const Layer& pv = layers[gi - 1];
@@ -812,7 +850,7 @@ int SlnVae::decoder_backward(hipStream_t st) {
     } else {
       BnView none = view(-1, 0, tr);
       RET_IF(k_gather_bwd(dG[slot], 3 * W, W, g, O, nullptr, 0, nullptr, 0, none, 0, dX0, W, nullptr, 0, st));
-      RET_IF(k_embed_bwd(g.p, 0, dG[slot], 3 * W, W, T, W, cfg.num_preds, t.d_pred_emb_dc, st));
+      if (!it_leaf) RET_IF(k_embed_bwd(g.p, 0, dG[slot], 3 * W, W, T, W, cfg.num_preds, t.d_pred_emb_dc, st));
     }
   }
   DecAssembleBwd db; std::memset(&db, 0, sizeof(db));
@@ -899,8 +937,14 @@ int SlnVae::encoder_backward(hipStream_t st) {
     } else {
       BnView none = view(-1, 0, tr);
       RET_IF(sln_launch_gather_bwd(dG[slot], 3 * W, W, g, O, nullptr, 0, nullptr, 0, none, 0, dX0, W, nullptr, 0, st));
-      RET_IF(sln_launch_embed_bwd_i32(g.p, dG[slot], 3 * W, W, T, W, cfg.num_preds, t.d_pred_emb_ec, st));
+      if (!it_leaf) RET_IF(sln_launch_embed_bwd_i32(g.p, dG[slot], 3 * W, W, T, W, cfg.num_preds, t.d_pred_emb_ec, st));
     }
+  }
+  if (it_leaf) {                                // every leaf of the iteration, side by side in one launch
+    RET_IF(sln_launch_vae_leaf(leaf_args(), st));
+    ++leaf_launches;
+    RET_IF(flush_deferred(it_one_flush ? 2 : 1, st));
+    return 0;
   }
   EncAssembleBwd eb; std::memset(&eb, 0, sizeof(eb));
   eb.objs = batch.objs; eb.attrs = batch.attributes; eb.angles = batch.angles; eb.boxes = batch.boxes; eb.dx0 = dX0;
@@ -938,6 +982,11 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
     bulk_zeroed = true;
     it_merge_bn = !no_merge && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);    // the two-half form hands the decoder's gradients out early
     it_one_flush = one_flush && !tn_per_layer && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);
+    // the leaf launch: only where the workspace holds the decoder's third dG buffer (carve: SLN_LEAF_MERGE on, a model with
+    // attribute tables and z in the decoder's input - the other two model shapes are listed fall-backs) and every job is on its
+    // LDS path; anything else - deterministic mode included - keeps the per-kernel sequence for the whole iteration
+    it_leaf = it_merge_bn && dG[2] != nullptr && T > 0 && sln_vae_leaf_fits(leaf_args()) != 0;
+    it_wt_prologue = it_prologue && leaf_merge && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);
     if (!it_prologue && draw_eps) r = sln_launch_randn(eps_buf, (long)O * E, scalars, st);       // Sg2ScVAE_model.py:182
     if (!r) r = encoder_forward(step_training, st);
     if (!r) r = decoder_forward(nullptr, eps, step_training, st);
@@ -954,7 +1003,7 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
     if (!r) r = encoder_backward(st);
   }
   bulk_zeroed = false;
-  it_prologue = it_fused_loss = it_merge_bn = it_zero_in_prologue = it_one_flush = false;
+  it_prologue = it_fused_loss = it_merge_bn = it_zero_in_prologue = it_one_flush = it_leaf = it_wt_prologue = false;
   RET_IF(r);
   if (mode == TRAIN_FULL) {
     RET_IF(sln_launch_adam(t.flat_params, t.flat_grads, t.adam_m, t.adam_v, (long)t.n_flat, scalars, losses + 3, st));
@@ -962,6 +1011,8 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
   }
   return 0;
 }
+
+long sln_vae_engine_leaf_launches(const SlnVae* h) { return h->leaf_launches; }        // for the test hook in vae_debug.hip
 
 // =============================================================================================
 // C ABI
@@ -1001,6 +1052,7 @@ static int read_engine_options(SlnVae* h) {
   h->no_merge = is("SLN_NO_MERGE", '1');
   h->tn_per_layer = is("SLN_TN_PER_LAYER", '1');
   h->one_flush = !is("SLN_TN_ONE_FLUSH", '0');
+  h->leaf_merge = !is("SLN_LEAF_MERGE", '0');
   h->tn_slots = 3 * (2 * h->L + 8 > 16 ? 2 * h->L + 8 : 16);
   h->tn_groups_store = new (std::nothrow) SlnVae::TnGroup[2 * (size_t)h->tn_slots * 2];
   return h->tn_groups_store ? 0 : SLN_E_BADARG;

@@ -154,7 +154,21 @@ struct StepPrologue {
   const float* pemb_ec; int n_ec; float* p0e;
   const float* pemb_dc; int n_dc; float* p0d;
   void* zero_ptr; long zero_bytes;      // optional: a region to clear (16-byte aligned, a multiple of 16 bytes): the iteration's loss accumulators and BatchNorm sums
+  const TransposeEntry* tr_tab; int n_tr, tr_max_tiles;      // optional: the transposed weights of the iteration's dgrads (sln_launch_transpose_table's arguments)
 };
 int sln_launch_step_prologue(const StepPrologue& a, hipStream_t st);
+
+// The leaves of a full training iteration as ONE launch (see vae_leaf_kernel): nothing reads their results before the optimizer.
+struct VaeLeaf {
+  EncAssembleBwd enc;                       // encoder assembly tables and the box embedding's Linear (as sln_launch_enc_assemble_bwd)
+  const int* pidx; int pred_rows, pred_table_rows;                  // predicate ids [T]; both predicate tables have pred_table_rows rows
+  const float* d_pdc; int ld_pdc, col0_pdc, n_pdc; float* d_pred_dc;   // d_pred_dc[pidx[t], :] += d_pdc[t, col0 : col0 + n]
+  const float* d_pec; int ld_pec, col0_pec, n_pec; float* d_pred_ec;
+  const int64_t* attr_idx; const float* d_attr; int ld_attr, col0_attr, n_attr_dc, attr_table_rows; float* d_attr_dc;   // n_attr_dc == 0: none
+  const BnTableEntry* bn_tab; int bn_n, bn_max_c, bn_independent;   // parameter gradients of the whole table (bn_n == 0: none) ...
+  int bn_update; float bn_momentum;                                  // ... and, when set, its running statistics (rows: pred_rows / enc.O)
+};
+int sln_vae_leaf_fits(const VaeLeaf& a);    // 1: every job takes its LDS-table path (and the mode is not deterministic)
+int sln_launch_vae_leaf(const VaeLeaf& a, hipStream_t st);
 // counts[obj][floor(cz (cs - 1))][floor(cx (cs - 1))] += 1 for every (trial, object != room row): testing/test_heatmap.py:80-99
 int sln_launch_layout_heatmap(const float* boxes, long n_trials, int O, int cs, int clip, float* counts, hipStream_t st);

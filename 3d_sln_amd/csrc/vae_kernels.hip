@@ -454,47 +454,53 @@ __global__ void enc_assemble_bwd_kernel(EncAssembleBwd a) {
   else { c -= a.n_box; atomicAdd(a.d_angle_emb + (size_t)a.angles[r] * a.n_angle + c, d); }
 }
 
-__global__ __launch_bounds__(CB* RL) void box_embed_bwd_kernel(EncAssembleBwd a, const int box_rows) {
+// (bx, by): block of the (column group, row group) grid; (tx, ty): thread of the (CB, RL) block; red: 7 * RL * CB floats of LDS
+__device__ __forceinline__ void box_embed_bwd_body(const EncAssembleBwd& a, const int box_rows, const int bx, const int by, const int tx, const int ty,
+                                                   float (*red)[RL][CB]) {
   // d_bb[j] += sum_r d[r,j];  d_wb[j,k] += sum_r d[r,j]*boxes[r,k]   (box_dim <= 6)
   const int W = a.n_obj + a.n_attr + a.n_box + a.n_angle, off = a.n_obj + a.n_attr;
-  const int j = blockIdx.x * CB + threadIdx.x;
+  const int j = bx * CB + tx;
   const bool jv = j < a.n_box;
   float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   // BOX_ROWS rows per block in batches of 16 (4 per thread, their loads issued together: one memory round trip per batch).  Every
   // block ends in 7 atomics per column on the same 7 x n_box addresses, which the L2 serialises - measured at 2 048 rows: 64 rows
   // walked one at a time 20.6 us; batches, 16 rows x 128 blocks 21.6 us, 256 x 8 15.9 us, 64 x 32 9.8 us
   // (deterministic mode: box_rows = O, one workgroup per column group walks every row - one add per element)
-  const int rb0 = (int)blockIdx.y * box_rows, r1 = min(a.O, rb0 + box_rows);
+  const int rb0 = by * box_rows, r1 = min(a.O, rb0 + box_rows);
   if (jv) {
     for (int rb = rb0; rb < r1; rb += 4 * RL) {
       float d[4], bx[4][6];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const int r = min(rb + (int)threadIdx.y + RL * u, a.O - 1);
+        const int r = min(rb + ty + RL * u, a.O - 1);
         d[u] = a.dx0[(size_t)r * W + off + j];
 #pragma unroll
         for (int k = 0; k < 6; ++k) bx[u][k] = a.boxes[(size_t)r * a.box_dim + min(k, a.box_dim - 1)];
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        if (rb + (int)threadIdx.y + RL * u >= r1) continue;
+        if (rb + ty + RL * u >= r1) continue;
         acc[6] += d[u];
 #pragma unroll
         for (int k = 0; k < 6; ++k) if (k < a.box_dim) acc[k] = fmaf(d[u], bx[u][k], acc[k]);
       }
     }
   }
-  __shared__ float red[7][RL][CB];
-  for (int k = 0; k < 7; ++k) red[k][threadIdx.y][threadIdx.x] = acc[k];
+  for (int k = 0; k < 7; ++k) red[k][ty][tx] = acc[k];
   __syncthreads();
-  if (threadIdx.y == 0 && jv) {
+  if (ty == 0 && jv) {
     for (int k = 0; k < 7; ++k) {
       float s = 0.f;
-      for (int i = 0; i < RL; ++i) s += red[k][i][threadIdx.x];
+      for (int i = 0; i < RL; ++i) s += red[k][i][tx];
       if (k == 6) atomicAdd(a.d_bb + j, s);
       else if (k < a.box_dim) atomicAdd(a.d_wb + j * a.box_dim + k, s);
     }
   }
+}
+
+__global__ __launch_bounds__(CB* RL) void box_embed_bwd_kernel(EncAssembleBwd a, const int box_rows) {
+  __shared__ float red[7][RL][CB];
+  box_embed_bwd_body(a, box_rows, (int)blockIdx.x, (int)blockIdx.y, (int)threadIdx.x, (int)threadIdx.y, red);
 }
 
 __device__ __forceinline__ void dec_assemble_body(DecAssemble a) {
@@ -543,12 +549,12 @@ __global__ void dec_assemble_bwd_kernel(DecAssembleBwd a) {
 template <typename IdxT>
 __device__ __forceinline__ void embed_bwd_lds_body(const IdxT* __restrict__ idx, const float* __restrict__ d, int ld,
                                                             int col0, int rows, int n, int table_rows, int rows_per_block,
-                                                            float* __restrict__ d_emb) {
+                                                            float* __restrict__ d_emb, const int bid) {
   extern __shared__ float tab[];
   const int tsz = table_rows * n;
   for (int i = threadIdx.x; i < tsz; i += 256) tab[i] = 0.f;
   __syncthreads();
-  const int r0 = blockIdx.x * rows_per_block, r1 = min(rows, r0 + rows_per_block);
+  const int r0 = bid * rows_per_block, r1 = min(rows, r0 + rows_per_block);
   const long iend = (long)r1 * n;
   for (long i = (long)r0 * n + threadIdx.x; i < iend; i += 256 * 8) {       // 8 independent loads per thread before the LDS atomics
     float v[8]; int slot[8];
@@ -572,7 +578,7 @@ __device__ __forceinline__ void embed_bwd_lds_body(const IdxT* __restrict__ idx,
 template <typename IdxT>
 __global__ __launch_bounds__(256) void embed_bwd_lds_kernel(const IdxT* __restrict__ idx, const float* __restrict__ d, int ld, int col0, int rows, int n, int table_rows, int rows_per_block,
                                                             float* __restrict__ d_emb) {
-  embed_bwd_lds_body<IdxT>(idx, d, ld, col0, rows, n, table_rows, rows_per_block, d_emb);
+  embed_bwd_lds_body<IdxT>(idx, d, ld, col0, rows, n, table_rows, rows_per_block, d_emb, (int)blockIdx.x);
 }
 
 // Deterministic form (SLN_DETERMINISTIC): one workgroup per (table row e, 64 columns).  Its four row lanes walk the source rows
@@ -780,9 +786,10 @@ __global__ void latent_bwd_kernel(const float* __restrict__ mu, const float* __r
 // ----------------------------------------------------------------------------------------------
 // rows_t / rows_o: the batch's triple / object counts; a table entry with rows == -1 / -2 means "the triples" / "the objects" (the
 // engine's table then does not change with the batch's shape: no upload per step on real rooms), rows > 0 is taken as it is
-__global__ void bn_running_update_kernel(const BnTableEntry* __restrict__ tab, int n, float mom, int per_entry, int rows_t, int rows_o) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e0 = per_entry ? blockIdx.y : 0, e1 = per_entry ? blockIdx.y + 1 : n;
+// c: the thread's column; ey: the block's entry (per_entry form)
+__device__ __forceinline__ void bn_running_update_body(const BnTableEntry* __restrict__ tab, int n, float mom, int per_entry, int rows_t, int rows_o,
+                                                       const int c, const int ey) {
+  const int e0 = per_entry ? ey : 0, e1 = per_entry ? ey + 1 : n;
   for (int e = e0; e < e1; ++e) {             // sequential form: application order, shared modules see ordered updates
     const BnTableEntry t = tab[e];
     if (c == 0 && t.nbt) t.nbt[0] += 1;
@@ -798,9 +805,12 @@ __global__ void bn_running_update_kernel(const BnTableEntry* __restrict__ tab, i
   }
 }
 
-__global__ void bn_param_grads_kernel(const BnTableEntry* __restrict__ tab, int n, int per_entry) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  const int e0 = per_entry ? blockIdx.y : 0, e1 = per_entry ? blockIdx.y + 1 : n;
+__global__ void bn_running_update_kernel(const BnTableEntry* __restrict__ tab, int n, float mom, int per_entry, int rows_t, int rows_o) {
+  bn_running_update_body(tab, n, mom, per_entry, rows_t, rows_o, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)blockIdx.y);
+}
+
+__device__ __forceinline__ void bn_param_grads_body(const BnTableEntry* __restrict__ tab, int n, int per_entry, const int c, const int ey) {
+  const int e0 = per_entry ? ey : 0, e1 = per_entry ? ey + 1 : n;
   for (int e = e0; e < e1; ++e) {
     const BnTableEntry t = tab[e];
     if (c >= t.C || t.dgamma == nullptr) continue;
@@ -808,13 +818,15 @@ __global__ void bn_param_grads_kernel(const BnTableEntry* __restrict__ tab, int 
     t.dgamma[c] += (float)t.gsums[t.cstride + c];
   }
 }
+__global__ void bn_param_grads_kernel(const BnTableEntry* __restrict__ tab, int n, int per_entry) {
+  bn_param_grads_body(tab, n, per_entry, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)blockIdx.y);
+}
 
-__global__ __launch_bounds__(256) void transpose_table_kernel(const TransposeEntry* __restrict__ tab) {
-  __shared__ float tile[32][33];
-  const TransposeEntry t = tab[blockIdx.y];
+// one 32 x 32 tile (index `tile`, row-major over the entry's tiles) of one table entry; 256 threads
+__device__ __forceinline__ void transpose_tile_body(const TransposeEntry& t, const int tile_id, float (*tile)[33]) {
   const int tr = (t.rows + 31) / 32, tc = (t.cols + 31) / 32;
-  if ((int)blockIdx.x >= tr * tc) return;
-  const int r0 = (blockIdx.x / tc) * 32, c0 = (blockIdx.x % tc) * 32;
+  if (tile_id >= tr * tc) return;
+  const int r0 = (tile_id / tc) * 32, c0 = (tile_id % tc) * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int i = ty; i < 32; i += 8) {
     const int r = r0 + i, c = c0 + tx;
@@ -825,6 +837,11 @@ __global__ __launch_bounds__(256) void transpose_table_kernel(const TransposeEnt
     const int c = c0 + i, r = r0 + tx;
     if (r < t.rows && c < t.cols) t.dst[(size_t)c * t.dst_ld + r] = tile[tx][i];
   }
+}
+__global__ __launch_bounds__(256) void transpose_table_kernel(const TransposeEntry* __restrict__ tab) {
+  __shared__ float tile[32][33];
+  const TransposeEntry t = tab[blockIdx.y];
+  transpose_tile_body(t, (int)blockIdx.x, tile);
 }
 
 // torch.optim.Adam defaults (train.py:15): no weight decay, no amsgrad.  train.py:79-81: a non-finite total loss is reported and
@@ -927,16 +944,23 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ eps, lon
   randn_body(eps, n, sc, blockIdx.x, gridDim.x);
 }
 
-// blocks [0, b0) draw eps, [b0, b1) assemble the encoder input, [b1, b2) / [b2, ..) gather the two predicate embeddings
-__global__ __launch_bounds__(256) void step_prologue_kernel(StepPrologue a, unsigned int b0, unsigned int b1, unsigned int b2, unsigned int b3) {
+// blocks [0, b0) draw eps, [b0, b1) assemble the encoder input, [b1, b2) / [b2, b3) gather the two predicate embeddings, [b3, b4) clear
+// the accumulators, [b4, ..) rebuild the transposed weights (tr_max_tiles blocks per table entry, as transpose_table_kernel's grid)
+__global__ __launch_bounds__(256) void step_prologue_kernel(StepPrologue a, unsigned int b0, unsigned int b1, unsigned int b2, unsigned int b3,
+                                                            unsigned int b4) {
+  __shared__ float tile[32][33];
   const unsigned int b = blockIdx.x;
   if (b < b0) randn_body(a.eps, a.n_eps, a.scalars, b, b0);
   else if (b < b1) enc_assemble_body(a.enc, b - b0);
   else if (b < b2) embed_gather_body(a.pidx, a.pemb_ec, a.T, a.n_ec, a.p0e, b - b1);
   else if (b < b3) embed_gather_body(a.pidx, a.pemb_dc, a.T, a.n_dc, a.p0d, b - b2);
-  else {                                  // the iteration's accumulators (one launch less than a memset node of their own)
+  else if (b < b4) {                      // the iteration's accumulators (one launch less than a memset node of their own)
     const long i = (long)(b - b3) * 256 + threadIdx.x;
     if (i * 16 < a.zero_bytes) reinterpret_cast<uint4*>(a.zero_ptr)[i] = make_uint4(0u, 0u, 0u, 0u);
+  } else {                                // W^T of every Linear for this iteration's dgrads: the weights are final since the last update
+    const unsigned int q = b - b4;
+    const TransposeEntry t = a.tr_tab[q / (unsigned int)a.tr_max_tiles];
+    transpose_tile_body(t, (int)(q % (unsigned int)a.tr_max_tiles), tile);
   }
 }
 
@@ -1124,11 +1148,11 @@ struct AssembleBwdLds {
   const float* dx0; int ld, O, rows_per_block, lds_floats;
   float* dz; int z_col0, n_z;               // decoder: dz[r, :] = dx0[r, z_col0 : z_col0 + n_z]  (dz may be null)
 };
-__device__ __forceinline__ void assemble_bwd_lds_body(AssembleBwdLds a) {
+__device__ __forceinline__ void assemble_bwd_lds_body(const AssembleBwdLds& a, const int bid) {
   extern __shared__ float tab[];
   for (int i = threadIdx.x; i < a.lds_floats; i += 256) tab[i] = 0.f;
   __syncthreads();
-  const int r0 = blockIdx.x * a.rows_per_block, r1 = min(a.O, r0 + a.rows_per_block);
+  const int r0 = bid * a.rows_per_block, r1 = min(a.O, r0 + a.rows_per_block);
   for (int s = 0; s < a.nseg; ++s) {
     const EmbSeg sg = a.seg[s];
     const long iend = (long)r1 * sg.n;
@@ -1163,7 +1187,7 @@ __device__ __forceinline__ void assemble_bwd_lds_body(AssembleBwdLds a) {
   }
 }
 __global__ __launch_bounds__(256) void assemble_bwd_lds_kernel(AssembleBwdLds a) {
-  assemble_bwd_lds_body(a);
+  assemble_bwd_lds_body(a, (int)blockIdx.x);
 }
 static int launch_assemble_bwd_lds(AssembleBwdLds a, hipStream_t st) {
   int off = 0;
@@ -1243,6 +1267,13 @@ int sln_launch_dec_assemble_bwd(DecAssembleBwd a, hipStream_t st) {
   return 0;
 }
 
+// rows per workgroup of the LDS-table embedding backward (SLN_EMB_RPB: lab override, read once)
+static int embed_rows_per_block() {
+  static const int rpb = std::getenv("SLN_EMB_RPB") && std::atoi(std::getenv("SLN_EMB_RPB")) > 0 ? std::atoi(std::getenv("SLN_EMB_RPB")) : 16;
+  return rpb;
+}
+constexpr int EMBED_LDS_MAX_FLOATS = 8192;          // largest table the LDS form of the embedding backward takes
+
 int sln_launch_embed_bwd_i32(const int* idx, const float* d, int ld, int col0, int rows, int n, int table_rows,
                              float* d_emb, hipStream_t st) {
   const long tot = (long)rows * n;
@@ -1252,10 +1283,10 @@ int sln_launch_embed_bwd_i32(const int* idx, const float* d, int ld, int col0, i
     SLN_CHECK_LAUNCH();
     return 0;
   }
-  if (table_rows > 0 && (long)table_rows * n <= 8192) {
+  if (table_rows > 0 && (long)table_rows * n <= EMBED_LDS_MAX_FLOATS) {
     // 16 rows per workgroup: 256 workgroups at 64 graphs (64 rows left three quarters of the CUs idle: 16 -> 6 us per launch;
     // 8 / 4 rows pay more flush atomics than they gain: SLN_EMB_RPB)
-    static const int rpb = std::getenv("SLN_EMB_RPB") ? std::atoi(std::getenv("SLN_EMB_RPB")) : 16;
+    const int rpb = embed_rows_per_block();
     hipLaunchKernelGGL(embed_bwd_lds_kernel<int>, dim3(sln_cdiv(rows, rpb)), dim3(256), sizeof(float) * table_rows * n, st, idx,
                        d, ld, col0, rows, n, table_rows, rpb, d_emb);
     SLN_CHECK_LAUNCH();
@@ -1276,10 +1307,10 @@ int sln_launch_embed_bwd_i64(const int64_t* idx, const float* d, int ld, int col
     SLN_CHECK_LAUNCH();
     return 0;
   }
-  if (table_rows > 0 && (long)table_rows * n <= 8192) {
+  if (table_rows > 0 && (long)table_rows * n <= EMBED_LDS_MAX_FLOATS) {
     // 16 rows per workgroup: 256 workgroups at 64 graphs (64 rows left three quarters of the CUs idle: 16 -> 6 us per launch;
     // 8 / 4 rows pay more flush atomics than they gain: SLN_EMB_RPB)
-    static const int rpb = std::getenv("SLN_EMB_RPB") ? std::atoi(std::getenv("SLN_EMB_RPB")) : 16;
+    const int rpb = embed_rows_per_block();
     hipLaunchKernelGGL(embed_bwd_lds_kernel<int64_t>, dim3(sln_cdiv(rows, rpb)), dim3(256), sizeof(float) * table_rows * n, st,
                        idx, d, ld, col0, rows, n, table_rows, rpb, d_emb);
     SLN_CHECK_LAUNCH();
@@ -1391,9 +1422,107 @@ int sln_launch_step_prologue(const StepPrologue& a, hipStream_t st) {
   const unsigned int ne = blocks((long)a.enc.O * (a.enc.n_obj + a.enc.n_attr + a.enc.n_box + a.enc.n_angle));
   const unsigned int n1 = blocks((long)a.T * a.n_ec), n2 = blocks((long)a.T * a.n_dc);
   const unsigned int nz = a.zero_ptr ? blocks(a.zero_bytes / 16) : 0;
-  const unsigned int tot = nr + ne + n1 + n2 + nz;
+  const unsigned int nt = (a.tr_tab && a.n_tr > 0 && a.tr_max_tiles > 0) ? (unsigned int)a.n_tr * (unsigned int)a.tr_max_tiles : 0;
+  const unsigned int tot = nr + ne + n1 + n2 + nz + nt;
   if (tot == 0) return 0;
-  hipLaunchKernelGGL(step_prologue_kernel, dim3(tot), dim3(256), 0, st, a, nr, nr + ne, nr + ne + n1, nr + ne + n1 + n2);
+  hipLaunchKernelGGL(step_prologue_kernel, dim3(tot), dim3(256), 0, st, a, nr, nr + ne, nr + ne + n1, nr + ne + n1 + n2, nr + ne + n1 + n2 + nz);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ----------------------------------------------------------------------------------------------
+// The leaves of a full training iteration as ONE launch: kernels whose results nothing reads before the optimizer - the three
+// embedding-table gradients that are not part of an assembly, the encoder's assembly tables, the box embedding's Linear, the
+// BatchNorm parameter gradients and the running-statistics update.  Each runs 30-260 workgroups for 5-10 us on its own; side
+// by side they take about as long as the longest.  The block index selects the job (longest jobs first); every job runs the
+// body of its stand-alone kernel.
+// ----------------------------------------------------------------------------------------------
+struct LeafEmbedJob { const void* idx; const float* d; float* d_emb; int ld, col0, rows, n, table_rows, rpb; };
+struct LeafArgs {
+  AssembleBwdLds asmb;
+  EncAssembleBwd box; int box_gx;
+  LeafEmbedJob pdc, pec, attr;          // int32 / int32 / int64 indices
+  const BnTableEntry* bn_tab; int bn_n, bn_per_entry, bn_gx, rows_t, rows_o; float mom;
+};
+// blocks [0, b0) encoder assembly tables, [b0, b1) box embedding, [b1, b2) / [b2, b3) decoder / encoder predicate table,
+// [b3, b4) decoder attribute table, [b4, b5) BatchNorm parameter gradients, [b5, ..) running statistics
+__global__ __launch_bounds__(256) void vae_leaf_kernel(unsigned int b0, unsigned int b1, unsigned int b2, unsigned int b3, unsigned int b4,
+                                                       unsigned int b5, LeafArgs a) {
+  extern __shared__ float tab[];
+  const unsigned int b = blockIdx.x;
+  if (b < b0) assemble_bwd_lds_body(a.asmb, (int)b);
+  else if (b < b1) {
+    const int q = (int)(b - b0);
+    box_embed_bwd_body(a.box, (int)BOX_ROWS, q % a.box_gx, q / a.box_gx, (int)(threadIdx.x % CB), (int)(threadIdx.x / CB),
+                       reinterpret_cast<float (*)[RL][CB]>(tab));
+  } else if (b < b2)
+    embed_bwd_lds_body<int>(static_cast<const int*>(a.pdc.idx), a.pdc.d, a.pdc.ld, a.pdc.col0, a.pdc.rows, a.pdc.n, a.pdc.table_rows, a.pdc.rpb,
+                            a.pdc.d_emb, (int)(b - b1));
+  else if (b < b3)
+    embed_bwd_lds_body<int>(static_cast<const int*>(a.pec.idx), a.pec.d, a.pec.ld, a.pec.col0, a.pec.rows, a.pec.n, a.pec.table_rows, a.pec.rpb,
+                            a.pec.d_emb, (int)(b - b2));
+  else if (b < b4)
+    embed_bwd_lds_body<int64_t>(static_cast<const int64_t*>(a.attr.idx), a.attr.d, a.attr.ld, a.attr.col0, a.attr.rows, a.attr.n,
+                                a.attr.table_rows, a.attr.rpb, a.attr.d_emb, (int)(b - b3));
+  else if (b < b5) {
+    const int q = (int)(b - b4);
+    bn_param_grads_body(a.bn_tab, a.bn_n, a.bn_per_entry, (q % a.bn_gx) * 256 + (int)threadIdx.x, q / a.bn_gx);
+  } else {
+    const int q = (int)(b - b5);
+    bn_running_update_body(a.bn_tab, a.bn_n, a.mom, a.bn_per_entry, a.rows_t, a.rows_o, (q % a.bn_gx) * 256 + (int)threadIdx.x, q / a.bn_gx);
+  }
+}
+
+// every job of the leaf launch on its LDS path (the stand-alone launchers' own conditions); deterministic mode never is
+int sln_vae_leaf_fits(const VaeLeaf& a) {
+  if (g_sln_deterministic) return 0;
+  const EncAssembleBwd& e = a.enc;
+  if (e.O <= 0 || a.pred_rows <= 0) return 0;
+  if (!(e.rows_obj > 0 && e.rows_angle > 0 && (e.n_attr == 0 || e.rows_attr > 0))) return 0;
+  if ((long)e.rows_obj * e.n_obj + (long)e.rows_attr * e.n_attr + (long)e.rows_angle * e.n_angle > ASSEMBLE_LDS_MAX_FLOATS) return 0;
+  if (a.pred_table_rows <= 0 || (long)a.pred_table_rows * a.n_pdc > EMBED_LDS_MAX_FLOATS || (long)a.pred_table_rows * a.n_pec > EMBED_LDS_MAX_FLOATS)
+    return 0;
+  if (a.n_attr_dc > 0 && (a.attr_table_rows <= 0 || (long)a.attr_table_rows * a.n_attr_dc > EMBED_LDS_MAX_FLOATS)) return 0;
+  if (a.n_pdc <= 0 || a.n_pec <= 0 || e.n_box <= 0) return 0;
+  return 1;
+}
+
+int sln_launch_vae_leaf(const VaeLeaf& v, hipStream_t st) {
+  if (!sln_vae_leaf_fits(v)) return -1;      // SLN_E_BADARG: the caller checks sln_vae_leaf_fits first
+  LeafArgs a; std::memset(&a, 0, sizeof(a));
+  const EncAssembleBwd& e = v.enc;
+  // the encoder's assembly tables: as sln_launch_enc_assemble_bwd / launch_assemble_bwd_lds
+  AssembleBwdLds& l = a.asmb;
+  l.dx0 = e.dx0; l.ld = e.n_obj + e.n_attr + e.n_box + e.n_angle; l.O = e.O;
+  int k = 0;
+  l.seg[k++] = EmbSeg{e.objs, e.d_obj_emb, e.n_obj, e.rows_obj, 0, 0};
+  if (e.n_attr > 0) l.seg[k++] = EmbSeg{e.attrs, e.d_attr_emb, e.n_attr, e.rows_attr, e.n_obj, 0};
+  l.seg[k++] = EmbSeg{e.angles, e.d_angle_emb, e.n_angle, e.rows_angle, e.n_obj + e.n_attr + e.n_box, 0};
+  l.nseg = k;
+  int off = 0;
+  for (int s = 0; s < l.nseg; ++s) { l.seg[s].lds0 = off; off += l.seg[s].rows * l.seg[s].n; }
+  l.lds_floats = off;
+  l.rows_per_block = l.O <= 8192 ? 16 : 64;
+  a.box = e; a.box_gx = sln_cdiv(e.n_box, CB);
+  const int rpb = embed_rows_per_block();
+  a.pdc = LeafEmbedJob{v.pidx, v.d_pdc, v.d_pred_dc, v.ld_pdc, v.col0_pdc, v.pred_rows, v.n_pdc, v.pred_table_rows, rpb};
+  a.pec = LeafEmbedJob{v.pidx, v.d_pec, v.d_pred_ec, v.ld_pec, v.col0_pec, v.pred_rows, v.n_pec, v.pred_table_rows, rpb};
+  if (v.n_attr_dc > 0) a.attr = LeafEmbedJob{v.attr_idx, v.d_attr, v.d_attr_dc, v.ld_attr, v.col0_attr, e.O, v.n_attr_dc, v.attr_table_rows, rpb};
+  a.bn_tab = v.bn_tab; a.bn_n = v.bn_n; a.bn_per_entry = v.bn_independent ? 1 : 0; a.bn_gx = sln_cdiv(v.bn_max_c > 0 ? v.bn_max_c : 1, 256);
+  a.rows_t = v.pred_rows; a.rows_o = e.O; a.mom = v.bn_momentum;
+  const unsigned int n_bn = v.bn_n > 0 ? (unsigned int)a.bn_gx * (unsigned int)(a.bn_per_entry ? v.bn_n : 1) : 0;
+  const unsigned int n_asm = (unsigned int)sln_cdiv(l.O, l.rows_per_block);
+  const unsigned int n_box = (unsigned int)a.box_gx * (unsigned int)sln_cdiv(e.O, BOX_ROWS);
+  const unsigned int n_pred = (unsigned int)sln_cdiv(v.pred_rows, rpb);
+  const unsigned int n_attr = v.n_attr_dc > 0 ? (unsigned int)sln_cdiv(e.O, rpb) : 0;
+  const unsigned int b0 = n_asm, b1 = b0 + n_box, b2 = b1 + n_pred, b3 = b2 + n_pred, b4 = b3 + n_attr, b5 = b4 + n_bn;
+  const unsigned int tot = b5 + (v.bn_update ? n_bn : 0);
+  // dynamic LDS: the largest table of any job, and the box job's 7 x RL x CB partial sums
+  size_t lds = sizeof(float) * 7 * RL * CB;
+  auto grow = [&lds](long floats) { if (sizeof(float) * (size_t)floats > lds) lds = sizeof(float) * (size_t)floats; };
+  grow(l.lds_floats); grow((long)v.pred_table_rows * v.n_pdc); grow((long)v.pred_table_rows * v.n_pec);
+  if (v.n_attr_dc > 0) grow((long)v.attr_table_rows * v.n_attr_dc);
+  hipLaunchKernelGGL(vae_leaf_kernel, dim3(tot), dim3(256), lds, st, b0, b1, b2, b3, b4, b5, a);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -1451,7 +1580,7 @@ static_assert(sizeof(MAsmLds) <= SLN_ASM_BLOB && sizeof(MDecAssembleBwd) <= SLN_
 __global__ __launch_bounds__(256) void assemble_bwd_lds_multi_kernel(const char* __restrict__ tab) {
   const MAsmLds& a = *reinterpret_cast<const MAsmLds*>(tab + (size_t)blockIdx.z * SLN_ASM_BLOB);
   if ((int)blockIdx.x >= a.gx) return;
-  assemble_bwd_lds_body(a.a);
+  assemble_bwd_lds_body(a.a, (int)blockIdx.x);
 }
 __global__ void dec_assemble_bwd_plain_multi_kernel(const char* __restrict__ tab) {
   const MDecAssembleBwd& a = *reinterpret_cast<const MDecAssembleBwd*>(tab + (size_t)blockIdx.z * SLN_ASM_BLOB);
@@ -1469,7 +1598,7 @@ __global__ __launch_bounds__(V == MV_EMBED_DET ? 1024 : 256) void embed_bwd_mult
   if ((int)blockIdx.x >= a.gx || (int)blockIdx.y >= a.gy) return;
   const IdxT* idx = static_cast<const IdxT*>(a.idx);
   if (V == MV_EMBED_DET) embed_bwd_det_body<IdxT>(idx, a.d, a.ld, a.col0, a.rows, a.n, a.d_emb);
-  else if (V == MV_EMBED_LDS) embed_bwd_lds_body<IdxT>(idx, a.d, a.ld, a.col0, a.rows, a.n, a.table_rows, a.rows_per_block, a.d_emb);
+  else if (V == MV_EMBED_LDS) embed_bwd_lds_body<IdxT>(idx, a.d, a.ld, a.col0, a.rows, a.n, a.table_rows, a.rows_per_block, a.d_emb, (int)blockIdx.x);
   else embed_bwd_body<IdxT>(idx, a.d, a.ld, a.col0, a.rows, a.n, a.d_emb);
 }
 __global__ void add2_multi_kernel(const MAdd2* __restrict__ tab) {

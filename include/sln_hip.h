@@ -467,6 +467,10 @@ typedef struct SlnDbgOpt {
 int sln_debug_vae_opt(SlnDbgOpt* desc, void* stream);
 /* sizeof of SlnDbgCsr, SlnDbgEdge, SlnDbgLoss, SlnDbgBnEntry, SlnDbgTranspose, SlnDbgOpt, SlnDbgEmbed; returns how many there are. */
 int sln_debug_vae_sizes(int* out, int max);
+/* How many times an engine issued the one-launch form of an iteration's leaf kernels (embedding-table, box-embedding and
+ * BatchNorm bookkeeping gradients deferred to the end of a full iteration); 0 while it keeps the per-kernel sequence
+ * (SLN_LEAF_MERGE=0, deterministic mode, tables past the LDS caps, the two-half form).  A captured iteration counts once. */
+int64_t sln_debug_vae_leaf_launches(const SlnVae* h);
 
 
 /* =============================================================================================
