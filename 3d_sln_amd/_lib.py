@@ -195,6 +195,7 @@ SIGNATURES = {
     "sln_vae_randn": (C.c_int, [C.c_void_p, c_f32p, C.c_int64, C.c_void_p]),
     "sln_layout_heatmap": (C.c_int, [c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p]),
     "sln_vae_set_training": (C.c_int, [C.c_void_p, C.c_int]),
+    "sln_vae_set_gemm_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "sln_vae_train_step": (C.c_int, [C.c_void_p, c_f32p, C.c_float, C.c_float, c_f32p, C.c_int, C.c_int, C.c_void_p]),
     "sln_vae_group_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(SlnVaeGroupIO), C.POINTER(C.c_void_p)]),
     "sln_vae_group_decoder": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -225,6 +226,8 @@ SIGNATURES = {
     "sln_debug_gemm_nt": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "sln_debug_gemm_tn": (C.c_int, [C.POINTER(SlnDbgGemmTN), C.c_int, C.c_int, C.c_void_p]),
     "sln_debug_gemm_nt_route": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.POINTER(SlnDbgNTRoute)]),
+    "sln_debug_gemm_nt_half": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.c_int, C.c_void_p]),
+    "sln_debug_gemm_nt_half_takes": (C.c_int, [C.POINTER(SlnDbgGemmNT)]),
     "sln_debug_gemm_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "sln_debug_vae_csr": (C.c_int, [c_i64p, C.c_int, C.c_int, C.c_int, C.POINTER(SlnDbgCsr), C.c_void_p, C.c_void_p]),
     "sln_debug_vae_edge": (C.c_int, [C.POINTER(SlnDbgEdge), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
@@ -234,6 +237,7 @@ SIGNATURES = {
     "sln_debug_vae_opt": (C.c_int, [C.POINTER(SlnDbgOpt), C.c_void_p]),
     "sln_debug_vae_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "sln_debug_vae_leaf_launches": (C.c_int64, [C.c_void_p]),
+    "sln_debug_vae_half_launches": (C.c_int64, [C.c_void_p]),
     "sln_project_faces": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p]),
     "sln_project_faces_backward": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p,
                                              c_f32p, C.c_void_p]),

@@ -563,6 +563,20 @@ extern "C" int sln_debug_gemm_nt(const SlnDbgGemmNT* desc, int n, int* grouped, 
   return 0;
 }
 
+// the fp16-MFMA launcher (gemm_half.hip) on a caller-built problem; the predicate alone is host only
+extern "C" int sln_debug_gemm_nt_half_takes(const SlnDbgGemmNT* desc) {
+  GemmNTArgs a;
+  if (!desc || !dbg_nt(*desc, a)) return SLN_E_BADARG;
+  return sln_nt_half_takes(a, desc->epi) ? 1 : 0;
+}
+
+extern "C" int sln_debug_gemm_nt_half(const SlnDbgGemmNT* desc, int terms, void* stream) {
+  GemmNTArgs a;
+  if (!desc || (terms != 1 && terms != 3) || !dbg_nt(*desc, a)) return SLN_E_BADARG;
+  if (!sln_nt_half_takes(a, desc->epi)) return SLN_E_UNSUPPORTED;
+  return sln_launch_gemm_nt_half(a, terms, (hipStream_t)stream);
+}
+
 extern "C" int sln_debug_gemm_tn(const SlnDbgGemmTN* desc, int n, int multi, void* stream) {
   if (!desc || n < 1 || n > SLN_TN_MULTI_MAX || (!multi && n != 1)) return SLN_E_BADARG;
   std::vector<GemmTNArgs> probs((size_t)n);

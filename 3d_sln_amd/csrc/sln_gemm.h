@@ -42,6 +42,11 @@ struct GemmTNArgs {
 // epi: EPI_*; tile: -1 = heuristic, 0 = 64x64, 1 = 128x64, 2 = 128x128
 int sln_launch_gemm_nt(const GemmNTArgs& a, int epi, int tile, hipStream_t st);
 int sln_launch_gemm_tn(const GemmTNArgs& a, hipStream_t st);
+// fp16-MFMA forms of the plain NT product (gemm_half.hip; the opt-in precision modes of the VAE's eval-mode Linears).
+// sln_nt_half_takes: host only, no device access; M plays no part in it.  terms: 1 = "f16" (operands rounded to fp16),
+// 3 = "f16x3" (hi / lo split of both operands, three products); returns SLN_E_UNSUPPORTED when the predicate refuses.
+bool sln_nt_half_takes(const GemmNTArgs& a, int epi);
+int sln_launch_gemm_nt_half(const GemmNTArgs& a, int terms, hipStream_t st);
 // up to two independent NT problems in one launch (gemm_group.hip); returns 1 without launching anything when the problems
 // cannot share a kernel - the caller launches them separately then
 int sln_launch_gemm_group(const GemmNTArgs* nt, const int* epi, int n_nt, hipStream_t st);

@@ -306,6 +306,10 @@ struct SlnVae {
   bool it_wt_prologue = false;    // this iteration's prologue rebuilds the transposed weights when they are stale
   bool leaf_merge = true;         // SLN_LEAF_MERGE=0 at creation: neither, the per-kernel sequence
   long leaf_launches = 0;         // leaf launches issued by this engine (sln_vae_leaf_launches)
+  // Opt-in precision of the eval-mode forward Linears (sln_vae_set_gemm_precision): 0 fp32, 1 "f16", 3 "f16x3" (gemm_half.hip)
+  int gemm_precision = 0;
+  bool in_iteration = false;      // train_iteration's forwards stay on fp32 whatever their BatchNorm mode
+  long half_launches = 0;         // fp16-MFMA launches issued by this engine (sln_debug_vae_half_launches)
   bool gconv_only = false;        // a bare GraphTripleConvNet (sln_gconv_net_*): units = the modules' four Linears, one net, no heads
   int unit_of(int net, int l, int k) const { return (gconv_only ? 0 : 8) + (net * nmod + (cfg.recurrent ? 0 : l)) * 4 + k; }
   int unit_boxnet(int k) const { return 8 + 2 * nmod * 4 + k; }
@@ -408,6 +412,11 @@ struct SlnVae {
     int epi = EPI_PLAIN;
     if (inst >= 0 && bn_mode(bns[inst], training) == SLN_BN_TRAIN) { epi = EPI_STATS; a.osums = bns[inst].sums; a.ocstride = bns[inst].C; }
     if (rec) { RecStep& r = rec_push(SK_NT); r.nt = a; r.epi = epi; return 0; }
+    // the opt-in half modes: eval-mode forwards only, launched directly (the problems of a group are independent of each other)
+    if (!training && !in_iteration && gemm_precision != 0 && epi == EPI_PLAIN && sln_nt_half_takes(a, epi)) {
+      ++half_launches;
+      return sln_launch_gemm_nt_half(a, gemm_precision == 3 ? 3 : 1, st);
+    }
     if (grouping) { group_items.push_back(GroupItem{a, epi}); return 0; }
     return sln_launch_gemm_nt(a, epi, -1, st);
   }
@@ -988,8 +997,10 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
     it_leaf = it_merge_bn && dG[2] != nullptr && T > 0 && sln_vae_leaf_fits(leaf_args()) != 0;
     it_wt_prologue = it_prologue && leaf_merge && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);
     if (!it_prologue && draw_eps) r = sln_launch_randn(eps_buf, (long)O * E, scalars, st);       // Sg2ScVAE_model.py:182
+    in_iteration = true;
     if (!r) r = encoder_forward(step_training, st);
     if (!r) r = decoder_forward(nullptr, eps, step_training, st);
+    in_iteration = false;
     if (!r) r = loss(boxes_pred, angles_pred, mu, logvar, true, st);
     // data-parallel guard: the total loss travels with the gradients (one more element of the all-reduced bucket); a
     // non-finite loss on ANY rank makes the reduced slot non-finite on EVERY rank, and sln_vae_adam_step skips on all of them
@@ -1013,6 +1024,7 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
 }
 
 long sln_vae_engine_leaf_launches(const SlnVae* h) { return h->leaf_launches; }        // for the test hook in vae_debug.hip
+long sln_vae_engine_half_launches(const SlnVae* h) { return h->half_launches; }
 
 // =============================================================================================
 // C ABI
@@ -1400,6 +1412,12 @@ int sln_vae_last_eps(SlnVae* h, float* eps_out, void* stream) {
 int sln_vae_set_training(SlnVae* h, int training) {
   if (!h) return SLN_E_BADARG;
   if (h->step_training != (training != 0)) { h->step_training = training != 0; h->drop_graphs(); }
+  return 0;
+}
+
+int sln_vae_set_gemm_precision(SlnVae* h, int mode) {      // eval-mode forwards only (linear_fwd); captured iterations never read it
+  if (!h || (mode != 0 && mode != 1 && mode != 3)) return SLN_E_BADARG;
+  h->gemm_precision = mode;
   return 0;
 }
 

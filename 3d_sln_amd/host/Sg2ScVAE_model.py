@@ -88,6 +88,9 @@ class _DecoderFn(torch.autograd.Function):
         return None, dz, None, None
 
 
+_GEMM_PRECISION = {"fp32": 0, "f16": 1, "f16x3": 3}      # mode values of sln_vae_set_gemm_precision
+
+
 class Sg2ScVAEModel(nn.Module):
     def __init__(self, vocab, embedding_dim=128, batch_size=32, train_3d=True, decoder_cat=False, Nangle=24,
                  gconv_mode='feedforward', gconv_pooling='avg', gconv_num_layers=5, mlp_normalization='none',
@@ -138,6 +141,7 @@ class Sg2ScVAEModel(nn.Module):
             m.apply(_init_weights)
 
         self.validate_inputs = True      # one host sync per NEW batch; set False in a tuned training loop
+        self._gemm_precision = "fp32"    # see the gemm_precision property; a plain attribute: not part of state_dict
         self._eng = None
         self._generation = 0
         self._batch_key = None
@@ -242,6 +246,23 @@ class Sg2ScVAEModel(nn.Module):
         out = self._new(int(rows), int(cols))
         _lib.check(_lib.lib().sln_vae_randn(self._eng, _lib.ptr(out), out.numel(), _lib.current_stream_ptr()), "sln_vae_randn")
         return out
+
+    @property
+    def gemm_precision(self):
+        """Precision of the eval-mode forward Linears: ``"fp32"`` (default: the fp32-MFMA launches, unchanged bits), ``"f16x3"``
+        (fp16 hi / lo split of both operands on the fp16 MFMA, three products: fp32-grade while the operands stay inside
+        +-65504) or ``"f16"`` (operands rounded to fp16: a preview mode with its own error budget, tools/vae_half_budget.py).
+        Training-mode forwards, ``train_step``, every backward pass and ``RefineBatch`` stay fp32 whatever this says.  Not part
+        of ``state_dict``."""
+        return self._gemm_precision
+
+    @gemm_precision.setter
+    def gemm_precision(self, mode):
+        if mode not in _GEMM_PRECISION:
+            raise ValueError("gemm_precision must be one of %s, not %r" % (", ".join(repr(k) for k in _GEMM_PRECISION), mode))
+        self._gemm_precision = mode
+        if getattr(self, "_eng", None) is not None:
+            _lib.check(_lib.lib().sln_vae_set_gemm_precision(self._eng, _GEMM_PRECISION[mode]), "sln_vae_set_gemm_precision")
 
     def params_changed(self):
         """Call after modifying parameters outside the engine (e.g. a torch optimizer step)."""
@@ -435,6 +456,7 @@ class Sg2ScVAEModel(nn.Module):
             # in the workspace - without this the update after a re-bind would be scaled as if it were the first one
             _lib.check(L.sln_vae_adam_reset(h, int(self._adam_steps), _lib.current_stream_ptr()), "sln_vae_adam_reset")
         _lib.check(L.sln_vae_set_grad_guard(h, C.c_void_p(self._gfull.data_ptr() + 4 * self._gflat.numel())), "sln_vae_set_grad_guard")
+        _lib.check(L.sln_vae_set_gemm_precision(h, _GEMM_PRECISION[self._gemm_precision]), "sln_vae_set_gemm_precision")
         if getattr(self, "_rng_seed", None) is None:
             self._rng_seed, self._rng_epoch = int(torch.initial_seed()) & (2 ** 64 - 1), 0
         # a re-created engine (larger batch) continues on a disjoint range of Philox offsets

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 from . import diff_render as DR
 from . import scene_pictures as SP
 from . import synthetic
+from .sampling import _precision
 from .. import _lib
 
 DO_NOT_VIS = ["wall", "ceiling", "floor", "person", "door", "window", "curtain", "blinds"]
@@ -755,7 +756,8 @@ class RefineBatch:
         scenes, targets, size_targets = [], [], []
         box_last, angle_last = torch.empty(R, 6, **f32), torch.empty(R, **f32)
         for r, rm in enumerate(rooms):
-            with torch.no_grad():
+            # (fp32 whatever model.gemm_precision says: the refinement loop's room engines are fp32 only, and so is its starting point)
+            with _precision(model, "fp32"), torch.no_grad():
                 mu, logvar = model.encoder(rm["objs"], rm["triples"], rm["boxes"], rm["angles"], rm["attributes"])
             gen = torch.Generator(device="cpu").manual_seed(noise_seed)          # torch.manual_seed(13) in front of every trial (:274-275)
             a, n = self.row0[r], self.rows[r]

@@ -8,6 +8,7 @@
     N(mean, cov) per object as ``np.random.multivariate_normal`` does (test_VAE.py:83-84), BatchNorm runs on its
     running statistics (``model.eval()``).
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -15,12 +16,28 @@ import torch
 from .. import _lib
 
 
-def posterior_stats(model, batches):
-    """batches: iterable of (objs, triples, boxes, angles, attributes).  -> (mean [E], cov [E,E]) float64 on the CPU."""
+@contextlib.contextmanager
+def _precision(model, precision):
+    """``precision`` (None: the model's own ``gemm_precision``) for the span of one call; the previous mode comes back even when
+    the call raises."""
+    if precision is None:
+        yield
+        return
+    was = model.gemm_precision
+    model.gemm_precision = precision
+    try:
+        yield
+    finally:
+        model.gemm_precision = was
+
+
+def posterior_stats(model, batches, precision=None):
+    """batches: iterable of (objs, triples, boxes, angles, attributes).  -> (mean [E], cov [E,E]) float64 on the CPU.
+    ``precision``: ``model.gemm_precision`` for this call (None: as the model is set)."""
     mus = []
     was_training = model.training
     model.eval()
-    with torch.no_grad():
+    with _precision(model, precision), torch.no_grad():
         for objs, triples, boxes, angles, attributes in batches:
             mu, _ = model.encoder(objs, triples, boxes, angles, attributes)
             mus.append(mu.double())
@@ -69,12 +86,13 @@ def _factor(mean, cov, E, dev):
     return hit[:2]
 
 
-def sample_layouts(model, objs, triples, attributes, n_samples=4, mean=None, cov=None, generator=None, z=None):
+def sample_layouts(model, objs, triples, attributes, n_samples=4, mean=None, cov=None, generator=None, z=None, precision=None):
     """-> boxes_pred [n_samples, O, box_dim], angle_bins [n_samples, O] (argmax of the log-probabilities), z [n_samples, O, E].
 
     The N(0,1) draw behind z comes from the DEVICE (the engine's Philox stream, ``model.manual_seed``) unless a CPU
     ``generator`` is passed (reproducible against a host-side reference) or ``z`` [n_samples * O, E] is injected;
-    z = mean + eps L^T with the Cholesky factor of ``cov`` is one GEMM of the engine's own family (sln_linear_forward)."""
+    z = mean + eps L^T with the Cholesky factor of ``cov`` is one GEMM of the engine's own family (sln_linear_forward), fp32 in
+    every mode.  ``precision``: ``model.gemm_precision`` for the decode of this call (None: as the model is set)."""
     dev = objs.device
     E, O = model.embedding_dim, objs.shape[0]
     ro, rt, ra = _replicated(objs, triples, attributes, n_samples)
@@ -93,9 +111,11 @@ def sample_layouts(model, objs, triples, attributes, n_samples=4, mean=None, cov
             z = torch.empty_like(eps)
             _lib.check(_lib.lib().sln_linear_forward(_lib.ptr(eps), eps.shape[0], E, _lib.ptr(L), _lib.ptr(mu), _lib.ptr(z), E, None, -1,
                                                      _lib.current_stream_ptr()), "sln_linear_forward")
-    with torch.no_grad():
-        bp, ap = model.decoder(z, ro, rt, ra)
-    model.train(was_training)
+    try:
+        with _precision(model, precision), torch.no_grad():
+            bp, ap = model.decoder(z, ro, rt, ra)
+    finally:
+        model.train(was_training)
     return bp.view(n_samples, O, -1), ap.view(n_samples, O, -1).argmax(2), z.view(n_samples, O, E)
 
 
@@ -154,7 +174,8 @@ def scene_graph_from_words(objs_in_scene, rels_in_scene, valid_classes=None, dev
 _WORD_GRAPHS = {}
 
 
-def heatmap_from_words(model, objs_in_scene, rels_in_scene, mean, cov, num_iter=20000, chunk=None, container_size=100, generator=None):
+def heatmap_from_words(model, objs_in_scene, rels_in_scene, mean, cov, num_iter=20000, chunk=None, container_size=100, generator=None,
+                       precision=None):
     """testing/test_heatmap.py:52-99 without the 20 000 single-graph decodes: ``chunk`` posterior samples of the scene (default: all
     of them) are decoded per engine call (replicated disjoint graphs) and accumulated into the per-object centre histograms on the
     device: z drawn there, one histogram launch per chunk, nothing crosses the bus but the result."""
@@ -169,13 +190,14 @@ def heatmap_from_words(model, objs_in_scene, rels_in_scene, mean, cov, num_iter=
     counts, done = None, 0
     while done < num_iter:
         n = min(chunk, num_iter - done)
-        bp, _, _ = sample_layouts(model, objs, triples, attrs, n_samples=n, mean=mean, cov=cov, generator=generator)
+        bp, _, _ = sample_layouts(model, objs, triples, attrs, n_samples=n, mean=mean, cov=cov, generator=generator, precision=precision)
         counts = layout_counts(bp, container_size, True, out=counts)
         done += n
     return counts / counts.sum((1, 2), keepdim=True).clamp(min=1.0)
 
 
-def footprints_from_words(model, objs_in_scene, rels_in_scene, mean, cov, num_iter=20000, chunk=None, size=100, generator=None):
+def footprints_from_words(model, objs_in_scene, rels_in_scene, mean, cov, num_iter=20000, chunk=None, size=100, generator=None,
+                          precision=None):
     """``heatmap_from_words`` with footprints instead of centres: ``num_iter`` posterior samples of the scene are decoded in chunks and
     every object's rotated footprint (the ring testing/test_plot2d.py:88-110 draws, with the decoded angle bin) is accumulated on the
     device (``plot2d.layout_footprints``) -> counts [n + 1, size, size] int32: per object row and pixel the number of samples that
@@ -195,7 +217,7 @@ def footprints_from_words(model, objs_in_scene, rels_in_scene, mean, cov, num_it
     counts, done = None, 0
     while done < num_iter:
         n = min(chunk, num_iter - done)
-        bp, ab, _ = sample_layouts(model, objs, triples, attrs, n_samples=n, mean=mean, cov=cov, generator=generator)
+        bp, ab, _ = sample_layouts(model, objs, triples, attrs, n_samples=n, mean=mean, cov=cov, generator=generator, precision=precision)
         counts = _P.layout_footprints(bp, ab, rr, rank, size=size, counts=counts)
         done += n
     return counts

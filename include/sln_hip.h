@@ -187,6 +187,15 @@ enum { SLN_TRAIN_BACKWARD = 0, SLN_TRAIN_FULL = 1, SLN_TRAIN_UPTO_DECODER = 2, S
 /* BatchNorm mode of sln_vae_train_step: 1 (default) = batch statistics + running-stat update, 0 = running statistics as a fixed
  * affine map (train.py:63-65: after --eval_mode_after the reference calls model.eval() and keeps training). */
 int sln_vae_set_training(SlnVae* h, int training);
+/* Precision of the eval-mode forward Linears (opt-in; DESIGN.md section 4, "A-half").  mode 0 (default): fp32 MFMA, the launches and
+ * bits of every earlier version.  1 ("f16"): operands rounded to fp16, one v_mfma_f32_32x32x16_f16 product, fp32 accumulation - a
+ * preview mode with its own error budget (tools/vae_half_budget.py).  3 ("f16x3"): fp16 hi / lo split of both operands, three
+ * products - fp32-grade while every staged operand lies inside +-65504 (larger values are clamped) and above fp16's subnormal
+ * range (lo is subnormal below 2^-14).  Taken by sln_vae_encoder / sln_vae_decoder / sln_vae_forward with training == 0 for the
+ * Linears csrc/gemm_half.hip accepts (N % 32 == 0, K % 16 == 0, segment widths % 16 == 0); the narrow heads (box_net.1,
+ * angle_net.1, mu / logvar) stay on fp32.  Never taken by training-mode forwards, sln_vae_train_step, any backward pass,
+ * sln_vae_group_* (recorded steps), sln_linear_forward or sln_gconv_*.  Any other mode value: SLN_E_BADARG. */
+int sln_vae_set_gemm_precision(SlnVae* h, int mode);
 int sln_vae_train_step(SlnVae* h, const float* eps, float kl_weight, float lr, float* losses_out, int use_graph,
                        int with_adam, void* stream);
 
@@ -367,6 +376,11 @@ int sln_debug_gemm_nt(const SlnDbgGemmNT* desc, int n, int* grouped, void* strea
 int sln_debug_gemm_tn(const SlnDbgGemmTN* desc, int n, int multi, void* stream);
 /* Host only: the kernel sln_launch_gemm_nt would run for this description (the launcher's own decision function). */
 int sln_debug_gemm_nt_route(const SlnDbgGemmNT* desc, SlnDbgNTRoute* out);
+/* The fp16-MFMA launcher (csrc/gemm_half.hip) on a caller-built problem; terms: 1 = "f16", 3 = "f16x3".  SLN_E_UNSUPPORTED, with
+ * nothing launched, when its route predicate refuses the description (tile is not read). */
+int sln_debug_gemm_nt_half(const SlnDbgGemmNT* desc, int terms, void* stream);
+/* Host only: 1 when the fp16-MFMA launcher takes the description, 0 when it refuses, SLN_E_BADARG for a malformed one. */
+int sln_debug_gemm_nt_half_takes(const SlnDbgGemmNT* desc);
 /* sizeof of the description structs, in the order SlnDbgBn, SlnDbgSeg, SlnDbgOperand, SlnDbgGemmNT, SlnDbgGemmTN, SlnDbgNTRoute;
  * returns how many there are (fills at most max). */
 int sln_debug_gemm_sizes(int* out, int max);
@@ -471,6 +485,8 @@ int sln_debug_vae_sizes(int* out, int max);
  * BatchNorm bookkeeping gradients deferred to the end of a full iteration); 0 while it keeps the per-kernel sequence
  * (SLN_LEAF_MERGE=0, deterministic mode, tables past the LDS caps, the two-half form).  A captured iteration counts once. */
 int64_t sln_debug_vae_leaf_launches(const SlnVae* h);
+/* Running count of the fp16-MFMA Linear launches an engine issued (sln_vae_set_gemm_precision). */
+int64_t sln_debug_vae_half_launches(const SlnVae* h);
 
 
 /* =============================================================================================
