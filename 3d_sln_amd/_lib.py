@@ -337,6 +337,9 @@ SIGNATURES = {
     "sln_scene_pictures_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "sln_scene_pictures": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sln_mesh_retrieve": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "sln_shell_retrieve": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

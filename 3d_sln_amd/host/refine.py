@@ -10,9 +10,10 @@ What is reproduced from the reference
     ``PSP_pool_new`` multi-scale pooling (:192-215), ``loss = 100*0.5*L1(depth) + 100*sum CE/800 + 2*size_loss``
     and the per-iteration ``SGD(lr=2e-4, momentum=0.1, nesterov)`` over ``z`` (model parameters at lr/10) (:286-359).
 What is replaced
-  * mesh retrieval (models/misc.py: SUNCG meshes + pywavefront + pymesh, out of scope): every object class gets a
-    procedural cuboid "model" with a fixed aspect ratio; walls / floor / ceiling are quads built from the room box;
-    meshes stay resident on the GPU instead of being re-read from disk every iteration (models/misc.py:111-121);
+  * mesh loading (models/misc.py: SUNCG meshes + pywavefront + pymesh, out of scope): without caller-supplied meshes every object
+    class gets a procedural cuboid "model" with a fixed aspect ratio and walls / floor / ceiling are quads built from the room box;
+    meshes stay resident on the GPU instead of being re-read from disk every iteration (models/misc.py:111-121).  The retrieval
+    AMONG a class's models (models/misc.py:34-64,123-152) is reproduced: ``retrieve_choice`` / host/retrieve.py;
   * the 33 raster passes per call: one fused HIP pass (diff_render.scene_render semantics).
 ``render_fn`` is injectable so that the tests can run the very same loss graph on the CPU oracle.
 """
@@ -26,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from . import diff_render as DR
+from . import retrieve as RT
 from . import scene_pictures as SP
 from . import synthetic
 from .sampling import _precision
@@ -56,7 +58,8 @@ def psp_pool(feats, sizes=(32, 48, 64, 96), as_list=False):
 
 
 class MeshBank:
-    """Procedural stand-in for the SUNCG model table: one cuboid model per class, resident on the device."""
+    """The model table, resident on the device.  Built plainly: a procedural stand-in, one cuboid model per class; ``from_arrays``: the
+    caller's meshes, one or many per class (``models[name]`` is a class's model 0, ``model_list(name)`` all of them)."""
 
     def __init__(self, class_names, device, subdiv=2, seed=0):
         rng = np.random.default_rng(seed)
@@ -71,41 +74,111 @@ class MeshBank:
 
     vocab = None        # class list of the scene tensor's planes (object_idx_to_name[1:], diff_render.py:65); None: synthetic.FURNITURE
     shell = None        # wall / floor / ceiling meshes + their table boxes (see from_arrays); None: quads built from the room box
+    shells = None       # every shell the caller listed (shell is entry 0)
 
     @classmethod
     def from_arrays(cls, meshes, device, vocab=None, shell=None):
         """Caller-supplied meshes - the seam of models/diff_render.py:62,131, where the reference hands the retrieved SUNCG model's
         vertices / faces to the placement: ``meshes`` = {class name: (V [n,3] float, F [m,3] int)} or (V, F, bbox_min, bbox_max)
-        (one model per class, any topology; faces index V).  The bounding box the placement scales by is the model table's
-        (diff_render.py:106-115 read ``bbox_min`` / ``bbox_max`` of suncg_data) - the vertices' own when none is given.
+        (one model per class, any topology; faces index V), or a LIST of such models per class, each (V, F, bbox_min, bbox_max[, id])
+        or a dict with those keys (``v, f, bbox_min, bbox_max, id``) - the class's rows of suncg_data_many.json, among which
+        ``retrieve.retrieve_models`` picks per object (models/misc.py:34-64); ids default to ``"<class>#<k>"`` and are unique within a
+        class.  The bounding box the placement scales by is the model table's (diff_render.py:106-115 read ``bbox_min`` / ``bbox_max`` of
+        suncg_data) - the vertices' own when none is given.
         ``vocab``: the class list that lays out the 70 planes (``object_idx_to_name[1:]``, diff_render.py:65-69,372-379).
         ``shell``: the room's retrieved wall / floor / ceiling (diff_render.py:166-342) as arrays - dict(wall_v [n,3], wall_f = list of
-        [m,3] sub-meshes over wall_v (models/misc.py:84-104), wall_bbox [2,3], floor_v, floor_f, floor_bbox [2,3], ceil_v, ceil_f);
-        without it the shell is five quads on the room box."""
+        [m,3] sub-meshes over wall_v (models/misc.py:84-104), wall_bbox [2,3], floor_v, floor_f, floor_bbox [2,3], ceil_v, ceil_f), or a
+        LIST of such dicts (the rows of wall_data_wfc.json, among which ``retrieve.retrieve_shell`` picks per room; entry 0 is the
+        default); without it the shell is five quads on the room box.
+        ``bank.table`` is the ``retrieve.ModelTable`` of the models, ``bank.shell_ratios`` the shell list's ratio tables."""
         bank = cls.__new__(cls)
-        bank.models = {}
+        bank.models, bank.model_lists = {}, {}
         for name, mesh in meshes.items():
-            V, F = mesh[0], mesh[1]
-            v = torch.as_tensor(np.asarray(V, dtype=np.float32)).reshape(-1, 3).to(device)
-            f = torch.as_tensor(np.asarray(F).astype(np.int32)).reshape(-1, 3).to(device)
-            if v.shape[0] == 0 or f.shape[0] == 0:
-                raise ValueError("mesh of class %r is empty" % (name,))
-            if int(f.min()) < 0 or int(f.max()) >= v.shape[0]:
-                raise IndexError("faces of class %r index vertices outside [0, %d)" % (name, v.shape[0]))
-            lo = torch.as_tensor(np.asarray(mesh[2], dtype=np.float32)).to(device) if len(mesh) > 2 else v.min(0).values
-            hi = torch.as_tensor(np.asarray(mesh[3], dtype=np.float32)).to(device) if len(mesh) > 3 else v.max(0).values
-            bank.models[name] = dict(v=v.contiguous(), f=f.contiguous(), bbox_min=lo, bbox_max=hi)
+            many = isinstance(mesh, list) and len(mesh) > 0 and all(isinstance(m, (tuple, dict)) for m in mesh)
+            entries, seen = [], set()
+            for k, one in enumerate(mesh if many else [mesh]):
+                if isinstance(one, dict):
+                    one = (one["v"], one["f"], one.get("bbox_min"), one.get("bbox_max"), one.get("id"))
+                one = tuple(one) + (None,) * (5 - len(one))
+                V, F, blo, bhi, mid = one[:5]
+                v = torch.as_tensor(np.asarray(V, dtype=np.float32)).reshape(-1, 3).to(device)
+                f = torch.as_tensor(np.asarray(F).astype(np.int32)).reshape(-1, 3).to(device)
+                if v.shape[0] == 0 or f.shape[0] == 0:
+                    raise ValueError("mesh of class %r is empty" % (name,))
+                if int(f.min()) < 0 or int(f.max()) >= v.shape[0]:
+                    raise IndexError("faces of class %r index vertices outside [0, %d)" % (name, v.shape[0]))
+                lo = torch.as_tensor(np.asarray(blo, dtype=np.float32)).to(device) if blo is not None else v.min(0).values
+                hi = torch.as_tensor(np.asarray(bhi, dtype=np.float32)).to(device) if bhi is not None else v.max(0).values
+                mid = str(mid) if mid is not None else "%s#%d" % (name, k)
+                if mid in seen:
+                    raise ValueError("class %r lists the model id %r twice" % (name, mid))
+                seen.add(mid)
+                # the table's own numbers (float64, as json gives them) for the retrieval's ratios
+                lo64 = np.asarray(blo, dtype=np.float64) if blo is not None else lo.double().cpu().numpy()
+                hi64 = np.asarray(bhi, dtype=np.float64) if bhi is not None else hi.double().cpu().numpy()
+                entries.append(dict(v=v.contiguous(), f=f.contiguous(), bbox_min=lo, bbox_max=hi, id=mid, lo64=lo64, hi64=hi64))
+            bank.models[name] = entries[0]
+            bank.model_lists[name] = entries
         bank.vocab = list(vocab) if vocab is not None else None
         if shell is not None:
-            sh = {k: (np.asarray(shell[k], dtype=np.float32) if not k.endswith("_f") else None) for k in shell}
-            sh["wall_f"] = [np.asarray(f).astype(np.int64).reshape(-1, 3) for f in shell["wall_f"]]
-            sh["floor_f"], sh["ceil_f"] = (np.asarray(shell[k]).astype(np.int64).reshape(-1, 3) for k in ("floor_f", "ceil_f"))
-            for f, nv, what in [(f, sh["wall_v"].shape[0], "wall") for f in sh["wall_f"]] + [(sh["floor_f"], sh["floor_v"].shape[0], "floor"),
-                                                                                                (sh["ceil_f"], sh["ceil_v"].shape[0], "ceiling")]:
-                if f.size and (int(f.min()) < 0 or int(f.max()) >= nv):
-                    raise IndexError("faces of the %s index vertices outside [0, %d)" % (what, nv))
-            bank.shell = sh
+            bank.shells = [cls._shell_arrays(sh) for sh in (shell if isinstance(shell, list) else [shell])]
+            if not bank.shells:
+                raise ValueError("shell is an empty list")
+            bank.shell = bank.shells[0]
         return bank
+
+    @staticmethod
+    def _shell_arrays(shell):
+        sh = {k: (np.asarray(shell[k], dtype=np.float32) if not k.endswith("_f") else None) for k in shell}
+        sh["wall_f"] = [np.asarray(f).astype(np.int64).reshape(-1, 3) for f in shell["wall_f"]]
+        sh["floor_f"], sh["ceil_f"] = (np.asarray(shell[k]).astype(np.int64).reshape(-1, 3) for k in ("floor_f", "ceil_f"))
+        for f, nv, what in [(f, sh["wall_v"].shape[0], "wall") for f in sh["wall_f"]] + [(sh["floor_f"], sh["floor_v"].shape[0], "floor"),
+                                                                                            (sh["ceil_f"], sh["ceil_v"].shape[0], "ceiling")]:
+            if f.size and (int(f.min()) < 0 or int(f.max()) >= nv):
+                raise IndexError("faces of the %s index vertices outside [0, %d)" % (what, nv))
+        sh["wall_bbox64"], sh["floor_bbox64"] = np.asarray(shell["wall_bbox"], dtype=np.float64), np.asarray(shell["floor_bbox"], dtype=np.float64)
+        return sh
+
+    def model_list(self, name):
+        """the models of a class in table order (a bank of one model per class: that model)"""
+        lists = getattr(self, "model_lists", None)
+        return [self.models[name]] + (lists[name][1:] if lists and name in lists else [])
+
+    def table_vocab(self):
+        """``object_idx_to_name`` as the model table indexes it: '__room__', the planes' classes, then any further class with a model"""
+        names = ["__room__"] + _classes_of(self)
+        return names + sorted(n for n in self.models if n not in names)
+
+    @property
+    def table(self):
+        """the ``retrieve.ModelTable`` of this bank's models, on the models' device (built on first use)"""
+        t = self.__dict__.get("_table")
+        if t is None:
+            data, dev = {}, "cpu"
+            for name in self.models:
+                entries = self.model_list(name)
+                dev = entries[0]["v"].device
+                data[name] = [dict(id=e.get("id", "%s#%d" % (name, k)), bbox_min=e.get("lo64", e["bbox_min"].double().cpu().numpy()),
+                                   bbox_max=e.get("hi64", e["bbox_max"].double().cpu().numpy())) for k, e in enumerate(entries)]
+            t = self.__dict__["_table"] = RT.ModelTable(data, self.table_vocab(), dev)
+        return t
+
+    @property
+    def shell_ratios(self):
+        """(wall_ratio [W, 2], floor_ratio [W]) float64 host tensors of the shell list; None for the procedural shell"""
+        shells = getattr(self, "shells", None)
+        if not shells:
+            return None
+        r = self.__dict__.get("_shell_ratios")
+        if r is None:
+            rows = [dict(wall_bbox_min=sh["wall_bbox64"][0], wall_bbox_max=sh["wall_bbox64"][1], floor_bbox_min=sh["floor_bbox64"][0],
+                         floor_bbox_max=sh["floor_bbox64"][1]) for sh in shells]
+            r = self.__dict__["_shell_ratios"] = tuple(torch.from_numpy(x) for x in RT.shell_ratios(rows))
+        return r
+
+    def has_choice(self):
+        """is there anything to retrieve: a class with more than one model, or more than one shell"""
+        return any(len(v) > 1 for v in getattr(self, "model_lists", {}).values()) or len(getattr(self, "shells", None) or ()) > 1
 
 
 def _classes_of(bank):
@@ -116,9 +189,24 @@ _PROCEDURAL_SHELL = ("floor", "ceiling", "wall", "wall", "wall")
 _SHELL_DIV = 6
 
 
-def shell_topology(bank):
-    """[(class, vertex count, faces [m,3] int64 numpy)] of the room shell in buffer order - does not depend on the room."""
+def _shell_of(bank, shell=None):
+    """the arrays of the chosen shell: ``shell`` = (wall entry, floor entry) of the bank's shell list (None, or an index < 0: entry 0).
+    The ceiling follows the wall entry, as load_ceil_obj(wall_data) does (diff_render.py:285)."""
     sh = getattr(bank, "shell", None)
+    if sh is None or shell is None:
+        return sh
+    shells = getattr(bank, "shells", None) or [sh]
+    w, f = (shells[int(k)] if int(k) >= 0 else shells[0] for k in shell)
+    if w is f:
+        return w
+    out = dict(w)
+    out.update(floor_v=f["floor_v"], floor_f=f["floor_f"], floor_bbox=f["floor_bbox"])
+    return out
+
+
+def shell_topology(bank, shell=None):
+    """[(class, vertex count, faces [m,3] int64 numpy)] of the room shell in buffer order - does not depend on the room."""
+    sh = _shell_of(bank, shell)
     if sh is None:
         unit = np.zeros(3), np.array([1.0, 0, 0]), np.array([0, 1.0, 0])
         v, f = synthetic._grid_quad(unit[0], unit[1], unit[2], _SHELL_DIV)
@@ -138,14 +226,15 @@ def _scaled_into_room(v, scale, model_center, center):
     return torch.matmul(torch.matmul(move, grow)[:3], hom).t().contiguous()
 
 
-def place_shell(bank, room_ext):
-    """Vertices of the room shell in room coordinates, [sum of shell_topology's vertex counts, 3] fp32 on the host.
+def place_shell(bank, room_ext, shell=None):
+    """Vertices of the room shell in room coordinates, [sum of shell_topology's vertex counts, 3] fp32 on the host.  ``shell``: the
+    chosen (wall, floor) entries of the bank's shell list (``retrieve.retrieve_shell``; None: entry 0) - the ceiling is the wall entry's.
     Procedural bank: floor, ceiling, back / left / right wall on the room box.  Bank with shell tables: diff_render.py:166-342 - the
     walls are scaled isotropically by the LARGEST ratio of room extent to the table's wall box and centred in the room, a wall
     sub-mesh that comes closer to the camera than 0.9 of the depth while its mean x lies in the middle 80 % of the width is dropped
     (:203-213; here: its vertices collapse to one point, so that the face list keeps its shape and order); floor: x / z ratios, y = 0;
     ceiling: x / z ratios of its own bounding box, resting on the room's height.  One-off per room: the room row is frozen (:55-60)."""
-    sh = getattr(bank, "shell", None)
+    sh = _shell_of(bank, shell)
     room = [float(x) for x in room_ext]
     if sh is None:
         quads = [((0, 0, 0), (0, 0, room[2]), (room[0], 0, 0)), ((0, room[1], 0), (room[0], 0, 0), (0, 0, room[2])),
@@ -174,10 +263,18 @@ def place_shell(bank, room_ext):
     return torch.cat(parts).contiguous()
 
 
-def assemble_scene(boxes, angles, class_names, bank, room_box, obj_size_target=None):
+def _model_index(models, i):
+    """row i's entry of a per-row model choice (None, a short list or an entry < 0: model 0)"""
+    if models is None or i >= len(models):
+        return 0
+    return max(int(models[i]), 0)
+
+
+def assemble_scene(boxes, angles, class_names, bank, room_box, obj_size_target=None, models=None, shell=None):
     """diff_render.py:76-165 for one room: returns vertices_buf [1,V,3] (differentiable w.r.t. boxes / angles),
     face_buf [1,F,3] int32, class_ranges, obj sizes, size_loss.  ``boxes`` [n,6] in room-normalised units with the
-    room row last, ``angles`` [n] in bins, ``room_box`` the frozen room row (6,)."""
+    room row last, ``angles`` [n] in bins, ``room_box`` the frozen room row (6,).  ``models``: per row, the index of the class's
+    model to place (``retrieve.retrieve_models``; None: model 0); ``shell``: the (wall, floor) entries (``place_shell``)."""
     dev = boxes.device
     ranges = {c: [] for c in _classes_of(bank)}
     ranges.update(wall=[], floor=[], ceiling=[])
@@ -187,7 +284,7 @@ def assemble_scene(boxes, angles, class_names, bank, room_box, obj_size_target=N
     for i, name in enumerate(class_names[:-1]):
         if name in DO_NOT_VIS or name not in bank.models:
             continue
-        m = bank.models[name]
+        m = bank.model_list(name)[_model_index(models, i)]
         bmin, bmax = boxes[i][:3] * room_box[3:], boxes[i][3:] * room_box[3:]
         center, size = (bmax + bmin) / 2, bmax - bmin
         if obj_size_target is not None:
@@ -206,13 +303,43 @@ def assemble_scene(boxes, angles, class_names, bank, room_box, obj_size_target=N
         ranges.setdefault(name, []).append([foff, foff + m["f"].shape[0]])
         voff += v.shape[0]; foff += m["f"].shape[0]
     # room shell for the frozen room box (diff_render.py:166-342; see place_shell)
-    shell_v = place_shell(bank, room_box[3:].detach().cpu().tolist()).to(dev)
+    shell_v = place_shell(bank, room_box[3:].detach().cpu().tolist(), shell).to(dev)
     at = 0
-    for nm, nv, f in shell_topology(bank):
+    for nm, nv, f in shell_topology(bank, shell):
         verts.append(shell_v[at:at + nv]); faces.append(torch.from_numpy(f.astype(np.int32)).to(dev) + voff)
         ranges[nm].append([foff, foff + f.shape[0]])
         voff += nv; foff += f.shape[0]; at += nv
     return torch.cat(verts)[None], torch.cat(faces)[None], ranges, sizes, size_loss
+
+
+def retrieve_choice(bank, boxes, class_names, rows=None):
+    """The retrieval of models/diff_render.py:62,171,241 for row-concatenated rooms: ``boxes`` [N, 6] (room-normalised, every room's room
+    row last), ``class_names`` the N rows' class names, ``rows`` the rooms' lengths (None: one room) ->
+    (models int32 [N] on the boxes' device, -1 where nothing is retrieved; shells: [(wall, floor)] per room, None for a bank without a
+    shell list).  One kernel launch each on the device (``retrieve.retrieve_models`` / ``retrieve_shell``); host tensors take the torch
+    restatement - the CPU route of ``finetune_vae`` with an injected ``render_fn``."""
+    table = bank.table
+    boxes = boxes.detach().float()
+    dev = boxes.device
+    rows = [int(boxes.shape[0])] if rows is None else [int(n) for n in rows]
+    index = {n: k for k, n in reversed(list(enumerate(table.vocab)))}
+    cls = torch.tensor([index.get(n, -1) for n in class_names], dtype=torch.int32)
+    last = np.cumsum(rows) - 1
+    room_row = torch.from_numpy(np.repeat(last, rows).astype(np.int32))
+    last_row = torch.from_numpy(last.astype(np.int32))
+    if cls.numel() != boxes.shape[0] or int(room_row.numel()) != boxes.shape[0]:
+        raise ValueError("class_names and rows must name every row of boxes")
+    if boxes.is_cuda:
+        if table.device != dev:
+            table.to(dev)
+        models = RT.retrieve_models(boxes, cls.to(dev), room_row.to(dev), table)
+    else:
+        models = RT.retrieve_models_torch(boxes, cls, room_row, table)
+    shells, ratios = None, bank.shell_ratios
+    if ratios is not None:
+        fn = RT.retrieve_shell if boxes.is_cuda else RT.retrieve_shell_torch
+        shells = [tuple(x) for x in fn(boxes, last_row.to(dev), ratios[0].to(dev), ratios[1].to(dev)).cpu().tolist()]
+    return models, shells
 
 
 _MESH_SOURCE = {"object_idx_to_name": None, "bank": None}
@@ -231,7 +358,9 @@ def mesh_render_func(boxes, angles, objs, model_ids_old=None, obj_size_target=No
     ``objs``: list of b class indices -> ``(final[1,70,256,256], model_ids_return, obj_size_return, size_loss)``.
     First call (``model_ids_old is None``) caches the room box ("box_info"), the retrieved model id per object and the
     object sizes; later calls reuse them, overload the room box (:55-57) and add the size / wall-drift penalties
-    (:98-100,160-165).  Mesh retrieval is the procedural ``MeshBank`` (see the module docstring)."""
+    (:98-100,160-165).  The first call retrieves every object's model from its own boxes (``retrieve_choice``: models/misc.py:34-64 over
+    the bank's table) and returns the ids in ``model_ids_return[i]``, the chosen wall in ``["wall"]`` (and the floor in ``["floor"]``
+    for a bank with a shell list); later calls place the meshes ``model_ids_old`` names, whatever their boxes have become."""
     src = _MESH_SOURCE
     if src["bank"] is None:
         raise RuntimeError("call refine.configure_meshes(object_idx_to_name) first (stands in for models/misc.py globals)")
@@ -245,19 +374,40 @@ def mesh_render_func(boxes, angles, objs, model_ids_old=None, obj_size_target=No
     else:
         model_ids_return["box_info"] = boxes[-1].detach().cpu().numpy()
     class_names = [names[int(o)] for o in objs]
-    for i, n in enumerate(class_names[:-1]):
-        if model_ids_old is None:
-            model_ids_return[i] = n + "#0"                       # one procedural model per class
+    table = bank.table
+    if model_ids_old is None:
+        # (:62,171,241) the retrieval on this call's own boxes; a row without a model to retrieve keeps the placeholder id
+        models, shells = retrieve_choice(bank, torch.stack([b.detach() for b in boxes]), class_names)
+        models = models.cpu().tolist()
+        shell = shells[0] if shells is not None else None
+        for i, n in enumerate(class_names[:-1]):
+            model_ids_return[i] = table.id_of(table.vocab.index(n), models[i]) if models[i] >= 0 else n + "#0"
+    else:
+        # (:85-86,172-173,242-243) the meshes stay those of the first call
+        models = []
+        for i, n in enumerate(class_names[:-1]):
+            ids = table.ids[table.vocab.index(n)] if n in table.vocab else []
+            models.append(ids.index(model_ids_old[i]) if model_ids_old[i] in ids else 0)
+        shell = None
+        if getattr(bank, "shells", None):
+            shell = (int(model_ids_old["wall"].get("index", 0)), int(model_ids_old.get("floor", {}).get("index", 0)))
     target = None
     if obj_size_target is not None:
         target = [torch.from_numpy(np.asarray(t)).float().to(dev) for t in obj_size_target[:-1]]
     v, f, ranges, sizes, size_loss = assemble_scene(torch.stack(boxes), torch.stack([a.reshape(()) for a in angles]).float(),
-                                                    class_names, bank, boxes[-1].detach(), target)
+                                                    class_names, bank, boxes[-1].detach(), target, models=models, shell=shell)
     if obj_size_target is not None:
         size_loss = size_loss + F.mse_loss(old_wall, torch.from_numpy(np.asarray(obj_size_target[-1])).float().to(dev))
     else:
         obj_size_return = [x.cpu().numpy() for x in sizes] + [boxes[-1].detach().cpu().numpy()]
-        model_ids_return["wall"] = {"wall_bbox_min": [0.0, 0.0, 0.0], "wall_bbox_max": [float(x) for x in boxes[-1][3:]]}
+    if model_ids_old is None or obj_size_target is None:
+        if shell is None:
+            model_ids_return["wall"] = {"wall_bbox_min": [0.0, 0.0, 0.0], "wall_bbox_max": [float(x) for x in boxes[-1][3:]]}
+        else:
+            sw, sf = bank.shells[shell[0]], bank.shells[shell[1]]
+            model_ids_return["wall"] = {"index": shell[0], "wall_bbox_min": sw["wall_bbox64"][0].tolist(), "wall_bbox_max": sw["wall_bbox64"][1].tolist()}
+            model_ids_return["floor"] = {"index": shell[1], "floor_bbox_min": sf["floor_bbox64"][0].tolist(),
+                                         "floor_bbox_max": sf["floor_bbox64"][1].tolist()}
     final = DR.scene_render(v, f, ranges, boxes[-1].detach())
     return final, model_ids_return, obj_size_return, size_loss
 
@@ -491,7 +641,9 @@ class RefineScene:
     lets a whole refinement iteration be captured into one hipGraph (``finetune_vae(..., capture=True)``).
     Built once per room: the room box is frozen (:55-60) and so are K, R, t."""
 
-    def __init__(self, class_names, bank, room_box, image_size=DR.final_out):
+    def __init__(self, class_names, bank, room_box, image_size=DR.final_out, models=None, shell=None):
+        """``models``: per row, the index of the class's model (``retrieve.retrieve_models``; None: model 0 everywhere);
+        ``shell``: the (wall, floor) entries of the bank's shell list (``retrieve.retrieve_shell``; None: entry 0)"""
         dev = room_box.device
         self.image_size = image_size
         self.room = room_box.detach().clone()
@@ -499,16 +651,19 @@ class RefineScene:
         # per (bank, class list) and shared by the rooms that use it - the refinement of a test set builds thousands of scenes from a
         # few dozen class lists; per room: the shell's vertices and the camera (round 5: 1.4 -> 0.3 ms per scene)
         cache = bank.__dict__.setdefault("_scene_cache", {})
-        key = (tuple(class_names), str(dev))
+        models = tuple(_model_index(models, i) for i in range(len(class_names) - 1))
+        shell = None if shell is None else tuple(max(int(k), 0) for k in shell)
+        self.models, self.shell = models, shell
+        key = (tuple(class_names), str(dev), models, shell)
         st = cache.get(key)
         if st is None:
-            st = cache[key] = self._static_part(class_names, bank, dev)
+            st = cache[key] = self._static_part(class_names, bank, dev, models, shell)
         for k_, v_ in st.items():
             setattr(self, k_, v_)
         Vm = self._Vm
         room_host = [float(x) for x in room_box.detach().cpu().tolist()]           # one device -> host copy per scene
         room = room_host[3:]
-        self.shell_v = place_shell(bank, room).to(dev)                             # (the order of shell_topology / _static_part)
+        self.shell_v = place_shell(bank, room, shell).to(dev)                      # (the order of shell_topology / _static_part)
         Kc, Rc, tc = DR.get_cam_mat([room_host], "cpu")
         self.K, self.R, self.t = Kc.to(dev), Rc.to(dev), tc.to(dev)
         # descriptor of the fused placement kernels (csrc/placement.hip)
@@ -523,9 +678,9 @@ class RefineScene:
         self.desc = d
 
     @staticmethod
-    def _static_part(class_names, bank, dev):
+    def _static_part(class_names, bank, dev, choice=None, shell=None):
         vis = [i for i, nm in enumerate(class_names[:-1]) if nm not in DO_NOT_VIS and nm in bank.models]
-        models = [bank.models[class_names[i]] for i in vis]
+        models = [bank.model_list(class_names[i])[_model_index(choice, i)] for i in vis]
         n_vis = len(vis)
         Vm = max([m["v"].shape[0] for m in models] + [1])
         mv = torch.zeros(max(n_vis, 1), Vm, 3, device=dev)
@@ -540,7 +695,7 @@ class RefineScene:
             faces.append(m["f"].long() + k * Vm)
             ranges.setdefault(class_names[i], []).append([foff, foff + m["f"].shape[0]]); foff += m["f"].shape[0]
         voff = n_vis * Vm
-        for nm, nv, f in shell_topology(bank):                                 # topology only: the corners are the room's (place_shell)
+        for nm, nv, f in shell_topology(bank, shell):                          # topology only: the corners are the room's (place_shell)
             faces.append(torch.from_numpy(f.astype(np.int64)).to(dev) + voff)
             ranges[nm].append([foff, foff + f.shape[0]]); voff += nv; foff += f.shape[0]
         faces = torch.cat(faces)                                             # [F,3] into the flattened vertex list
@@ -613,9 +768,15 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
     gen = torch.Generator(device="cpu").manual_seed(noise_seed)
     z = (mu + torch.randn(mu.shape, generator=gen).to(dev) * torch.exp(0.5 * logvar)).detach().clone().requires_grad_(True)
     room_box = boxes_gt[-1].detach().clone()
-    scene = RefineScene(class_names, bank, room_box, image_size)
+    # the target shows the meshes retrieved for the ground-truth boxes (test_render_refine.py:319), the iterates those retrieved for
+    # iteration 0's boxes (:324-326) - two scenes when the bank leaves a choice
+    models_gt, shell = None, None
+    if bank.has_choice():
+        models_gt, shells = retrieve_choice(bank, boxes_gt, class_names)
+        models_gt, shell = models_gt.cpu().tolist(), (shells[0] if shells is not None else None)
+    target_scene = scene = RefineScene(class_names, bank, room_box, image_size, models=models_gt, shell=shell)
     with torch.no_grad():
-        target, _, sizes = scene.render(boxes_gt, angles_gt.float())
+        target, _, sizes = target_scene.render(boxes_gt, angles_gt.float())
     labels = target_labels(target)
     fused = RefineLoss(target) if fused_loss else None             # the PSP / L1 / cross-entropy block as two C calls
     size_target = sizes.detach().clone()                           # (a buffer: filled with the FIRST iterate's sizes below)
@@ -641,7 +802,10 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
             bp0, ap0 = model.decoder(z, objs, triples, attributes)
             b0 = torch.cat([bp0[:-1], boxes_gt[-1:]], 0)
             i0 = torch.cat([(softargmax(ap0, sum_dim=1) + noise_all[0] / 10.0)[:-1], angles_gt[-1:].float()], 0)
-            size_target.copy_(_PlaceFn.apply(b0, i0, scene, None)[2])
+            size_target.copy_(_PlaceFn.apply(b0, i0, target_scene, None)[2])              # (sizes do not depend on the model)
+            if bank.has_choice():
+                scene = RefineScene(class_names, bank, room_box, image_size, models=retrieve_choice(bank, b0, class_names)[0].cpu().tolist(),
+                                    shell=shell)
 
     def iteration():
         boxes_pred, angles_pred = model.decoder(z, objs, triples, attributes)
@@ -730,9 +894,17 @@ class RefineBatch:
     sln_scene_pictures (three launches) on ``image`` with ``live`` after the loss forward and fills slot j of ``pictures.depth8`` /
     ``labels`` [n_pictured, R, S, S], ``rgb`` [n_pictured, R, S, S, 3] and ``status`` [n_pictured, R]; ``pictures.iterations[j]`` names the
     iteration.  ``target_pictures`` (``scene_pictures.Pictures``, [R, S, S(, 3)]) is filled once at set-up from the target renders.
-    Needs image_size % 4 == 0."""
+    Needs image_size % 4 == 0.
 
-    def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None):
+    ``retrieve``: False (default: every row shows model 0 of its class, the launches are those above), or True - the targets show the
+    models retrieved for the ground-truth boxes (one ``retrieve.retrieve_models`` launch over all rooms' rows at construction,
+    :319), the iterates those retrieved for the FIRST iterate's boxes (one launch over ``boxes`` behind ``_first_iterate_sizes``' forward
+    in the first ``run()``, :324-326; read back - set-up, outside any capture - after which the iterates' scenes are built and bound,
+    ``_bind_scenes``), frozen from then on.  ``target_models`` / ``models`` (int32 [N], -1 where nothing is retrieved) and
+    ``model_ids()`` expose the choice; a bank with a shell list gets its (wall, floor) entries per room the same way."""
+
+    def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
+                 retrieve=False):
         L = _lib.lib()
         self.model, self.R, self.iters, self.lr = model, len(rooms), int(iters), float(learning_rate)
         R = self.R
@@ -754,6 +926,16 @@ class RefineBatch:
         z = torch.empty(N, E, **f32)
         noise = torch.zeros(max(self.iters, 1), N)
         scenes, targets, size_targets = [], [], []
+        # ---- retrieve=True: the targets' meshes from ONE retrieval launch over all rooms' ground-truth rows (read back: this is set-up) ----
+        self._retrieve, self._bank, self._class_names = bool(retrieve), bank, [list(rm["class_names"]) for rm in rooms]
+        self.target_models = self.models = None
+        tm, self._shells = None, None
+        if self._retrieve:
+            if any(len(nm) != n for nm, n in zip(self._class_names, self.rows)):
+                raise ValueError("class_names must name every row of a room")
+            gt = torch.cat([rm["boxes"].detach().float() for rm in rooms]).to(dev)
+            self.target_models, self._shells = retrieve_choice(bank, gt, [n for nm in self._class_names for n in nm], self.rows)
+            tm = self.target_models.cpu().tolist()
         box_last, angle_last = torch.empty(R, 6, **f32), torch.empty(R, **f32)
         for r, rm in enumerate(rooms):
             # (fp32 whatever model.gemm_precision says: the refinement loop's room engines are fp32 only, and so is its starting point)
@@ -764,12 +946,13 @@ class RefineBatch:
             z[a:a + n] = mu + torch.randn(mu.shape, generator=gen).to(dev) * torch.exp(0.5 * logvar)
             if self.iters > 0:           # one randn(n) per iteration, as the reference draws them (:304); one strided copy into the table
                 noise[:self.iters, a:a + n] = torch.stack([torch.randn(n, generator=gen) for _ in range(self.iters)])
-            sc = RefineScene(rm["class_names"], bank, rm["boxes"][-1].detach().clone(), S)
+            sc = RefineScene(rm["class_names"], bank, rm["boxes"][-1].detach().clone(), S, models=tm[a:a + n] if tm is not None else None,
+                             shell=self._shells[r] if self._shells is not None else None)
             with torch.no_grad():
                 tgt, _, sizes = sc.render(rm["boxes"], rm["angles"].float())
             scenes.append(sc); targets.append(tgt); size_targets.append(sizes.detach().clone().contiguous())
             box_last[r] = rm["boxes"][-1].detach().float(); angle_last[r] = rm["angles"][-1].detach().float()
-        self.z, self.scenes = z, scenes
+        self.z, self.scenes, self.target_scenes = z, scenes, scenes
         self._report_all = report == "all"
         if report is None:
             self._report_at = None
@@ -853,15 +1036,11 @@ class RefineBatch:
         # ---- head / placement tables ----
         self.room_of_row = torch.cat([torch.full((n,), r, dtype=torch.int32) for r, n in enumerate(self.rows)]).to(dev)
         self.last_row = torch.tensor([a + n - 1 for a, n in zip(self.row0, self.rows)], dtype=torch.int32, device=dev)
-        if self._report_at is not None:
+        if self._report_at is not None or self._retrieve:
             self._room_row = self.last_row[self.room_of_row.long()].contiguous()         # [N]: every row's room row
         self.boxes, self.idx = torch.empty(N, 6, **f32), torch.empty(N, **f32)
         self.g_boxes, self.g_idx = torch.empty(N, 6, **f32), torch.empty(N, **f32)
-        self.F2 = 2 * max(sc.desc.F for sc in scenes)
         self.n_max = max(self.rows)
-        self.faces = torch.zeros(R, self.F2, 3, 3, **f32)             # rows beyond a room's 2 F stay degenerate triangles of no class
-        self.g_faces = torch.empty(R, self.F2, 3, 3, **f32)
-        cls = torch.full((R, self.F2), -1, dtype=torch.int32, device=dev)
         self.sizes = torch.zeros(R, max(max(sc.n_vis for sc in scenes), 1), 3, **f32)
         self.size_loss = torch.zeros(R, **f32)
         self.g_size_loss = torch.full((1,), 2.0, **f32)               # loss = ... + 2 * size_loss (test_render_refine.py:350-352)
@@ -870,30 +1049,8 @@ class RefineBatch:
         # iteration k is row k of noise_all, k a device counter the backward launch advances)
         self._fused_head = max(self.rows) <= 128 and not os.environ.get("SLN_REFINE_SEPARATE_HEAD")
         self._noise_step = torch.zeros(1, dtype=torch.int32, device=dev)
-        tab = (_lib.SlnPlacementRoom * R)()
-        for r, sc in enumerate(scenes):
-            cls[r, :2 * sc.desc.F] = sc.cls2[0]
-            e, a = tab[r], self.row0[r]
-            e.P = sc.desc
-            e.boxes, e.angles = self.boxes.data_ptr() + 24 * a, self.idx.data_ptr() + 4 * a
-            e.size_target = size_targets[r].data_ptr() if sc.n_vis else None
-            e.faces_out, e.sizes, e.size_loss = self.faces[r].data_ptr(), self.sizes[r].data_ptr(), self.size_loss.data_ptr() + 4 * r
-            e.grad_faces, e.grad_size_loss = self.g_faces[r].data_ptr(), self.g_size_loss.data_ptr()
-            e.grad_boxes, e.grad_angles = self.g_boxes.data_ptr() + 24 * a, self.g_idx.data_ptr() + 4 * a
-            if self._fused_head:
-                e.boxes_pred, e.angles_pred = self.boxes_pred.data_ptr() + 24 * a, self.angles_pred.data_ptr() + 4 * na * a
-                e.noise, e.noise_step, e.noise_stride = self.noise_all.data_ptr() + 4 * a, self._noise_step.data_ptr(), N
-                e.box_last, e.angle_last = self.box_last.data_ptr() + 24 * r, self.angle_last.data_ptr() + 4 * r
-                e.grad_boxes_pred, e.grad_angles_pred = self.d_boxes_pred.data_ptr() + 32 * a, self.d_angles_pred.data_ptr() + 4 * na * a
-                e.n_angle, e.ld_gb, e.beta = na, 8, 2.0
-        self._place_tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
-        self.cls = cls
-        self.chan, self.dch = scenes[0].chan, scenes[0].dch
-        for sc in scenes[1:]:
-            if not (torch.equal(sc.chan, self.chan) and torch.equal(sc.dch, self.dch)):
-                raise _lib.SlnError("rooms of one batch must share the class tables")
         self.S = S
-        self.scene_ws = torch.empty(int(L.sln_scene_workspace_bytes(R, self.F2, S)), dtype=torch.uint8, device=dev)
+        self._bind_scenes(scenes)
         self.image = torch.zeros(R, DR.N_SCENE_CHANNELS, S, S, **f32)         # (planes flagged dead are never written, nor read)
         self.g_image = torch.zeros(R, DR.N_SCENE_CHANNELS, S, S, **f32)
         self.loss_out = torch.empty(R, 3, **f32)
@@ -944,6 +1101,74 @@ class RefineBatch:
         # synchronises that stream: here, at set-up, not inside the first iteration's asynchronous calls (csrc/streams.hip)
         if not torch.cuda.is_current_stream_capturing():
             L.sln_side_stream_prepare(st)
+
+    def _bind_scenes(self, scenes):
+        """Everything of the launch program that follows the rooms' SCENES (their models' vertices and face lists): the padded face
+        buffers, the class table of the faces, the placement table and the scene pass's workspace.  Called at construction with the
+        target scenes and, with retrieve=True, once more by the first ``run()`` with the scenes of the iterates' meshes (which may
+        change F2); the size targets, the head's buffers and everything per row stay where they are."""
+        L = _lib.lib()
+        R, N, na, dev = self.R, self.N, self.model.Nangle, self.boxes.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.scenes = scenes
+        self.F2 = 2 * max(sc.desc.F for sc in scenes)
+        self.faces = torch.zeros(R, self.F2, 3, 3, **f32)             # rows beyond a room's 2 F stay degenerate triangles of no class
+        self.g_faces = torch.empty(R, self.F2, 3, 3, **f32)
+        cls = torch.full((R, self.F2), -1, dtype=torch.int32, device=dev)
+        size_targets = self._size_targets
+        tab = (_lib.SlnPlacementRoom * R)()
+        for r, sc in enumerate(scenes):
+            cls[r, :2 * sc.desc.F] = sc.cls2[0]
+            e, a = tab[r], self.row0[r]
+            e.P = sc.desc
+            e.boxes, e.angles = self.boxes.data_ptr() + 24 * a, self.idx.data_ptr() + 4 * a
+            e.size_target = size_targets[r].data_ptr() if sc.n_vis else None
+            e.faces_out, e.sizes, e.size_loss = self.faces[r].data_ptr(), self.sizes[r].data_ptr(), self.size_loss.data_ptr() + 4 * r
+            e.grad_faces, e.grad_size_loss = self.g_faces[r].data_ptr(), self.g_size_loss.data_ptr()
+            e.grad_boxes, e.grad_angles = self.g_boxes.data_ptr() + 24 * a, self.g_idx.data_ptr() + 4 * a
+            if self._fused_head:
+                e.boxes_pred, e.angles_pred = self.boxes_pred.data_ptr() + 24 * a, self.angles_pred.data_ptr() + 4 * na * a
+                e.noise, e.noise_step, e.noise_stride = self.noise_all.data_ptr() + 4 * a, self._noise_step.data_ptr(), N
+                e.box_last, e.angle_last = self.box_last.data_ptr() + 24 * r, self.angle_last.data_ptr() + 4 * r
+                e.grad_boxes_pred, e.grad_angles_pred = self.d_boxes_pred.data_ptr() + 32 * a, self.d_angles_pred.data_ptr() + 4 * na * a
+                e.n_angle, e.ld_gb, e.beta = na, 8, 2.0
+        self._place_tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+        self.cls = cls
+        self.chan, self.dch = scenes[0].chan, scenes[0].dch
+        for sc in scenes[1:]:
+            if not (torch.equal(sc.chan, self.chan) and torch.equal(sc.dch, self.dch)):
+                raise _lib.SlnError("rooms of one batch must share the class tables")
+        self.scene_ws = torch.empty(int(L.sln_scene_workspace_bytes(R, self.F2, self.S)), dtype=torch.uint8, device=dev)
+
+    def _retrieve_iterates(self):
+        """retrieve=True: the iterates' meshes are those retrieved for the FIRST iterate's boxes (testing/test_render_refine.py:324-326:
+        ``model_infos`` is what the first ``mesh_render_func`` call on ``boxes_pred`` returns) - one launch over ``self.boxes`` behind
+        ``_first_iterate_sizes``' forward, read back (set-up, outside any capture), frozen from then on.  The room rows are the ground
+        truth's, so the shells stay the targets'."""
+        table = self._bank.table
+        index = {n: k for k, n in reversed(list(enumerate(table.vocab)))}
+        cls = torch.tensor([index.get(n, -1) for nm in self._class_names for n in nm], dtype=torch.int32, device=self.boxes.device)
+        self.models = RT.retrieve_models(self.boxes, cls, self._room_row, table)
+        host = self.models.cpu().tolist()
+        if host == self.target_models.cpu().tolist():
+            return
+        scenes = []
+        for r, sc in enumerate(self.target_scenes):
+            a, n = self.row0[r], self.rows[r]
+            scenes.append(RefineScene(self._class_names[r], self._bank, sc.room, self.S, models=host[a:a + n], shell=sc.shell))
+        self._bind_scenes(scenes)
+
+    def model_ids(self, target=False):
+        """[[id per row, None where nothing is retrieved (room rows, classes without a model)] per room] of the iterates' meshes
+        (``target=True``: the targets'); needs retrieve=True and, for the iterates, the first ``run()``"""
+        models = self.target_models if target else self.models
+        if models is None:
+            raise ValueError("no retrieval yet: RefineBatch(retrieve=True), and run() for the iterates' meshes")
+        table, host = self._bank.table, models.cpu().tolist()
+        out = []
+        for names, a in zip(self._class_names, self.row0):
+            out.append([table.id_of(table.vocab.index(n), host[a + i]) if host[a + i] >= 0 else None for i, n in enumerate(names)])
+        return out
 
     def _first_iterate_sizes(self):
         """The size penalty holds every object to the size of the FIRST iterate (testing/test_render_refine.py:319-327: ``size_infos`` is
@@ -1029,6 +1254,8 @@ class RefineBatch:
             pic_scratch = tuple(torch.empty_like(t[0]) for t in self.pictures[:4])
         if n > 0 and self.k == 0:
             self._first_iterate_sizes()
+            if self._retrieve and self.models is None:
+                self._retrieve_iterates()
         for _ in range(n):
             k = self.k
             rep = self.report[k] if self._report_at is not None and k in self._report_at else None
@@ -1083,13 +1310,13 @@ class RefineBatch:
 
 
 def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None,
-                            pictures=None):
+                            pictures=None, retrieve=False):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
     noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
     ``report`` is given, the report [iters, R, 3] as a further element; only when ``pictures`` is given, the pair
     (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one."""
     rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report,
-                     pictures=pictures)
+                     pictures=pictures, retrieve=retrieve)
     try:
         out = (rb.run(capture=capture).clone(), [(b.clone(), i.clone()) for b, i in rb.results()])
         if report is not None:
@@ -1114,7 +1341,12 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
     gen = torch.Generator(device="cpu").manual_seed(noise_seed)
     z = (mu + torch.randn(mu.shape, generator=gen).to(dev) * torch.exp(0.5 * logvar)).detach().requires_grad_(True)
     room_box = boxes_gt[-1].detach().clone()
-    v, f, ranges, sizes, _ = assemble_scene(boxes_gt, angles_gt.float(), class_names, bank, room_box)
+    # target: the meshes retrieved for the ground truth (test_render_refine.py:319); iterates: those of iteration 0's boxes (:324-326)
+    choose, models_gt, models_it, shell = bank.has_choice(), None, None, None
+    if choose:
+        models_gt, shells = retrieve_choice(bank, boxes_gt, class_names)
+        models_gt, shell = models_gt.cpu().tolist(), (shells[0] if shells is not None else None)
+    v, f, ranges, sizes, _ = assemble_scene(boxes_gt, angles_gt.float(), class_names, bank, room_box, models=models_gt, shell=shell)
     with torch.no_grad():
         target = render_fn(v, f, ranges, room_box, image_size=image_size)
     labels = target_labels(target)
@@ -1130,7 +1362,9 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         idx = softargmax(angles_pred, sum_dim=1) + torch.randn(angles_pred.shape[0], generator=gen).to(dev) / 10.0
         idx.register_hook(quad_grad)
         idx = torch.cat([idx[:-1], angles_gt[-1:].float()], 0)
-        v, f, ranges, sizes_k, size_loss = assemble_scene(boxes_pred, idx, class_names, bank, room_box, size_target)
+        if choose and models_it is None:
+            models_it = retrieve_choice(bank, boxes_pred, class_names)[0].cpu().tolist()
+        v, f, ranges, sizes_k, size_loss = assemble_scene(boxes_pred, idx, class_names, bank, room_box, size_target, models=models_it, shell=shell)
         if size_target is None:
             size_target = [s.clone() for s in sizes_k]
         image = render_fn(v, f, ranges, room_box, image_size=image_size)

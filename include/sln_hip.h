@@ -956,6 +956,26 @@ int sln_scene_pictures(const float* image, int B, int channels, int S, const uns
                        void* workspace, unsigned char* depth8, unsigned char* labels, unsigned char* rgb, unsigned char* masks8,
                        int32_t* status, void* stream);
 
+/* Mesh retrieval (models/misc.py:34-64 suncg_retrieve): for every object row the model of the row's class whose bounding-box edge
+ * ratios are nearest to the predicted box's.  boxes [S, N, 6] float32: S >= 1 layouts of the same N row-concatenated rows; room_row
+ * [N] int32: every row's room row (the last row of its room); objs [N] int32: the class index (object_idx_to_name); class_ptr
+ * [n_classes + 1] int32: models class_ptr[c] .. class_ptr[c + 1] of model_ratio [M, 2] float64 (16-byte aligned) belong to class c,
+ * model_ratio[m] = (size_y / size_x, size_z / size_x) of the table's bbox_max - bbox_min, formed in float64 on the host (:58-59).
+ * Per row, in the reference's order: float32 - the six box entries times the room row's [3], [4], [5] (one multiplication each), the
+ * three differences, the correctly rounded quotients dy/dx, dz/dx; float64 - |t0 - r0| + |t1 - r1| per model; np.argmin: the first
+ * minimum wins, a NaN distance beats everything and the first NaN is kept.  choice [S, N] int32: the index WITHIN the class, -1 for
+ * a room row (room_row[i] == i or outside [0, N)), a class without models and a class outside [0, n_classes).  dist [S, N] float64
+ * (or NULL): the winning distance, NaN where choice is -1.  One launch on `stream`, one row per lane, the table staged through LDS in
+ * chunks of 2048 models; no atomics, no allocation, nothing read back: legal inside a stream capture.  S <= 65535 per call. */
+int sln_mesh_retrieve(const float* boxes, const int32_t* room_row, const int32_t* objs, const int32_t* class_ptr, int n_classes,
+                      const double* model_ratio, int M, int S, int N, int32_t* choice, double* dist, void* stream);
+/* wall_retrieve / floor_retrieve (models/misc.py:123-152) for R rooms: boxes [N, 6] float32, last_row [R] int32 the rooms' room rows.
+ * With (X, Y, Z) the room row's [3:6] promoted to float64: out[r][0] = argmin_j |wall_ratio[j][0] - Y / X| + |wall_ratio[j][1] - Z / X|
+ * over wall_ratio [W, 2], out[r][1] = argmin_j |floor_ratio[j] - Z / X| over floor_ratio [W] (both float64, host-formed), the argmin
+ * rules above; -1 for W == 0 or a last_row entry outside [0, N).  out [R, 2] int32.  One launch, one room per lane. */
+int sln_shell_retrieve(const float* boxes, const int32_t* last_row, int R, int N, const double* wall_ratio, const double* floor_ratio,
+                       int W, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
