@@ -1703,7 +1703,7 @@ int sln_layernorm_stats(const float* x, int B, int64_t n, float eps, double* scr
 }
 
 int sln_resize(const float* src, int BC, int Hi, int Wi, int Ho, int Wo, int mode, float* dst, void* stream) {
-  if (!src || !dst || BC <= 0) return SLN_E_BADARG;
+  if (!src || !dst || BC <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return SLN_E_BADARG;
   const long n = (long)BC * Ho * Wo;
   hipLaunchKernelGGL(resize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, 0, Hi, Wi, Ho, Wo, mode,
                      n, dst);
@@ -1714,8 +1714,9 @@ int sln_resize(const float* src, int BC, int Hi, int Wi, int Ho, int Wo, int mod
 int sln_spade_depth_concat(const float* seg, int B, int Cs, int H, int W, const float* wpd, const float* bpd, int nd, float* out,
                            int copy_masks, void* stream) {
   if (!seg || !wpd || !bpd || !out) return SLN_E_BADARG;
+  if (Cs < 1 || nd < 0 || H < 2 || W < 2) return SLN_E_BADARG;      // ReflectionPad2d(1) needs two rows and two columns
   const int cw = copy_masks ? nd + Cs - 1 : nd;
-  if (B <= 0 || cw <= 0 || H <= 0 || W <= 0 || (long)H * W > (1L << 30) || B > 65535 || cw > 65535) return SLN_E_BADARG;
+  if (B <= 0 || cw <= 0 || (long)H * W > (1L << 30) || B > 65535 || cw > 65535) return SLN_E_BADARG;
   hipLaunchKernelGGL(depth_concat_kernel, dim3((unsigned)(((long)H * W + 255) / 256), cw, B), dim3(256), 0, (hipStream_t)stream, seg, Cs, H, W,
                      wpd, bpd, nd, out);
   SLN_CHECK_LAUNCH();
@@ -1725,7 +1726,7 @@ int sln_spade_depth_concat(const float* seg, int B, int Cs, int H, int W, const 
 // out = xs + dx * sigmoid(W2 relu(W0 GAP(dx)))      scratch: B*C (gap) + B*C (scale) floats
 int sln_se_scale_add(const float* xs, const float* dx, int B, int C, int64_t hw, const float* w0, const float* w2, float* scratch,
                      float* out, void* stream) {
-  if (!xs || !dx || !w0 || !w2 || !scratch || !out || C % 8 != 0) return SLN_E_BADARG;
+  if (!xs || !dx || !w0 || !w2 || !scratch || !out || B <= 0 || C <= 0 || C % 8 != 0 || hw <= 0) return SLN_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   float* gap = scratch; float* scale = scratch + (size_t)B * C;
   hipLaunchKernelGGL(gap_kernel, dim3(B * C), dim3(256), 0, st, dx, (long)hw, gap);
@@ -1738,7 +1739,7 @@ int sln_se_scale_add(const float* xs, const float* dx, int B, int C, int64_t hw,
 }
 
 int sln_upsample2x(const float* x, int BC, int H, int W, int mode, float* y, void* stream) {
-  if (!x || !y) return SLN_E_BADARG;
+  if (!x || !y || BC <= 0 || H <= 0 || W <= 0) return SLN_E_BADARG;
   const long n = (long)BC * 4 * H * W;
   hipLaunchKernelGGL(upsample2x_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, H, W, mode, n, y);
   SLN_CHECK_LAUNCH();

@@ -763,17 +763,23 @@ int sln_spade_apply_up(const float* xin, int xin_up, const float* gb, int B, int
                        int act, float slope, float* out, void* stream);
 /* stats[b] = (mean, 1 / (unbiased std + eps)) over the n elements of sample b; scratch: 16 * B doubles */
 int sln_layernorm_stats(const float* x, int B, int64_t n, float eps, double* scratch, float* stats, void* stream);
-/* F.interpolate(size=...): mode 0 nearest, 1 bilinear(align_corners=False) over BC planes */
+/* F.interpolate(size=...): mode 0 nearest (source = min(floor(dst * ((float)in / out)), in - 1), torch's float rule), 1
+ * bilinear(align_corners=False) over BC planes.  src [BC, Hi, Wi], dst [BC, Ho, Wo].
+ * Sizes: BC, Hi, Wi, Ho, Wo >= 1, else SLN_E_BADARG (nothing launched). */
 int sln_resize(const float* src, int BC, int Hi, int Wi, int Ho, int Wo, int mode, float* dst, void* stream);
 /* [LeakyReLU_0.01(conv3x3_reflect(seg[:,0:1])) | seg[:,1:]] (SPADE4.mlp_preshared_depth + cat, :1445-1446) into
  * out [B, nd + Cs - 1, H, W].  copy_masks = 0 writes the nd depth features only: the mask channels of a per-resolution
- * buffer are filled once (copy_masks = 1) and shared by every SPADE layer of that resolution. */
+ * buffer are filled once (copy_masks = 1) and shared by every SPADE layer of that resolution.
+ * Sizes: 1 <= B <= 65535, Cs >= 1, nd >= 0, H >= 2 and W >= 2 (ReflectionPad2d(1)), H * W <= 2^30, and 1 <= channels written
+ * (nd, or nd + Cs - 1 with copy_masks) <= 65535, else SLN_E_BADARG (nothing launched).  seg [B, Cs, H, W], wpd [nd, 9], bpd [nd]. */
 int sln_spade_depth_concat(const float* seg, int B, int Cs, int H, int W, const float* wpd, const float* bpd, int nd, float* out,
                            int copy_masks, void* stream);
-/* x_s + SEBlock2(dx) (:1492-1493); scratch 2*B*C floats */
+/* x_s + SEBlock2(dx) (:1492-1493); xs, dx, out [B, C, hw]; w0 [C/8, C], w2 [C, C/8]; scratch 2*B*C floats (the pool values, then
+ * the scale vector in scratch[B*C:]).  Sizes: B >= 1, C >= 8 and C % 8 == 0, hw >= 1, else SLN_E_BADARG (nothing launched). */
 int sln_se_scale_add(const float* xs, const float* dx, int B, int C, int64_t hw, const float* w0, const float* w2, float* scratch,
                      float* out, void* stream);
-/* nn.Upsample(scale_factor=2): mode 0 nearest, 1 bilinear */
+/* nn.Upsample(scale_factor=2): mode 0 nearest, 1 bilinear (align_corners=False); x [BC, H, W], y [BC, 2H, 2W].
+ * Sizes: BC, H, W >= 1, else SLN_E_BADARG (nothing launched). */
 int sln_upsample2x(const float* x, int BC, int H, int W, int mode, float* y, void* stream);
 /* tanh(conv5x5_zero_pad(LeakyReLU_0.2(x))) (:1602-1603); w [Cout,Cin,5,5], Cout <= 4 */
 int sln_conv_img_tanh(const float* x, int B, int Cin, int H, int W, const float* w, const float* bias, int Cout, float* y, void* stream);

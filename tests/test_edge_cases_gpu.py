@@ -174,6 +174,17 @@ def test_c_abi_rejects_null_pointers_and_bad_sizes_without_launching():
     assert L.sln_block_tail(p, 0, p, 1, 12, 4, 4, None, p, p, p, -1, p, None, 1, 1e-5, None, st) < 0         # C % 8
     assert L.sln_block_tail(p, 0, p, 1, 8, 4, 4, None, p, p, p, 0, p, None, 1, 1e-5, p, st) < 0              # stats without accumulators
     assert L.sln_spade_apply_up(p, 1, p, 1, 32, 3, 4, 64, p, 0, 0.2, p, st) < 0
+    # sizes that would become a grid size: every argument but the one named is valid, so only the size check can refuse the call
+    for hi, wi, ho, wo in ((0, 4, 4, 4), (4, 0, 4, 4), (4, 4, 0, 4), (4, 4, 4, 0), (-2, 4, 4, 4), (4, 4, 4, -1)):
+        assert L.sln_resize(p, 1, hi, wi, ho, wo, 0, p, st) == -1, (hi, wi, ho, wo)
+        assert L.sln_resize(p, 1, hi, wi, ho, wo, 1, p, st) == -1, (hi, wi, ho, wo)
+    for bc, h, w in ((0, 2, 2), (-1, 2, 2), (1, 0, 2), (1, 2, 0), (1, -3, 2), (1, 2, -3)):
+        assert L.sln_upsample2x(p, bc, h, w, 0, p, st) == -1 and L.sln_upsample2x(p, bc, h, w, 1, p, st) == -1, (bc, h, w)
+    for b, c, hw in ((0, 8, 4), (-1, 8, 4), (1, 0, 4), (1, -8, 4), (1, 8, 0), (1, 8, -4)):
+        assert L.sln_se_scale_add(p, p, b, c, hw, p, p, p, p, st) == -1, (b, c, hw)
+    for cs, h, w, nd, cm in ((0, 4, 4, 16, 1), (0, 4, 4, 16, 0), (41, 4, 4, -1, 1), (41, 1, 4, 16, 1), (41, 4, 1, 16, 1), (41, 1, 4, 16, 0),
+                             (41, 4, 1, 16, 0), (41, 0, 4, 16, 0), (41, 4, -2, 16, 1), (2, 4, 4, -1, 1)):
+        assert L.sln_spade_depth_concat(p, 1, cs, h, w, p, p, nd, p, cm, st) == -1, (cs, h, w, nd, cm)
     assert L.sln_refine_loss_forward(None, p, p, None, p, p, p, st) < 0
     d = Lm.SlnRefineLoss()                                                       # all-zero descriptor
     assert L.sln_refine_loss_forward(d, p, p, p, p, p, p, st) < 0 and L.sln_refine_loss_backward(d, p, p, p, st) < 0
