@@ -84,6 +84,36 @@ def nmr_backward_pixel_map(faces, fi, rgb, grad_rgb, eps=1e-3):
     return gf.reshape(B, F, 3, 3)
 
 
+I64P, F64P = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+# rows of the counter table of nmr_backward_pixel_map_f64 (enum PMC_* of raster_ref.cpp)
+PM_COUNTERS = ("longest_walk", "rows_ge64", "rows_lt64", "rows_gt128", "steps_off_image", "steps_slot_unused", "inward_rejected")
+
+
+def nmr_backward_depth_f64(faces, fi, w, d, grad_depth):
+    """The terms of nmr_backward_depth (fp32 operands and decisions) multiplied and summed in double.
+    Returns g64, S = sum |term| (float64) and n = number of terms (int64), each [B,F,3,3]."""
+    B, F, is_ = faces.shape[0], faces.shape[1], fi.shape[1]
+    faces = np.ascontiguousarray(faces.reshape(B, F, 9), np.float32)
+    g, S, n = np.zeros((B, F, 9), np.float64), np.zeros((B, F, 9), np.float64), np.zeros((B, F, 9), np.int64)
+    lib().nmr_backward_depth_f64(_p(faces), _p(np.ascontiguousarray(fi, np.int32), I32P), _p(np.ascontiguousarray(w, np.float32)),
+                                 _p(np.ascontiguousarray(d, np.float32)), _p(np.ascontiguousarray(grad_depth, np.float32)),
+                                 B, F, is_, _p(g, F64P), _p(S, F64P), _p(n, I64P))
+    return g.reshape(B, F, 3, 3), S.reshape(B, F, 3, 3), n.reshape(B, F, 3, 3)
+
+
+def nmr_backward_pixel_map_f64(faces, fi, rgb, grad_rgb, eps=1e-3):
+    """The terms of nmr_backward_pixel_map, -(double)diff / (double)dist, summed in double.
+    Returns g64, S, n as above and the call's path counters as a dict keyed by PM_COUNTERS."""
+    B, F, is_, Cn = faces.shape[0], faces.shape[1], fi.shape[1], rgb.shape[-1]
+    faces = np.ascontiguousarray(faces.reshape(B, F, 9), np.float32)
+    g, S, n = np.zeros((B, F, 9), np.float64), np.zeros((B, F, 9), np.float64), np.zeros((B, F, 9), np.int64)
+    cnt = np.zeros(len(PM_COUNTERS), np.int64)
+    lib().nmr_backward_pixel_map_f64(_p(faces), _p(np.ascontiguousarray(fi, np.int32), I32P), _p(np.ascontiguousarray(rgb, np.float32)),
+                                     _p(np.ascontiguousarray(grad_rgb, np.float32)), B, F, is_, Cn, C.c_float(eps),
+                                     _p(g, F64P), _p(S, F64P), _p(n, I64P), _p(cnt, I64P))
+    return g.reshape(B, F, 3, 3), S.reshape(B, F, 3, 3), n.reshape(B, F, 3, 3), dict(zip(PM_COUNTERS, (int(v) for v in cnt)))
+
+
 # ----------------------------------------------------------------------------------------------
 # torch wrappers
 # ----------------------------------------------------------------------------------------------
