@@ -164,6 +164,13 @@ class SlnDbgOpt(C.Structure):
                 ("pad_", C.c_int)]
 
 
+class SlnViewPlace(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("bank_v", "bank_f", "voff", "foff", "voff_host", "foff_host", "A", "tr", "row_model", "row_label",
+                                          "shell_v", "shell_f", "shell_f_host", "shell_label", "K", "Rm", "t")] + \
+               [(n, C.c_int32) for n in ("M", "Vtot", "Ftot", "Fm", "Vs", "Fs", "R", "V", "N", "reserved")] + \
+               [("orig_size", C.c_float), ("near", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/sln_hip.h declares must be listed here
 # (tests/test_abi.py checks the header against this table and against the built library).
 SIGNATURES = {
@@ -340,6 +347,10 @@ SIGNATURES = {
     "sln_mesh_retrieve": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "sln_shell_retrieve": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "sln_view_place_project": (C.c_int, [C.POINTER(SlnViewPlace), c_f32p, C.c_void_p, C.c_void_p]),
+    "sln_view_compose_workspace_bytes": (C.c_int64, [C.c_int]),
+    "sln_view_compose": (C.c_int, [C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -982,6 +982,58 @@ int sln_mesh_retrieve(const float* boxes, const int32_t* room_row, const int32_t
 int sln_shell_retrieve(const float* boxes, const int32_t* last_row, int R, int N, const double* wall_ratio, const double* floor_ratio,
                        int W, int32_t* out, void* stream);
 
+/* =============================================================================================
+ * Viewpoint render of render/render_semantic_depth.py::render_test (:152-377), the hand-off between the placed meshes and the SPADE
+ * input (csrc/shade_view.hip; host/shade.py).  Rasterisation in between is sln_raster_forward.
+ * ============================================================================================= */
+/* R rooms of N rows each (rows beyond a room's length are padding), V candidate views per room.  Face slot f of a room:
+ *   f <  N * Fm : row f / Fm, face f % Fm of the row's model (bank.f, corner indices local to the model);
+ *   f >= N * Fm : face f - N * Fm of the shell (shell_f over the room's Vs placed shell vertices).
+ * so F = N * Fm + Fs for every room and every shape is fixed.  Pointers are device pointers unless named *_host. */
+typedef struct SlnViewPlace {
+  /* the bank's resident models: model m owns vertices voff[m] .. voff[m + 1] of v [Vtot, 3] and faces foff[m] .. foff[m + 1] of f */
+  const float* bank_v;
+  const int32_t* bank_f;          /* [Ftot, 3] */
+  const int32_t* voff;            /* [M + 1] */
+  const int32_t* foff;            /* [M + 1] */
+  const int32_t* voff_host;       /* the same two tables on the host: what the call checks before it launches */
+  const int32_t* foff_host;
+  /* per row [R * N]: v' = A v + tr (fp32, row-major 3 x 3), the bank model of the row (< 0: none - not imported, no model, padding),
+   * the class byte of its faces (1 + NYU class; 0 with row_model < 0) */
+  const float* A;
+  const float* tr;
+  const int32_t* row_model;
+  const unsigned char* row_label;
+  /* the shell: placed vertices [R, Vs, 3], one topology for all rooms */
+  const float* shell_v;
+  const int32_t* shell_f;         /* [Fs, 3] */
+  const int32_t* shell_f_host;    /* [Fs, 3] on the host (checked against Vs) */
+  const unsigned char* shell_label; /* [Fs] */
+  const float* K;                 /* [R * V, 3, 3] */
+  const float* Rm;                /* [R * V, 3, 3] */
+  const float* t;                 /* [R * V, 3] */
+  int32_t M, Vtot, Ftot, Fm, Vs, Fs, R, V, N, reserved;
+  float orig_size, near;
+} SlnViewPlace;
+/* faces_xyz [R * V, F, 3, 3] = (x_ndc, y_ndc, z_cam) per corner, as sln_project_faces defines them (eps 1e-9) for the row's
+ * placed model; a face with a corner nearer than `near`, a slot beyond its model's face count and every slot of a row without a
+ * model collapse to the point (0, 0, 0): they cover no pixel.  face_label [R, F] uint8: the row's class byte on the slots of its
+ * model's faces, the shell's bytes, 0 on empty slots.  One launch, forward only, no atomics, no allocation: legal inside a stream
+ * capture.  Checked on the host before the launch (SLN_E_BADARG, nothing launched): null pointers, sizes < 1 (Fs, Vs, M may be 0),
+ * R * V > 65535, voff_host / foff_host not starting at 0, decreasing, ending past Vtot / Ftot, a model with more than Fm faces,
+ * a shell corner outside [0, Vs), F > 2^24, orig_size <= 0.  What only the device holds (row_model, the
+ * corner indices in bank_f, the device copies of the tables) is range-checked per lane: a value outside its range makes the slot
+ * an empty one, never an out-of-bounds read. */
+int sln_view_place_project(const SlnViewPlace* d, float* faces_xyz, unsigned char* face_label, void* stream);
+/* From the rasterizer's maps (raster order: row 0 = bottom) of B = R * V views: labels [B, S, S] uint8 and depth_out [B, S, S]
+ * float32 in IMAGE row order (row 0 = top): face_label [B / V, F] of the hit face and its depth, 0 and 1e10 (Blender's empty Z)
+ * where face_index is outside [0, F); per view sum [B] float64 and count [B] int64 of the depth_out entries below 1e5.  The
+ * reduction is fixed-order (per-workgroup partials into the workspace, one last pass): repeatable, whatever sln_set_deterministic
+ * says.  Two launches, no atomics, no allocation.  workspace: sln_view_compose_workspace_bytes(B) bytes, 8-byte aligned. */
+int64_t sln_view_compose_workspace_bytes(int B);
+int sln_view_compose(const int32_t* face_index, const float* depth, const unsigned char* face_label, int B, int V, int F, int S,
+                     void* workspace, unsigned char* labels, float* depth_out, double* sum, int64_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
