@@ -511,7 +511,9 @@ int sln_raster_forward(const float* faces, int B, int F, int image_size, float n
 int sln_raster_forward_dual(const float* faces, int B, int F, int image_size, float near_a, float near_b, float far,
                             void* workspace, int32_t* fi_a, float* w_a, float* d_a, int32_t* fi_b, float* w_b,
                             float* d_b, void* stream);
-/* forward_texture_sampling: textures [B,F,ts,ts,ts,3] -> rgb [B,is,is,3] (background 0) */
+/* forward_texture_sampling: textures [B,F,ts,ts,ts,3] -> rgb [B,is,is,3] (background 0).  The index map is an operand: any values in
+ * [-1, F) are legal (not only a map sln_raster_forward wrote); anything else is the caller's error - the kernel forms the face and
+ * texture addresses from the map and tests only its sign. */
 int sln_raster_texture_sample(const float* faces, const float* textures, const int32_t* face_index, const float* weight,
                               const float* depth, int B, int F, int image_size, int texture_size, float eps, float* rgb,
                               void* stream);
@@ -524,7 +526,9 @@ int sln_raster_backward_rgb(const float* faces, const int32_t* face_index, const
 /* Renderer.__call__(mode="rgb") (models/diff_render.py:398) behind cached maps, one launch: forward_texture_sampling + ambient
  * light (factor `scale`) + the package's permute / row flip -> rgb_chw [B,3,is,is].  textures [B,F_tex,ts,ts,ts,3] with
  * F_tex == F, or F_tex == F / 2 for fill_back: face f >= F_tex samples cube f - F_tex with texture axes 0 and 2 swapped
- * (the package's torch.cat((textures, textures.permute((0, 1, 4, 3, 2, 5))), dim=1)). */
+ * (the package's torch.cat((textures, textures.permute((0, 1, 4, 3, 2, 5))), dim=1)).  The index map is an operand here too: any
+ * values in [-1, F) are legal, anything else is the caller's error (tests/test_raster_texture_chw_gpu.py holds both halves: a
+ * random in-range map, and a host check of every map before the launch). */
 int sln_raster_texture_sample_chw(const float* faces, const float* textures, const int32_t* face_index, const float* weight,
                                   const float* depth, int B, int F, int F_tex, int image_size, int texture_size, float eps, float scale,
                                   float* rgb_chw, void* stream);

@@ -21,6 +21,7 @@
 // Expressions keep the published code's mixed float/double arithmetic (double literals promote), because it
 // decides on which side of an edge a pixel centre falls.  Build with -ffp-contract=off.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -120,6 +121,14 @@ struct PixAccF64 {
   }
 };
 
+// (int)x as v_cvt_i32_f32 (and CUDA's cvt.rzi.s32.f32) define it where C++ does not: saturating, NaN -> 0
+inline int device_int(float x) {
+  if (x != x) return 0;
+  if (x >= 2147483648.f) return INT_MAX;
+  if (x <= -2147483648.f) return INT_MIN;
+  return (int)x;
+}
+
 template <class Acc>
 void backward_pixel_map_body(const float* faces, const int32_t* face_index, const float* rgb, const float* grad_rgb,
                              int B, int F, int is, int C, float eps, const Acc& proto) {
@@ -194,7 +203,10 @@ void backward_pixel_map_body(const float* faces, const int32_t* face_index, cons
             float cross2;
             if ((d0 - p[0][0]) * (d0 - p[2][0]) < 0) cross2 = (p[2][1] - p[0][1]) / (p[2][0] - p[0][0]) * (d0 - p[0][0]) + p[0][1];
             else cross2 = (p[1][1] - p[2][1]) / (p[1][0] - p[2][0]) * (d0 - p[2][0]) + p[2][1];
-            const int lim = dir > 0 ? (int)std::ceil(cross2) : (int)std::floor(cross2);
+            // cross2 is +-inf at the step through the vertex p[0] when the opposite edge runs along the scan axis (the pixel-centre
+            // triangle), NaN when that step is also its end: converted as the device converts (saturating, NaN -> 0) - the C++
+            // conversion is undefined for them and x86 returns INT_MIN for all three, which scanned towards the wrong border
+            const int lim = dir > 0 ? device_int(std::ceil(cross2)) : device_int(std::floor(cross2));
             const int from = std::max(std::min(d1_in, lim), 0), to = std::min(std::max(d1_in, lim), is - 1);
             if (Acc::counting) count_row(to - from + 1);
             long q = axis == 0 ? base + (long)from * is + d0 : base + (long)d0 * is + from;

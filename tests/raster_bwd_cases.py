@@ -292,7 +292,8 @@ def scene_geometry(is_, b):
     cls += [-1] * (F_STD - len(cls))
     near = _front(np.array([[-0.5, 0.1, 0.05], [-0.1, 0.15, 0.05], [-0.3, 0.6, 0.05]], np.float32))
     faces = list(base) + [near, near[[2, 1, 0]]] + padding(SCENE_F - F_STD - 2)
-    cls += [3, 3, 2, 2] + [-1] * (SCENE_F - F_STD - 6)
+    cls += [3, 3, 2, 2] + [-1] * (SCENE_F - F_STD - 4)
+    assert len(cls) == len(faces) == SCENE_F
     return np.stack(faces).astype(np.float32), np.array(cls, np.int32)
 
 
