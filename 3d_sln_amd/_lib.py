@@ -351,6 +351,9 @@ SIGNATURES = {
     "sln_view_compose_workspace_bytes": (C.c_int64, [C.c_int]),
     "sln_view_compose": (C.c_int, [C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "sln_observed_target_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "sln_observed_target": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, c_f32p,
+                                      C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -27,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 from . import diff_render as DR
+from . import observe as OB
 from . import retrieve as RT
 from . import scene_pictures as SP
 from . import synthetic
@@ -901,16 +902,29 @@ class RefineBatch:
     :319), the iterates those retrieved for the FIRST iterate's boxes (one launch over ``boxes`` behind ``_first_iterate_sizes``' forward
     in the first ``run()``, :324-326; read back - set-up, outside any capture - after which the iterates' scenes are built and bound,
     ``_bind_scenes``), frozen from then on.  ``target_models`` / ``models`` (int32 [N], -1 where nothing is retrieved) and
-    ``model_ids()`` expose the choice; a bank with a shell list gets its (wall, floor) entries per room the same way."""
+    ``model_ids()`` expose the choice; a bank with a shell list gets its (wall, floor) entries per room the same way.
+
+    ``observed``: None (default: every room's target is the render of its own ``boxes``, the launches are those above), or
+    ``(depth [R, S, S] float32, labels [R, S, S] uint8)`` on the device - one observation per room of the refinement camera
+    (``get_cam_mat`` of the room row; host/observe.py) from which ONE ``ObservedTarget`` call on the batch's class tables builds the R
+    targets; nothing is rendered from ``rm["boxes"]``.  The encoder start, the frozen room row, the camera and the size targets stay
+    ``rm[...]``'s; ``report``'s depth term and ``target_pictures`` read the observed targets; ``target_status`` [R] holds the status
+    words of the observations (None without ``observed``).  Does not combine with ``retrieve=True``."""
 
     def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
-                 retrieve=False):
+                 retrieve=False, observed=None):
         L = _lib.lib()
         self.model, self.R, self.iters, self.lr = model, len(rooms), int(iters), float(learning_rate)
         R = self.R
         if R < 1:
             raise ValueError("RefineBatch needs at least one room")
         dev = model.flat_params.device
+        if observed is not None:                                # refused here, in front of the first launch
+            if retrieve:
+                raise ValueError("observed targets show no meshes to retrieve: observed and retrieve=True do not combine")
+            if not isinstance(observed, (tuple, list)) or len(observed) != 2:
+                raise ValueError("observed is (depth [R, S, S] float32, labels [R, S, S] uint8)")
+            OB.ObservedTarget.check_tensors(observed[0], observed[1], (R, int(image_size), int(image_size)), dev)
         names_all = set(n for rm in rooms for n in rm["class_names"])
         bank = bank or MeshBank([n for n in names_all if n not in DO_NOT_VIS and n != "__room__"], dev)
         model.eval()
@@ -949,9 +963,22 @@ class RefineBatch:
             sc = RefineScene(rm["class_names"], bank, rm["boxes"][-1].detach().clone(), S, models=tm[a:a + n] if tm is not None else None,
                              shell=self._shells[r] if self._shells is not None else None)
             with torch.no_grad():
-                tgt, _, sizes = sc.render(rm["boxes"], rm["angles"].float())
+                if observed is None:
+                    tgt, _, sizes = sc.render(rm["boxes"], rm["angles"].float())
+                else:                   # the placement alone, for the sizes: the target is not rendered from the room's boxes
+                    tgt = None
+                    _, _, sizes = _PlaceFn.apply(rm["boxes"], rm["angles"].float(), sc, None)
             scenes.append(sc); targets.append(tgt); size_targets.append(sizes.detach().clone().contiguous())
             box_last[r] = rm["boxes"][-1].detach().float(); angle_last[r] = rm["angles"][-1].detach().float()
+        self.target_status = None
+        if observed is not None:
+            # ---- all R targets from ONE ObservedTarget call on the batch's class tables (csrc/observed_target.hip) ----
+            for sc in scenes[1:]:
+                if not (torch.equal(sc.chan, scenes[0].chan) and torch.equal(sc.dch, scenes[0].dch)):
+                    raise _lib.SlnError("rooms of one batch must share the class tables")
+            built, status = OB.ObservedTarget(scenes[0].chan, scenes[0].dch, S, batch=R, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)
+            targets = [built[r:r + 1] for r in range(R)]
+            self.target_status = status.clone()
         self.z, self.scenes, self.target_scenes = z, scenes, scenes
         self._report_all = report == "all"
         if report is None:

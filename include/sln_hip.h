@@ -1038,6 +1038,36 @@ int64_t sln_view_compose_workspace_bytes(int B);
 int sln_view_compose(const int32_t* face_index, const float* depth, const unsigned char* face_label, int B, int V, int F, int S,
                      void* workspace, unsigned char* labels, float* depth_out, double* sum, int64_t* count, void* stream);
 
+/* =============================================================================================
+ * The refinement target of an observed room (csrc/observed_target.hip; host/observe.py): the 70-plane tensor sln_scene_forward
+ * composes from its rasterisation, composed from a depth image and a class-index image instead.
+ * ============================================================================================= */
+/* depth [B, S, S] float32 (metric, the refinement camera's: plane 0 of a scene tensor) and labels [B, S, S] uint8 (0 = no class,
+ * 1 + c = NYU class c: sln_scene_pictures' labels) on the device, both in the row order of the scene tensor's planes (no row is
+ * flipped).  chan / dch [NC] int32 are the VALUES of the tables sln_scene_forward takes (class 0 is the wall; chan = NYU channel,
+ * dch = depth-hot channel or -1), read on the HOST: they are checked before anything is launched and travel as launch arguments.
+ * out [B, nch, S, S] float32, every plane written; status [B] int32.  Per room, d the depth and y the byte of a pixel:
+ *   reading      0 < d <= 15; a NaN, an infinity, d <= 0 and d > 15 are none.  d0 = d with a reading, else -1 (the renderer's
+ *                background value); l = y where y <= 40 and the pixel has a reading, else 0.
+ *   out[0]       d0
+ *   out[1 + c]   exactly 1.0 where l == 1 + c, else exactly 0.0, c = 0 .. 39 - whether or not a class of the tables has channel c
+ *   mask_c       {l == chan[c] + 1};  cnt_c its pixel count;  sum_c = (double)(sum over the mask of rint((double)d0 * 2^32), a 64-bit
+ *                integer: order-independent) * 2^-32 - the fixed point of the scene pass's statistics;  wall_max = max of d0 over
+ *                mask_0, 10 where mask_0 is empty
+ *   out[41 + k]  for the class c with dch[c] == k:  d0 / wall_max inside mask_c,  fill_c / wall_max outside,
+ *                fill_c = cnt_c > 0 ? (float)(sum_c / cnt_c) : wall_max  (the scene pass's compose expressions: float32, correctly
+ *                rounded quotients);  all 0 for a k no class owns
+ *   status       bit 0: a byte > 40;  bit 1: an l > 0 whose NYU channel no class of the tables has;  bit 2: mask_0 is empty (no wall
+ *                pixel);  bit 3: a byte in 1 .. 40 on a pixel without a reading
+ * Two launches on `stream` (at most three); no allocation, no synchronisation, nothing read back, no floating-point atomics: legal
+ * inside a stream capture and bit-identical from call to call.  workspace: sln_observed_target_workspace_bytes(B, S) bytes.
+ * SLN_E_UNSUPPORTED, nothing launched: S % 4 != 0, S < 4 or S > 4096 (the integer sum stays below 2^63), B < 1 or > 65535, NC < 1 or
+ * > 64, nch > 72 or nch != 41 + (number of dch >= 0).  SLN_E_BADARG, nothing launched: a null pointer; depth or out not 16-byte, any
+ * other buffer not 4-byte aligned; chan[c] outside [0, 40), dch[c] outside [-1, nch - 41), a depth channel owned by two classes. */
+int64_t sln_observed_target_workspace_bytes(int B, int S);
+int sln_observed_target(const float* depth, const unsigned char* labels, int B, int S, int NC, const int32_t* chan, const int32_t* dch,
+                        int nch, void* workspace, float* out, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
