@@ -171,6 +171,12 @@ class SlnViewPlace(C.Structure):
                [("orig_size", C.c_float), ("near", C.c_float)]
 
 
+class SlnDraw3D(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("faces_xyz", "face_index", "depth", "face_label", "chosen", "K", "light_cam", "albedo")] + \
+               [(n, C.c_int32) for n in ("R", "V", "F", "S", "k", "shadows")] + \
+               [(n, C.c_float) for n in ("ambient", "intensity", "min_dist", "bias")] + [("background", C.c_float * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/sln_hip.h declares must be listed here
 # (tests/test_abi.py checks the header against this table and against the built library).
 SIGNATURES = {
@@ -354,6 +360,8 @@ SIGNATURES = {
     "sln_observed_target_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "sln_observed_target": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, c_f32p,
                                       C.c_void_p, C.c_void_p]),
+    "sln_draw3d_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "sln_draw3d": (C.c_int, [C.POINTER(SlnDraw3D), C.c_void_p, C.c_void_p, c_f32p, C.c_void_p]),
 }
 
 _lib = None

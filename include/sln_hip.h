@@ -1068,6 +1068,37 @@ int64_t sln_observed_target_workspace_bytes(int B, int S);
 int sln_observed_target(const float* depth, const unsigned char* labels, int B, int S, int NC, const int32_t* chan, const int32_t* dch,
                         int nch, void* workspace, float* out, int32_t* status, void* stream);
 
+/* =============================================================================================
+ * The --draw_3d picture (render/render_room_color.py::render_test): a lit colour picture with hard shadows of the view the viewpoint
+ * render accepted (csrc/draw3d.hip; host/draw3d.py).  The shading model is this project's, stated in DESIGN §4 "3-D drawing".
+ * ============================================================================================= */
+/* What sln_view_place_project, sln_raster_forward and the choice leave on the device, all device pointers.  Room r is drawn from view
+ * b = r * V + chosen[r] (chosen is read on the device and clamped to [0, V)). */
+typedef struct SlnDraw3D {
+  const float* faces_xyz;           /* [R * V, F, 3, 3] (x_ndc, y_ndc, z_cam) */
+  const int32_t* face_index;        /* [R * V, S, S] raster order (row 0 = bottom); outside [0, F): background */
+  const float* depth;               /* [R * V, S, S] the rasterizer's depth */
+  const unsigned char* face_label;  /* [R, F]; a byte above 40 reads albedo entry 0 */
+  const int64_t* chosen;            /* [R] */
+  const float* K;                   /* [R * V, 3, 3]: fx, fy, cx, cy are read, no skew, orig_size = S */
+  const float* light_cam;           /* [R, 3] the lamp in the drawn view's camera frame */
+  const float* albedo;              /* [41, 3] linear colour per class byte */
+  int32_t R, V, F, S, k, shadows;   /* k: samples per output pixel and axis, P = S / k */
+  float ambient, intensity, min_dist, bias, background[3];
+} SlnDraw3D;
+/* picture [R, P, P, 3] uint8 in image row order (row 0 = top): per output pixel the mean of its k x k linear samples (added row by
+ * row), clamped to [0, 1], sRGB-encoded, times 255, rounded to nearest.  linear [R, S, S, 3] float32 in raster order, or NULL.  A
+ * sample's linear colour: background where face_index is outside [0, F); else albedo[label] * (ambient + intensity * vis * c / d^2)
+ * with p = ray(pixel centre) * depth, n the face's normal turned towards the camera, l = light - p, d^2 = max(|l|^2, min_dist^2),
+ * c = max(0, n.l / |l|), and vis = 0 when the segment from p + bias * n to the light meets another face of the view (two-sided
+ * Moller-Trumbore, t in (0, 1), barycentrics in [0, 1], a zero determinant is no hit), tested only with `shadows` and c > 0.
+ * Two launches (faces of the chosen view into the workspace; lighting and picture), no atomics, no allocation, fixed-order sums:
+ * legal inside a stream capture, the same bytes from call to call.  workspace: sln_draw3d_workspace_bytes(R, F) bytes, 16-byte
+ * aligned.  SLN_E_BADARG, nothing launched: a null pointer (linear may be NULL), a size < 1, S % k != 0, k > 16, S > 32768,
+ * R * V > 65535, F > 2^24, a misaligned workspace. */
+int64_t sln_draw3d_workspace_bytes(int R, int F);
+int sln_draw3d(const SlnDraw3D* d, void* workspace, unsigned char* picture, float* linear, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
