@@ -13,7 +13,8 @@ What is replaced
   * mesh loading (models/misc.py: SUNCG meshes + pywavefront + pymesh, out of scope): without caller-supplied meshes every object
     class gets a procedural cuboid "model" with a fixed aspect ratio and walls / floor / ceiling are quads built from the room box;
     meshes stay resident on the GPU instead of being re-read from disk every iteration (models/misc.py:111-121).  The retrieval
-    AMONG a class's models (models/misc.py:34-64,123-152) is reproduced: ``retrieve_choice`` / host/retrieve.py;
+    AMONG a class's models (models/misc.py:34-64,123-152) is reproduced: ``retrieve_choice`` / host/retrieve.py; so is the splitting
+    of long edges (:79,100), by a rule of this project's own: ``MeshBank.from_arrays(max_edge=)`` / host/mesh_prep.py;
   * the 33 raster passes per call: one fused HIP pass (diff_render.scene_render semantics).
 ``render_fn`` is injectable so that the tests can run the very same loss graph on the CPU oracle.
 """
@@ -27,6 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from . import diff_render as DR
+from . import mesh_prep as MP
 from . import observe as OB
 from . import retrieve as RT
 from . import scene_pictures as SP
@@ -78,7 +80,7 @@ class MeshBank:
     shells = None       # every shell the caller listed (shell is entry 0)
 
     @classmethod
-    def from_arrays(cls, meshes, device, vocab=None, shell=None):
+    def from_arrays(cls, meshes, device, vocab=None, shell=None, max_edge=None):
         """Caller-supplied meshes - the seam of models/diff_render.py:62,131, where the reference hands the retrieved SUNCG model's
         vertices / faces to the placement: ``meshes`` = {class name: (V [n,3] float, F [m,3] int)} or (V, F, bbox_min, bbox_max)
         (one model per class, any topology; faces index V), or a LIST of such models per class, each (V, F, bbox_min, bbox_max[, id])
@@ -91,7 +93,11 @@ class MeshBank:
         [m,3] sub-meshes over wall_v (models/misc.py:84-104), wall_bbox [2,3], floor_v, floor_f, floor_bbox [2,3], ceil_v, ceil_f), or a
         LIST of such dicts (the rows of wall_data_wfc.json, among which ``retrieve.retrieve_shell`` picks per room; entry 0 is the
         default); without it the shell is five quads on the room box.
-        ``bank.table`` is the ``retrieve.ModelTable`` of the models, ``bank.shell_ratios`` the shell list's ratio tables."""
+        ``bank.table`` is the ``retrieve.ModelTable`` of the models, ``bank.shell_ratios`` the shell list's ratio tables.
+        ``max_edge``: split every edge longer than this (models/misc.py:79,100 pass 0.6 to pymesh.split_long_edges_raw) - one
+        ``mesh_prep.split_meshes`` call over every model of every class and every shell's wall, floor and ceiling, on ``device``.  A
+        wall is split as one mesh over ``wall_v`` and its sub-meshes keep their faces' children.  Boxes, ids and the retrieval table
+        stay those of the input (a midpoint never leaves the hull).  None: the meshes enter as they are."""
         bank = cls.__new__(cls)
         bank.models, bank.model_lists = {}, {}
         for name, mesh in meshes.items():
@@ -126,7 +132,31 @@ class MeshBank:
             if not bank.shells:
                 raise ValueError("shell is an empty list")
             bank.shell = bank.shells[0]
+        if max_edge is not None:
+            cls._split_long_edges(bank, torch.device(device), max_edge)
         return bank
+
+    @staticmethod
+    def _split_long_edges(bank, dev, max_edge):
+        entries = [e for lst in bank.model_lists.values() for e in lst]
+        jobs = [(e["v"], e["f"]) for e in entries]
+        shells = getattr(bank, "shells", None) or []
+        for sh in shells:
+            wall_f = np.concatenate(sh["wall_f"]) if sh["wall_f"] else np.zeros((0, 3), dtype=np.int64)
+            for v, f in ((sh["wall_v"], wall_f), (sh["floor_v"], sh["floor_f"]), (sh["ceil_v"], sh["ceil_f"])):
+                jobs.append((torch.from_numpy(np.ascontiguousarray(v.reshape(-1, 3))).to(dev), torch.from_numpy(f.astype(np.int32)).to(dev)))
+        res = MP.split_meshes(jobs, max_edge)
+        for e, (v, f, _) in zip(entries, res):
+            e["v"], e["f"] = v.clone(), f.clone()                 # (their own storage: the results are slices of the bank-wide tables)
+        at = len(entries)
+        for sh in shells:
+            (wv, wf, winfo), (fv, ff, _), (cv, cf, _) = res[at:at + 3]
+            at += 3
+            origin, wf = winfo["origin"].cpu().numpy(), wf.cpu().numpy().astype(np.int64)
+            ends = np.cumsum([0] + [f.shape[0] for f in sh["wall_f"]])
+            sh["wall_f"] = [wf[(origin >= a) & (origin < b)] for a, b in zip(ends[:-1], ends[1:])]
+            sh["wall_v"], sh["floor_v"], sh["ceil_v"] = (x.cpu().numpy() for x in (wv, fv, cv))
+            sh["floor_f"], sh["ceil_f"] = ff.cpu().numpy().astype(np.int64), cf.cpu().numpy().astype(np.int64)
 
     @staticmethod
     def _shell_arrays(shell):

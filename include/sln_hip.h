@@ -1099,6 +1099,34 @@ typedef struct SlnDraw3D {
 int64_t sln_draw3d_workspace_bytes(int R, int F);
 int sln_draw3d(const SlnDraw3D* d, void* workspace, unsigned char* picture, float* linear, void* stream);
 
+/* =============================================================================================
+ * Splitting long mesh edges before models enter the bank (csrc/mesh_split.hip; host/mesh_prep.py): one pass of the rule of DESIGN §4
+ * "Splitting long edges" is three launches, with the host's sort / unique of the keys and scan of the counts between them.  All
+ * pointers are device pointers.  No atomics, no allocation, nothing read back; the same bytes from call to call whatever
+ * sln_set_deterministic says.  status [4] int32, zeroed by the caller once: word 0 = 1 after a face with an index outside [0, V)
+ * (mark), word 1 = 2 after a key that names a vertex outside [0, V) (midpoints), word 2 = 4 after an offset outside the output or
+ * a new vertex index outside [V, V + U) (emit).  Nothing is ever read outside v.
+ * ============================================================================================= */
+/* v [V, 3] float32, f [F, 3] int32.  Edge k of a face joins corners k and (k + 1) % 3; its squared length is (dx*dx + dy*dy) + dz*dz
+ * in float64 from the float32 coordinates; it is marked when that exceeds max_edge_sq.  mask [F] int32: bit k = edge k marked;
+ * count [F] int32 = 1 + marked edges (the face's children); keys [F, 3] int64 = (min(i, j) << 32) | max(i, j) of a marked edge, -1
+ * otherwise.  A face with an index outside [0, V) gets mask 0, count 1, keys -1: it is copied through unsplit.  SLN_E_BADARG,
+ * nothing launched: a null pointer, F < 1, V < 1, max_edge_sq not finite or <= 0, V + 3 F >= 2^31. */
+int sln_mesh_split_mark(const float* v, int V, const int32_t* f, int F, double max_edge_sq, int32_t* mask, int32_t* count,
+                        int64_t* keys, int32_t* status, void* stream);
+/* ukeys [U] int64: the sorted unique marked keys.  v_new [U, 3]: float32((double(a) + double(b)) * 0.5) per coordinate of the key's
+ * two vertices - vertex V + u of the pass's output; (0, 0, 0) for a key outside the table.  SLN_E_BADARG: a null pointer, V < 1,
+ * U < 1, V + U >= 2^31. */
+int sln_mesh_split_midpoints(const float* v, int V, const int64_t* ukeys, int U, float* v_new, int32_t* status, void* stream);
+/* v_out [V + U, 3]: the old vertices followed by v_new.  mid [F, 3] int32: the new vertex index of every marked edge; offsets [F]
+ * int64: the exclusive prefix sum of count; F_out its total.  Writes the children of face i (in the order of DESIGN §4, winding
+ * kept) to f_out [F_out, 3] at offsets[i] and origin[i] to origin_out [F_out] beside each.  The quad of a face with two marked
+ * edges is cut by the shorter diagonal, compared as squared float64 lengths of the float32 positions in v_out, a tie going to
+ * A-M1.  SLN_E_BADARG: a null pointer, F < 1, V < 1, U < 0, V + 3 F or V + U >= 2^31, F_out outside [F, 4 F]. */
+int sln_mesh_split_emit(const float* v_out, int V, int U, const int32_t* f, const int32_t* origin, const int32_t* mask,
+                        const int64_t* offsets, const int32_t* mid, int F, int F_out, int32_t* f_out, int32_t* origin_out,
+                        int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
