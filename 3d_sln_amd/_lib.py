@@ -171,6 +171,12 @@ class SlnViewPlace(C.Structure):
                [("orig_size", C.c_float), ("near", C.c_float)]
 
 
+class SlnReproject(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("depth_src", "k_src", "pose", "K_tgt")] + \
+               [(n, C.c_int32) for n in ("B", "Hs", "Ws", "reserved")] + \
+               [(n, C.c_float) for n in ("orig_size", "near", "gap", "reserved_f")]
+
+
 class SlnDraw3D(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("faces_xyz", "face_index", "depth", "face_label", "chosen", "K", "light_cam", "albedo")] + \
                [(n, C.c_int32) for n in ("R", "V", "F", "S", "k", "shadows")] + \
@@ -360,6 +366,9 @@ SIGNATURES = {
     "sln_observed_target_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "sln_observed_target": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, c_f32p,
                                       C.c_void_p, C.c_void_p]),
+    "sln_reproject_faces": (C.c_int, [C.POINTER(SlnReproject), c_f32p, C.c_void_p]),
+    "sln_reproject_compose": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "sln_draw3d_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "sln_draw3d": (C.c_int, [C.POINTER(SlnDraw3D), C.c_void_p, C.c_void_p, c_f32p, C.c_void_p]),
     "sln_mesh_split_mark": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

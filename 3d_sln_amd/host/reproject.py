@@ -1,0 +1,239 @@
+"""An observed depth and label frame of ANY pinhole camera -> the pair ``observe.ObservedTarget`` takes: ``depth`` [B, S, S] float32
+and ``labels`` [B, S, S] uint8 as ``get_cam_mat``'s camera of the room row sees them, in the row order of the scene tensor's planes
+(csrc/observed_reproject.hip; DESIGN §4 "Observed frames from any camera" is the definition).
+
+The frame is a depth image seen as a mesh: every cell of four neighbouring pixels gives two triangles in the source camera, the pose
+takes them to the target camera, ``sln_raster_forward`` draws them, and a compose step reads depth and the label of the nearest source
+pixel out of the rasterizer's maps.
+
+  * ``ObservedReprojector``   static buffers, three steps of launches (faces, raster, compose), nothing read back;
+  * ``reproject_torch``       the definition in torch ops with the caller's rasterizer: the yardstick of the tests and the CPU route;
+  * ``relative_pose``, ``refine_view``, ``scene_as_source``   the cameras: source -> target pose from two world poses, the refinement
+    view of a room row, and the source intrinsics under which a scene tensor's own planes are a frame of their own camera.
+
+A target pixel no face covers - a disocclusion, a cut at a depth step, the frame's border - reads "no reading" (-1, label 0); the
+refinement loss has no validity mask, so ``hits`` is the caller's signal.  There is no pre-filter when the frame is finer than the
+target, and one frame per room: fusing several is not done here.
+"""
+import numpy as np
+import torch
+
+from .. import _lib as L
+from . import diff_render as DR
+from .observe import FAR
+
+PROJ_EPS = 1e-9
+NO_READING = -1.0
+MAX_FACES = 1 << 24
+MAX_S = 4096
+MAX_B = 65535
+# corner -> (row, column) offset inside the cell, per slot: (a, b, c) and (d, c, b)
+_DI = ((0, 1, 0), (1, 0, 1))
+_DJ = ((0, 0, 1), (1, 1, 0))
+
+
+def n_faces(Hs, Ws):
+    return 2 * (int(Hs) - 1) * (int(Ws) - 1)
+
+
+def _check_sizes(B, Hs, Ws, S):
+    if B < 1 or B > MAX_B or Hs < 2 or Ws < 2 or S < 1 or S > MAX_S or n_faces(Hs, Ws) > MAX_FACES:
+        raise ValueError("batch in [1, 65535], a frame of at least 2 x 2 pixels and at most 2^24 faces, S in [1, 4096] expected, got "
+                         "batch = %r, Hs = %r, Ws = %r, S = %r" % (B, Hs, Ws, S))
+
+
+def _check_scalars(orig_size, near, gap):
+    if not orig_size > 0 or not gap >= 0 or not near > 0:
+        raise ValueError("orig_size > 0, gap >= 0 and near > 0 expected, got %r, %r, %r" % (orig_size, gap, near))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# cameras
+# ------------------------------------------------------------------------------------------------------------------------------
+def relative_pose(R_src, t_src, R_tgt, t_tgt):
+    """World -> camera poses ``p = R w + t`` of the source and the target camera ([..., 3, 3] and [..., 3] or [..., 1, 3]) -> the pose
+    [..., 3, 4] float32 that takes source-camera coordinates to target-camera coordinates, ``[R_t R_s^T | t_t - R_t R_s^T t_s]``,
+    computed in float64 and rounded once."""
+    Rs, Rt = torch.as_tensor(R_src).double(), torch.as_tensor(R_tgt).double()
+    ts = torch.as_tensor(t_src).double().reshape(*Rs.shape[:-2], 3, 1)
+    tt = torch.as_tensor(t_tgt).double().reshape(*Rt.shape[:-2], 3, 1)
+    rel = torch.matmul(Rt, Rs.transpose(-1, -2))
+    return torch.cat((rel, tt - torch.matmul(rel, ts)), -1).float().contiguous()
+
+
+def refine_view(room_box, S):
+    """The refinement view of a room row (``diff_render.get_cam_mat``): -> (K_tgt [3, 3], R [3, 3], t [3], orig_size) on the host.  K is
+    in pixels of ``orig_size`` whatever the image size ``S`` of the render."""
+    if int(S) < 1:
+        raise ValueError("S: a positive image size expected")
+    room = [float(x) for x in torch.as_tensor(room_box).detach().cpu().reshape(-1).tolist()]
+    K, R, t = DR.get_cam_mat([room], "cpu")
+    return K[0].contiguous(), R[0].contiguous(), t.reshape(3).contiguous(), float(DR.inter_out)
+
+
+def scene_as_source(K_tgt, orig_size, S):
+    """The ``k_src`` [..., 4] (fx, fy, cx, cy) under which the planes of a scene tensor rendered at ``S`` with ``K_tgt`` [..., 3, 3] and
+    ``orig_size`` are a source frame of that same camera, with the identity pose: plane row r, column c is the rasterizer's pixel
+    (S - 1 - r, c), whose centre projects from ``K (x / z, y / z, 1) = orig_size / S * (c + 0.5, r + 0.5)`` - an ordinary x-right,
+    y-down image of ``K * S / orig_size`` (no axis is mirrored; K's skew entry must be 0)."""
+    K = torch.as_tensor(K_tgt).double()
+    s = float(S) / float(orig_size)
+    return (torch.stack((K[..., 0, 0], K[..., 1, 1], K[..., 0, 2], K[..., 1, 2]), -1) * s).float().contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the definition in torch ops
+# ------------------------------------------------------------------------------------------------------------------------------
+def faces_torch(depth_src, k_src, pose, K_tgt, orig_size, near=0.1, gap=0.05, dtype=torch.float64):
+    """csrc/observed_reproject.hip's first kernel in torch ops, in ``dtype``: -> faces_xyz [B, F, 3, 3].  The two decisions on the
+    source depths (reading, depth step) are float32 operations in either precision: they are part of the definition."""
+    _check_scalars(orig_size, near, gap)
+    d32 = depth_src.float()
+    B, Hs, Ws = d32.shape
+    dev = d32.device
+    reading = (d32 > 0) & (d32 <= FAR)
+    d = d32.to(dtype)
+    k, P, K = k_src.to(dtype), pose.to(dtype), K_tgt.to(dtype)
+    fx, fy, cx, cy = (k[:, e, None, None] for e in range(4))
+    u = (torch.arange(Ws, device=dev).to(dtype) + 0.5)[None, None, :]
+    v = (torch.arange(Hs, device=dev).to(dtype) + 0.5)[None, :, None]
+    xs, ys = (u - cx) / fx * d, (v - cy) / fy * d
+    cam = [(xs * P[:, i, 0, None, None] + ys * P[:, i, 1, None, None]) + d * P[:, i, 2, None, None] + P[:, i, 3, None, None] for i in range(3)]
+    os_ = float(orig_size)
+    xh, yh = cam[0] / (cam[2] + PROJ_EPS), cam[1] / (cam[2] + PROJ_EPS)
+    uu = (xh * K[:, 0, 0, None, None] + yh * K[:, 0, 1, None, None]) + K[:, 0, 2, None, None]
+    vv = os_ - ((xh * K[:, 1, 0, None, None] + yh * K[:, 1, 1, None, None]) + K[:, 1, 2, None, None])
+    vert = torch.stack((2.0 * (uu - os_ / 2.0) / os_, 2.0 * (vv - os_ / 2.0) / os_, cam[2]), -1)          # [B, Hs, Ws, 3]
+
+    def cell(t):
+        a, b, c, dd = t[:, :-1, :-1], t[:, 1:, :-1], t[:, :-1, 1:], t[:, 1:, 1:]
+        return torch.stack((torch.stack((a, b, c), 3), torch.stack((dd, c, b), 3)), 3)                     # [B, Hs-1, Ws-1, 2, 3, ...]
+    faces = cell(vert)
+    ok = cell(reading).all(-1)
+    dc = cell(torch.where(reading, d32, torch.ones_like(d32)))
+    dmin, dmax = dc.min(-1).values, dc.max(-1).values
+    step = (dmax - dmin) > torch.tensor(gap, dtype=torch.float32, device=dev) * dmin
+    behind = ~(faces[..., 2] >= near).all(-1)
+    frame_ok = ((k_src[:, 0] > 0) & (k_src[:, 1] > 0))[:, None, None, None]
+    cull = ~ok | step | behind | ~frame_ok
+    faces = torch.where(cull[..., None, None], torch.zeros_like(faces), faces)
+    return faces.reshape(B, n_faces(Hs, Ws), 3, 3).contiguous()
+
+
+def compose_torch(face_index, weight, raster_depth, labels_src):
+    """csrc/observed_reproject.hip's compose in torch ops: maps [B, S, S] in raster order and ``labels_src`` [B, Hs, Ws] uint8 ->
+    (depth [B, S, S] float32, labels [B, S, S] uint8) in the planes' row order, hits [B] int64"""
+    B, Hs, Ws = labels_src.shape
+    Wc, F = Ws - 1, n_faces(Hs, Ws)
+    dev = face_index.device
+    fi = face_index.long()
+    w = weight.float()
+    hit = (fi >= 0) & (fi < F) & ~torch.isnan(w).any(-1)
+    k = fi.clamp(0, F - 1)
+    cell, which = k // 2, k % 2
+    ci, cj = cell // Wc, cell % Wc
+    first = w[..., 1] > w[..., 0]
+    corner = first.long()
+    corner = torch.where(w[..., 2] > torch.where(first, w[..., 1], w[..., 0]), torch.full_like(corner, 2), corner)
+    di, dj = torch.tensor(_DI, device=dev)[which, corner], torch.tensor(_DJ, device=dev)[which, corner]
+    frame = torch.arange(B, device=dev)[:, None, None]
+    lab = labels_src[frame, ci + di, cj + dj]
+    labels = torch.where(hit, lab, torch.zeros((), dtype=torch.uint8, device=dev))
+    depth = torch.where(hit, raster_depth.float(), torch.full((), NO_READING, dtype=torch.float32, device=dev))
+    return torch.flip(depth, [1]).contiguous(), torch.flip(labels, [1]).contiguous(), hit.sum(dim=(1, 2))
+
+
+def reproject_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near=0.1, far=100.0, gap=0.05, dtype=torch.float64):
+    """The route of ``ObservedReprojector`` in torch ops on the tensors' device, in ``dtype``.  ``rasterize(faces float32 numpy
+    [B, F, 3, 3], image_size, near, far) -> (face_index, weight, depth)`` numpy maps in raster order is the caller's rasterizer (the
+    tests pass the C restatement the rasterizer kernels are held to).  -> dict(depth [B, S, S] float32, labels [B, S, S] uint8,
+    hits [B] int64, faces_xyz [B, F, 3, 3] in ``dtype``, face_index, weight)"""
+    if depth_src.dim() != 3 or labels_src.shape != depth_src.shape or labels_src.dtype != torch.uint8:
+        raise ValueError("depth_src [B, Hs, Ws] float and labels_src [B, Hs, Ws] uint8 expected")
+    B, Hs, Ws = depth_src.shape
+    _check_sizes(B, Hs, Ws, int(S))
+    dev = depth_src.device
+    fxyz = faces_torch(depth_src, k_src, pose, K_tgt, orig_size, near, gap, dtype)
+    fi, w, dep = rasterize(fxyz.float().cpu().numpy(), int(S), float(near), float(far))
+    fi, w, dep = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (fi, w, dep))
+    depth, labels, hits = compose_torch(fi, w, dep, labels_src)
+    return dict(depth=depth, labels=labels, hits=hits, faces_xyz=fxyz, face_index=fi, weight=w)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the device route
+# ------------------------------------------------------------------------------------------------------------------------------
+def _stream(out):
+    """the current stream of a device buffer; host tensors (the argument checks' tests: refused before any launch) have none"""
+    return L.current_stream_ptr() if out.is_cuda else None
+
+
+def faces(depth_src, k_src, pose, K_tgt, orig_size, near, gap, faces_xyz):
+    """the bare launch of ``sln_reproject_faces`` over the caller's buffers (contiguous float32 on the device)"""
+    d = L.SlnReproject()
+    d.depth_src, d.k_src, d.pose, d.K_tgt = depth_src.data_ptr(), k_src.data_ptr(), pose.data_ptr(), K_tgt.data_ptr()
+    d.B, d.Hs, d.Ws = (int(x) for x in depth_src.shape)
+    d.orig_size, d.near, d.gap = float(orig_size), float(near), float(gap)
+    L.check(L.lib().sln_reproject_faces(d, L.ptr(faces_xyz), _stream(faces_xyz)), "sln_reproject_faces")
+
+
+def compose(face_index, weight, raster_depth, labels_src, depth_out, labels_out, hits):
+    """the bare ``sln_reproject_compose`` call over the caller's buffers"""
+    B, Hs, Ws = (int(x) for x in labels_src.shape)
+    L.check(L.lib().sln_reproject_compose(L.ptr(face_index), L.ptr(weight), L.ptr(raster_depth), L.ptr(labels_src), B, Hs, Ws,
+                                          int(face_index.shape[1]), L.ptr(depth_out), L.ptr(labels_out), L.ptr(hits), _stream(depth_out)),
+            "sln_reproject_compose")
+
+
+class ObservedReprojector:
+    """Frames of ``batch`` rooms, each ``Hs`` x ``Ws``, brought into target views of ``S`` x ``S`` on the device.
+
+        rp = ObservedReprojector(480, 640, 256, batch=16)
+        depth, labels, hits = rp(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
+        rb = RefineBatch(model, rooms, observed=(depth, labels), image_size=256, ...)
+
+    ``depth_src`` [B, Hs, Ws] float32 (metric, along the optical axis; a reading when 0 < d <= 15), ``labels_src`` [B, Hs, Ws] uint8
+    (0 none, 1 + c NYU class c; any byte passes through), ``k_src`` [B, 4] float32 (fx, fy, cx, cy in source pixels; a frame whose
+    focal lengths are not positive yields nothing), ``pose`` [B, 3, 4] float32 (source camera -> target camera: ``relative_pose``),
+    ``K_tgt`` [B, 3, 3] float32 and ``orig_size`` (``refine_view``).  -> ``depth`` [B, S, S] float32 (-1 where no face was hit),
+    ``labels`` [B, S, S] uint8, ``hits`` [B] int64 (hit pixels per frame).  These are the instance's static buffers: the next call
+    overwrites them.  A call makes three steps of launches (faces, raster, compose) on the current stream, allocates nothing and reads
+    nothing back: legal under a graph capture.  Tensors of another dtype, device or shape are refused before anything is launched."""
+
+    def __init__(self, Hs, Ws, S, batch=1, near=0.1, far=100.0, gap=0.05, device="cuda"):
+        self.Hs, self.Ws, self.S, self.batch = int(Hs), int(Ws), int(S), int(batch)
+        self.near, self.far, self.gap = float(near), float(far), float(gap)
+        _check_sizes(self.batch, self.Hs, self.Ws, self.S)
+        _check_scalars(1.0, self.near, self.gap)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.SlnError("ObservedReprojector runs on the MI355X only (no CPU fallback); reproject_torch restates it for CPU tensors")
+        B, S, dev = self.batch, self.S, self.device
+        self.F = n_faces(self.Hs, self.Ws)
+        self.faces_xyz = torch.zeros(B, self.F, 3, 3, dtype=torch.float32, device=dev)
+        self.face_index = torch.empty(B, S, S, dtype=torch.int32, device=dev)
+        self.weight = torch.empty(B, S, S, 3, dtype=torch.float32, device=dev)
+        self.raster_depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+        self._raster_ws = torch.empty(int(L.lib().sln_raster_workspace_bytes(B, self.F)), dtype=torch.uint8, device=dev)
+        self.depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+        self.labels = torch.empty(B, S, S, dtype=torch.uint8, device=dev)
+        self.hits = torch.zeros(B, dtype=torch.int64, device=dev)
+
+    def check(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
+        B, dev = self.batch, self.depth.device
+        for t, dt, shape, what in ((depth_src, torch.float32, (B, self.Hs, self.Ws), "depth_src"), (labels_src, torch.uint8, (B, self.Hs, self.Ws), "labels_src"),
+                                   (k_src, torch.float32, (B, 4), "k_src"), (pose, torch.float32, (B, 3, 4), "pose"), (K_tgt, torch.float32, (B, 3, 3), "K_tgt")):
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != dev:
+                raise ValueError("%s: a %s tensor on %s expected" % (what, str(dt).replace("torch.", ""), dev))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s: shape %s is not a contiguous %s" % (what, tuple(t.shape), list(shape)))
+        _check_scalars(float(orig_size), self.near, self.gap)
+
+    def __call__(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
+        self.check(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
+        faces(depth_src, k_src, pose, K_tgt, orig_size, self.near, self.gap, self.faces_xyz)
+        L.check(L.lib().sln_raster_forward(L.ptr(self.faces_xyz), self.batch, self.F, self.S, self.near, self.far, L.ptr(self._raster_ws),
+                                           L.ptr(self.face_index), L.ptr(self.weight), L.ptr(self.raster_depth), L.current_stream_ptr()),
+                "sln_raster_forward")
+        compose(self.face_index, self.weight, self.raster_depth, labels_src, self.depth, self.labels, self.hits)
+        return self.depth, self.labels, self.hits

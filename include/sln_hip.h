@@ -1069,6 +1069,43 @@ int sln_observed_target(const float* depth, const unsigned char* labels, int B, 
                         int nch, void* workspace, float* out, int32_t* status, void* stream);
 
 /* =============================================================================================
+ * An observed frame of any pinhole camera, brought into the refinement view (csrc/observed_reproject.hip; host/reproject.py): the
+ * step in front of sln_observed_target.  The frame is a triangle mesh over its pixel grid; rasterisation in between is
+ * sln_raster_forward.  DESIGN §4 "Observed frames from any camera" is the definition.
+ * ============================================================================================= */
+/* B frames of Hs x Ws pixels, all device pointers.  Pixel (i, j) - row i from the top - with depth d has a READING when 0 < d <= 15
+ * (a NaN, an infinity and anything outside have none) and is the point ((j + 0.5 - cx) / fx * d, (i + 0.5 - cy) / fy * d, d) of the
+ * source camera (x right, y down, z forward); pose takes it to the frame sln_project_faces projects from (R p + t of the target view),
+ * and K_tgt, orig_size project it with that function's expressions (eps 1e-9). */
+typedef struct SlnReproject {
+  const float* depth_src;         /* [B, Hs, Ws] metric depth along the optical axis */
+  const float* k_src;             /* [B, 4] fx, fy, cx, cy in source pixels; read on the device only */
+  const float* pose;              /* [B, 3, 4] source camera -> target camera, [R | t] row-major */
+  const float* K_tgt;             /* [B, 3, 3] */
+  int32_t B, Hs, Ws, reserved;
+  float orig_size, near, gap, reserved_f;
+} SlnReproject;
+/* faces_xyz [B, F, 3, 3] = (x_ndc, y_ndc, z_cam) per corner, F = 2 (Hs - 1) (Ws - 1): the cell of the pixels a = (i, j), b = (i + 1, j),
+ * c = (i, j + 1), d = (i + 1, j + 1) owns the slots 2 (i (Ws - 1) + j) + {0, 1} = (a, b, c), (d, c, b) - front-facing for
+ * sln_raster_forward when source and target see the surface from the same side.  A slot collapses to the point (0, 0, 0) - it covers
+ * no pixel - when one of its three pixels has no reading, when dmax - dmin > gap * dmin over its three depths (one float32 difference
+ * against one float32 product: a depth step, not a surface), when a projected corner has !(z >= near), or when its frame has
+ * !(fx > 0 && fy > 0).  One launch, no atomics, no allocation: legal inside a stream capture.  SLN_E_BADARG, nothing launched: a null
+ * pointer, B < 1 or > 65535, Hs < 2, Ws < 2, F > 2^24, orig_size <= 0, !(gap >= 0), !(near > 0), faces_xyz not 8-byte aligned. */
+int sln_reproject_faces(const SlnReproject* d, float* faces_xyz, void* stream);
+/* From the rasterizer's maps (raster order: row 0 = bottom) of the B frames' faces: depth_out [B, S, S] float32 and labels_out
+ * [B, S, S] uint8 in the row order of the scene tensor's planes (row 0 = top), hits [B] int64.  A pixel is HIT when its face_index
+ * lies in [0, F) and none of its three weights is a NaN: depth_out takes raster_depth's bits and labels_out the byte of labels_src
+ * [B, Hs, Ws] at the face's corner of largest weight (ties: the lower corner number in the emitted order) - nearest neighbour in the
+ * source image, any byte passes through.  Elsewhere depth_out = -1 (the renderer's background) and labels_out = 0.  hits counts the hit
+ * pixels per frame with integer additions only: the same from call to call.  Two launches (hits is cleared first), no allocation,
+ * nothing read back: legal inside a stream capture.  Every index read from a map is compared with its range before it addresses
+ * anything.  SLN_E_BADARG, nothing launched: a null pointer, B < 1 or > 65535, Hs < 2, Ws < 2, F > 2^24, S < 1 or > 4096, hits not
+ * 8-byte aligned. */
+int sln_reproject_compose(const int32_t* face_index, const float* weight, const float* raster_depth, const unsigned char* labels_src, int B,
+                          int Hs, int Ws, int S, float* depth_out, unsigned char* labels_out, int64_t* hits, void* stream);
+
+/* =============================================================================================
  * The --draw_3d picture (render/render_room_color.py::render_test): a lit colour picture with hard shadows of the view the viewpoint
  * render accepted (csrc/draw3d.hip; host/draw3d.py).  The shading model is this project's, stated in DESIGN §4 "3-D drawing".
  * ============================================================================================= */
