@@ -230,6 +230,7 @@ SIGNATURES = {
     "sln_set_deterministic": (C.c_int, [C.c_int]),
     "sln_get_deterministic": (C.c_int, []),
     "sln_debug_tn_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "sln_debug_tn_plan_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "sln_prof_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "sln_vae_tap": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, c_f32p, C.c_void_p]),
     "sln_gconv_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -244,6 +245,7 @@ SIGNATURES = {
     "sln_linear_wgrad": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_void_p]),
     "sln_debug_gemm_nt": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "sln_debug_gemm_tn": (C.c_int, [C.POINTER(SlnDbgGemmTN), C.c_int, C.c_int, C.c_void_p]),
+    "sln_debug_gemm_tn_mixed": (C.c_int, [C.POINTER(SlnDbgGemmTN), C.c_int, C.c_void_p]),
     "sln_debug_gemm_nt_route": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.POINTER(SlnDbgNTRoute)]),
     "sln_debug_gemm_nt_half": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.c_int, C.c_void_p]),
     "sln_debug_gemm_nt_half_takes": (C.c_int, [C.POINTER(SlnDbgGemmNT)]),
@@ -257,6 +259,7 @@ SIGNATURES = {
     "sln_debug_vae_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "sln_debug_vae_leaf_launches": (C.c_int64, [C.c_void_p]),
     "sln_debug_vae_half_launches": (C.c_int64, [C.c_void_p]),
+    "sln_debug_vae_tail_launches": (C.c_int64, [C.c_void_p]),
     "sln_project_faces": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p]),
     "sln_project_faces_backward": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p,
                                              c_f32p, C.c_void_p]),

@@ -1549,6 +1549,15 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTNArgs& a, const int bx, 
 }
 
 
+// One item of the mixed wgrad table (sln_gemm.h: TnMixedMeta) - the body its problem needs, by the item's gather bit (uniform over
+// the workgroup).  Shared by gemm_tn_mixed_kernel (gemm_f32.hip) and the wgrad half of vae_tail_kernel (vae_kernels.hip).
+template <bool G_X2>
+__device__ __forceinline__ void gemm_tn_mixed_item(const GemmTNArgs* __restrict__ probs, const TnMultiItem it, char* smem) {
+  if (it.prob < 0) return;
+  if (it.xg) gemm_tn_body<64, 64, 2, 2, G_X2, true>(probs[it.prob], it.tile, it.chunk, smem);
+  else gemm_tn_body<64, 64, 2, 2, G_X2, false>(probs[it.prob], it.tile, it.chunk, smem);
+}
+
 inline bool tn_gathers(const GemmTNArgs& a) {
   bool g = false;
   for (int s = 0; s < a.X.nseg; ++s) g |= a.X.seg[s].which != 0;

@@ -184,6 +184,14 @@ __global__ __launch_bounds__(256) void gemm_tn_multi_kernel(const GemmTNArgs* __
   gemm_tn_body<64, 64, 2, 2, G_X2, XG>(probs[it.prob], it.tile, it.chunk, smem);
 }
 
+// ... and of a whole iteration, gathered X rows or not, in one grid (sln_gemm.h: TnMixedMeta): the item says which of the two
+// bodies its problem needs.  The branch is uniform over the workgroup; the kernel's registers are the larger body's.
+template <bool G_X2>
+__global__ __launch_bounds__(256) void gemm_tn_mixed_kernel(const GemmTNArgs* __restrict__ probs, const TnMixedMeta* __restrict__ meta) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemm_tn_mixed_item<G_X2>(probs, meta->item[blockIdx.x], smem);
+}
+
 template <int BM, int BN, int WM, int WN, bool G_X2>
 int launch_tn(const GemmTNArgs& a, hipStream_t st) {
   const size_t smem = tn_smem_bytes(BM, BN);
@@ -221,6 +229,7 @@ static int init_nt_tile() {
 }
 
 int sln_gemm_group_init();
+int sln_vae_tail_init();      // vae_kernels.hip: the tail launch runs the wgrad body
 int sln_gemm_init() {
   static bool done = false;
   if (done) return 0;
@@ -254,7 +263,10 @@ int sln_gemm_init() {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   SLN_SET_TNM(true, true) SLN_SET_TNM(true, false) SLN_SET_TNM(false, true) SLN_SET_TNM(false, false)
 #undef SLN_SET_TNM
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (!r) r = sln_gemm_group_init();
+  if (!r) r = sln_vae_tail_init();
   done = r == 0;
   return r;
 }
@@ -354,8 +366,12 @@ int sln_launch_gemm_tn(const GemmTNArgs& a0, hipStream_t st) {
   return launch_tn<64, 64, 2, 2, false>(a, st);
 }
 
-int sln_tn_multi_plan(GemmTNArgs* probs, int n, TnMultiMeta* meta, int* blocks, bool* x2, bool* xg, double* flops) {
-  if (n < 1 || n > SLN_TN_MULTI_MAX) return -1;
+// The planner of both table launches.  mixed: the one launch of a whole iteration (items carry their problem's gather bit, plain
+// problems keep their null index arrays, and a list that does not fit max_items at the target chunk length is refused instead of
+// given longer chunks - see sln_gemm.h).
+static int tn_plan(GemmTNArgs* probs, int n, int max_probs, int max_items, bool mixed, int* nprob, int* nblocks, TnMultiItem* item,
+                   int* blocks, bool* x2, bool* xg, double* flops) {
+  if (n < 1 || n > max_probs) return -1;
   // rows per block: long chunks (tools/gemm_bench.py: a 256-row block spends as long in its prologue, its first-tile latency and
   // its 64 x 64 atomics as in its 8 tiles - 46 TF at R = 4096 against 79 TF with 1.6 k-row chunks)
   static const int target0 = std::getenv("SLN_TN_MULTI_ROWS") ? std::atoi(std::getenv("SLN_TN_MULTI_ROWS")) : 768;
@@ -401,29 +417,39 @@ int sln_tn_multi_plan(GemmTNArgs* probs, int n, TnMultiMeta* meta, int* blocks, 
     }
     int mx = 0;
     for (int x = 0; x < 8; ++x) mx = per_xcd[x] > mx ? per_xcd[x] : mx;
-    if (8 * mx <= SLN_TN_MULTI_ITEMS) break;
-    if (target > (1L << 30)) return -1;
+    if (8 * mx <= max_items) break;
+    if (mixed || target > (1L << 30)) return -1;
   }
-  if (any_xg) {        // the index pipeline of the gathering body loads indices unconditionally: every X needs a valid array
+  if (any_xg && !mixed) {        // the index pipeline of the gathering body loads indices unconditionally: every X needs a valid array
     const int* any = nullptr;
     for (int i = 0; i < n; ++i) { if (probs[i].X.idx_a) any = probs[i].X.idx_a; else if (probs[i].X.idx_b) any = probs[i].X.idx_b; }
     for (int i = 0; i < n; ++i) if (!probs[i].X.idx_a && !probs[i].X.idx_b) probs[i].X.idx_a = any;
   }
   int mx = 0;
   for (int x = 0; x < 8; ++x) mx = per_xcd[x] > mx ? per_xcd[x] : mx;
-  std::memset(meta, 0, sizeof(*meta));
-  meta->nprob = n; meta->nblocks = 8 * mx;
-  for (int b = 0; b < 8 * mx; ++b) meta->item[b].prob = -1;
+  *nprob = n; *nblocks = 8 * mx;
+  std::memset(item, 0, sizeof(TnMultiItem) * (size_t)(mixed ? 8 * mx : max_items));      // (the mixed table is used by its prefix only)
+  for (int b = 0; b < 8 * mx; ++b) item[b].prob = -1;
   int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (size_t g = 0; g < groups.size(); ++g) {          // cost order: an XCD starts with its longest groups
     const int x = owner[g];
+    const int gathers = mixed && tn_gathers(probs[groups[g].prob]) ? 1 : 0;
     for (int t = 0; t < groups[g].tiles; ++t) {
-      TnMultiItem& it = meta->item[8 * (fill[x]++) + x];  // the j-th workgroup of XCD x is workgroup 8 j + x of the grid
-      it.prob = groups[g].prob; it.tile = t; it.chunk = groups[g].chunk;
+      TnMultiItem& it = item[8 * (fill[x]++) + x];        // the j-th workgroup of XCD x is workgroup 8 j + x of the grid
+      it.prob = groups[g].prob; it.tile = t; it.chunk = groups[g].chunk; it.xg = gathers;
     }
   }
   *blocks = 8 * mx; *x2 = any_x2; *xg = any_xg; *flops = work;
   return 0;
+}
+
+int sln_tn_multi_plan(GemmTNArgs* probs, int n, TnMultiMeta* meta, int* blocks, bool* x2, bool* xg, double* flops) {
+  return tn_plan(probs, n, SLN_TN_MULTI_MAX, SLN_TN_MULTI_ITEMS, false, &meta->nprob, &meta->nblocks, meta->item, blocks, x2, xg, flops);
+}
+
+int sln_tn_mixed_plan(GemmTNArgs* probs, int n, TnMixedMeta* meta, int* blocks, bool* x2, double* flops) {
+  bool xg = false;
+  return tn_plan(probs, n, SLN_TN_MIXED_MAX, SLN_TN_MIXED_ITEMS, true, &meta->nprob, &meta->nblocks, meta->item, blocks, x2, &xg, flops);
 }
 
 int sln_launch_gemm_tn_multi(const GemmTNArgs* dev_probs, const TnMultiMeta* dev_meta, int blocks, bool x2, bool xg, double flops,
@@ -436,6 +462,17 @@ int sln_launch_gemm_tn_multi(const GemmTNArgs* dev_probs, const TnMultiMeta* dev
   else if (x2) hipLaunchKernelGGL((gemm_tn_multi_kernel<true, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   else if (xg) hipLaunchKernelGGL((gemm_tn_multi_kernel<false, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   else hipLaunchKernelGGL((gemm_tn_multi_kernel<false, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_launch_gemm_tn_mixed(const GemmTNArgs* dev_probs, const TnMixedMeta* dev_meta, int blocks, bool x2, double flops, hipStream_t st) {
+  if (blocks <= 0) return 0;
+  SlnProfScope prof(SLN_FAM_GEMM_TN, flops, st);
+  const size_t smem = tn_smem_bytes(64, 64);
+  if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
+  if (x2) hipLaunchKernelGGL((gemm_tn_mixed_kernel<true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+  else hipLaunchKernelGGL((gemm_tn_mixed_kernel<false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -463,6 +500,30 @@ extern "C" int sln_debug_tn_plan(const int* R, const int* Nout, const int* Kin, 
   return blocks;
 }
 
+// ... and of the mixed launch's plan: gathers[i] != 0 marks a problem whose X rows are gathered; items[4 * workgroup] = (problem or
+// -1, output tile, row chunk, gather bit).  -1 also when the list does not fit the table at the target chunk length.
+extern "C" int sln_debug_tn_plan_mixed(const int* R, const int* Nout, const int* Kin, const int* gathers, int n, int* rows_per_block,
+                                       int* items, int max_items) {
+  if (!R || !Nout || !Kin || !gathers || !rows_per_block || !items || n < 1 || n > SLN_TN_MIXED_MAX) return -1;
+  std::vector<GemmTNArgs> probs((size_t)n);
+  std::vector<TnMixedMeta> meta(1);
+  std::memset(probs.data(), 0, sizeof(GemmTNArgs) * (size_t)n);
+  for (int i = 0; i < n; ++i) {
+    probs[i].R = R[i]; probs[i].Nout = Nout[i]; probs[i].Kin = Kin[i];
+    probs[i].G.nseg = 1; probs[i].X.nseg = 1; probs[i].X.seg[0].which = gathers[i] ? 1 : 0; probs[i].lddw = i;
+  }
+  int blocks = 0; bool x2 = false; double flops = 0.0;
+  const int r = sln_tn_mixed_plan(probs.data(), n, meta.data(), &blocks, &x2, &flops);
+  if (r) return r;
+  if (blocks > max_items) return -2;
+  for (int i = 0; i < n; ++i) rows_per_block[probs[i].lddw] = probs[i].rows_per_block;
+  for (int b = 0; b < blocks; ++b) {
+    const TnMultiItem& it = meta[0].item[b];
+    items[4 * b] = it.prob < 0 ? -1 : probs[it.prob].lddw; items[4 * b + 1] = it.tile; items[4 * b + 2] = it.chunk; items[4 * b + 3] = it.xg;
+  }
+  return blocks;
+}
+
 // ---- test hooks: an arbitrary operand through the dispatchers above (include/sln_hip.h) ----------------------------------------
 #include "sln_debug.h"
 
@@ -481,20 +542,24 @@ bool sln_dbg_bn(const SlnDbgBn& d, int coef, BnView& v) {
 
 namespace {
 
-// gather_ok: whether segments may be row-gathered; x2_ok: whether a second source is read at all
-bool dbg_operand(const SlnDbgOperand& d, int rows, int cols, bool gather_ok, bool x2_ok, Operand& op) {
+// gather_ok: whether segments may be row-gathered; x2_ok: whether a second source is read at all; ragged_ok (wgrad operands): the
+// last segment may end inside a group of four columns when its rows are stored up to the group's end - the body loads whole
+// float4s and the coefficients of columns behind the width are zero (box_net.1's six output columns in rows of eight)
+bool dbg_operand(const SlnDbgOperand& d, int rows, int cols, bool gather_ok, bool x2_ok, Operand& op, bool ragged_ok = false) {
   std::memset(&op, 0, sizeof(op));
   if (d.nseg < 1 || d.nseg > 3 || rows <= 0) return false;
   int tot = 0;
   for (int s = 0; s < d.nseg; ++s) {
     const SlnDbgSeg& g = d.seg[s];
     Seg& o = op.seg[s];
-    if (!g.x1 || g.len <= 0 || (g.len & 3)) return false;      // (a boundary inside a k-tile: the MULTI = 2 form, nt_route)
-    if ((g.ld1 & 3) || (g.c1 & 3) || g.c1 < 0 || g.ld1 < g.c1 + g.len) return false;
+    const bool ragged = ragged_ok && s == d.nseg - 1 && (g.len & 3);
+    const int len4 = (g.len + 3) & ~3;
+    if (!g.x1 || g.len <= 0 || ((g.len & 3) && !ragged)) return false;      // (a boundary inside a k-tile: the MULTI = 2 form, nt_route)
+    if ((g.ld1 & 3) || (g.c1 & 3) || g.c1 < 0 || g.ld1 < g.c1 + len4) return false;
     if (g.coef < SLN_COEF_IDENT || g.coef > SLN_COEF_BWD || g.which < 0 || g.which > 2) return false;
     if (g.which && (!gather_ok || !(g.which == 1 ? d.idx_a : d.idx_b))) return false;
     if (g.x2) {
-      if (!x2_ok || g.coef != SLN_COEF_BWD || (g.ld2 & 3) || (g.c2 & 3) || g.c2 < 0 || g.ld2 < g.c2 + g.len) return false;
+      if (!x2_ok || g.coef != SLN_COEF_BWD || (g.ld2 & 3) || (g.c2 & 3) || g.c2 < 0 || g.ld2 < g.c2 + len4) return false;
     } else if (g.coef == SLN_COEF_BWD && g.bn.mode == SLN_BN_TRAIN) return false;      // p1 multiplies the pre-activation
     if (g.coef == SLN_COEF_BWD && !x2_ok) return false;
     o.x1 = g.x1; o.x2 = g.x2; o.ld1 = g.ld1; o.ld2 = g.ld2; o.c1 = g.c1; o.c2 = g.c2; o.len = g.len; o.which = g.which; o.coef = g.coef;
@@ -522,11 +587,11 @@ bool dbg_nt(const SlnDbgGemmNT& d, GemmNTArgs& a) {
   return true;
 }
 
-bool dbg_tn(const SlnDbgGemmTN& d, GemmTNArgs& a) {
+bool dbg_tn(const SlnDbgGemmTN& d, GemmTNArgs& a, bool ragged_ok = false) {
   std::memset(&a, 0, sizeof(a));
   if (d.R <= 0 || d.Nout <= 0 || d.Kin <= 0 || !d.dW || d.lddw < d.Kin) return false;
-  if (!dbg_operand(d.G, d.R, d.Nout, false, true, a.G)) return false;       // the gradient operand is addressed by plain rows
-  if (!dbg_operand(d.X, d.R, d.Kin, true, false, a.X)) return false;        // the input operand has one source
+  if (!dbg_operand(d.G, d.R, d.Nout, false, true, a.G, ragged_ok)) return false;       // the gradient operand is addressed by plain rows
+  if (!dbg_operand(d.X, d.R, d.Kin, true, false, a.X, ragged_ok)) return false;        // the input operand has one source
   a.dW = d.dW; a.db = d.db; a.lddw = d.lddw; a.R = d.R; a.Nout = d.Nout; a.Kin = d.Kin;
   a.rows_per_block = d.rows_per_block; a.sgd_step = d.sgd_step;
   return true;
@@ -594,6 +659,30 @@ extern "C" int sln_debug_gemm_tn(const SlnDbgGemmTN* desc, int n, int multi, voi
   if (!r) r = (int)hipMemcpy(dprobs, probs.data(), pbytes, hipMemcpyHostToDevice);
   if (!r) r = (int)hipMemcpy(dmeta, meta.data(), sizeof(TnMultiMeta), hipMemcpyHostToDevice);
   if (!r) r = sln_launch_gemm_tn_multi(dprobs, dmeta, blocks, x2, xg, flops, st);
+  const int rs = (int)hipStreamSynchronize(st);         // the table must outlive the launch
+  if (!r) r = rs;
+  if (dprobs) (void)hipFree(dprobs);
+  if (dmeta) (void)hipFree(dmeta);
+  return r;
+}
+
+// the mixed launch (gathered and plain problems in ONE grid) on caller-built problems, 1 <= n <= SLN_TN_MIXED_MAX; tables as above
+extern "C" int sln_debug_gemm_tn_mixed(const SlnDbgGemmTN* desc, int n, void* stream) {
+  if (!desc || n < 1 || n > SLN_TN_MIXED_MAX) return SLN_E_BADARG;
+  std::vector<GemmTNArgs> probs((size_t)n);
+  for (int i = 0; i < n; ++i) if (!dbg_tn(desc[i], probs[(size_t)i], true)) return SLN_E_BADARG;      // (widths as the engine's: any)
+  hipStream_t st = (hipStream_t)stream;
+  if (sln_capturing(st)) return SLN_E_CAPTURE;
+  std::vector<TnMixedMeta> meta(1);
+  int blocks = 0; bool x2 = false; double flops = 0.0;
+  if (sln_tn_mixed_plan(probs.data(), n, meta.data(), &blocks, &x2, &flops)) return SLN_E_BADARG;
+  GemmTNArgs* dprobs = nullptr; TnMixedMeta* dmeta = nullptr;
+  const size_t pbytes = sizeof(GemmTNArgs) * (size_t)n, mbytes = offsetof(TnMixedMeta, item) + sizeof(TnMultiItem) * (size_t)blocks;
+  int r = (int)hipMalloc((void**)&dprobs, pbytes);
+  if (!r) r = (int)hipMalloc((void**)&dmeta, sizeof(TnMixedMeta));
+  if (!r) r = (int)hipMemcpy(dprobs, probs.data(), pbytes, hipMemcpyHostToDevice);
+  if (!r) r = (int)hipMemcpy(dmeta, meta.data(), mbytes, hipMemcpyHostToDevice);
+  if (!r) r = sln_launch_gemm_tn_mixed(dprobs, dmeta, blocks, x2, flops, st);
   const int rs = (int)hipStreamSynchronize(st);         // the table must outlive the launch
   if (!r) r = rs;
   if (dprobs) (void)hipFree(dprobs);

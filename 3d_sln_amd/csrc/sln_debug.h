@@ -7,5 +7,7 @@
 bool sln_dbg_bn(const SlnDbgBn& d, int coef, BnView& v);
 // leaf launches an engine issued so far (vae_engine.hip; read by sln_debug_vae_leaf_launches)
 long sln_vae_engine_leaf_launches(const SlnVae* h);
+// iterations whose wgrads ran as one mixed launch (vae_engine.hip; read by sln_debug_vae_tail_launches)
+long sln_vae_engine_tail_launches(const SlnVae* h);
 // fp16-MFMA Linear launches an engine issued so far (vae_engine.hip; read by sln_debug_vae_half_launches)
 long sln_vae_engine_half_launches(const SlnVae* h);

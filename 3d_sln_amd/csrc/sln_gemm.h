@@ -60,12 +60,24 @@ enum { SLN_TN_MULTI_MAX = 64, SLN_TN_MULTI_ITEMS = 4096 };
 // which then come out of THAT XCD's L2 once instead of from the fabric once per XCD (profiles/r03: 645 MB fetched per launch for
 // 100 MB of operands before) - and the (problem, chunk) groups are dealt to the eight XCDs longest first, so that every XCD gets
 // the same amount of work.  XCDs with fewer items are padded with empty entries (prob < 0).
-struct TnMultiItem { int prob, tile, chunk, pad_; };
+// xg: the mixed launch only (below) - this item's problem gathers its X rows and runs the gathering body.
+struct TnMultiItem { int prob, tile, chunk, xg; };
 struct TnMultiMeta { int nprob, nblocks; TnMultiItem item[SLN_TN_MULTI_ITEMS]; };
+// The whole iteration's wgrads - gathered X rows or not - as ONE launch: every workgroup picks its body by its item's `xg` bit
+// (block-uniform), so a plain problem never pays the gathering body's index loads.  Same chunking, same XCD dealing and the same
+// atomics as the two per-kind launches it replaces; the table is longer (a 64-graph step: 52 problems, 4 880 items) and has its
+// own limits, the per-kind launches keep theirs.  A problem list that does not fit at the planner's target chunk length is
+// refused (the caller then runs the per-kind launches, whose planner lengthens chunks): the row chunks of a problem - and with
+// them its per-element sums - are the same on both routes.
+enum { SLN_TN_MIXED_MAX = 128, SLN_TN_MIXED_ITEMS = 16384 };
+struct TnMixedMeta { int nprob, nblocks; TnMultiItem item[SLN_TN_MIXED_ITEMS]; };
 // host side: fills rows_per_block of every problem (long chunks: the per-block prologue / 64x64 atomics are paid once per
 // ~1 k rows instead of once per 256; longer still when the launch would not fit the table) and builds the item table.
 // Returns 0, or a negative value when a problem cannot run on the TN body.
 int sln_tn_multi_plan(GemmTNArgs* probs, int n, TnMultiMeta* meta, int* blocks, bool* x2, bool* xg, double* flops);
 int sln_launch_gemm_tn_multi(const GemmTNArgs* dev_probs, const TnMultiMeta* dev_meta, int blocks, bool x2, bool xg, double flops,
                              hipStream_t st);
+// the mixed launch: plan (0, or negative: a problem the TN body cannot run, or a list past SLN_TN_MIXED_MAX / _ITEMS) and launch
+int sln_tn_mixed_plan(GemmTNArgs* probs, int n, TnMixedMeta* meta, int* blocks, bool* x2, double* flops);
+int sln_launch_gemm_tn_mixed(const GemmTNArgs* dev_probs, const TnMixedMeta* dev_meta, int blocks, bool x2, double flops, hipStream_t st);
 int sln_gemm_init();   // raises dynamic-LDS limits; call once outside any stream capture

@@ -2,9 +2,9 @@
 // models/Sg2ScVAE_model.py:115-188, models/graph.py:57-143, utils.py:12-33, train.py:62-84) and
 // exposes it through the C ABI of include/sln_hip.h.  One engine per process/GPU; every call
 // enqueues kernels on the caller's stream.  A whole training iteration (zero_grad, forward, loss,
-// backward, Adam) is 136 launches at train.py's defaults (one per forward Linear / dgrad, 30 edge
-// launches, two wgrad launches - every wgrad of the iteration runs in one multi-problem grid per kind, see
-// flush_deferred -, half a dozen bookkeeping launches), captured once into a hipGraph and replayed.
+// backward, Adam) is 133 launches at train.py's defaults (one per forward Linear / dgrad, 30 edge
+// launches, one tail launch - every wgrad of the iteration in one multi-problem grid with the iteration's leaf jobs behind
+// them, see flush_deferred -, a handful of bookkeeping launches), captured once into a hipGraph and replayed.
 #include <cstddef>
 #include <new>
 #include <type_traits>
@@ -114,6 +114,7 @@ struct SlnVae {
   // backward temporaries
   float *dbp = nullptr, *dlogits = nullptr, *g_bn = nullptr, *g_an = nullptr, *d_bx = nullptr, *d_ax = nullptr;
   float *dM = nullptr, *dG[3] = {nullptr, nullptr, nullptr};   // [2]: the decoder's layer 0 when its predicate-table job waits for the leaf launch
+  float* dX0_dc = nullptr;        // the decoder's dX0 where its assembly backward is a leaf job (carve)
   float *dX0 = nullptr, *dz = nullptr, *dmu = nullptr, *dlv = nullptr;
   float *g_h2 = nullptr, *g_h1 = nullptr, *d_xb = nullptr, *d_xa = nullptr, *tmp_d = nullptr;
   float *g_h2b = nullptr, *g_h1b = nullptr, *tmp_db = nullptr;     // the angle branch's copies (both branches run grouped)
@@ -129,7 +130,8 @@ struct SlnVae {
   unsigned long long host_seed[2] = {0, 0};
 
   // Deferral: a wgrad has no consumer before the optimizer, so nothing forces it to run next to the dgrad of the same
-  // Linear.  The problems of a backward pass are recorded and run as ONE launch per pass (two when some gather their X rows)
+  // Linear.  The problems of a backward pass are recorded and run as ONE launch per pass (two when some gather their X rows; a full
+  // iteration: one for all of them, see flush_mixed)
   // through sln_launch_gemm_tn_multi: chunks of ~1 k rows instead of 256 (the prologue, the first-tile latency and the 64 x 64
   // atomics of a block are paid a quarter as often), no launch boundary per wgrad, and the dgrad chain - alone in its
   // launches - gets the chip to itself.
@@ -172,7 +174,10 @@ struct SlnVae {
   int stage_upload(void* dev0, const void* src0, size_t n0, void* dev1, const void* src1, size_t n1, hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return SLN_E_CAPTURE;   // a caller's capture would record a copy out of a ring slot
-    const size_t cap0 = sizeof(GemmTNArgs) * (size_t)SLN_TN_MULTI_MAX, cap = cap0 + sizeof(TnMultiMeta);
+    // (a slot holds the largest table this engine can upload: the mixed form only where the engine can take the mixed launch -
+    //  fixed at creation, so every slot of an engine has one capacity)
+    const size_t cap0 = sizeof(GemmTNArgs) * (size_t)(tn_mixed_store ? SLN_TN_MIXED_MAX : SLN_TN_MULTI_MAX);
+    const size_t cap = cap0 + (tn_mixed_store ? sizeof(TnMixedMeta) : sizeof(TnMultiMeta));
     if (n0 > cap0 || n1 > cap - cap0) return SLN_E_BADARG;
     TnStage& sl = tn_stage[tn_stage_next];
     tn_stage_next = (tn_stage_next + 1) % TN_STAGE_SLOTS;
@@ -202,12 +207,78 @@ struct SlnVae {
         TnGroup& g = tn_group(0, w, k);
         if (g.n > 0 && g.dirty) { int r = upload_group(g); if (r) return r; }
       }
+    if (tn_mixed_store && tn_mixed_store[0].n > 0 && tn_mixed_store[0].dirty) { int r = upload_mixed(tn_mixed_store[0]); if (r) return r; }
     tn_upload_pending = false;
     return 0;
   }
+  // Round 10: a full iteration's ONE flush runs gathered and plain problems as one launch (sln_launch_gemm_tn_mixed) out of a table
+  // region of its own - [0] the captured iterations', [1] eager calls', [2] the planner's scratch; carved and allocated only in
+  // engines that can take it (tail_merge).  Same upload rules as the per-kind tables above.
+  struct TnMixedGroup {
+    GemmTNArgs probs[SLN_TN_MIXED_MAX]; TnMixedMeta meta; int n = 0, blocks = 0; bool x2 = false; double flops = 0.0;
+    bool dirty = true; GemmTNArgs* dev_probs = nullptr; TnMixedMeta* dev_meta = nullptr;
+  };
+  TnMixedGroup* tn_mixed_store = nullptr;
+  bool tail_merge = true;         // SLN_TN_MIXED=0 at creation: one wgrad launch per kind, as before round 10
+  bool it_tail = false;           // this iteration's one flush takes the mixed launch
+  bool tail_dec = true;           // SLN_TN_MIXED=2 at creation: ... and the decoder's assembly backward stays in the chain (lab)
+  bool it_dec_leaf = false;       // this iteration runs the decoder's assembly backward as a leaf job
+  bool tail_leaf = true;          // SLN_TN_MIXED=1 at creation: the leaf jobs keep their own launch in front of it (lab: part by part)
+  long tail_launches = 0;         // mixed launches issued by this engine (sln_debug_vae_tail_launches)
+  static size_t mixed_meta_bytes(const TnMixedMeta& m) { return offsetof(TnMixedMeta, item) + sizeof(TnMultiItem) * (size_t)m.nblocks; }
+  int upload_mixed(TnMixedGroup& g) {
+    hipError_t e = hipMemcpy(g.dev_probs, g.probs, sizeof(GemmTNArgs) * (size_t)g.n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(g.dev_meta, &g.meta, mixed_meta_bytes(g.meta), hipMemcpyHostToDevice);
+    g.dirty = e != hipSuccess;
+    return (int)e;
+  }
+  // 0: launched; TN_MIXED_NO_FIT: the list does not fit the mixed table (or holds a problem the planner refuses) - the caller runs
+  // one launch per kind; anything else: an error
+  enum { TN_MIXED_NO_FIT = 1 << 20 };
+  // leaf (may be null): the iteration's leaf jobs, which then ride as trailing workgroups of the same launch
+  int flush_mixed(int set, const VaeLeaf* leaf, hipStream_t st) {
+    if (!tn_mixed_store || !tn_mixed_store[set].dev_probs) return TN_MIXED_NO_FIT;
+    TnMixedGroup& tmp = tn_mixed_store[2];
+    int n = 0;
+    for (const GemmTNArgs& t : deferred) {
+      if (t.R <= 0) continue;                 // a batch without triples: a product over no rows adds nothing
+      if (n == SLN_TN_MIXED_MAX) return TN_MIXED_NO_FIT;
+      tmp.probs[n++] = t;
+    }
+    if (n == 0) return leaf ? TN_MIXED_NO_FIT : 0;
+    tmp.n = n;
+    if (sln_tn_mixed_plan(tmp.probs, n, &tmp.meta, &tmp.blocks, &tmp.x2, &tmp.flops) != 0) return TN_MIXED_NO_FIT;
+    TnMixedGroup& g = tn_mixed_store[set];
+    if (g.n != n || g.meta.nblocks != tmp.meta.nblocks || std::memcmp(g.probs, tmp.probs, sizeof(GemmTNArgs) * (size_t)n) != 0 ||
+        std::memcmp(&g.meta, &tmp.meta, mixed_meta_bytes(tmp.meta)) != 0) {
+      std::memcpy(g.probs, tmp.probs, sizeof(GemmTNArgs) * (size_t)n);
+      std::memcpy(&g.meta, &tmp.meta, mixed_meta_bytes(tmp.meta));
+      g.n = n; g.blocks = tmp.blocks; g.x2 = tmp.x2; g.flops = tmp.flops; g.dirty = true;
+    }
+    if (g.dirty) {
+      if (capturing) tn_upload_pending = true;
+      else {
+        const int r = stage_upload(g.dev_probs, g.probs, sizeof(GemmTNArgs) * (size_t)g.n, g.dev_meta, &g.meta, mixed_meta_bytes(g.meta), st);
+        if (r) return r;
+        g.dirty = false;
+      }
+    }
+    const int r = leaf ? sln_launch_vae_tail(g.dev_probs, g.dev_meta, g.blocks, g.x2, g.flops, *leaf, st)
+                       : sln_launch_gemm_tn_mixed(g.dev_probs, g.dev_meta, g.blocks, g.x2, g.flops, st);
+    if (r == 0) { ++tail_launches; if (leaf) ++leaf_launches; }
+    return r;
+  }
   hipStream_t tn_eager_stream = nullptr;         // the stream whose launches read the eager table set (set 1) last
-  int flush_deferred(int which, hipStream_t st) {
+  // leaf (full iterations that defer their leaves): launched here too - inside the mixed wgrad launch where that is taken, as a
+  // launch of its own in front of the per-kind wgrad launches otherwise
+  int flush_deferred(int which, hipStream_t st, const VaeLeaf* leaf = nullptr) {
     if (rec) { rec_push(SK_TN_FLUSH); return 0; }
+    if (leaf && (deferred.empty() || !(which == 2 && it_tail && tail_leaf))) {
+      const int r = sln_launch_vae_leaf(*leaf, st);
+      if (r) { deferred.clear(); return r; }
+      ++leaf_launches;
+      leaf = nullptr;
+    }
     if (deferred.empty()) return 0;
     const int set = capturing ? 0 : 1;
     if (set == 1 && tn_eager_stream != st) {
@@ -221,6 +292,15 @@ struct SlnVae {
         if (tn_eager_stream != nullptr && hipStreamIsCapturing(tn_eager_stream, &cs_old) == hipSuccess && cs_old == hipStreamCaptureStatusNone)
           (void)hipStreamSynchronize(tn_eager_stream);
         tn_eager_stream = st;
+      }
+    }
+    if (which == 2 && it_tail) {        // the whole iteration's list as one launch, whatever its problems' kinds
+      int r = flush_mixed(set, leaf, st);
+      if (r != TN_MIXED_NO_FIT) { deferred.clear(); return r; }
+      if (leaf) {                          // the list does not fit one table: the leaf launch on its own, as before
+        r = sln_launch_vae_leaf(*leaf, st);
+        if (r) { deferred.clear(); return r; }
+        ++leaf_launches;
       }
     }
     static thread_local TnGroup tmp;
@@ -617,11 +697,20 @@ size_t SlnVae::carve(void* base, int mo, int mt) {
           tg.dev_probs = dp; tg.dev_meta = dm; tg.dirty = true; tg.n = 0;
         }
       }
+  if (tn_mixed_store)               // the mixed wgrad launch's tables (0.7 MB; engines that can take it only)
+    for (int set = 0; set < 2; ++set) {
+      GemmTNArgs* dp = b.take<GemmTNArgs>(SLN_TN_MIXED_MAX);
+      TnMixedMeta* dm = b.take<TnMixedMeta>(1);
+      if (!b.dry) { TnMixedGroup& tg = tn_mixed_store[set]; tg.dev_probs = dp; tg.dev_meta = dm; tg.dirty = true; tg.n = 0; }
+    }
   dG[0] = b.take<float>(Tm * 3 * Dm); dG[1] = b.take<float>(Tm * 3 * Dm);
   // the encoder's backward pass reuses both slots: the decoder's layer-0 dG, whose predicate columns the leaf launch reads at the
   // end of the iteration, gets a slice of its own - only in engines that can take the leaf launch at all (the whole [T, 3 Ddc]
   // block: the layer's dgrad writes it in one piece and its gather reads the outer thirds; 6.3 MB at 64 graphs, 403 MB at 4 096)
   dG[2] = (gconv_only || !leaf_merge || no_merge || n_attr_e == 0 || !cfg.decoder_cat) ? nullptr : b.take<float>(Tm * 3 * (size_t)Ddc);
+  // ... and so does the decoder's input gradient: its embedding tables are a leaf job too, and latent_bwd reads its z columns in place
+  // (engines that take the leaf launch and the tail launch only: +1 MB at 64 graphs, +67 MB at 4 096)
+  dX0_dc = (!tail_merge || gconv_only || !leaf_merge || no_merge || n_attr_e == 0 || !cfg.decoder_cat) ? nullptr : b.take<float>(Om * (size_t)Ddc);
   dX0 = b.take<float>(Om * Dm); dz = b.take<float>(Om * E); dmu = b.take<float>(Om * E); dlv = b.take<float>(Om * E);
   g_h2 = b.take<float>(Om * W); g_h1 = b.take<float>(Om * H); d_xb = b.take<float>(Om * W); d_xa = b.take<float>(Om * W);
   tmp_d = b.take<float>(Om * W);
@@ -656,6 +745,13 @@ VaeLeaf SlnVae::leaf_args() const {
   for (auto& bi : bns) maxc = bi.C > maxc ? bi.C : maxc;
   v.bn_tab = bn_table_dev; v.bn_n = (int)bns.size(); v.bn_max_c = maxc; v.bn_independent = cfg.recurrent ? 0 : 1;
   v.bn_update = step_training ? 1 : 0; v.bn_momentum = kBnMomentum;
+  if (it_dec_leaf) {               // the decoder's assembly tables, out of its own dX0 (decoder_backward)
+    DecAssembleBwd& db = v.dec;
+    db.objs = batch.objs; db.attrs = batch.attributes; db.dx0 = dX0_dc; db.O = O; db.n_obj = n_obj_e; db.n_attr = n_attr_e; db.n_z = E;
+    db.d_obj_emb = t.d_obj_emb_dc; db.d_attr_emb = t.d_attr_emb_dc; db.dz = nullptr; db.z_in_x0 = 1;
+    db.rows_obj = cfg.num_objs; db.rows_attr = cfg.num_attrs;
+    v.dec_ld = Ddc;
+  }
   return v;
 }
 
@@ -858,7 +954,7 @@ int SlnVae::decoder_backward(hipStream_t st) {
                           v.mode != SLN_BN_NONE ? bns[pv.bn[3]].gsums : nullptr, W, st));
     } else {
       BnView none = view(-1, 0, tr);
-      RET_IF(k_gather_bwd(dG[slot], 3 * W, W, g, O, nullptr, 0, nullptr, 0, none, 0, dX0, W, nullptr, 0, st));
+      RET_IF(k_gather_bwd(dG[slot], 3 * W, W, g, O, nullptr, 0, nullptr, 0, none, 0, it_dec_leaf ? dX0_dc : dX0, W, nullptr, 0, st));
       if (!it_leaf) RET_IF(k_embed_bwd(g.p, 0, dG[slot], 3 * W, W, T, W, cfg.num_preds, t.d_pred_emb_dc, st));
     }
   }
@@ -866,7 +962,7 @@ int SlnVae::decoder_backward(hipStream_t st) {
   db.objs = batch.objs; db.attrs = batch.attributes; db.dx0 = dX0; db.O = O; db.n_obj = n_obj_e; db.n_attr = n_attr_e; db.n_z = E;
   db.d_obj_emb = t.d_obj_emb_dc; db.d_attr_emb = t.d_attr_emb_dc; db.dz = dz; db.z_in_x0 = cfg.decoder_cat ? 1 : 0;
   db.rows_obj = cfg.num_objs; db.rows_attr = cfg.num_attrs;
-  RET_IF(k_dec_assemble_bwd(db, st));
+  if (!it_dec_leaf) RET_IF(k_dec_assemble_bwd(db, st));      // (a leaf job otherwise: leaf_args)
   const int nb = (int)bns.size() - n_bn_enc;
   if (nb > 0 && !it_merge_bn && !rec) {
     int maxc = 0;
@@ -950,9 +1046,8 @@ int SlnVae::encoder_backward(hipStream_t st) {
     }
   }
   if (it_leaf) {                                // every leaf of the iteration, side by side in one launch
-    RET_IF(sln_launch_vae_leaf(leaf_args(), st));
-    ++leaf_launches;
-    RET_IF(flush_deferred(it_one_flush ? 2 : 1, st));
+    const VaeLeaf lf = leaf_args();
+    RET_IF(flush_deferred(it_one_flush ? 2 : 1, st, &lf));
     return 0;
   }
   EncAssembleBwd eb; std::memset(&eb, 0, sizeof(eb));
@@ -991,10 +1086,15 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
     bulk_zeroed = true;
     it_merge_bn = !no_merge && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);    // the two-half form hands the decoder's gradients out early
     it_one_flush = one_flush && !tn_per_layer && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);
+    // ... and that flush as ONE launch for both kinds of problems; deterministic mode, shared weights and the lab switches that
+    // restore older sequences keep one launch per kind (a recorded room group never comes here)
+    it_tail = it_one_flush && tail_merge && tn_mixed_store != nullptr && !g_sln_deterministic && !cfg.recurrent && !rec;
     // the leaf launch: only where the workspace holds the decoder's third dG buffer (carve: SLN_LEAF_MERGE on, a model with
     // attribute tables and z in the decoder's input - the other two model shapes are listed fall-backs) and every job is on its
     // LDS path; anything else - deterministic mode included - keeps the per-kernel sequence for the whole iteration
+    it_dec_leaf = it_tail && tail_leaf && tail_dec && it_merge_bn && dG[2] != nullptr && dX0_dc != nullptr && T > 0;      // (read by leaf_args)
     it_leaf = it_merge_bn && dG[2] != nullptr && T > 0 && sln_vae_leaf_fits(leaf_args()) != 0;
+    it_dec_leaf = it_dec_leaf && it_leaf;
     it_wt_prologue = it_prologue && leaf_merge && (mode == TRAIN_BACKWARD || mode == TRAIN_FULL);
     if (!it_prologue && draw_eps) r = sln_launch_randn(eps_buf, (long)O * E, scalars, st);       // Sg2ScVAE_model.py:182
     in_iteration = true;
@@ -1007,14 +1107,16 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
     if (!r && grad_guard && mode != TRAIN_FULL)
       r = (int)hipMemcpyAsync(grad_guard, losses + 3, sizeof(float), hipMemcpyDeviceToDevice, st);
     if (!r) r = decoder_backward(st);
-    if (!r) r = sln_launch_latent_bwd(mu, logvar, eps, dz, &scalars->kl_weight, O, E, cfg.use_ae, dmu, dlv, st);
+    // (the decoder's assembly backward deferred: dz is the z columns of its dX0, which nothing overwrites before the tail launch)
+    if (!r) r = it_dec_leaf ? sln_launch_latent_bwd(mu, logvar, eps, dX0_dc + n_obj_e + n_attr_e, &scalars->kl_weight, O, E, cfg.use_ae, dmu, dlv, st, Ddc)
+                            : sln_launch_latent_bwd(mu, logvar, eps, dz, &scalars->kl_weight, O, E, cfg.use_ae, dmu, dlv, st);
   }
   if (mode != TRAIN_UPTO_DECODER) {
     bulk_zeroed = true;                // zeroed by the first half of this iteration
     if (!r) r = encoder_backward(st);
   }
   bulk_zeroed = false;
-  it_prologue = it_fused_loss = it_merge_bn = it_zero_in_prologue = it_one_flush = it_leaf = it_wt_prologue = false;
+  it_prologue = it_fused_loss = it_merge_bn = it_zero_in_prologue = it_one_flush = it_tail = it_leaf = it_dec_leaf = it_wt_prologue = false;
   RET_IF(r);
   if (mode == TRAIN_FULL) {
     RET_IF(sln_launch_adam(t.flat_params, t.flat_grads, t.adam_m, t.adam_v, (long)t.n_flat, scalars, losses + 3, st));
@@ -1024,6 +1126,7 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
 }
 
 long sln_vae_engine_leaf_launches(const SlnVae* h) { return h->leaf_launches; }        // for the test hook in vae_debug.hip
+long sln_vae_engine_tail_launches(const SlnVae* h) { return h->tail_launches; }
 long sln_vae_engine_half_launches(const SlnVae* h) { return h->half_launches; }
 
 // =============================================================================================
@@ -1067,7 +1170,16 @@ static int read_engine_options(SlnVae* h) {
   h->leaf_merge = !is("SLN_LEAF_MERGE", '0');
   h->tn_slots = 3 * (2 * h->L + 8 > 16 ? 2 * h->L + 8 : 16);
   h->tn_groups_store = new (std::nothrow) SlnVae::TnGroup[2 * (size_t)h->tn_slots * 2];
-  return h->tn_groups_store ? 0 : SLN_E_BADARG;
+  if (!h->tn_groups_store) return SLN_E_BADARG;
+  // SLN_TN_MIXED=0: two wgrad launches per full iteration (plain rows, gathered rows) as before round 10, in the same build
+  h->tail_merge = !is("SLN_TN_MIXED", '0') && !h->no_merge && h->leaf_merge && h->one_flush && !h->tn_per_layer && !h->cfg.recurrent && !h->gconv_only;
+  h->tail_leaf = !is("SLN_TN_MIXED", '1');
+  h->tail_dec = !is("SLN_TN_MIXED", '2');
+  if (h->tail_merge) {
+    h->tn_mixed_store = new (std::nothrow) SlnVae::TnMixedGroup[3];
+    if (!h->tn_mixed_store) return SLN_E_BADARG;
+  }
+  return 0;
 }
 
 int sln_vae_create(const SlnVaeConfig* c, SlnVae** out) {
@@ -1125,6 +1237,7 @@ void sln_vae_destroy(SlnVae* h) {
   if (!h) return;
   h->drop_graphs();
   delete[] h->tn_groups_store;
+  delete[] h->tn_mixed_store;
   for (auto& sl : h->tn_stage) {
     if (sl.done) { (void)hipEventSynchronize(sl.done); (void)hipEventDestroy(sl.done); }
     if (sl.host) (void)hipHostFree(sl.host);

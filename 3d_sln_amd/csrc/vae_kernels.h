@@ -113,9 +113,10 @@ int sln_launch_i64_to_i32(const int64_t* src, int* dst, int n, hipStream_t st);
 int sln_launch_log_softmax(const float* logits, float* out, int O, int n, hipStream_t st);
 int sln_launch_loss(LossArgs a, hipStream_t st);
 // dmu = w*mu/O + dz ; dlogvar = w*0.5*(exp(lv)-1)/O + dz*eps*0.5*exp(0.5 lv)
+// ld_dz: row stride of dz (0: n_z) - dz may be the z columns of the decoder's input gradient, read in place
 int sln_launch_latent_bwd(const float* mu, const float* logvar, const float* eps, const float* dz,
                           const float* kl_weight, int O, int n_z, int use_ae, float* dmu, float* dlogvar,
-                          hipStream_t st);
+                          hipStream_t st, int ld_dz = 0);
 
 // ---- parameters -------------------------------------------------------------------------------
 struct BnTableEntry {      // one BatchNorm application (module may repeat in 'recurrent' mode)
@@ -167,8 +168,17 @@ struct VaeLeaf {
   const int64_t* attr_idx; const float* d_attr; int ld_attr, col0_attr, n_attr_dc, attr_table_rows; float* d_attr_dc;   // n_attr_dc == 0: none
   const BnTableEntry* bn_tab; int bn_n, bn_max_c, bn_independent;   // parameter gradients of the whole table (bn_n == 0: none) ...
   int bn_update; float bn_momentum;                                  // ... and, when set, its running statistics (rows: pred_rows / enc.O)
+  // optional (dec.dx0 != NULL): the decoder's assembly tables (as sln_launch_dec_assemble_bwd; dec.dz must be NULL - the iteration's
+  // latent_bwd reads the z columns of dec.dx0 in place); dec_ld: row stride of dec.dx0
+  DecAssembleBwd dec; int dec_ld;
 };
 int sln_vae_leaf_fits(const VaeLeaf& a);    // 1: every job takes its LDS-table path (and the mode is not deterministic)
 int sln_launch_vae_leaf(const VaeLeaf& a, hipStream_t st);
+// The iteration's tail as ONE launch: the mixed wgrad table (sln_gemm.h: sln_tn_mixed_plan) followed by the leaf jobs as trailing
+// workgroup ranges.  `a` must pass sln_vae_leaf_fits.
+struct GemmTNArgs; struct TnMixedMeta;
+int sln_launch_vae_tail(const GemmTNArgs* dev_probs, const TnMixedMeta* dev_meta, int blocks, bool x2, double flops, const VaeLeaf& a,
+                        hipStream_t st);
+int sln_vae_tail_init();   // called by sln_gemm_init
 // counts[obj][floor(cz (cs - 1))][floor(cx (cs - 1))] += 1 for every (trial, object != room row): testing/test_heatmap.py:80-99
 int sln_launch_layout_heatmap(const float* boxes, long n_trials, int O, int cs, int clip, float* counts, hipStream_t st);

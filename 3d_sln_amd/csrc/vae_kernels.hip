@@ -6,6 +6,7 @@
 #include <cstring>
 #include "vae_kernels.h"
 #include "sln_prof.h"
+#include "gemm_bodies.h"      // the wgrad body: the iteration's tail launch (vae_tail_kernel) runs it next to the leaf jobs
 
 namespace {
 
@@ -770,10 +771,10 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
 __global__ void latent_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv,
                                   const float* __restrict__ eps, const float* __restrict__ dz,
                                   const float* __restrict__ klw, int O, int nz, int use_ae, float* __restrict__ dmu,
-                                  float* __restrict__ dlv) {
+                                  float* __restrict__ dlv, int ld_dz) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)O * nz) return;
-  const float g = dz[i];
+  const float g = ld_dz == nz ? dz[i] : dz[(i / nz) * ld_dz + (i % nz)];
   if (use_ae) { dmu[i] = g; dlv[i] = 0.f; return; }
   const float w = klw[0] / (float)O;
   const float l = lv[i];
@@ -1363,11 +1364,12 @@ int sln_launch_loss(LossArgs a, hipStream_t st) {
 }
 
 int sln_launch_latent_bwd(const float* mu, const float* logvar, const float* eps, const float* dz, const float* kl_weight,
-                          int O, int n_z, int use_ae, float* dmu, float* dlogvar, hipStream_t st) {
+                          int O, int n_z, int use_ae, float* dmu, float* dlogvar, hipStream_t st, int ld_dz) {
   const long n = (long)O * n_z;
   if (n <= 0) return 0;
+  if (ld_dz != 0 && ld_dz < n_z) return -1;
   hipLaunchKernelGGL(latent_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mu, logvar, eps, dz,
-                     kl_weight, O, n_z, use_ae, dmu, dlogvar);
+                     kl_weight, O, n_z, use_ae, dmu, dlogvar, ld_dz ? ld_dz : n_z);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -1439,17 +1441,16 @@ int sln_launch_step_prologue(const StepPrologue& a, hipStream_t st) {
 // ----------------------------------------------------------------------------------------------
 struct LeafEmbedJob { const void* idx; const float* d; float* d_emb; int ld, col0, rows, n, table_rows, rpb; };
 struct LeafArgs {
-  AssembleBwdLds asmb;
+  AssembleBwdLds asmb, asmb_dc;         // encoder / (optional) decoder assembly tables
   EncAssembleBwd box; int box_gx;
   LeafEmbedJob pdc, pec, attr;          // int32 / int32 / int64 indices
   const BnTableEntry* bn_tab; int bn_n, bn_per_entry, bn_gx, rows_t, rows_o; float mom;
 };
 // blocks [0, b0) encoder assembly tables, [b0, b1) box embedding, [b1, b2) / [b2, b3) decoder / encoder predicate table,
-// [b3, b4) decoder attribute table, [b4, b5) BatchNorm parameter gradients, [b5, ..) running statistics
-__global__ __launch_bounds__(256) void vae_leaf_kernel(unsigned int b0, unsigned int b1, unsigned int b2, unsigned int b3, unsigned int b4,
-                                                       unsigned int b5, LeafArgs a) {
+// [b3, b4) decoder attribute table, [b4, b5) BatchNorm parameter gradients, [b5, b6) running statistics, [b6, ..) decoder assembly tables
+__device__ __forceinline__ void vae_leaf_dispatch(const unsigned int b, unsigned int b0, unsigned int b1, unsigned int b2, unsigned int b3,
+                                                  unsigned int b4, unsigned int b5, unsigned int b6, const LeafArgs& a) {
   extern __shared__ float tab[];
-  const unsigned int b = blockIdx.x;
   if (b < b0) assemble_bwd_lds_body(a.asmb, (int)b);
   else if (b < b1) {
     const int q = (int)(b - b0);
@@ -1467,10 +1468,29 @@ __global__ __launch_bounds__(256) void vae_leaf_kernel(unsigned int b0, unsigned
   else if (b < b5) {
     const int q = (int)(b - b4);
     bn_param_grads_body(a.bn_tab, a.bn_n, a.bn_per_entry, (q % a.bn_gx) * 256 + (int)threadIdx.x, q / a.bn_gx);
-  } else {
+  } else if (b < b6) {
     const int q = (int)(b - b5);
     bn_running_update_body(a.bn_tab, a.bn_n, a.mom, a.bn_per_entry, a.rows_t, a.rows_o, (q % a.bn_gx) * 256 + (int)threadIdx.x, q / a.bn_gx);
-  }
+  } else assemble_bwd_lds_body(a.asmb_dc, (int)(b - b6));
+}
+__global__ __launch_bounds__(256) void vae_leaf_kernel(unsigned int b0, unsigned int b1, unsigned int b2, unsigned int b3, unsigned int b4,
+                                                       unsigned int b5, unsigned int b6, LeafArgs a) {
+  vae_leaf_dispatch(blockIdx.x, b0, b1, b2, b3, b4, b5, b6, a);
+}
+
+// The tail of a full iteration as ONE launch: workgroups [0, nwg) are the items of the mixed wgrad table (gemm_f32.hip:
+// gemm_tn_mixed_kernel - the same body choice), the workgroups behind them the leaf jobs above.  Nothing reads either before the
+// optimizer, and neither reads what the other writes (wgrads: dW / db; leaves: embedding tables, BatchNorm parameter gradients
+// and running statistics - a train-mode wgrad reads the batch statistics, and running statistics are only updated in train mode).
+// The short leaf workgroups come last and fill the CUs that the long wgrad workgroups (704-row chunks, three per CU) leave one
+// by one at the end of the grid.  Registers and LDS are the wgrad body's; the leaf jobs' tables fit inside its tile buffers.
+struct LeafRanges { unsigned int b0, b1, b2, b3, b4, b5, b6; };
+template <bool G_X2>
+__global__ __launch_bounds__(256) void vae_tail_kernel(const GemmTNArgs* __restrict__ probs, const TnMixedMeta* __restrict__ meta,
+                                                       const unsigned int nwg, const LeafRanges r, const LeafArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  if (blockIdx.x >= nwg) { vae_leaf_dispatch(blockIdx.x - nwg, r.b0, r.b1, r.b2, r.b3, r.b4, r.b5, r.b6, a); return; }
+  gemm_tn_mixed_item<G_X2>(probs, meta->item[blockIdx.x], smem);
 }
 
 // every job of the leaf launch on its LDS path (the stand-alone launchers' own conditions); deterministic mode never is
@@ -1484,12 +1504,17 @@ int sln_vae_leaf_fits(const VaeLeaf& a) {
     return 0;
   if (a.n_attr_dc > 0 && (a.attr_table_rows <= 0 || (long)a.attr_table_rows * a.n_attr_dc > EMBED_LDS_MAX_FLOATS)) return 0;
   if (a.n_pdc <= 0 || a.n_pec <= 0 || e.n_box <= 0) return 0;
+  if (a.dec.dx0) {
+    const DecAssembleBwd& d = a.dec;
+    if (d.dz || d.O != e.O || d.n_obj <= 0 || !(d.rows_obj > 0 && (d.n_attr == 0 || d.rows_attr > 0)) || a.dec_ld < d.n_obj + d.n_attr) return 0;
+    if ((long)d.rows_obj * d.n_obj + (long)d.rows_attr * d.n_attr > ASSEMBLE_LDS_MAX_FLOATS) return 0;
+  }
   return 1;
 }
 
-int sln_launch_vae_leaf(const VaeLeaf& v, hipStream_t st) {
-  if (!sln_vae_leaf_fits(v)) return -1;      // SLN_E_BADARG: the caller checks sln_vae_leaf_fits first
-  LeafArgs a; std::memset(&a, 0, sizeof(a));
+// the leaf jobs' argument block, block ranges and dynamic LDS; returns the number of workgroups
+static unsigned int leaf_build(const VaeLeaf& v, LeafArgs& a, LeafRanges& rg, size_t& lds_out) {
+  std::memset(&a, 0, sizeof(a));
   const EncAssembleBwd& e = v.enc;
   // the encoder's assembly tables: as sln_launch_enc_assemble_bwd / launch_assemble_bwd_lds
   AssembleBwdLds& l = a.asmb;
@@ -1516,13 +1541,59 @@ int sln_launch_vae_leaf(const VaeLeaf& v, hipStream_t st) {
   const unsigned int n_pred = (unsigned int)sln_cdiv(v.pred_rows, rpb);
   const unsigned int n_attr = v.n_attr_dc > 0 ? (unsigned int)sln_cdiv(e.O, rpb) : 0;
   const unsigned int b0 = n_asm, b1 = b0 + n_box, b2 = b1 + n_pred, b3 = b2 + n_pred, b4 = b3 + n_attr, b5 = b4 + n_bn;
-  const unsigned int tot = b5 + (v.bn_update ? n_bn : 0);
+  const unsigned int b6 = b5 + (v.bn_update ? n_bn : 0);
+  unsigned int n_dasm = 0;
+  if (v.dec.dx0) {                     // the decoder's assembly tables: as sln_launch_dec_assemble_bwd / launch_assemble_bwd_lds, no dz
+    AssembleBwdLds& d = a.asmb_dc;
+    d.dx0 = v.dec.dx0; d.ld = v.dec_ld; d.O = v.dec.O;
+    int kd = 0;
+    d.seg[kd++] = EmbSeg{v.dec.objs, v.dec.d_obj_emb, v.dec.n_obj, v.dec.rows_obj, 0, 0};
+    if (v.dec.n_attr > 0) d.seg[kd++] = EmbSeg{v.dec.attrs, v.dec.d_attr_emb, v.dec.n_attr, v.dec.rows_attr, v.dec.n_obj, 0};
+    d.nseg = kd;
+    int offd = 0;
+    for (int s = 0; s < d.nseg; ++s) { d.seg[s].lds0 = offd; offd += d.seg[s].rows * d.seg[s].n; }
+    d.lds_floats = offd;
+    d.rows_per_block = d.O <= 8192 ? 16 : 64;
+    n_dasm = (unsigned int)sln_cdiv(d.O, d.rows_per_block);
+  }
+  const unsigned int tot = b6 + n_dasm;
   // dynamic LDS: the largest table of any job, and the box job's 7 x RL x CB partial sums
   size_t lds = sizeof(float) * 7 * RL * CB;
   auto grow = [&lds](long floats) { if (sizeof(float) * (size_t)floats > lds) lds = sizeof(float) * (size_t)floats; };
   grow(l.lds_floats); grow((long)v.pred_table_rows * v.n_pdc); grow((long)v.pred_table_rows * v.n_pec);
   if (v.n_attr_dc > 0) grow((long)v.attr_table_rows * v.n_attr_dc);
-  hipLaunchKernelGGL(vae_leaf_kernel, dim3(tot), dim3(256), lds, st, b0, b1, b2, b3, b4, b5, a);
+  grow(a.asmb_dc.lds_floats);
+  rg = LeafRanges{b0, b1, b2, b3, b4, b5, b6};
+  lds_out = lds;
+  return tot;
+}
+
+int sln_launch_vae_leaf(const VaeLeaf& v, hipStream_t st) {
+  if (!sln_vae_leaf_fits(v)) return -1;      // SLN_E_BADARG: the caller checks sln_vae_leaf_fits first
+  LeafArgs a; LeafRanges r; size_t lds = 0;
+  const unsigned int tot = leaf_build(v, a, r, lds);
+  hipLaunchKernelGGL(vae_leaf_kernel, dim3(tot), dim3(256), lds, st, r.b0, r.b1, r.b2, r.b3, r.b4, r.b5, r.b6, a);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_vae_tail_init() {
+  int r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  return r;
+}
+
+int sln_launch_vae_tail(const GemmTNArgs* dev_probs, const TnMixedMeta* dev_meta, int blocks, bool x2, double flops, const VaeLeaf& v,
+                        hipStream_t st) {
+  if (blocks < 0 || !sln_vae_leaf_fits(v)) return -1;
+  LeafArgs a; LeafRanges r; size_t lds = 0;
+  const unsigned int tot = leaf_build(v, a, r, lds);
+  const size_t smem = tn_smem_bytes(64, 64);
+  if (lds > smem) return -1;                 // (the tables are capped at 40 KB, the wgrad tiles take 50 KB)
+  { const int e = sln_gemm_init(); if (e) return e; }       // raises the dynamic-LDS limit of this kernel too
+  SlnProfScope prof(SLN_FAM_GEMM_TN, flops, st);
+  if (x2) hipLaunchKernelGGL((vae_tail_kernel<true>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
+  else hipLaunchKernelGGL((vae_tail_kernel<false>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
   SLN_CHECK_LAUNCH();
   return 0;
 }

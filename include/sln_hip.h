@@ -271,6 +271,11 @@ int sln_get_deterministic(void);
  * problems given as (rows, outputs, inputs).  Returns the number of workgroups (< 0: error), fills rows_per_block[n] and
  * items[3 * workgroup] = (problem or -1 for padding, output tile, row chunk). */
 int sln_debug_tn_plan(const int* R, const int* Nout, const int* Kin, int n, int* rows_per_block, int* items, int max_items);
+/* The same for the ONE wgrad launch of a whole iteration (gathered and plain problems in one table; 1 <= n <= 128):
+ * gathers[i] != 0 marks a problem whose input rows are gathered; items[4 * workgroup] = (problem or -1, output tile, row chunk,
+ * gather bit).  -1 also when the list does not fit the table at the target chunk length (the engine then keeps one launch per kind). */
+int sln_debug_tn_plan_mixed(const int* R, const int* Nout, const int* Kin, const int* gathers, int n, int* rows_per_block, int* items,
+                            int max_items);
 int sln_prof_read(double* ms_by_family, double* work_by_family, int64_t* launches_by_family, int n_families);
 
 /* Debug/test tap: copy an internal activation to `dst` (device).  what: 0 A1,1 A2,2 M,3 A3,4 A4 of
@@ -374,6 +379,11 @@ int sln_debug_gemm_nt(const SlnDbgGemmNT* desc, int n, int* grouped, void* strea
 /* multi == 0 (n must be 1): sln_launch_gemm_tn.  multi != 0 (1 <= n <= 64): the planner and the one-launch-per-pass kernel; the
  * problem table lives in device memory the hook owns and frees after synchronising the stream. */
 int sln_debug_gemm_tn(const SlnDbgGemmTN* desc, int n, int multi, void* stream);
+/* The iteration's one wgrad launch on caller-built problems (1 <= n <= 128): problems that gather their input rows and problems that
+ * do not (their index arrays may be NULL) share one grid, each workgroup running the body its problem needs.  Here the last
+ * segment of an operand may have a length that is no multiple of 4 when its rows are stored up to the next multiple (ld >= c +
+ * the rounded length): the engine's box_net.1 gradient, 6 columns in rows of 8. */
+int sln_debug_gemm_tn_mixed(const SlnDbgGemmTN* desc, int n, void* stream);
 /* Host only: the kernel sln_launch_gemm_nt would run for this description (the launcher's own decision function). */
 int sln_debug_gemm_nt_route(const SlnDbgGemmNT* desc, SlnDbgNTRoute* out);
 /* The fp16-MFMA launcher (csrc/gemm_half.hip) on a caller-built problem; terms: 1 = "f16", 3 = "f16x3".  SLN_E_UNSUPPORTED, with
@@ -483,8 +493,14 @@ int sln_debug_vae_opt(SlnDbgOpt* desc, void* stream);
 int sln_debug_vae_sizes(int* out, int max);
 /* How many times an engine issued the one-launch form of an iteration's leaf kernels (embedding-table, box-embedding and
  * BatchNorm bookkeeping gradients deferred to the end of a full iteration); 0 while it keeps the per-kernel sequence
- * (SLN_LEAF_MERGE=0, deterministic mode, tables past the LDS caps, the two-half form).  A captured iteration counts once. */
+ * (SLN_LEAF_MERGE=0, deterministic mode, tables past the LDS caps, the two-half form).  A captured iteration counts once.  The
+ * jobs count whether they ran as a launch of their own or as trailing workgroups of the iteration's wgrad launch (below). */
 int64_t sln_debug_vae_leaf_launches(const SlnVae* h);
+/* Running count of the iterations whose wgrads ran as ONE launch (gathered and plain problems in one table); 0 while an engine
+ * keeps one launch per kind (SLN_TN_MIXED=0, SLN_NO_MERGE=1, SLN_LEAF_MERGE=0, deterministic mode, shared 'recurrent' weights,
+ * the two-half form, a problem list past the table).  A captured iteration counts once.  By default the leaf jobs and the
+ * decoder's assembly backward ride in that launch (SLN_TN_MIXED=1: neither, =2: the leaf jobs only). */
+int64_t sln_debug_vae_tail_launches(const SlnVae* h);
 /* Running count of the fp16-MFMA Linear launches an engine issued (sln_vae_set_gemm_precision). */
 int64_t sln_debug_vae_half_launches(const SlnVae* h);
 
