@@ -229,6 +229,9 @@ SIGNATURES = {
     "sln_prof_enable": (C.c_int, [C.c_int]),
     "sln_set_deterministic": (C.c_int, [C.c_int]),
     "sln_get_deterministic": (C.c_int, []),
+    "sln_set_store_policy": (C.c_int, [C.c_int]),
+    "sln_get_store_policy": (C.c_int, []),
+    "sln_parse_store_policy_env": (C.c_int, [C.c_char_p, C.c_int]),
     "sln_debug_tn_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "sln_debug_tn_plan_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "sln_prof_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -260,6 +263,7 @@ SIGNATURES = {
     "sln_debug_vae_leaf_launches": (C.c_int64, [C.c_void_p]),
     "sln_debug_vae_half_launches": (C.c_int64, [C.c_void_p]),
     "sln_debug_vae_tail_launches": (C.c_int64, [C.c_void_p]),
+    "sln_debug_vae_graph_captures": (C.c_int64, [C.c_void_p]),
     "sln_project_faces": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p]),
     "sln_project_faces_backward": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p,
                                              c_f32p, C.c_void_p]),

@@ -201,7 +201,7 @@ __device__ __forceinline__ void nt_helper_tables(const GemmNTArgs& a, float4* co
 // atomics) are the slowest round trip in front of a block's first MFMA, and in the staging waves they queue behind the operand
 // loads and hold back - vmcnt retires in order - every later wait.  In wavefronts of their own they go out at once, next to the
 // operand loads of the others.
-template <int BM, int BN, int WM, int WN, int AMODE, int EPI, int MULTI, bool HELP = false>
+template <int BM, int BN, int WM, int WN, int AMODE, int EPI, int MULTI, bool HELP = false, int ST = 0>      // ST: how Y is stored (SLN_ST_*, sln_common.h)
 __device__ __forceinline__ void gemm_nt_body(const GemmNTArgs& a, const int bid, const int nwg, char* smem) {
   constexpr int NT = 256;
   constexpr bool HAS_X2 = AMODE == 1;        // AMODE: 0 = per-column affine (+relu), 1 = two sources (BatchNorm backward), 2 = identity
@@ -618,7 +618,7 @@ __device__ __forceinline__ void gemm_nt_body(const GemmNTArgs& a, const int bid,
         y = ok ? y : 0.f;
         if (EPI == EPI_STATS) { d1 += (double)y; d2 = fma((double)y, (double)y, d2); }
         if (EPI == EPI_MASK) { s1 += y; s2 = fmaf(y, (xpv[r] - ec.z) * ec.w, s2); }
-        if (ok) a.Y[(size_t)row * a.ldy + a.ycol0 + col] = y;
+        if (ok) sln_st_y<ST>(a.Y + (size_t)row * a.ldy + a.ycol0 + col, y);
       }
     }
     if (EPI == EPI_STATS) {
@@ -664,7 +664,7 @@ __device__ __forceinline__ void gemm_nt_body(const GemmNTArgs& a, const int bid,
 // that consume .x .. .w each see k = c, c + 4, c + 8, c + 12 - any fixed permutation of k is as good as another, A and B use the
 // same one).  Single-segment operands only.  Staging, masks (none: zero coefficient rows) and the statistics are those of
 // gemm_nt_body; sums are taken in a different order (per 16 x 16 block), results agree to fp32 rounding.
-template <int J, int AMODE, int EPI, bool HELP = false>      // HELP: 512 threads, wavefronts 4 .. 7 build the coefficient tables (see gemm_nt_body)
+template <int J, int AMODE, int EPI, bool HELP = false, int ST = 0>      // HELP: 512 threads, wavefronts 4 .. 7 build the coefficient tables (see gemm_nt_body)
 __device__ __forceinline__ void gemm_nt_body16(const GemmNTArgs& a, const int bid, const int nwg, char* smem) {
   constexpr int NT = 256, BM = 64, BN = 32 * J, WN16 = 16 * J;
   constexpr bool HAS_X2 = AMODE == 1;
@@ -901,7 +901,7 @@ __device__ __forceinline__ void gemm_nt_body16(const GemmNTArgs& a, const int bi
       y = ok ? y : 0.f;
       if (EPI == EPI_STATS) { d1 += (double)y; d2 = fma((double)y, (double)y, d2); }
       if (EPI == EPI_MASK) { s1 += y; s2 = fmaf(y, (xpv[q] - ec.z) * ec.w, s2); }
-      if (ok) a.Y[(size_t)row * a.ldy + a.ycol0 + col] = y;
+      if (ok) sln_st_y<ST>(a.Y + (size_t)row * a.ldy + a.ycol0 + col, y);
     }
     if (EPI == EPI_STATS) {
       d1 += __shfl_xor(d1, 16, 64); d2 += __shfl_xor(d2, 16, 64);
@@ -968,7 +968,7 @@ inline int nt16_pick(const GemmNTArgs& a) {
 // Linear with tile-aligned segments - for graphs of a few rows only (the refinement loop's 13-object room, BASELINE config c1):
 // there the 64 x 64 body is 4 workgroups walking 12 k-tiles each (14.8 us per launch, the slowest kernel of a refinement
 // iteration's decoder); at 64 graphs the 64 x 64 body stays (measured in round 2: 2.54 -> 2.57 ms per step with this one).
-template <int AMODE, int EPI, bool HELP = false, int NSEG = 1>   // HELP: 512 threads, wavefronts 4 .. 7 build the coefficient tables (see gemm_nt_body)
+template <int AMODE, int EPI, bool HELP = false, int NSEG = 1, int ST = 0>   // HELP: 512 threads, wavefronts 4 .. 7 build the coefficient tables (see gemm_nt_body)
 __device__ __forceinline__ void gemm_nt_small_body(const GemmNTArgs& a, const int bid, char* smem, const bool small_xcd = true) {
   constexpr bool HAS_X2 = AMODE == 1;
   constexpr bool IDENT = AMODE == 2;
@@ -1145,7 +1145,7 @@ __device__ __forceinline__ void gemm_nt_small_body(const GemmNTArgs& a, const in
     y = ok ? y : 0.f;
     if (EPI == EPI_STATS) { d1 += (double)y; d2 = fma((double)y, (double)y, d2); }
     if (EPI == EPI_MASK) { s1 += y; s2 = fmaf(y, (xpv[q] - ec.z) * ec.w, s2); }
-    if (ok) a.Y[(size_t)row * a.ldy + a.ycol0 + col] = y;
+    if (ok) sln_st_y<ST>(a.Y + (size_t)row * a.ldy + a.ycol0 + col, y);
   }
   if (EPI != EPI_PLAIN) {
     if (EPI == EPI_MASK) { d1 = (double)wave_sum_halves(s1); d2 = (double)wave_sum_halves(s2); }

@@ -32,26 +32,26 @@ namespace {
 constexpr bool nt_coef_helpers(int amode, int epi) { return amode != 2 || epi == EPI_MASK; }      // there is a coefficient table to build
 template <int BM, int BN, int AMODE, int EPI>
 constexpr bool nt_helpers() { return BM == 64 && BN == 64 && nt_coef_helpers(AMODE, EPI); }
-template <int BM, int BN, int WM, int WN, int AMODE, int EPI, int MULTI>
+template <int BM, int BN, int WM, int WN, int AMODE, int EPI, int MULTI, int ST = 0>
 __global__ __launch_bounds__((nt_helpers<BM, BN, AMODE, EPI>() ? 512 : 256)) void gemm_nt_kernel(const GemmNTArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // the grid is exactly the tile count (launch_nt): computed from M and N, which the body needs anyway, instead of read from the
   // dispatch packet's block count - one kernel-argument cache line less in front of the first address
-  gemm_nt_body<BM, BN, WM, WN, AMODE, EPI, MULTI, nt_helpers<BM, BN, AMODE, EPI>()>(a, blockIdx.x, ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN), smem);
+  gemm_nt_body<BM, BN, WM, WN, AMODE, EPI, MULTI, nt_helpers<BM, BN, AMODE, EPI>(), ST>(a, blockIdx.x, ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN), smem);
 }
 
 template <int AMODE, int EPI>
 constexpr bool nt_helpers2() { return nt_coef_helpers(AMODE, EPI); }
-template <int J, int AMODE, int EPI>
+template <int J, int AMODE, int EPI, int ST = 0>
 __global__ __launch_bounds__((nt_helpers2<AMODE, EPI>() ? 512 : 256)) void gemm_nt16_kernel(const GemmNTArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemm_nt_body16<J, AMODE, EPI, nt_helpers2<AMODE, EPI>()>(a, blockIdx.x, ((a.M + 63) / 64) * ((a.N + 32 * J - 1) / (32 * J)), smem);
+  gemm_nt_body16<J, AMODE, EPI, nt_helpers2<AMODE, EPI>(), ST>(a, blockIdx.x, ((a.M + 63) / 64) * ((a.N + 32 * J - 1) / (32 * J)), smem);
 }
 
-template <int AMODE, int EPI, int NSEG = 1>
+template <int AMODE, int EPI, int NSEG = 1, int ST = 0>
 __global__ __launch_bounds__((nt_helpers2<AMODE, EPI>() ? 512 : 256)) void gemm_nt_small_kernel(const GemmNTArgs a, const int xcd) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemm_nt_small_body<AMODE, EPI, nt_helpers2<AMODE, EPI>(), NSEG>(a, blockIdx.x, smem, xcd != 0);
+  gemm_nt_small_body<AMODE, EPI, nt_helpers2<AMODE, EPI>(), NSEG, ST>(a, blockIdx.x, smem, xcd != 0);
 }
 
 // Forward Linears / dgrads of R rooms (R parameter copies) in one grid: blockIdx.y = room, the room's problem comes out of a device
@@ -81,6 +81,8 @@ namespace {
 // workgroup size differs from the route's refuses to launch, so what sln_debug_gemm_nt_route reports is what runs.
 enum { NT_BODY_64 = 0, NT_BODY_128x64 = 1, NT_BODY_128 = 2, NT_BODY_16J3 = 3, NT_BODY_16J5 = 4, NT_BODY_SMALL = 5, NT_BODY_SMALL3 = 6 };
 struct NtRoute { int body, multi, amode, threads; };      // multi: 0 one segment, 1 boundaries on k-tiles, 2 a boundary inside a k-tile
+// the store form of a launch's epilogue, from the process-wide policy word (sln_common.h)
+inline int nt_store_mode() { return (g_sln_store_policy & SLN_STORE_NT_WT) ? SLN_ST_WT : SLN_ST_PLAIN; }
 
 template <int AMODE, int EPI, int NSEG = 1>
 int launch_nt_small(const GemmNTArgs& a, const NtRoute& rt, hipStream_t st) {
@@ -90,7 +92,8 @@ int launch_nt_small(const GemmNTArgs& a, const NtRoute& rt, hipStream_t st) {
   if (grid <= 0) return 0;
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
   static const int xcd = std::getenv("SLN_NT_SMALL_NO_XCD") ? 0 : 1;      // lab switch: plain workgroup order
-  hipLaunchKernelGGL((gemm_nt_small_kernel<AMODE, EPI, NSEG>), dim3(grid), dim3(nt_helpers2<AMODE, EPI>() ? 512 : 256), smem, st, a, xcd);
+  if (nt_store_mode() == SLN_ST_WT) hipLaunchKernelGGL((gemm_nt_small_kernel<AMODE, EPI, NSEG, SLN_ST_WT>), dim3(grid), dim3(nt_helpers2<AMODE, EPI>() ? 512 : 256), smem, st, a, xcd);
+  else hipLaunchKernelGGL((gemm_nt_small_kernel<AMODE, EPI, NSEG>), dim3(grid), dim3(nt_helpers2<AMODE, EPI>() ? 512 : 256), smem, st, a, xcd);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -102,7 +105,8 @@ int launch_nt16(const GemmNTArgs& a, const NtRoute& rt, hipStream_t st) {
   const int grid = sln_cdiv(a.M, 64) * sln_cdiv(a.N, 32 * J);
   if (grid <= 0) return 0;
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
-  hipLaunchKernelGGL((gemm_nt16_kernel<J, AMODE, EPI>), dim3(grid), dim3(nt_helpers2<AMODE, EPI>() ? 512 : 256), smem, st, a);
+  if (nt_store_mode() == SLN_ST_WT) hipLaunchKernelGGL((gemm_nt16_kernel<J, AMODE, EPI, SLN_ST_WT>), dim3(grid), dim3(nt_helpers2<AMODE, EPI>() ? 512 : 256), smem, st, a);
+  else hipLaunchKernelGGL((gemm_nt16_kernel<J, AMODE, EPI>), dim3(grid), dim3(nt_helpers2<AMODE, EPI>() ? 512 : 256), smem, st, a);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -115,12 +119,15 @@ int launch_nt(const GemmNTArgs& a, const NtRoute& rt, hipStream_t st) {
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
   constexpr int NTHR = nt_helpers<BM, BN, AMODE, EPI>() ? 512 : 256;
   if (rt.threads != NTHR) return -3;
-  if (rt.multi == 2) {
-    if constexpr (BM == 64 && BN == 64) hipLaunchKernelGGL((gemm_nt_kernel<64, 64, WM, WN, AMODE, EPI, 2>), dim3(grid), dim3(NTHR), smem, st, a);
-    else return -2;   // SLN_E_UNSUPPORTED (nt_route forces the 64 x 64 tile for such operands)
-  }
-  else if (rt.multi == 1) hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, AMODE, EPI, 1>), dim3(grid), dim3(NTHR), smem, st, a);
-  else hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, AMODE, EPI, 0>), dim3(grid), dim3(NTHR), smem, st, a);
+#define SLN_NT_GO(ST_)                                                                                                                   \
+  if (rt.multi == 2) {                                                                                                                   \
+    if constexpr (BM == 64 && BN == 64) hipLaunchKernelGGL((gemm_nt_kernel<64, 64, WM, WN, AMODE, EPI, 2, ST_>), dim3(grid), dim3(NTHR), smem, st, a); \
+    else return -2;   /* SLN_E_UNSUPPORTED (nt_route forces the 64 x 64 tile for such operands) */                                       \
+  }                                                                                                                                      \
+  else if (rt.multi == 1) hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, AMODE, EPI, 1, ST_>), dim3(grid), dim3(NTHR), smem, st, a); \
+  else hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, AMODE, EPI, 0, ST_>), dim3(grid), dim3(NTHR), smem, st, a);
+  if (nt_store_mode() == SLN_ST_WT) { SLN_NT_GO(SLN_ST_WT) } else { SLN_NT_GO(SLN_ST_PLAIN) }
+#undef SLN_NT_GO
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -208,18 +215,18 @@ int launch_tn(const GemmTNArgs& a, hipStream_t st) {
 }  // namespace
 
 // Raise the dynamic-LDS limit of every instantiation once (must not happen inside a stream capture).
-template <int BM, int BN, int WM, int WN>
+template <int BM, int BN, int WM, int WN, int ST>
 static int init_nt_tile() {
   hipError_t e = hipSuccess;
 #define SLN_SET(X2, EPI)                                                                                          \
   if (e == hipSuccess)                                                                                            \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<BM, BN, WM, WN, X2, EPI, 0>),           \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<BM, BN, WM, WN, X2, EPI, 0, ST>),       \
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                              \
   if (e == hipSuccess)                                                                                            \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<BM, BN, WM, WN, X2, EPI, 1>),           \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<BM, BN, WM, WN, X2, EPI, 1, ST>),       \
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                              \
   if (e == hipSuccess && BM == 64 && BN == 64)                                                                    \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<64, 64, WM, WN, X2, EPI, 2>),           \
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<64, 64, WM, WN, X2, EPI, 2, ST>),       \
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   SLN_SET(0, EPI_PLAIN) SLN_SET(0, EPI_STATS) SLN_SET(0, EPI_MASK)
   SLN_SET(1, EPI_PLAIN) SLN_SET(1, EPI_STATS) SLN_SET(1, EPI_MASK)
@@ -233,17 +240,24 @@ int sln_vae_tail_init();      // vae_kernels.hip: the tail launch runs the wgrad
 int sln_gemm_init() {
   static bool done = false;
   if (done) return 0;
-  int r = init_nt_tile<64, 64, 2, 2>();
+  int r = init_nt_tile<64, 64, 2, 2, SLN_ST_PLAIN>();
+  if (!r) r = init_nt_tile<64, 64, 2, 2, SLN_ST_WT>();
 #define SLN_SET_S(AM, EPI)                                                                                        \
   if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_small_kernel<AM, EPI, 1>),         \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
   if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_small_kernel<AM, EPI, 3>),         \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_small_kernel<AM, EPI, 1, SLN_ST_WT>), \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_small_kernel<AM, EPI, 3, SLN_ST_WT>), \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   SLN_SET_S(0, EPI_PLAIN) SLN_SET_S(0, EPI_STATS) SLN_SET_S(0, EPI_MASK) SLN_SET_S(1, EPI_PLAIN) SLN_SET_S(1, EPI_STATS)
   SLN_SET_S(1, EPI_MASK) SLN_SET_S(2, EPI_PLAIN) SLN_SET_S(2, EPI_STATS) SLN_SET_S(2, EPI_MASK)
 #undef SLN_SET_S
 #define SLN_SET_16(J, AM, EPI)                                                                                    \
   if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt16_kernel<J, AM, EPI>),             \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt16_kernel<J, AM, EPI, SLN_ST_WT>),  \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #define SLN_SET_16J(J)                                                                                            \
   SLN_SET_16(J, 0, EPI_PLAIN) SLN_SET_16(J, 0, EPI_STATS) SLN_SET_16(J, 0, EPI_MASK) SLN_SET_16(J, 1, EPI_PLAIN) SLN_SET_16(J, 1, EPI_STATS) \
@@ -251,8 +265,10 @@ int sln_gemm_init() {
   SLN_SET_16J(3) SLN_SET_16J(5)
 #undef SLN_SET_16J
 #undef SLN_SET_16
-  if (!r) r = init_nt_tile<128, 64, 2, 2>();
-  if (!r) r = init_nt_tile<128, 128, 2, 2>();
+  if (!r) r = init_nt_tile<128, 64, 2, 2, SLN_ST_PLAIN>();
+  if (!r) r = init_nt_tile<128, 64, 2, 2, SLN_ST_WT>();
+  if (!r) r = init_nt_tile<128, 128, 2, 2, SLN_ST_PLAIN>();
+  if (!r) r = init_nt_tile<128, 128, 2, 2, SLN_ST_WT>();
 #define SLN_SET_TN(X2, XG)                                                                                        \
   if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<64, 64, 2, 2, X2, XG>),     \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -14,22 +14,25 @@ struct GroupArgs {
 
 // the problem descriptions are SEPARATE kernel parameters: as members of one struct parameter hipcc copied them to
 // scratch memory (2.6 KB per lane) and the two-source variants ran 4x slower
-template <int AMODE, int EPI, bool MULTI>
+template <int AMODE, int EPI, bool MULTI, int ST>
 // The block counts that decide which problem a workgroup belongs to are LEADING scalar arguments: they arrive in SGPRs with the
 // wavefront (kernarg preload, build.py) - as the last member of the argument block they were a scalar-cache miss of their own
 // in front of the first field of the chosen problem.
 __global__ __launch_bounds__(256) void gemm_group_kernel(const int nt_blocks0, const int nt_blocks1, const GemmNTArgs a0, const GemmNTArgs a1) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int b = blockIdx.x;
-  if (b < nt_blocks0) { gemm_nt_body<64, 64, 2, 2, AMODE, EPI, MULTI>(a0, b, nt_blocks0, smem); return; }
+  if (b < nt_blocks0) { gemm_nt_body<64, 64, 2, 2, AMODE, EPI, MULTI, false, ST>(a0, b, nt_blocks0, smem); return; }
   b -= nt_blocks0;
-  if (b < nt_blocks1) gemm_nt_body<64, 64, 2, 2, AMODE, EPI, MULTI>(a1, b, nt_blocks1, smem);
+  if (b < nt_blocks1) gemm_nt_body<64, 64, 2, 2, AMODE, EPI, MULTI, false, ST>(a1, b, nt_blocks1, smem);
 }
 
 template <int AMODE, int EPI, bool MULTI>
 int launch_group(const GroupArgs& g, size_t smem, int blocks, hipStream_t st) {
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
-  hipLaunchKernelGGL((gemm_group_kernel<AMODE, EPI, MULTI>), dim3(blocks), dim3(256), smem, st, g.nt_blocks[0], g.nt_blocks[1], g.nt[0], g.nt[1]);
+  if (g_sln_store_policy & SLN_STORE_NT_WT)
+    hipLaunchKernelGGL((gemm_group_kernel<AMODE, EPI, MULTI, SLN_ST_WT>), dim3(blocks), dim3(256), smem, st, g.nt_blocks[0], g.nt_blocks[1], g.nt[0], g.nt[1]);
+  else
+    hipLaunchKernelGGL((gemm_group_kernel<AMODE, EPI, MULTI, SLN_ST_PLAIN>), dim3(blocks), dim3(256), smem, st, g.nt_blocks[0], g.nt_blocks[1], g.nt[0], g.nt[1]);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -38,8 +41,11 @@ inline bool nt_multi(const GemmNTArgs& a) { return a.A.nseg > 1; }
 
 template <int AMODE, int EPI, bool MULTI>
 int raise_lds_limit() {
-  return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_group_kernel<AMODE, EPI, MULTI>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  int r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_group_kernel<AMODE, EPI, MULTI, SLN_ST_PLAIN>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_group_kernel<AMODE, EPI, MULTI, SLN_ST_WT>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  return r;
 }
 
 }  // namespace

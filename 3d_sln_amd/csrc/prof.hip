@@ -3,8 +3,18 @@
 #include <vector>
 #include "../../include/sln_hip.h"
 #include "sln_prof.h"
+#include "sln_common.h"
 
 bool g_sln_prof_on = false;
+// SLN_STORE_POLICY: bits of SLN_STORE_* (sln_common.h); unset, empty or malformed = the shipped default
+int sln_parse_store_policy(const char* v, int dflt) {
+  if (!v || !*v) return dflt;
+  char* end = nullptr;
+  const long x = std::strtol(v, &end, 10);
+  if (*end != 0 || x < 0 || (x & ~(long)SLN_STORE_ALL)) return dflt;
+  return (int)x;
+}
+int g_sln_store_policy = sln_parse_store_policy(std::getenv("SLN_STORE_POLICY"), SLN_STORE_DEFAULT);
 int g_sln_deterministic = [] { const char* v = std::getenv("SLN_DETERMINISTIC"); return (v && v[0] == '1') ? 1 : 0; }();
 
 namespace {
@@ -30,6 +40,13 @@ void sln_prof_end(hipStream_t st) {
 
 extern "C" int sln_set_deterministic(int on) { g_sln_deterministic = on != 0; return 0; }
 extern "C" int sln_get_deterministic(void) { return g_sln_deterministic; }
+extern "C" int sln_set_store_policy(int bits) {
+  if (bits < 0 || (bits & ~SLN_STORE_ALL)) return SLN_E_BADARG;
+  g_sln_store_policy = bits;
+  return 0;
+}
+extern "C" int sln_get_store_policy(void) { return g_sln_store_policy; }
+extern "C" int sln_parse_store_policy_env(const char* value, int dflt) { return sln_parse_store_policy(value, dflt); }
 extern "C" int sln_prof_enable(int enable) {
   g_sln_prof_on = enable != 0;
   return 0;

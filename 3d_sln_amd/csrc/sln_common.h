@@ -287,6 +287,24 @@ __device__ __forceinline__ float wave_sum_halves(float v) {   // lanes l and l^3
   return v + __shfl_xor(v, 32, 64);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Store policy of the NT GEMM epilogues (LAB_NOTES 31).  A plain store leaves its line dirty in the producing XCD's L2 until the
+// kernel ends; an epilogue dirties its whole tile in one burst, and the end-of-kernel release then writes every line back before
+// the dependent launch may start.  A write-through (sc1) store sends the bytes on while the other workgroups still compute.  Values
+// are the same either way.  The launchers read the process-wide word (prof.hip: SLN_STORE_POLICY / sln_set_store_policy) and pick
+// the kernel instantiation: the store form is a template parameter of the bodies, not a kernel argument (a run-time flag put a
+// branch around each of a lane's 16 stores and cost the step 44 us).
+// ---------------------------------------------------------------------------------------------
+enum { SLN_STORE_PLAIN = 0, SLN_STORE_NT_WT = 1, SLN_STORE_ALL = 1, SLN_STORE_DEFAULT = SLN_STORE_NT_WT };
+extern int g_sln_store_policy;
+enum { SLN_ST_PLAIN = 0, SLN_ST_WT = 1 };      // ST of gemm_nt_body / gemm_nt_body16 / gemm_nt_small_body
+// one element of Y, 4 bytes per lane: plain, or write-through (global_store_dword ... sc1; relaxed, agent scope: no fence)
+template <int ST>
+__device__ __forceinline__ void sln_st_y(float* p, float v) {
+  if (ST == SLN_ST_WT) __hip_atomic_store((float __attribute__((address_space(1)))*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+}
+
 static inline int sln_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Zero-fill as a kernel, for buffers a caller may have just re-allocated inside a stream capture.  A captured hipMemsetAsync on

@@ -11,3 +11,5 @@ long sln_vae_engine_leaf_launches(const SlnVae* h);
 long sln_vae_engine_tail_launches(const SlnVae* h);
 // fp16-MFMA Linear launches an engine issued so far (vae_engine.hip; read by sln_debug_vae_half_launches)
 long sln_vae_engine_half_launches(const SlnVae* h);
+// training iterations an engine captured into a graph so far (vae_engine.hip; read by sln_debug_vae_graph_captures)
+long sln_vae_engine_graph_captures(const SlnVae* h);

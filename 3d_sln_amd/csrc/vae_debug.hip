@@ -393,3 +393,4 @@ extern "C" int sln_debug_vae_opt(SlnDbgOpt* d, void* stream) {
 extern "C" int64_t sln_debug_vae_leaf_launches(const SlnVae* h) { return h ? (int64_t)sln_vae_engine_leaf_launches(h) : (int64_t)SLN_E_BADARG; }
 extern "C" int64_t sln_debug_vae_tail_launches(const SlnVae* h) { return h ? (int64_t)sln_vae_engine_tail_launches(h) : (int64_t)SLN_E_BADARG; }
 extern "C" int64_t sln_debug_vae_half_launches(const SlnVae* h) { return h ? (int64_t)sln_vae_engine_half_launches(h) : (int64_t)SLN_E_BADARG; }
+extern "C" int64_t sln_debug_vae_graph_captures(const SlnVae* h) { return h ? (int64_t)sln_vae_engine_graph_captures(h) : (int64_t)SLN_E_BADARG; }

@@ -150,6 +150,8 @@ struct SlnVae {
   std::vector<GemmTNArgs> tn_kind_scratch;
   bool capturing = false, tn_upload_pending = false;
   int det_seen = 0;                              // g_sln_deterministic the captured iterations were recorded with
+  int store_seen = 0;                            // g_sln_store_policy likewise (the NT launches are other instantiations)
+  long graph_captures = 0;                       // iterations captured by sln_vae_train_step so far (sln_debug_vae_graph_captures)
   bool tn_per_layer = false;                     // flush after every GraphTripleConv instead of once per pass
   int tn_slot_next[3] = {0, 0, 0};
   std::vector<GemmTNArgs> deferred;
@@ -1128,6 +1130,7 @@ int SlnVae::train_iteration(const float* eps, int mode, hipStream_t st) {
 long sln_vae_engine_leaf_launches(const SlnVae* h) { return h->leaf_launches; }        // for the test hook in vae_debug.hip
 long sln_vae_engine_tail_launches(const SlnVae* h) { return h->tail_launches; }
 long sln_vae_engine_half_launches(const SlnVae* h) { return h->half_launches; }
+long sln_vae_engine_graph_captures(const SlnVae* h) { return h->graph_captures; }
 
 // =============================================================================================
 // C ABI
@@ -1555,6 +1558,7 @@ int sln_vae_train_step(SlnVae* h, const float* eps, float kl_weight, float lr, f
     if (draw != h->draw_eps) { HIP_RET(hipStreamSynchronize(st)); h->draw_eps = draw; h->drop_graphs(); }
   }
   if (h->det_seen != g_sln_deterministic) { h->det_seen = g_sln_deterministic; h->drop_graphs(); }   // other launch sequence: re-capture
+  if (h->store_seen != g_sln_store_policy) { h->store_seen = g_sln_store_policy; h->drop_graphs(); }  // other kernel instantiations: re-capture
   if (use_graph && st != nullptr) {
     hipGraphExec_t& ge = h->graph_exec[mode];
     if (!ge || h->graph_O[mode] != h->O || h->graph_T[mode] != h->T) {
@@ -1575,6 +1579,7 @@ int sln_vae_train_step(SlnVae* h, const float* eps, float kl_weight, float lr, f
       (void)hipGraphDestroy(graph);
       if (e != hipSuccess) { ge = nullptr; return (int)e; }
       h->graph_O[mode] = h->O; h->graph_T[mode] = h->T;
+      ++h->graph_captures;
     }
     HIP_RET(hipGraphLaunch(ge, st));
     h->enc_training = h->dec_training = h->step_training; h->have_enc = h->have_dec = true; h->z_from_latent = true;

@@ -267,6 +267,20 @@ int sln_prof_enable(int enable);
  * re-captured. */
 int sln_set_deterministic(int on);
 int sln_get_deterministic(void);
+/* Store policy of the NT GEMM epilogues (also: environment SLN_STORE_POLICY=<bits> at load time).  bit 0 (the default, 1): the
+ * forward Linears and dgrads store Y write-through, so the bytes leave the producing XCD's L2 while the launch still runs instead
+ * of behind its last workgroup.  0 = plain stores everywhere.  Values never depend on it.  An unknown bit is SLN_E_BADARG and
+ * leaves the policy as it was.  The word is process-wide: every single-problem and grouped NT launch reads it when it is ISSUED -
+ * the training step, the forward / inference passes, the bare GraphTripleConv calls and the single-launch fallback of a room group
+ * (the multi-room NT launches keep plain stores).  Only sln_vae_train_step follows a change through a graph: it drops the iterations
+ * it captured under the other word and captures again (sln_debug_vae_graph_captures counts).  A graph a CALLER captured around
+ * launches of this library (torch.cuda.graph around a refinement iteration, say) replays the instantiations it recorded: set the
+ * policy before capturing.
+ * sln_parse_store_policy_env: what the loader makes of a value of the environment variable when `dflt` is the built-in default
+ * (host only; NULL, empty, malformed or unknown bits = dflt). */
+int sln_set_store_policy(int bits);
+int sln_get_store_policy(void);
+int sln_parse_store_policy_env(const char* value, int dflt);
 /* Test hook (host only, no device work): the workgroup table of the per-pass wgrad launch (csrc/sln_gemm.h: TnMultiMeta) for n
  * problems given as (rows, outputs, inputs).  Returns the number of workgroups (< 0: error), fills rows_per_block[n] and
  * items[3 * workgroup] = (problem or -1 for padding, output tile, row chunk). */
@@ -501,6 +515,9 @@ int64_t sln_debug_vae_leaf_launches(const SlnVae* h);
  * the two-half form, a problem list past the table).  A captured iteration counts once.  By default the leaf jobs and the
  * decoder's assembly backward ride in that launch (SLN_TN_MIXED=1: neither, =2: the leaf jobs only). */
 int64_t sln_debug_vae_tail_launches(const SlnVae* h);
+/* Running count of the iterations sln_vae_train_step captured into a graph for this engine (first use of a mode, a new batch shape,
+ * and every change that drops the captured iterations: deterministic mode, the store policy, the eps source, ...). */
+int64_t sln_debug_vae_graph_captures(const SlnVae* h);
 /* Running count of the fp16-MFMA Linear launches an engine issued (sln_vae_set_gemm_precision). */
 int64_t sln_debug_vae_half_launches(const SlnVae* h);
 
