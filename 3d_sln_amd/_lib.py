@@ -232,6 +232,9 @@ SIGNATURES = {
     "sln_set_store_policy": (C.c_int, [C.c_int]),
     "sln_get_store_policy": (C.c_int, []),
     "sln_parse_store_policy_env": (C.c_int, [C.c_char_p, C.c_int]),
+    "sln_set_tn_split": (C.c_int, [C.c_int]),
+    "sln_get_tn_split": (C.c_int, []),
+    "sln_parse_tn_split_env": (C.c_int, [C.c_char_p, C.c_int]),
     "sln_debug_tn_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "sln_debug_tn_plan_mixed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "sln_prof_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),

@@ -1549,11 +1549,295 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTNArgs& a, const int bx, 
 }
 
 
+// ---------------------------------------------------------------------------------------------
+// TN kernel (wgrad) on the 16-bit matrix pipe: every operand value as three bf16 parts (LAB_NOTES 32)
+// ---------------------------------------------------------------------------------------------
+// gemm_tn_body spends 32 v_mfma_f32_32x32x2_f32 x 64 clocks per wave and 32-row tile.  Here each transformed fp32 value v is split
+// while it is staged: p1 = bf16(v), p2 = bf16(v - p1), p3 = bf16(v - p1 - p2) (round to nearest; both differences are exact in fp32,
+// and bf16 has fp32's exponent range: no scale, no clamp, a gradient of 1e-30 splits like one of 1), and a 16-row k-step is six
+// v_mfma_f32_32x32x16_bf16 per accumulator, smallest first: g1 x3, g3 x1, g2 x2, g1 x2, g2 x1, g1 x1.  The three dropped products are
+// below 2^-24 of g x.  12 MFMAs x 32 clocks per wave and tile.
+// Everything around that is gemm_tn_body's: the tables, the loads and their register stages, the transforms, the fp32 bias sum, the
+// wave split (16 of the tile's 32 rows, 32 of X's columns, two accumulators) and the epilogue - except that accumulator ja holds the
+// output rows n0 + 32 ja + i (the transposed read hands a lane ONE column; any fixed permutation of dW's rows is as good as another).
+// LDS: one row-major bf16 image [32 k rows][64 columns] (128-byte rows, 4 KB) per part, operand and buffer = 48 KB, the size of the
+// fp32 tiles.  A thread writes its four columns of a part with one 8-byte store; fragments come out with ds_read_b64_tr_b16 (4 rows x
+// 16 columns per group of 16 lanes).  The 32 lanes of a half read 4 rows x 64 bytes: at a 128-byte stride rows q and q + 2 would meet
+// on the same banks (2-way), so the 64-byte halves of rows 2, 3 (mod 4) are swapped (byte ^= ((row >> 1) & 1) << 6) - the four rows
+// then cover the four quarters of the 256-byte bank row.  No padding (padded images would not fit three workgroups per CU).
+// Operands that are already broken come out differently from the fp32 body: v = +-inf gives p1 = inf and v - p1 = NaN, and a finite
+// |v| above bf16's largest value less half a step (3.39e38 (1 - 2^-9)) rounds p1 to inf likewise - NaN where the fp32 body gives inf.
+// The transposed read needs EXEC = all ones: the body runs under workgroup-uniform branches only and no lane is ever masked.
+typedef __bf16 sln_bf16x8 __attribute__((ext_vector_type(8)));
+typedef short sln_s16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) sln_s16x4* sln_lds_s16x4p;
+
+__device__ __forceinline__ unsigned tn_cvt_pk_bf16(float lo, float hi) {      // (no builtin; hipcc converts element by element)
+  unsigned r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+// two values -> their three bf16 parts, packed (lo, hi)
+__device__ __forceinline__ void tn_split2(float a, float b, unsigned& p1, unsigned& p2, unsigned& p3) {
+  p1 = tn_cvt_pk_bf16(a, b);
+  a -= __uint_as_float(p1 << 16); b -= __uint_as_float(p1 & 0xffff0000u);
+  p2 = tn_cvt_pk_bf16(a, b);
+  a -= __uint_as_float(p2 << 16); b -= __uint_as_float(p2 & 0xffff0000u);
+  p3 = tn_cvt_pk_bf16(a, b);
+}
+__device__ __forceinline__ sln_bf16x8 tn_tr_frag(const char* p) {             // k = 8 h .. 8 h + 7 of the lane's column: rows +0..3, +4..7
+  const sln_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((sln_lds_s16x4p)(p));
+  const sln_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((sln_lds_s16x4p)(p + 4 * 128));
+  return __builtin_bit_cast(sln_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+template <bool G_X2, bool XG>
+__device__ __forceinline__ void gemm_tn_split_body(const GemmTNArgs& a, const int bx, const int by, char* smem) {
+  constexpr int BM = 64, BN = 64;
+  constexpr int TPR = 16, RPP = 16;                   // threads per row, rows per staging pass (two passes per operand and tile)
+  constexpr int ROWB = 128, IMG = BK * ROWB, OPB = 3 * IMG, BUFB = 2 * OPB;      // bytes: image row, image, operand (3 parts), buffer (G, X)
+  static_assert(BK == 32 && 2 * BUFB == 2 * BK * (BM + TN_PAD + BN + TN_PAD) * 4, "the bf16 images fill the fp32 tiles' LDS (tn_smem_bytes)");
+  float4* coefG = reinterpret_cast<float4*>(smem);          // [BM]
+  float4* coefX = coefG + BM;                               // [BN]
+  char* img = reinterpret_cast<char*>(coefX + BN);          // [2 buffers][G, X][3 parts][BK rows][128 bytes]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tiles_k = (a.Kin + BN - 1) / BN;
+  const int n0 = (bx / tiles_k) * BM, k0 = (bx % tiles_k) * BN;
+  const int rbeg = by * a.rows_per_block;
+  const int rend = min(a.R, rbeg + a.rows_per_block);
+
+  float* coefGp = reinterpret_cast<float*>(coefG);            // G_X2: [4 kinds][BM], see gemm_tn_body
+  if (tid < BM) {
+    const int c = tid;
+    const float4 v = coef_for_col(a.G, n0 + c);
+    if (G_X2) { coefGp[c] = v.x; coefGp[BM + c] = v.y; coefGp[2 * BM + c] = v.z; coefGp[3 * BM + c] = v.w; }
+    else coefG[c] = v;
+  } else if (tid < BM + BN) {
+    const int c = tid - BM;
+    coefX[c] = coef_for_col(a.X, k0 + c);
+  }
+
+  const int ca = 4 * (tid % TPR), ra0 = tid / TPR;          // this thread's four columns and first row, of both operands
+  const ColSel gs = pick_col(a.G, n0 + ca);
+  const ColSel xs = pick_col(a.X, k0 + ca);
+
+  const int ntiles = (rend - rbeg + BK - 1) / BK;
+  const int last = ntiles - 1;          // ntiles >= 1: every launched block owns at least one row
+  constexpr int NST = 2;
+  float4 g1[NST][2], g2[NST][2], x1[NST][2];
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int* x_ip = xs.which == 2 ? a.X.idx_b : a.X.idx_a;
+  if (x_ip == nullptr) x_ip = a.X.idx_a ? a.X.idx_a : a.X.idx_b;
+  const float* g_x2 = gs.x2 ? gs.x2 : gs.x1;
+  const int g_ld2 = gs.x2 ? gs.ld2 : gs.ld1;
+  int xi[NST][2];
+  auto iload = [&](int rt, auto stage) {
+    constexpr int S = decltype(stage)::value;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) xi[S][p] = ldi(x_ip + min(rbeg + rt * BK + ra0 + RPP * p, rend - 1));
+  };
+  auto gload = [&](int rt, int rt_idx, auto stage) {
+    constexpr int S = decltype(stage)::value;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int row = min(rbeg + rt * BK + ra0 + RPP * p, rend - 1);
+      g1[S][p] = ld4(gs.x1 + (size_t)row * gs.ld1);
+      if (G_X2) g2[S][p] = ld4(g_x2 + (size_t)row * g_ld2);
+    }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int row = min(rbeg + rt * BK + ra0 + RPP * p, rend - 1);
+      const int r = XG ? (xs.which ? xi[S][p] : row) : row;
+      x1[S][p] = ld4(xs.x1 + (size_t)r * xs.ld1);
+    }
+    if (XG) iload(rt_idx, stage);
+  };
+  float4 dbacc = z4;
+  float4 cG[4], cX[4];
+  // byte offset of this thread's 8 bytes in an image (row ra0, + 16 rows for the second pass: the swapped halves do not move)
+  const int woff = ra0 * ROWB + ((2 * ca) ^ (((ra0 >> 1) & 1) << 6));
+  auto put = [&](char* dst, float4 t) __attribute__((always_inline)) {
+    uint2 q1, q2, q3;
+    tn_split2(t.x, t.y, q1.x, q2.x, q3.x);
+    tn_split2(t.z, t.w, q1.y, q2.y, q3.y);
+    *reinterpret_cast<uint2*>(dst) = q1;
+    *reinterpret_cast<uint2*>(dst + IMG) = q2;
+    *reinterpret_cast<uint2*>(dst + 2 * IMG) = q3;
+  };
+  // the staging passes, as gemm_tn_body's scheduled loop cuts them: pass p of tile rt + 1 goes to buffer buf ^ 1 and its register
+  // stage is refilled with tile rt + 3.  Rows behind the chunk's end are stored as zeros (G only, see gemm_tn_body).
+  auto pieceG = [&](int rt, int buf, int p, auto stage) __attribute__((always_inline)) {
+    constexpr int S = decltype(stage)::value;
+    const int rl = ra0 + RPP * p;
+    const bool v = (rbeg + (rt + 1) * BK + rl) < rend;
+    float4 t = G_X2 ? xform_planar(g1[S][p], g2[S][p], *reinterpret_cast<const float4*>(coefGp + ca),
+                                   *reinterpret_cast<const float4*>(coefGp + BM + ca), *reinterpret_cast<const float4*>(coefGp + 2 * BM + ca),
+                                   *reinterpret_cast<const float4*>(coefGp + 3 * BM + ca))
+                    : xform1(g1[S][p], cG);
+    t.x = v ? t.x : 0.f; t.y = v ? t.y : 0.f; t.z = v ? t.z : 0.f; t.w = v ? t.w : 0.f;
+    dbacc.x += t.x; dbacc.y += t.y; dbacc.z += t.z; dbacc.w += t.w;
+    put(img + (buf ^ 1) * BUFB + p * RPP * ROWB + woff, t);
+    __builtin_amdgcn_sched_barrier(0);
+    const int row = min(rbeg + min(rt + 3, last) * BK + rl, rend - 1);
+    g1[S][p] = ld4(gs.x1 + (size_t)row * gs.ld1);
+    if (G_X2) g2[S][p] = ld4(g_x2 + (size_t)row * g_ld2);
+  };
+  auto pieceX = [&](int rt, int buf, int p, auto stage) __attribute__((always_inline)) {
+    constexpr int S = decltype(stage)::value;
+    put(img + (buf ^ 1) * BUFB + OPB + p * RPP * ROWB + woff, xform1(x1[S][p], cX));
+    __builtin_amdgcn_sched_barrier(0);
+    const int row = min(rbeg + min(rt + 3, last) * BK + ra0 + RPP * p, rend - 1);
+    const int r = XG ? (xs.which ? xi[S][p] : row) : row;
+    x1[S][p] = ld4(xs.x1 + (size_t)r * xs.ld1);
+  };
+  auto pieceI = [&](int rt, int p, auto stage) __attribute__((always_inline)) {
+    constexpr int S = decltype(stage)::value;
+    if (XG) xi[S][p] = ldi(x_ip + min(rbeg + min(rt + 5, last) * BK + ra0 + RPP * p, rend - 1));
+  };
+
+  f32x16 acc[2];                           // [ja]: output rows n0 + 32 ja + i, columns k0 + 32 wc + lane % 32
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+
+  using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>;
+  if (XG) { iload(0, S0{}); iload(min(1, last), S1{}); }
+  gload(0, min(2, last), S0{});
+  gload(min(1, last), min(3, last), S1{});
+  __syncthreads();            // coefficient tables visible
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { if (!G_X2) cG[j] = coefG[ca + j]; cX[j] = coefX[ca + j]; }
+  // tile 0 out of stage 0 (pieces of "tile -1": they store tile 0 into buffer 0 and refill the stage with tile 2)
+  pieceG(-1, 1, 0, S0{}); pieceG(-1, 1, 1, S0{}); pieceX(-1, 1, 0, S0{}); pieceX(-1, 1, 1, S0{});
+  if (XG) { pieceI(-1, 0, S0{}); pieceI(-1, 1, S0{}); }
+  __syncthreads();
+  const int lrow = lane & 31, lk = lane >> 5;
+  const int wr = wave >> 1, wc = wave & 1;
+  // transposed reads: lane 4 q + p of a 16-lane group gives the address of row q, columns 4 p .. 4 p + 3 of the group's 4 x 16
+  // block and receives column (lane % 16) of the four rows.  Groups 0 / 1 of a half: columns 0-15 / 16-31 of the wave's 32.
+  const int tq = (lane >> 2) & 3, tp = lane & 3;
+  const int rbase = (16 * wr + 8 * lk + tq) * ROWB + 32 * ((lane >> 4) & 1) + 8 * tp;
+  const int aG0 = rbase + 64 * (tq >> 1), aG1 = rbase + 64 * ((tq >> 1) ^ 1), aX = OPB + rbase + 64 * (wc ^ (tq >> 1));
+  sln_bf16x8 fg[3][2], fx[3];
+  // fragments are read as the products come to need them (all eighteen up front are 36 registers: the two-source kernels then
+  // pass 168 and lose the third workgroup per CU): g1 and x3 behind the barrier, g3 and x1 under the first product, g2 and x2 under
+  // the second.  Every read of a buffer is issued before the barrier that ends its tile.
+  using P1 = std::integral_constant<int, 0>; using P2 = std::integral_constant<int, 1>; using P3 = std::integral_constant<int, 2>;
+  auto rdG = [&](int buf, auto part) __attribute__((always_inline)) {
+    constexpr int P = decltype(part)::value;
+    fg[P][0] = tn_tr_frag(img + buf * BUFB + P * IMG + aG0);
+    fg[P][1] = tn_tr_frag(img + buf * BUFB + P * IMG + aG1);
+  };
+  auto rdX = [&](int buf, auto part) __attribute__((always_inline)) {
+    constexpr int P = decltype(part)::value;
+    fx[P] = tn_tr_frag(img + buf * BUFB + P * IMG + aX);
+  };
+  rdG(0, P1{}); rdX(0, P3{});
+#define SLN_SB __builtin_amdgcn_sched_barrier(0)
+  // one product of the six for both accumulators (gp, xp: parts 0 .. 2), hook() behind it - every staging pass sits behind its own
+  // pair of MFMAs, as in gemm_tn_body's scheduled loop
+  auto mma2 = [&](auto gp, auto xp, auto&& hook) __attribute__((always_inline)) {
+    constexpr int GP = decltype(gp)::value, XP = decltype(xp)::value;
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fg[GP][0], fx[XP], acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fg[GP][1], fx[XP], acc[1], 0, 0, 0);
+    SLN_SB; hook(); SLN_SB;
+  };
+  auto sbody = [&](int rt, auto stage_next) __attribute__((always_inline)) {
+    const int buf = rt & 1;
+    rdG(buf, P3{}); rdX(buf, P1{});
+    SLN_SB;
+    mma2(P1{}, P3{}, [&]() __attribute__((always_inline)) { pieceG(rt, buf, 0, stage_next); });
+    mma2(P3{}, P1{}, [&]() __attribute__((always_inline)) { rdG(buf, P2{}); rdX(buf, P2{}); SLN_SB; pieceG(rt, buf, 1, stage_next); });
+    mma2(P2{}, P2{}, [&]() __attribute__((always_inline)) { pieceX(rt, buf, 0, stage_next); });
+    mma2(P1{}, P2{}, [&]() __attribute__((always_inline)) { pieceX(rt, buf, 1, stage_next); });
+    mma2(P2{}, P1{}, [&]() __attribute__((always_inline)) { pieceI(rt, 0, stage_next); pieceI(rt, 1, stage_next); });
+    mma2(P1{}, P1{}, [&]() __attribute__((always_inline)) {});
+    __syncthreads();
+    rdG(buf ^ 1, P1{}); rdX(buf ^ 1, P3{});
+    SLN_SB;
+  };
+#undef SLN_SB
+  for (int rt = 0; rt < ntiles; rt += 2) { sbody(rt, S1{}); sbody(rt + 1, S0{}); }
+
+  // ---- the two row halves meet: wave (wr, wc) finishes accumulator ja = wr of column half wc (gemm_tn_body's epilogue) ----
+  __syncthreads();                          // every wave is done with the images
+  float* red = reinterpret_cast<float*>(img);      // [wave 4][16][64] floats = 16 KB of the images
+  {
+    float* dst = red + (wave * 16) * 64 + lane;
+    if (wr == 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dst[r * 64] = tn_acc_read(acc[1][r]);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dst[r * 64] = tn_acc_read(acc[0][r]);
+    }
+  }
+  __syncthreads();
+  {
+    const float* src = red + ((wave ^ 2) * 16) * 64 + lane;
+    const float sc = a.sgd_step != nullptr ? -a.sgd_step[0] : 1.f;
+    const int k = k0 + 32 * wc + lrow;
+    float* dcol = a.dW + min(k, a.Kin - 1);
+    const bool kv = k < a.Kin;
+    // sum order (row half 0) + (row half 1) whichever wave finishes
+    if (wr == 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = (tn_acc_read(acc[0][r]) + src[r * 64]) * sc;
+        const int n = n0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        if (kv && n < a.Nout) sln_gatomic_add(dcol + (size_t)n * a.lddw, v);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = (src[r * 64] + tn_acc_read(acc[1][r])) * sc;
+        const int n = n0 + 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        if (kv && n < a.Nout) sln_gatomic_add(dcol + (size_t)n * a.lddw, v);
+      }
+    }
+  }
+
+  if (a.db != nullptr && (bx % tiles_k) == 0) {
+#pragma unroll
+    for (int off = TPR; off < 64; off <<= 1) {
+      dbacc.x += __shfl_xor(dbacc.x, off, 64); dbacc.y += __shfl_xor(dbacc.y, off, 64);
+      dbacc.z += __shfl_xor(dbacc.z, off, 64); dbacc.w += __shfl_xor(dbacc.w, off, 64);
+    }
+    __syncthreads();                          // the accumulator hand-over above is done with `red`
+    float4* dbs = reinterpret_cast<float4*>(red);            // [4 waves][TPR]
+    if (lane < TPR) dbs[wave * TPR + lane] = dbacc;
+    __syncthreads();
+    if (tid < TPR) {
+      const float4 p0 = dbs[tid], p1 = dbs[TPR + tid], p2 = dbs[2 * TPR + tid], p3 = dbs[3 * TPR + tid];
+      const int n = n0 + 4 * tid;
+      const float sb = a.sgd_step != nullptr ? -a.sgd_step[0] : 1.f;
+      if (n + 0 < a.Nout) sln_gatomic_add(a.db + n + 0, (((p0.x + p1.x) + p2.x) + p3.x) * sb);
+      if (n + 1 < a.Nout) sln_gatomic_add(a.db + n + 1, (((p0.y + p1.y) + p2.y) + p3.y) * sb);
+      if (n + 2 < a.Nout) sln_gatomic_add(a.db + n + 2, (((p0.z + p1.z) + p2.z) + p3.z) * sb);
+      if (n + 3 < a.Nout) sln_gatomic_add(a.db + n + 3, (((p0.w + p1.w) + p2.w) + p3.w) * sb);
+    }
+  }
+}
+
+// whether a problem runs the split body under the split word (sln_common.h: g_sln_tn_split).  A function of the PROBLEM - on the host
+// (single-problem launch) and in the table kernels alike - so every route takes the same body for it: problems that step the
+// parameters in their epilogue (the refinement loop) and the multi-room programs' problems (keep_f32) stay on the fp32 pipe.
+__host__ __device__ __forceinline__ bool tn_split_takes(const GemmTNArgs& a) { return a.sgd_step == nullptr && a.keep_f32 == 0; }
+
 // One item of the mixed wgrad table (sln_gemm.h: TnMixedMeta) - the body its problem needs, by the item's gather bit (uniform over
 // the workgroup).  Shared by gemm_tn_mixed_kernel (gemm_f32.hip) and the wgrad half of vae_tail_kernel (vae_kernels.hip).
-template <bool G_X2>
+// SPLIT (the launcher's template argument: split word set, not deterministic): problems that take it run gemm_tn_split_body -
+// chosen here, once per workgroup, uniformly.  SPLIT = false is the kernel of before the split body, instruction for instruction.
+template <bool G_X2, bool SPLIT = false>
 __device__ __forceinline__ void gemm_tn_mixed_item(const GemmTNArgs* __restrict__ probs, const TnMultiItem it, char* smem) {
   if (it.prob < 0) return;
+  if (SPLIT && tn_split_takes(probs[it.prob])) {
+    if (it.xg) gemm_tn_split_body<G_X2, true>(probs[it.prob], it.tile, it.chunk, smem);
+    else gemm_tn_split_body<G_X2, false>(probs[it.prob], it.tile, it.chunk, smem);
+    return;
+  }
   if (it.xg) gemm_tn_body<64, 64, 2, 2, G_X2, true>(probs[it.prob], it.tile, it.chunk, smem);
   else gemm_tn_body<64, 64, 2, 2, G_X2, false>(probs[it.prob], it.tile, it.chunk, smem);
 }

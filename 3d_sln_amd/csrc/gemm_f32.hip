@@ -199,6 +199,26 @@ __global__ __launch_bounds__(256) void gemm_tn_mixed_kernel(const GemmTNArgs* __
   gemm_tn_mixed_item<G_X2>(probs, meta->item[blockIdx.x], smem);
 }
 
+// ---- the same three launches under the split word (sln_common.h): kernels of their own, so that the ones above stay what they were.
+// A single problem is decided on the host; the table kernels ask each workgroup's problem (gemm_tn_mixed_item).
+template <bool G_X2, bool XG>
+__global__ __launch_bounds__(256) void gemm_tn_split_kernel(const GemmTNArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemm_tn_split_body<G_X2, XG>(a, blockIdx.x, blockIdx.y, smem);
+}
+template <bool G_X2, bool XG>
+__global__ __launch_bounds__(256) void gemm_tn_multi_split_kernel(const GemmTNArgs* __restrict__ probs, const TnMultiMeta* __restrict__ meta) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  TnMultiItem it = meta->item[blockIdx.x];
+  it.xg = XG ? 1 : 0;                          // the per-kind table carries no gather bit: the launch's kind stands for every item
+  gemm_tn_mixed_item<G_X2, true>(probs, it, smem);
+}
+template <bool G_X2>
+__global__ __launch_bounds__(256) void gemm_tn_mixed_split_kernel(const GemmTNArgs* __restrict__ probs, const TnMixedMeta* __restrict__ meta) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemm_tn_mixed_item<G_X2, true>(probs, meta->item[blockIdx.x], smem);
+}
+
 template <int BM, int BN, int WM, int WN, bool G_X2>
 int launch_tn(const GemmTNArgs& a, hipStream_t st) {
   const size_t smem = tn_smem_bytes(BM, BN);
@@ -206,6 +226,12 @@ int launch_tn(const GemmTNArgs& a, hipStream_t st) {
   const int gy = sln_cdiv(a.R, a.rows_per_block);
   if (gx <= 0 || gy <= 0) return 0;
   if (!tn_supported(a)) return -1;
+  if (sln_tn_split_launch() && tn_split_takes(a)) {
+    if (tn_gathers(a)) hipLaunchKernelGGL((gemm_tn_split_kernel<G_X2, true>), dim3(gx, gy), dim3(256), smem, st, a);
+    else hipLaunchKernelGGL((gemm_tn_split_kernel<G_X2, false>), dim3(gx, gy), dim3(256), smem, st, a);
+    SLN_CHECK_LAUNCH();
+    return 0;
+  }
   if (tn_gathers(a)) hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, WM, WN, G_X2, true>), dim3(gx, gy), dim3(256), smem, st, a);
   else hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, WM, WN, G_X2, false>), dim3(gx, gy), dim3(256), smem, st, a);
   SLN_CHECK_LAUNCH();
@@ -281,6 +307,15 @@ int sln_gemm_init() {
 #undef SLN_SET_TNM
   if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+#define SLN_SET_TNS(X2, XG)                                                                                       \
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_split_kernel<X2, XG>),             \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_multi_split_kernel<X2, XG>),       \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  SLN_SET_TNS(true, true) SLN_SET_TNS(true, false) SLN_SET_TNS(false, true) SLN_SET_TNS(false, false)
+#undef SLN_SET_TNS
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (!r) r = sln_gemm_group_init();
   if (!r) r = sln_vae_tail_init();
   done = r == 0;
@@ -469,11 +504,19 @@ int sln_tn_mixed_plan(GemmTNArgs* probs, int n, TnMixedMeta* meta, int* blocks, 
 }
 
 int sln_launch_gemm_tn_multi(const GemmTNArgs* dev_probs, const TnMultiMeta* dev_meta, int blocks, bool x2, bool xg, double flops,
-                             hipStream_t st) {
+                             hipStream_t st, bool all_keep_f32) {
   if (blocks <= 0) return 0;
   SlnProfScope prof(SLN_FAM_GEMM_TN, flops, st);
   const size_t smem = tn_smem_bytes(64, 64);
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
+  if (sln_tn_split_launch() && !all_keep_f32) {
+    if (x2 && xg) hipLaunchKernelGGL((gemm_tn_multi_split_kernel<true, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+    else if (x2) hipLaunchKernelGGL((gemm_tn_multi_split_kernel<true, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+    else if (xg) hipLaunchKernelGGL((gemm_tn_multi_split_kernel<false, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+    else hipLaunchKernelGGL((gemm_tn_multi_split_kernel<false, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+    SLN_CHECK_LAUNCH();
+    return 0;
+  }
   if (x2 && xg) hipLaunchKernelGGL((gemm_tn_multi_kernel<true, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   else if (x2) hipLaunchKernelGGL((gemm_tn_multi_kernel<true, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   else if (xg) hipLaunchKernelGGL((gemm_tn_multi_kernel<false, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
@@ -487,6 +530,12 @@ int sln_launch_gemm_tn_mixed(const GemmTNArgs* dev_probs, const TnMixedMeta* dev
   SlnProfScope prof(SLN_FAM_GEMM_TN, flops, st);
   const size_t smem = tn_smem_bytes(64, 64);
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
+  if (sln_tn_split_launch()) {
+    if (x2) hipLaunchKernelGGL((gemm_tn_mixed_split_kernel<true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+    else hipLaunchKernelGGL((gemm_tn_mixed_split_kernel<false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+    SLN_CHECK_LAUNCH();
+    return 0;
+  }
   if (x2) hipLaunchKernelGGL((gemm_tn_mixed_kernel<true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   else hipLaunchKernelGGL((gemm_tn_mixed_kernel<false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   SLN_CHECK_LAUNCH();

@@ -15,6 +15,12 @@ int sln_parse_store_policy(const char* v, int dflt) {
   return (int)x;
 }
 int g_sln_store_policy = sln_parse_store_policy(std::getenv("SLN_STORE_POLICY"), SLN_STORE_DEFAULT);
+// SLN_TN_SPLIT: 0 or 1 (sln_common.h); anything else = the shipped default
+int sln_parse_tn_split(const char* v, int dflt) {
+  if (!v || (v[0] != '0' && v[0] != '1') || v[1] != 0) return dflt;
+  return v[0] - '0';
+}
+int g_sln_tn_split = sln_parse_tn_split(std::getenv("SLN_TN_SPLIT"), SLN_TN_SPLIT_DEFAULT);
 int g_sln_deterministic = [] { const char* v = std::getenv("SLN_DETERMINISTIC"); return (v && v[0] == '1') ? 1 : 0; }();
 
 namespace {
@@ -47,6 +53,13 @@ extern "C" int sln_set_store_policy(int bits) {
 }
 extern "C" int sln_get_store_policy(void) { return g_sln_store_policy; }
 extern "C" int sln_parse_store_policy_env(const char* value, int dflt) { return sln_parse_store_policy(value, dflt); }
+extern "C" int sln_set_tn_split(int word) {
+  if (word != SLN_TN_SPLIT_OFF && word != SLN_TN_SPLIT_ON) return SLN_E_BADARG;
+  g_sln_tn_split = word;
+  return 0;
+}
+extern "C" int sln_get_tn_split(void) { return g_sln_tn_split; }
+extern "C" int sln_parse_tn_split_env(const char* value, int dflt) { return sln_parse_tn_split(value, dflt); }
 extern "C" int sln_prof_enable(int enable) {
   g_sln_prof_on = enable != 0;
   return 0;

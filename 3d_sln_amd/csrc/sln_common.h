@@ -305,6 +305,17 @@ __device__ __forceinline__ void sln_st_y(float* p, float v) {
   else *p = v;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Split word of the TN (wgrad) launches (LAB_NOTES 32).  1 (the default): problems that take it (gemm_bodies.h: tn_split_takes)
+// run gemm_tn_split_body - operands as three bf16 parts on v_mfma_f32_32x32x16_bf16, fp32-grade sums; 0: every problem on the
+// fp32 matrix pipe, the kernels of before.  Deterministic mode keeps the fp32 body.  Like the store policy the word picks a kernel
+// INSTANTIATION when a launch is issued (prof.hip: SLN_TN_SPLIT / sln_set_tn_split), never a branch inside a K loop.
+// ---------------------------------------------------------------------------------------------
+enum { SLN_TN_SPLIT_OFF = 0, SLN_TN_SPLIT_ON = 1, SLN_TN_SPLIT_DEFAULT = SLN_TN_SPLIT_ON };
+extern int g_sln_tn_split;
+extern int g_sln_deterministic;
+static inline bool sln_tn_split_launch() { return g_sln_tn_split == SLN_TN_SPLIT_ON && !g_sln_deterministic; }
+
 static inline int sln_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Zero-fill as a kernel, for buffers a caller may have just re-allocated inside a stream capture.  A captured hipMemsetAsync on

@@ -33,6 +33,9 @@ struct GemmTNArgs {
   int lddw;
   int R, Nout, Kin;
   int rows_per_block;   // <= 0: choose
+  // != 0: stays on the fp32 matrix pipe whatever the split word says (gemm_bodies.h: tn_split_takes; the multi-room programs set
+  // it).  Sits in what was padding in front of the pointer below: the layout of every other field is unchanged.
+  int keep_f32;
   // SGD in the epilogue (the refinement loop's R rooms in flight, vae_engine.hip SlnVaeGroup): when set (DEVICE pointer to the step),
   // dW / db point at the PARAMETERS and receive -step * (the gradient) - the same atomic add, one pass over the weights instead of
   // three (gradient +=, then the optimizer's read of both and write)
@@ -75,8 +78,10 @@ struct TnMixedMeta { int nprob, nblocks; TnMultiItem item[SLN_TN_MIXED_ITEMS]; }
 // ~1 k rows instead of once per 256; longer still when the launch would not fit the table) and builds the item table.
 // Returns 0, or a negative value when a problem cannot run on the TN body.
 int sln_tn_multi_plan(GemmTNArgs* probs, int n, TnMultiMeta* meta, int* blocks, bool* x2, bool* xg, double* flops);
+// all_keep_f32: the caller knows that every problem of the table has keep_f32 set (the multi-room programs) - the launch is then the
+// fp32 kernel itself whatever the split word says, not the split kernel with every workgroup on its fp32 branch
 int sln_launch_gemm_tn_multi(const GemmTNArgs* dev_probs, const TnMultiMeta* dev_meta, int blocks, bool x2, bool xg, double flops,
-                             hipStream_t st);
+                             hipStream_t st, bool all_keep_f32 = false);
 // the mixed launch: plan (0, or negative: a problem the TN body cannot run, or a list past SLN_TN_MIXED_MAX / _ITEMS) and launch
 int sln_tn_mixed_plan(GemmTNArgs* probs, int n, TnMixedMeta* meta, int* blocks, bool* x2, double* flops);
 int sln_launch_gemm_tn_mixed(const GemmTNArgs* dev_probs, const TnMixedMeta* dev_meta, int blocks, bool x2, double flops, hipStream_t st);

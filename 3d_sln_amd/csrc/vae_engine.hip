@@ -151,6 +151,7 @@ struct SlnVae {
   bool capturing = false, tn_upload_pending = false;
   int det_seen = 0;                              // g_sln_deterministic the captured iterations were recorded with
   int store_seen = 0;                            // g_sln_store_policy likewise (the NT launches are other instantiations)
+  int split_seen = 0;                            // g_sln_tn_split likewise (the wgrad launches are other kernels)
   long graph_captures = 0;                       // iterations captured by sln_vae_train_step so far (sln_debug_vae_graph_captures)
   bool tn_per_layer = false;                     // flush after every GraphTripleConv instead of once per pass
   int tn_slot_next[3] = {0, 0, 0};
@@ -1559,6 +1560,7 @@ int sln_vae_train_step(SlnVae* h, const float* eps, float kl_weight, float lr, f
   }
   if (h->det_seen != g_sln_deterministic) { h->det_seen = g_sln_deterministic; h->drop_graphs(); }   // other launch sequence: re-capture
   if (h->store_seen != g_sln_store_policy) { h->store_seen = g_sln_store_policy; h->drop_graphs(); }  // other kernel instantiations: re-capture
+  if (h->split_seen != g_sln_tn_split) { h->split_seen = g_sln_tn_split; h->drop_graphs(); }          // other wgrad kernels: re-capture
   if (use_graph && st != nullptr) {
     hipGraphExec_t& ge = h->graph_exec[mode];
     if (!ge || h->graph_O[mode] != h->O || h->graph_T[mode] != h->T) {
@@ -1894,6 +1896,7 @@ struct SlnVaeGroup {
       if (kind == SK_TN) {
         for (int r = 0; r < R; ++r) {
           GemmTNArgs t = recs[r].steps[s].tn;
+          t.keep_f32 = 1;                                       // the multi-room programs stay on the fp32 matrix pipe (sln_gemm.h)
           if (io.sgd_step != nullptr && t.lddw == t.Kin) {      // SGD in the wgrad's epilogue: the add lands in the parameter itself
             for (const Unit& u : eng[r]->units)
               if (u.p.d_weight == t.dW && (t.db == nullptr || u.p.d_bias == t.db)) {
@@ -2013,7 +2016,7 @@ struct SlnVaeGroup {
           if (tr_pending) { r = (int)hipStreamWaitEvent(main_st, ev_tr, 0); tr_pending = false; }
           break;
         case L_NT: r = sln_launch_gemm_nt_small_multi(static_cast<const GemmNTArgs*>(l.tab), l.tiles, l.count, l.variant, l.gx, l.maxK, l.flops, st); break;
-        case L_TN_MULTI: r = sln_launch_gemm_tn_multi(l.tn_probs, l.tn_meta, l.blocks, l.x2, l.xg, l.flops, st); break;
+        case L_TN_MULTI: r = sln_launch_gemm_tn_multi(l.tn_probs, l.tn_meta, l.blocks, l.x2, l.xg, l.flops, st, true); break;
         case L_TN_SINGLE: r = sln_launch_gemm_tn(singles[l.single].tn, st); break;
         case L_SINGLE_STEP: r = run_single(singles[l.single], st); break;
         case SK_SCATTER_FWD: r = sln_launch_scatter_avg_fwd_multi(static_cast<const MScatterFwd*>(l.tab), l.count, l.variant, l.gx, l.gy, st); break;

@@ -1492,6 +1492,14 @@ __global__ __launch_bounds__(256) void vae_tail_kernel(const GemmTNArgs* __restr
   if (blockIdx.x >= nwg) { vae_leaf_dispatch(blockIdx.x - nwg, r.b0, r.b1, r.b2, r.b3, r.b4, r.b5, r.b6, a); return; }
   gemm_tn_mixed_item<G_X2>(probs, meta->item[blockIdx.x], smem);
 }
+// ... under the split word (sln_common.h): a kernel of its own, the one above stays what it was
+template <bool G_X2>
+__global__ __launch_bounds__(256) void vae_tail_split_kernel(const GemmTNArgs* __restrict__ probs, const TnMixedMeta* __restrict__ meta,
+                                                             const unsigned int nwg, const LeafRanges r, const LeafArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  if (blockIdx.x >= nwg) { vae_leaf_dispatch(blockIdx.x - nwg, r.b0, r.b1, r.b2, r.b3, r.b4, r.b5, r.b6, a); return; }
+  gemm_tn_mixed_item<G_X2, true>(probs, meta->item[blockIdx.x], smem);
+}
 
 // every job of the leaf launch on its LDS path (the stand-alone launchers' own conditions); deterministic mode never is
 int sln_vae_leaf_fits(const VaeLeaf& a) {
@@ -1580,6 +1588,8 @@ int sln_launch_vae_leaf(const VaeLeaf& v, hipStream_t st) {
 int sln_vae_tail_init() {
   int r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   return r;
 }
 
@@ -1592,6 +1602,12 @@ int sln_launch_vae_tail(const GemmTNArgs* dev_probs, const TnMixedMeta* dev_meta
   if (lds > smem) return -1;                 // (the tables are capped at 40 KB, the wgrad tiles take 50 KB)
   { const int e = sln_gemm_init(); if (e) return e; }       // raises the dynamic-LDS limit of this kernel too
   SlnProfScope prof(SLN_FAM_GEMM_TN, flops, st);
+  if (sln_tn_split_launch()) {
+    if (x2) hipLaunchKernelGGL((vae_tail_split_kernel<true>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
+    else hipLaunchKernelGGL((vae_tail_split_kernel<false>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
+    SLN_CHECK_LAUNCH();
+    return 0;
+  }
   if (x2) hipLaunchKernelGGL((vae_tail_kernel<true>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
   else hipLaunchKernelGGL((vae_tail_kernel<false>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
   SLN_CHECK_LAUNCH();

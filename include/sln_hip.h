@@ -281,6 +281,17 @@ int sln_get_deterministic(void);
 int sln_set_store_policy(int bits);
 int sln_get_store_policy(void);
 int sln_parse_store_policy_env(const char* value, int dflt);
+/* Split word of the wgrad (TN GEMM) launches (also: environment SLN_TN_SPLIT=0|1 at load time; anything else reads as the default).
+ * 1 (the default): a wgrad splits each operand value into three bf16 parts while staging it and sums six products per k-step on
+ * the 16-bit matrix pipe into fp32 accumulators - errors of the fp32 route's size at a fifth of its matrix-pipe time.  0: every
+ * wgrad on the fp32 matrix pipe.  Which body a problem runs depends on the word, on deterministic mode (always fp32) and on the
+ * problem (those that step the parameters in their epilogue, and the multi-room programs' problems, stay fp32) - never on the launch
+ * that carries it.  Any other value is SLN_E_BADARG and leaves the word as it was.  Read when a launch is ISSUED, like the store
+ * policy; sln_vae_train_step drops the iterations it captured under the other word (sln_debug_vae_graph_captures counts).
+ * sln_parse_tn_split_env: what the loader makes of a value of the environment variable (host only). */
+int sln_set_tn_split(int word);
+int sln_get_tn_split(void);
+int sln_parse_tn_split_env(const char* value, int dflt);
 /* Test hook (host only, no device work): the workgroup table of the per-pass wgrad launch (csrc/sln_gemm.h: TnMultiMeta) for n
  * problems given as (rows, outputs, inputs).  Returns the number of workgroups (< 0: error), fills rows_per_block[n] and
  * items[3 * workgroup] = (problem or -1 for padding, output tile, row chunk). */
