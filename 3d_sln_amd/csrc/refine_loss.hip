@@ -154,12 +154,19 @@ __global__ __launch_bounds__(256) void pool_lds_kernel(const float* __restrict__
 
 // one thread per pooled pixel of one scale and part (blockIdx.y: 0 = log-softmax / NLL over the semantic channels, 1.. = |.| over
 // DCH depth channels); overwrites pooled with d loss / d pooled.  partial = per-block {sum |diff|, sum_s CE_s / 800 / valid count}.
+//
+// MASKED (SlnRefineLoss::valid_pooled): the depth part of an invalid pooled pixel forms no difference - its target is not loaded, it
+// adds nothing to the partial and stores a gradient of exactly 0 (a branch, not a product with 0: the target may hold NaN there) -
+// and gd comes from the room's count of valid pooled pixels (depth_count) instead of the closed form; one mask byte per lane, loaded
+// once in front of the channel loops.  The semantic part needs nothing: sln_refine_loss_mask has set the labels to -100.  The
+// unmasked instantiation is the kernel of before.
 constexpr int DCH = 8;               // depth channels per thread of loss_kernel's parts 1..
-template <int NSEM>
+template <int NSEM, bool MASKED>
 __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, RefineDims d, const float* __restrict__ tgt_depth,
                                                    const int* __restrict__ labels, const float* __restrict__ inv_count,
                                                    float2* __restrict__ partial, const unsigned char* __restrict__ live,
-                                                   const float* __restrict__ pooled_ones) {
+                                                   const float* __restrict__ pooled_ones, const unsigned char* __restrict__ valid_pooled,
+                                                   const int32_t* __restrict__ depth_count) {
   const int nc = d.n_sem + d.n_dep;
   const long pp = (long)d.P * d.P;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -203,7 +210,13 @@ __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, R
         for (int c = 0; c < NSEM; ++c) if (lm >> c & 1) p[c * pp] = 0.f;
       }
     } else {                                                                       // depth channels, DCH per thread
-      const float gd = 50.f / (float)((double)(d.per_room ? 1 : d.B) * d.n_scales * d.n_dep * pp);      // 100 * 0.5 / numel
+      float gd = 50.f / (float)((double)(d.per_room ? 1 : d.B) * d.n_scales * d.n_dep * pp);      // 100 * 0.5 / numel
+      bool ok = true;
+      if (MASKED) {                                                                 // numel = n_dep * N, N the valid pooled pixels (0: no depth term)
+        const int nv = depth_count[b];
+        gd = nv > 0 ? 50.f / (float)((double)d.n_dep * nv) : 0.f;
+        ok = valid_pooled[i] != 0;
+      }
       const float* tg = tgt_depth + ((long)(b * d.n_scales + s) * d.n_dep) * pp + pix;
       float* q = p + (long)d.n_sem * pp;
       const int c0 = ((int)blockIdx.y - 1) * DCH;
@@ -216,14 +229,14 @@ __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, R
       for (int u = 0; u < DCH; ++u) {
         const int c = min(c0 + u, d.n_dep - 1);
         cst[u] = live != nullptr && pooled_ones != nullptr && live[b * d.C + d.dep0 + c] == 1;
-        a[u] = cst[u] ? one_p : q[c * pp]; t[u] = tg[c * pp];
+        a[u] = cst[u] ? one_p : q[c * pp]; t[u] = ok ? tg[c * pp] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < DCH; ++u) {
         if (c0 + u < d.n_dep) {
           const float diff = a[u] - t[u];
-          l_abs += fabsf(diff);
-          if (!cst[u]) q[(c0 + u) * pp] = diff > 0.f ? gd : (diff < 0.f ? -gd : 0.f);
+          l_abs += ok ? fabsf(diff) : 0.f;
+          if (!cst[u]) q[(c0 + u) * pp] = !ok ? 0.f : (diff > 0.f ? gd : (diff < 0.f ? -gd : 0.f));
         }
       }
     }
@@ -240,8 +253,9 @@ __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, R
 
 // per_room: workgroup b sums room b's partials - gx blocks per part row of which the room owns bpr consecutive ones (a block of
 // loss_kernel never straddles two rooms, checked by the launcher) - in the order the B = 1 launch sums its own
+// depth_count (the masked route): the mean's element number is n_dep * depth_count[b] instead of the closed form; 0 gives depth 0
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float2* __restrict__ partial, int n, RefineDims d, float* __restrict__ loss_out,
-                                                            const int gx, const int bpr) {
+                                                            const int gx, const int bpr, const int32_t* __restrict__ depth_count) {
   __shared__ double red[4][2];
   double a = 0.0, c = 0.0;
   if (d.per_room) {
@@ -255,7 +269,11 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float2* __rest
   __syncthreads();
   if (threadIdx.x == 0) {
     a = red[0][0] + red[1][0] + red[2][0] + red[3][0]; c = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-    const double depth = 0.5 * a / ((double)(d.per_room ? 1 : d.B) * d.n_scales * d.n_dep * d.P * d.P);
+    double depth = 0.5 * a / ((double)(d.per_room ? 1 : d.B) * d.n_scales * d.n_dep * d.P * d.P);
+    if (depth_count != nullptr) {
+      const int nv = depth_count[d.per_room ? blockIdx.x : 0];
+      depth = nv > 0 ? 0.5 * a / ((double)d.n_dep * nv) : 0.0;
+    }
     loss_out[0] = (float)(100.0 * depth + 100.0 * c); loss_out[1] = (float)depth; loss_out[2] = (float)c;
   }
 }
@@ -266,9 +284,13 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float2* __rest
 // report_depth_kernel: REPORT_BLOCKS workgroups per room, each over a run of pixels of all n_dep planes (dead planes enter as the
 // constants they are, unread); report_finalize_kernel sums a room's partials and the last scale's blocks of loss_kernel's partials
 // (a block of loss_kernel lies inside one (room, scale) when P * P is a multiple of 128) in a fixed order.
+// MASKED (SlnRefineLoss::valid_image): a pixel outside the mask adds nothing and its target is not read; the mean's element number is
+// n_dep * the room's valid pixels (depth_count row 1; 0 pixels: depth_l1 = 0).  Same loops, same order.
 constexpr int REPORT_BLOCKS = 64;
+template <bool MASKED>
 __global__ __launch_bounds__(256) void report_depth_kernel(const float* __restrict__ img, const float* __restrict__ tgt, const unsigned char* __restrict__ null,
-                                                           const unsigned char* __restrict__ live, RefineDims d, double* __restrict__ scratch) {
+                                                           const unsigned char* __restrict__ live, RefineDims d, double* __restrict__ scratch,
+                                                           const unsigned char* __restrict__ valid) {
   __shared__ double red[4];
   const int b = blockIdx.y;
   const long plane = (long)d.S * d.S, per = (plane + REPORT_BLOCKS - 1) / REPORT_BLOCKS;
@@ -283,6 +305,7 @@ __global__ __launch_bounds__(256) void report_depth_kernel(const float* __restri
     const float cst = (lv & 1) ? 1.f : 0.f;
     float a = 0.f;
     for (long p = p0 + threadIdx.x; p < p1; p += 256) {
+      if (MASKED && !valid[(long)b * plane + p]) continue;
       float v = lv == 3 ? src[c * plane + p] : cst;
       if (last && nm[p]) v = 1.f;
       a += fabsf(v - tg[c * plane + p]);
@@ -296,7 +319,8 @@ __global__ __launch_bounds__(256) void report_depth_kernel(const float* __restri
 }
 
 __global__ __launch_bounds__(64) void report_finalize_kernel(const double* __restrict__ scratch, const float2* __restrict__ partial, RefineDims d,
-                                                             double* __restrict__ iou_mean, float* __restrict__ report) {
+                                                             double* __restrict__ iou_mean, float* __restrict__ report,
+                                                             const int32_t* __restrict__ image_count) {
   const int b = blockIdx.x, bps = d.P * d.P / 128;                      // blocks of loss_kernel per (room, scale)
   double a = scratch[b * REPORT_BLOCKS + threadIdx.x], c = 0.0;
   const float2* ps = partial + (long)(b * d.n_scales + d.n_scales - 1) * bps;      // part row 0 (the semantic part), the last scale
@@ -306,8 +330,100 @@ __global__ __launch_bounds__(64) void report_finalize_kernel(const double* __res
     float iou = __builtin_nanf("");
     if (iou_mean != nullptr) { iou = (float)iou_mean[b]; iou_mean[b] = 0.0; }
     report[3 * b + 0] = iou;
-    report[3 * b + 1] = (float)(a / ((double)d.n_dep * d.S * d.S));
+    double l1 = a / ((double)d.n_dep * d.S * d.S);
+    if (image_count != nullptr) l1 = image_count[b] > 0 ? a / ((double)d.n_dep * image_count[b]) : 0.0;
+    report[3 * b + 1] = (float)l1;
     report[3 * b + 2] = (float)(c * 800.0);
+  }
+}
+
+// The validity mask of a target (sln_refine_loss_mask; once per target, in front of the loop).
+//   refine_mask_kernel        one lane per pooled pixel, one workgroup inside one (room, scale): the AND over the 16 image pixels
+//                             pool_kernel addresses for it - its index expressions, the weights ignored - is the pooled pixel's validity;
+//                             an invalid one loses its label.  The taps are read as 16 single bytes: the mask of a room is S * S bytes (9 KB at
+//                             96, 64 KB at 256) and stays in L1 / L2 for the 4 scales' lanes that read it, the two columns of a pair are
+//                             adjacent only where i1 = i0 + 1 and sit on no 4-byte boundary, and the call runs once per target - staging
+//                             the intermediate through LDS as pool_lds_kernel does would buy nothing here.
+//   refine_mask_image_kernel  the non-zero pixels of a room's mask (the report's element number)
+//   counts: a ballot per wavefront, one integer atomic per workgroup and counter - exact, the same in any order - into counters
+//   that a launch of their own clears; refine_mask_finalize_kernel turns them into inv_count, depth_count and mask_status.
+//   cnt layout (int32, in the loss workspace): [B][n_scales] labels kept, [B][n_scales] valid pooled pixels, [B] valid image pixels
+__global__ void refine_mask_clear_kernel(int* __restrict__ cnt, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) cnt[i] = 0;
+}
+
+__global__ __launch_bounds__(256) void refine_mask_kernel(const unsigned char* __restrict__ valid, RefineDims d,
+                                                          const int* __restrict__ s2_k0, const int* __restrict__ s2_k1,
+                                                          const int* __restrict__ s1_i0, const int* __restrict__ s1_i1,
+                                                          int* __restrict__ labels, unsigned char* __restrict__ valid_pooled, int* __restrict__ cnt) {
+  const int pp = d.P * d.P;
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  const int s = blockIdx.y % d.n_scales, b = blockIdx.y / d.n_scales;
+  bool ok = false, lab = false;
+  if (o < pp) {
+    const int oy = o / d.P, ox = o % d.P;
+    const int ky[2] = {s2_k0[s * d.P + oy], s2_k1[s * d.P + oy]}, kx[2] = {s2_k0[s * d.P + ox], s2_k1[s * d.P + ox]};
+    int yy[4], xx[4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      yy[2 * a] = s1_i0[s * d.pmax + ky[a]]; yy[2 * a + 1] = s1_i1[s * d.pmax + ky[a]];
+      xx[2 * a] = s1_i0[s * d.pmax + kx[a]]; xx[2 * a + 1] = s1_i1[s * d.pmax + kx[a]];
+    }
+    const unsigned char* vm = valid + (long)b * d.S * d.S;
+    ok = true;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ok = ok && vm[(long)yy[a] * d.S + xx[e]] != 0;
+    const long i = ((long)b * d.n_scales + s) * pp + o;
+    valid_pooled[i] = ok ? 1 : 0;
+    if (!ok) labels[i] = -100;
+    lab = ok && labels[i] >= 0;
+  }
+  __shared__ int red[4][2];
+  const int c_ok = __popcll(__ballot(ok)), c_lab = __popcll(__ballot(lab));
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = c_lab; red[threadIdx.x >> 6][1] = c_ok; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int n_lab = red[0][0] + red[1][0] + red[2][0] + red[3][0], n_ok = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+    if (n_lab) atomicAdd(cnt + b * d.n_scales + s, n_lab);                       // (integers: the total does not depend on the order)
+    if (n_ok) atomicAdd(cnt + (d.B + b) * d.n_scales + s, n_ok);
+  }
+}
+
+__global__ __launch_bounds__(256) void refine_mask_image_kernel(const unsigned char* __restrict__ valid, RefineDims d, int* __restrict__ cnt) {
+  const int plane = d.S * d.S, p = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  const bool ok = p < plane && valid[(long)b * plane + p] != 0;
+  __shared__ int red[4];
+  const int c = __popcll(__ballot(ok));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int n = red[0] + red[1] + red[2] + red[3];
+    if (n) atomicAdd(cnt + 2 * d.B * d.n_scales + b, n);
+  }
+}
+
+// one workgroup, a thread per room (strided): B * n_scales is a few dozen numbers
+__global__ __launch_bounds__(256) void refine_mask_finalize_kernel(const int* __restrict__ cnt, RefineDims d, float* __restrict__ inv_count,
+                                                                   int* __restrict__ depth_count, int* __restrict__ mask_status) {
+  const int ns = d.n_scales;
+  const int* c_lab = cnt; const int* c_ok = cnt + d.B * ns; const int* c_img = cnt + 2 * d.B * ns;
+  for (int b = threadIdx.x; b < d.B; b += 256) {
+    int n = 0, none = 0;
+    if (d.per_room) {
+      for (int s = 0; s < ns; ++s) { n += c_ok[b * ns + s]; none |= c_lab[b * ns + s] == 0; inv_count[b * ns + s] = 1.f / (float)c_lab[b * ns + s]; }
+    } else {
+      for (int s = 0; s < ns; ++s) {
+        int l = 0;
+        for (int r = 0; r < d.B; ++r) { n += c_ok[r * ns + s]; l += c_lab[r * ns + s]; }
+        none |= l == 0;
+        if (b == 0) inv_count[s] = 1.f / (float)l;
+      }
+    }
+    depth_count[b] = n; depth_count[d.B + b] = c_img[b];
+    mask_status[b] = (n == 0 ? 1 : 0) | (none ? 2 : 0);
   }
 }
 
@@ -424,10 +540,13 @@ __global__ __launch_bounds__(256) void refine_bwd_sep_kernel(const float* __rest
   const bool last = c == d.dep0 + d.n_dep - 1;
   for (int r = 0; r < ROWS && y0 + r < d.S; ++r) {
     float g = 0.f;
+    // (a scale the descriptor does not have has no row of T: stage 1 never wrote it, and a weight of 0 does not make what LDS holds
+    //  there harmless - 0 * NaN is NaN)
 #pragma unroll
     for (int s = 0; s < MAX_SCALES; ++s)
+      if (s < d.n_scales)
 #pragma unroll
-      for (int f = 0; f < MAXX; ++f) g = fmaf(wx[s][f], T[s][r][ox[s][f]], g);
+        for (int f = 0; f < MAXX; ++f) g = fmaf(wx[s][f], T[s][r][ox[s][f]], g);
     if (last && null[(long)b * d.S * d.S + (long)(y0 + r) * d.S + x]) g = 0.f;
     out[(long)(y0 + r) * d.S + x] = g * gs;
   }
@@ -461,6 +580,9 @@ static int check(const SlnRefineLoss* L) {
   // per_room: a 128-row block of loss_kernel must not cover two rooms (checked here - init and every entry point - so that an
   // unsupported geometry fails before anything is launched or overwritten)
   if (L->per_room && ((long)L->n_scales * L->pooled_size * L->pooled_size) % 128 != 0) return SLN_E_UNSUPPORTED;
+  // the validity mask: all three fields or none
+  const int n_mask = (L->valid_pooled != nullptr) + (L->valid_image != nullptr) + (L->depth_count != nullptr);
+  if (n_mask != 0 && n_mask != 3) return SLN_E_BADARG;
   return 0;
 }
 
@@ -543,10 +665,35 @@ int sln_refine_loss_forward(const SlnRefineLoss* L, const float* image, const fl
   launch_pool(L, d, image, ext_mask ? 2 : 1, mask, pooled, live, st);
   const long nl = (long)d.B * d.n_scales * d.P * d.P;
   const dim3 lg((unsigned)((nl + 127) / 128), 1 + sln_cdiv(d.n_dep, DCH));
-  hipLaunchKernelGGL((loss_kernel<40>), lg, dim3(128), 0, st, pooled, d, target_depth_pooled, labels, inv_count, partial, live, L->pooled_ones);
+  if (L->valid_pooled != nullptr)
+    hipLaunchKernelGGL((loss_kernel<40, true>), lg, dim3(128), 0, st, pooled, d, target_depth_pooled, labels, inv_count, partial, live, L->pooled_ones,
+                       L->valid_pooled, L->depth_count);
+  else
+    hipLaunchKernelGGL((loss_kernel<40, false>), lg, dim3(128), 0, st, pooled, d, target_depth_pooled, labels, inv_count, partial, live, L->pooled_ones,
+                       (const unsigned char*)nullptr, (const int32_t*)nullptr);
   const long per_room_rows = (long)d.n_scales * d.P * d.P;
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(d.per_room ? d.B : 1), dim3(256), 0, st, partial, (int)(lg.x * lg.y), d, loss_out, (int)lg.x,
-                     (int)(per_room_rows / 128));
+                     (int)(per_room_rows / 128), L->valid_pooled != nullptr ? L->depth_count : (const int32_t*)nullptr);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_refine_loss_mask(const SlnRefineLoss* L, const unsigned char* valid, int32_t* labels, unsigned char* valid_pooled, float* inv_count,
+                         int32_t* depth_count, int32_t* mask_status, void* workspace, void* stream) {
+  int r = check(L);
+  if (r) return r;
+  if (!valid || !labels || !valid_pooled || !inv_count || !depth_count || !mask_status || !workspace) return SLN_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const RefineDims d = dims_of(L);
+  float* pooled; unsigned char* mask; float2* partial;
+  carve(L, workspace, &pooled, &mask, &partial);
+  int* cnt = reinterpret_cast<int*>(pooled);                  // (2 n_scales + 1) B counters at the head of the pooled maps, which every forward rewrites
+  const int n_cnt = (2 * d.n_scales + 1) * d.B;
+  hipLaunchKernelGGL(refine_mask_clear_kernel, dim3(sln_cdiv(n_cnt, 256)), dim3(256), 0, st, cnt, n_cnt);
+  hipLaunchKernelGGL(refine_mask_kernel, dim3(sln_cdiv(d.P * d.P, 256), d.B * d.n_scales), dim3(256), 0, st, valid, d, L->s2_k0, L->s2_k1, L->s1_i0,
+                     L->s1_i1, labels, valid_pooled, cnt);
+  hipLaunchKernelGGL(refine_mask_image_kernel, dim3(sln_cdiv(d.S * d.S, 256), d.B), dim3(256), 0, st, valid, d, cnt);
+  hipLaunchKernelGGL(refine_mask_finalize_kernel, dim3(1), dim3(256), 0, st, cnt, d, inv_count, depth_count, mask_status);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -585,8 +732,13 @@ int sln_refine_report(const SlnRefineLoss* L, const float* image, const float* t
   const unsigned char* live = live_of(L, d);
   if (live != nullptr && L->null_mask != nullptr) mask = const_cast<unsigned char*>(L->null_mask);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(report_depth_kernel, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch);
-  hipLaunchKernelGGL(report_finalize_kernel, dim3(d.B), dim3(64), 0, st, scratch, partial, d, iou_mean, report_out);
+  if (L->valid_image != nullptr)
+    hipLaunchKernelGGL(report_depth_kernel<true>, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch, L->valid_image);
+  else
+    hipLaunchKernelGGL(report_depth_kernel<false>, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch,
+                       (const unsigned char*)nullptr);
+  hipLaunchKernelGGL(report_finalize_kernel, dim3(d.B), dim3(64), 0, st, scratch, partial, d, iou_mean, report_out,
+                     L->valid_image != nullptr ? L->depth_count + d.B : (const int32_t*)nullptr);
   SLN_CHECK_LAUNCH();
   return 0;
 }

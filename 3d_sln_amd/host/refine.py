@@ -478,6 +478,104 @@ def _bilinear_taps(in_size, out_size, align_corners):
     return i0, i1.astype(np.int32), (src - i0.astype(np.float32)).astype(np.float32)
 
 
+def pool_tap_sets(S, sizes=(32, 48, 64, 96)):
+    """int64 [n_scales, P, 4]: the image indices the two resampling stages address for a pooled index - pool_kernel's
+    ``{s1_i0[k], s1_i1[k] : k in {s2_k0[o], s2_k1[o]}}`` - whatever their weights (an exactly-hit sample still addresses its upper
+    neighbour, with weight 0).  Rows and columns share the table; a pooled pixel's 16 taps are ``sets[s, oy] x sets[s, ox]``."""
+    P = sizes[-1]
+    out = np.zeros((len(sizes), P, 4), np.int64)
+    for k, sz in enumerate(sizes):
+        i0, i1, _ = _bilinear_taps(S, sz, True)
+        k0, k1, _ = _bilinear_taps(sz, P, False)
+        out[k] = np.stack([i0[k0], i1[k0], i0[k1], i1[k1]], 1)
+    return torch.from_numpy(out)
+
+
+def valid_pooled_torch(valid, sizes=(32, 48, 64, 96)):
+    """``valid`` [B, S, S] (non-zero: the target means something here) -> bool [B, n_scales, P, P]: a pooled pixel is valid iff every
+    image pixel of its tap set is (``pool_tap_sets``).  Integer-exact and separable: rows first, then columns."""
+    v = valid != 0
+    sets = pool_tap_sets(v.shape[-1], sizes).to(v.device)
+    out = []
+    for k in range(len(sizes)):
+        rows = v[:, sets[k]].all(dim=2)                            # [B, P, S]: every addressed row valid, per image column
+        out.append(rows[:, :, sets[k]].all(dim=3))                # [B, P, P]
+    return torch.stack(out, 1)
+
+
+def mask_counts_torch(valid, labels, per_room, sizes=(32, 48, 64, 96)):
+    """What sln_refine_loss_mask derives, in torch ops: ``labels`` [B, n_scales, P, P] (as ``RefineLoss`` derives them, -100 = none) ->
+    dict(valid_pooled uint8, labels int32, inv_count float32, depth_count int32 [2, B], mask_status int32 [B])."""
+    vp = valid_pooled_torch(valid, sizes)
+    lab = torch.where(vp, labels.to(torch.int32), torch.full_like(labels, -100, dtype=torch.int32))
+    kept, ok = (lab >= 0).sum(dim=(2, 3)), vp.sum(dim=(2, 3))                                 # [B, n_scales]
+    B = vp.shape[0]
+    if not per_room:
+        kept, ok = kept.sum(0, keepdim=True).expand(B, -1), ok.sum(0, keepdim=True).expand(B, -1)
+    n = ok.sum(1)
+    inv = 1.0 / (kept if per_room else kept[0]).to(torch.float32)
+    status = (n == 0).to(torch.int32) | ((kept == 0).any(dim=1).to(torch.int32) << 1)
+    return dict(valid_pooled=vp.to(torch.uint8), labels=lab, inv_count=inv,
+                depth_count=torch.stack([n, (valid != 0).sum(dim=(1, 2))]).to(torch.int32), mask_status=status)
+
+
+def refinement_loss_masked(iter_image, target, target_container, size_loss, valid, sizes=(32, 48, 64, 96)):
+    """``refinement_loss`` under a validity mask (DESIGN §4 "Refinement loss under a validity mask"), in torch ops for any dtype and
+    device - the CPU route and the yardstick of csrc/refine_loss.hip's masked kernels.  ``valid`` [B, S, S] (non-zero: the target means
+    something at this pixel); ``target_container``: the per-scale labels as ``target_labels`` gives them.
+      depth = 0.5 * sum over the VALID pooled pixels of |pool(iter) - pool(target)| / (29 * N), N the valid pooled pixels of all scales
+              (0 when there is none); sem = sum_s CE_s / 800 over the labels of valid pooled pixels (a scale without one adds 0).
+    Selects, never multiplies by 0: whatever ``target`` holds where ``valid`` is 0 (NaN and infinities included) reaches neither the
+    value nor the gradient - an invalid image pixel is replaced by 0 before the target is pooled, which no valid pooled pixel reads.
+    The iterate's planes enter detached at invalid pixels, so that their gradient is exactly 0 there whatever the dtype's rounding
+    makes of a tap that lands on a sample (the definition's tap sets are float32's)."""
+    v = (valid != 0)[:, None]
+    vp = valid_pooled_torch(valid, sizes)                                                      # [B, ns, P, P]
+    iter_image = torch.where(v, iter_image, iter_image.detach())
+    null = torch.sum(iter_image[:, 41:], dim=1) < 0.5
+    last = iter_image[:, -1]
+    iter_image = torch.cat([iter_image[:, :-1], torch.where(null, torch.ones_like(last), last)[:, None]], 1)
+    clean = torch.where(v, target, torch.zeros_like(target))
+    B, ns, P = vp.shape[0], len(sizes), sizes[-1]
+    diff = (psp_pool(iter_image[:, 41:], sizes) - psp_pool(clean[:, 41:], sizes)).abs().reshape(B, ns, -1, P, P)
+    n = int(vp.sum())
+    zero = (iter_image[:1, :1, :1, :1] * 0).sum()                    # (of the iterate: a loss without a term still has a - zero - gradient)
+    depth_loss = torch.where(vp[:, :, None], diff, torch.zeros_like(diff)).sum() / (diff.shape[2] * n) * 0.5 if n > 0 else zero
+    sem = zero
+    for k, (pooled, tgt) in enumerate(zip(psp_pool(iter_image[:, 1:41], sizes, as_list=True), target_container)):
+        lab = torch.where(vp[:, k], tgt[:, 0], torch.full_like(tgt[:, 0], -100))
+        kept = int((lab >= 0).sum())
+        if kept > 0:
+            sem = sem + F.cross_entropy(pooled, lab, reduction="sum") / kept / 800.0
+    return depth_loss * 100 + sem * 100 + size_loss * 2.0, depth_loss, sem
+
+
+def check_mask(mask, shape, device, observed):
+    """the ``mask=`` argument of the refinement entry points, refused before anything is launched: None, "readings" (needs ``observed``)
+    or a uint8 / bool tensor of ``shape`` on ``device``"""
+    if mask is None:
+        return
+    if isinstance(mask, str):
+        if mask != "readings":
+            raise ValueError("mask is None, 'readings' or a uint8 / bool tensor %s" % (list(shape),))
+        if observed is None:
+            raise ValueError("mask='readings' marks the pixels where the observed depth has a reading: it needs observed=")
+        return
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("mask: a uint8 or bool tensor expected (None and 'readings' are the other choices)")
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError("mask: shape %s is not %s" % (tuple(mask.shape), list(shape)))
+    if mask.device != torch.device(device):
+        raise ValueError("mask: a tensor on %s expected, got one on %s" % (device, mask.device))
+
+
+def _valid_of(mask, target):
+    """uint8 [B, S, S] of a checked ``mask``: 'readings' - where plane 0 of the built target (the cleaned depth) has a reading"""
+    if isinstance(mask, str):
+        return (target[:, 0] >= 0).to(torch.uint8).contiguous()
+    return (mask != 0).to(torch.uint8).contiguous()
+
+
 class _RefineLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, rl):
@@ -509,10 +607,15 @@ class RefineLoss:
     ``rl(image)`` -> tensor [100*depth + 100*sem, depth, sem]; gradients flow to ``image`` through element 0.  The
     workspace holds d loss / d pooled between forward and backward: one outstanding forward per instance."""
 
-    def __init__(self, target, sizes=(32, 48, 64, 96), per_room=False):
+    def __init__(self, target, sizes=(32, 48, 64, 96), per_room=False, valid=None):
+        """``valid``: None, or [B, S, S] uint8 / bool on the target's device - the validity mask of the target (non-zero: the target
+        means something at this pixel).  One ``sln_refine_loss_mask`` call derives ``valid_pooled`` [B, n_scales, P, P],
+        masks ``labels``, recounts ``inv_count`` and fills ``mask_count`` [2, B] (valid pooled pixels the depth mean runs over, valid image
+        pixels) and ``mask_status`` [B] (bit 0: no valid pooled pixel; bit 1: a scale without a label); all None without a mask."""
         self.per_room = bool(per_room)
         dev = target.device
         B, C, S, _ = target.shape
+        check_mask(valid, (B, S, S), dev, None)
         P, ns, pmax = sizes[-1], len(sizes), max(sizes)
         # the resampling tables depend on the geometry only (image size, scales), not on the room: built once per geometry and device
         # (python / numpy loops over 4 x 256 image rows: ~5 ms of the ~7 ms per-room set-up of the refinement loop)
@@ -522,7 +625,7 @@ class RefineLoss:
             cached = _REFINE_TABLES[key] = self._build_tables(S, sizes, dev)
         self._keep, max_col = cached
         d = self._describe(B, S, P, C, ns, pmax, max_col)
-        self._finish(d, target, B, S, P, C, ns, dev)
+        self._finish(d, target, B, S, P, C, ns, dev, valid)
 
     @staticmethod
     def _build_tables(S, sizes, dev):
@@ -562,8 +665,9 @@ class RefineLoss:
         d.per_room = int(getattr(self, "per_room", False))
         return d
 
-    def _finish(self, d, target, B, S, P, C, ns, dev):
+    def _finish(self, d, target, B, S, P, C, ns, dev, valid=None):
         self.desc = d
+        self.valid = self.valid_pooled = self.mask_count = self.mask_status = None
         L = _lib.lib()
         self.ws = torch.empty(int(L.sln_refine_loss_workspace_bytes(B, S, P, ns, 40, C - 41)), dtype=torch.uint8, device=dev)
         _lib.check(L.sln_refine_loss_init(d, _lib.ptr(self.ws), _lib.current_stream_ptr()), "sln_refine_loss_init")
@@ -580,6 +684,19 @@ class RefineLoss:
         # per_room: every image is its own room - its cross-entropy means run over its own labels ([B, ns] counts)
         cnt = (lab >= 0).sum(dim=(2, 3) if self.per_room else (0, 2, 3)).to(torch.float32)
         self.inv_count = (1.0 / cnt).contiguous()                                                       # 1/0: nan loss, as torch's empty mean
+        if valid is not None:
+            # the mask (one call, four launches): pooled validity from pool_kernel's own tap indices, labels of invalid pooled pixels
+            # to -100, the counts by integer sums on the device.  What the target holds under the mask stays where it is - in
+            # target_depth and in the labels just derived - and is not read from here on.
+            self.valid = (valid != 0).to(torch.uint8).contiguous()
+            self.valid_pooled = torch.empty(B, ns, P, P, dtype=torch.uint8, device=dev)
+            self.mask_count = torch.empty(2, B, dtype=torch.int32, device=dev)
+            self.mask_status = torch.empty(B, dtype=torch.int32, device=dev)
+            self.inv_count = torch.empty_like(self.inv_count)
+            _lib.check(L.sln_refine_loss_mask(d, _lib.ptr(self.valid), _lib.ptr(self.labels), _lib.ptr(self.valid_pooled), _lib.ptr(self.inv_count),
+                                              _lib.ptr(self.mask_count), _lib.ptr(self.mask_status), _lib.ptr(self.ws), _lib.current_stream_ptr()),
+                       "sln_refine_loss_mask")
+            d.valid_pooled, d.valid_image, d.depth_count = self.valid_pooled.data_ptr(), self.valid.data_ptr(), self.mask_count.data_ptr()
 
     def pooled_ones(self):
         """[n_scales, P, P]: what the resampling kernel makes of an all-ones plane (one per geometry and device; see
@@ -591,6 +708,7 @@ class RefineLoss:
             L, dev = _lib.lib(), self.ws.device
             d1 = type(d).from_buffer_copy(d)
             d1.B, d1.per_room, d1.live_planes, d1.pooled_ones = 1, 0, None, None
+            d1.valid_pooled = d1.valid_image = d1.depth_count = None
             C_, S, P, ns = d.channels, d.image_size, d.pooled_size, d.n_scales
             ws1 = torch.empty(int(L.sln_refine_loss_workspace_bytes(1, S, P, ns, 40, C_ - 41)), dtype=torch.uint8, device=dev)
             pooled = torch.empty(1, ns, C_ - 1, P, P, device=dev)
@@ -781,7 +899,7 @@ class RefineScene:
 
 
 def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, bank=None, learning_rate=1e-4,
-                      noise_seed=13, image_size=256, capture=False, log=None, fused_loss=True, fused_head=True):
+                      noise_seed=13, image_size=256, capture=False, log=None, fused_loss=True, fused_head=True, observed=None, mask=None):
     """``finetune_vae`` with the batched ``RefineScene`` and no per-iteration python optimiser objects: the reference builds a
     NEW SGD(momentum=0.1, nesterov) every iteration (test_render_refine.py:286-292), so its step is exactly
     ``p -= lr * (1 + momentum) * grad``; that closed form is applied to ``z`` (lr 2e-4) and to the flat parameter buffer
@@ -790,8 +908,15 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
     each way (``_HeadFn``) and both parameter updates plus the gradient zero-fill as one launch (``sln_refine_sgd``).
     ``capture=True`` records one iteration (decoder, placement, fused render, PSP losses,
     backward, both updates) into a hipGraph and replays it; the noise of the angle soft-argmax is then drawn on the device.
+    ``observed``: None, or ``(depth [S, S] or [1, S, S] float32, labels likewise uint8)`` on the device - the target is built from this
+    observation with one ``ObservedTarget`` call on the room's class tables instead of rendered from ``boxes_gt`` (``RefineBatch``'s
+    ``observed``, for one room).  ``mask``: None, "readings" or a uint8 / bool tensor [S, S] or [1, S, S] - the loss under a validity mask
+    (``RefineBatch``'s ``mask``).
     Returns (losses [iters] tensor on the device, (boxes_pred, angle_idx))."""
     dev = boxes_gt.device
+    observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, cuda=True)
+    if observed is not None and bank is not None and bank.has_choice():
+        raise ValueError("observed targets show no meshes to retrieve: observed does not combine with a bank that leaves a choice")
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
     model.eval()
     with torch.no_grad():
@@ -807,9 +932,15 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
         models_gt, shell = models_gt.cpu().tolist(), (shells[0] if shells is not None else None)
     target_scene = scene = RefineScene(class_names, bank, room_box, image_size, models=models_gt, shell=shell)
     with torch.no_grad():
-        target, _, sizes = target_scene.render(boxes_gt, angles_gt.float())
-    labels = target_labels(target)
-    fused = RefineLoss(target) if fused_loss else None             # the PSP / L1 / cross-entropy block as two C calls
+        if observed is None:
+            target, _, sizes = target_scene.render(boxes_gt, angles_gt.float())
+        else:                            # the placement alone, for the sizes; the target from the observation (csrc/observed_target.hip)
+            _, _, sizes = _PlaceFn.apply(boxes_gt, angles_gt.float(), target_scene, None)
+            built, _ = OB.ObservedTarget(target_scene.chan, target_scene.dch, int(image_size), batch=1, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)
+            target = built.clone()
+    valid = _valid_of(mask, target) if mask is not None else None
+    labels = target_labels(torch.where(valid[:, None] != 0, target, torch.zeros_like(target)) if valid is not None else target)
+    fused = RefineLoss(target, valid=valid) if fused_loss else None    # the PSP / L1 / cross-entropy block as two C calls
     size_target = sizes.detach().clone()                           # (a buffer: filled with the FIRST iterate's sizes below)
     n = boxes_gt.shape[0]
     noise = torch.zeros(n, device=dev)
@@ -851,6 +982,8 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
         image, size_loss, _ = scene.render(boxes_full, idx, size_target)
         if fused is not None:
             loss = torch.add(fused(image)[0], size_loss, alpha=2.0)
+        elif valid is not None:
+            loss, _, _ = refinement_loss_masked(image, target, labels, size_loss, valid)
         else:
             loss, _, _ = refinement_loss(image, target, labels, size_loss)
         z.grad = None
@@ -939,10 +1072,17 @@ class RefineBatch:
     (``get_cam_mat`` of the room row; host/observe.py) from which ONE ``ObservedTarget`` call on the batch's class tables builds the R
     targets; nothing is rendered from ``rm["boxes"]``.  The encoder start, the frozen room row, the camera and the size targets stay
     ``rm[...]``'s; ``report``'s depth term and ``target_pictures`` read the observed targets; ``target_status`` [R] holds the status
-    words of the observations (None without ``observed``).  Does not combine with ``retrieve=True``."""
+    words of the observations (None without ``observed``).  Does not combine with ``retrieve=True``.
+
+    ``mask``: None (default: the loss reads every pixel of the targets, the launches are those above), "readings" (needs ``observed``: a
+    pixel is valid where the cleaned depth has a reading, ``d0 >= 0`` in plane 0 of the built target - the holes of a reprojected frame
+    are not), or a uint8 / bool tensor [R, S, S] on the device (non-zero: valid; works with rendered targets too).  The loss then runs
+    under the validity mask (``RefineLoss(valid=)``): the depth term and its gradient over the valid pooled pixels only, the
+    labels of the others ignored, ``report``'s depth_l1 over the valid image pixels.  ``mask_status`` [R] int32 (None without a mask):
+    bit 0 - the room has no valid pooled pixel (its depth term is 0), bit 1 - one of its scales keeps no label."""
 
     def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
-                 retrieve=False, observed=None):
+                 retrieve=False, observed=None, mask=None):
         L = _lib.lib()
         self.model, self.R, self.iters, self.lr = model, len(rooms), int(iters), float(learning_rate)
         R = self.R
@@ -955,6 +1095,7 @@ class RefineBatch:
             if not isinstance(observed, (tuple, list)) or len(observed) != 2:
                 raise ValueError("observed is (depth [R, S, S] float32, labels [R, S, S] uint8)")
             OB.ObservedTarget.check_tensors(observed[0], observed[1], (R, int(image_size), int(image_size)), dev)
+        check_mask(mask, (R, int(image_size), int(image_size)), dev, observed)
         names_all = set(n for rm in rooms for n in rm["class_names"])
         bank = bank or MeshBank([n for n in names_all if n not in DO_NOT_VIS and n != "__room__"], dev)
         model.eval()
@@ -1053,8 +1194,10 @@ class RefineBatch:
         self.noise_all = noise.to(dev)
         self.box_last, self.angle_last = box_last, angle_last
         # ---- the loss of all rooms: one descriptor, per-room normalisation ----
-        self.loss = RefineLoss(torch.cat(targets, 0), per_room=True)
-        del targets
+        all_targets = torch.cat(targets, 0)
+        self.loss = RefineLoss(all_targets, per_room=True, valid=_valid_of(mask, all_targets) if mask is not None else None)
+        self.mask_status = self.loss.mask_status
+        del targets, all_targets
         # ---- R parameter copies, R engines, one launch program ----
         nflat = model.flat_params.numel()
         self.params = model.flat_params.detach().unsqueeze(0).repeat(R, 1).contiguous()
@@ -1367,13 +1510,13 @@ class RefineBatch:
 
 
 def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None,
-                            pictures=None, retrieve=False):
+                            pictures=None, retrieve=False, observed=None, mask=None):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
     noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
     ``report`` is given, the report [iters, R, 3] as a further element; only when ``pictures`` is given, the pair
-    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one."""
+    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask``: as ``RefineBatch``'s."""
     rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report,
-                     pictures=pictures, retrieve=retrieve)
+                     pictures=pictures, retrieve=retrieve, observed=observed, mask=mask)
     try:
         out = (rb.run(capture=capture).clone(), [(b.clone(), i.clone()) for b, i in rb.results()])
         if report is not None:
@@ -1385,12 +1528,33 @@ def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-
     return out
 
 
+def _one_room_arguments(observed, mask, S, dev, cuda):
+    """``observed`` / ``mask`` of the one-room loops, checked before anything is launched and brought to [1, S, S]"""
+    if observed is not None:
+        if not isinstance(observed, (tuple, list)) or len(observed) != 2 or not all(torch.is_tensor(t) for t in observed):
+            raise ValueError("observed is (depth [S, S] or [1, S, S] float32, labels likewise uint8)")
+        observed = tuple(t[None] if t.dim() == 2 else t for t in observed)
+        if cuda:
+            OB.ObservedTarget.check_tensors(observed[0], observed[1], (1, S, S), dev)
+        elif any(tuple(t.shape) != (1, S, S) or t.device != dev for t in observed) or observed[1].dtype != torch.uint8:
+            raise ValueError("observed: depth and uint8 labels of shape [%d, %d] on %s expected" % (S, S, dev))
+    if torch.is_tensor(mask) and mask.dim() == 2:
+        mask = mask[None]
+    check_mask(mask, (1, S, S), dev, observed)
+    return observed, mask
+
+
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,
-                 learning_rate=1e-4, noise_seed=13, image_size=256, log=None):
+                 learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None):
     """finetune_VAE's inner loop for ONE room (test_render_refine.py:265-359) on synthetic meshes.
+    ``observed`` / ``mask``: as ``finetune_vae_fast``'s, on the boxes' device whichever it is - the target from ``observed_target_torch`` on
+    the room's class tables, the loss from ``refinement_loss_masked``.
     Returns the list of per-iteration losses and the final (boxes_pred, angles_idx)."""
     render_fn = render_fn or DR.scene_render
     dev = boxes_gt.device
+    observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, cuda=False)
+    if observed is not None and bank is not None and bank.has_choice():
+        raise ValueError("observed targets show no meshes to retrieve: observed does not combine with a bank that leaves a choice")
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
     model.eval()
     with torch.no_grad():
@@ -1405,8 +1569,13 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         models_gt, shell = models_gt.cpu().tolist(), (shells[0] if shells is not None else None)
     v, f, ranges, sizes, _ = assemble_scene(boxes_gt, angles_gt.float(), class_names, bank, room_box, models=models_gt, shell=shell)
     with torch.no_grad():
-        target = render_fn(v, f, ranges, room_box, image_size=image_size)
-    labels = target_labels(target)
+        if observed is None:
+            target = render_fn(v, f, ranges, room_box, image_size=image_size)
+        else:
+            _, chan, dch = DR.class_tables(ranges.keys())
+            target, _ = OB.observed_target_torch(observed[0], observed[1], chan, dch, nch=DR.N_SCENE_CHANNELS)
+    valid = _valid_of(mask, target) if mask is not None else None
+    labels = target_labels(torch.where(valid[:, None] != 0, target, torch.zeros_like(target)) if valid is not None else target)
     size_target = None                   # the sizes of the FIRST iterate, not the target's (test_render_refine.py:319-327: the target render's
     #                                      sizes are "unused_sizes"; size_infos is what the first render of boxes_pred returns)
     losses = []
@@ -1425,7 +1594,10 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         if size_target is None:
             size_target = [s.clone() for s in sizes_k]
         image = render_fn(v, f, ranges, room_box, image_size=image_size)
-        loss, dl, sl = refinement_loss(image, target, labels, size_loss)
+        if valid is not None:
+            loss, dl, sl = refinement_loss_masked(image, target, labels, size_loss, valid)
+        else:
+            loss, dl, sl = refinement_loss(image, target, labels, size_loss)
         opt.zero_grad()
         loss.backward()
         opt.step()

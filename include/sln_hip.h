@@ -717,6 +717,14 @@ typedef struct {
                                                  * does not compute it */
   const float* pooled_ones;                     /* optional [n_scales, P, P] (device): sln_refine_pool of an all-ones plane.  With live_planes,
                                                  * the planes flagged "constant 1" are then not pooled per image: the loss reads this table */
+  /* The validity mask of the target (all three or none: anything else is SLN_E_BADARG), as sln_refine_loss_mask leaves them */
+  const unsigned char* valid_pooled;            /* optional [B, n_scales, P, P] (device): 0 - the pooled pixel addresses an image pixel the
+                                                 * target says nothing about: its depth difference is neither formed nor summed, its depth
+                                                 * gradient is exactly 0 (its label is -100 already).  NULL: no mask, the launches of before */
+  const unsigned char* valid_image;             /* [B, S, S] (device): the mask itself - sln_refine_report's depth_l1 runs over its non-zero pixels */
+  const int32_t* depth_count;                   /* [2, B] (device): row 0 the number N of valid pooled pixels room b's depth mean is divided by
+                                                 * (all scales; per_room: the room's own, else the batch's in every entry), row 1 the number of
+                                                 * non-zero pixels of valid_image[b] */
 } SlnRefineLoss;
 int64_t sln_refine_loss_workspace_bytes(int B, int image_size, int pooled_size, int n_scales, int n_sem, int n_dep);
 /* 1 when live_planes / null_mask / pooled_ones of L would be honoured (the refinement loop's shapes), 0 when every plane is processed
@@ -734,6 +742,20 @@ int sln_refine_pool(const SlnRefineLoss* L, const float* image, int null_fill, v
 int sln_refine_loss_forward(const SlnRefineLoss* L, const float* image, const float* target_depth_pooled, const int32_t* labels,
                             const float* inv_count, void* workspace, float* loss_out, void* stream);
 int sln_refine_loss_backward(const SlnRefineLoss* L, const void* workspace, const float* grad_scale, float* grad_image, void* stream);
+/* The validity mask of a target, once per target (four launches, the first of which clears the counters; integer sums only: the same
+ * from call to call whatever sln_set_deterministic says; no allocation, synchronisation or read-back, legal under a capture).
+ *   valid        [B, S, S] uint8 in the planes' row order: non-zero - the target means something at this pixel
+ *   valid_pooled [B, n_scales, P, P] (out): 1 iff EVERY image pixel the two resampling stages address for the pooled pixel is valid,
+ *                whatever the tap's weight (0 * NaN is NaN): the 16 taps {s1_i0[k], s1_i1[k] : k in {s2_k0[o], s2_k1[o]}} of rows x columns
+ *   labels       [B, n_scales, P, P] (in-out): -100 wherever valid_pooled is 0
+ *   inv_count    [B, n_scales] (per_room) or [n_scales] (out): 1.f / the number of labels >= 0 that are left (inf for none)
+ *   depth_count  [2, B] (out): SlnRefineLoss::depth_count
+ *   mask_status  [B] (out): bit 0 - depth_count[0][b] is 0 (depth and its gradient are then 0, not NaN); bit 1 - a scale keeps no label
+ *                (of the room under per_room, of the batch otherwise)
+ * The mask fields of L itself are not read (L may or may not carry them yet); `workspace` is the loss's, whose contents between a
+ * forward and its backward this call destroys. */
+int sln_refine_loss_mask(const SlnRefineLoss* L, const unsigned char* valid, int32_t* labels, unsigned char* valid_pooled, float* inv_count,
+                         int32_t* depth_count, int32_t* mask_status, void* workspace, void* stream);
 
 /* =============================================================================================
  * C. SPADE generator (models/SPADE_related.py: SPADEGenerator4 :1507-1605, SPADEResnetBlock4 :1457-1505,
@@ -964,6 +986,8 @@ int sln_layout_footprint_counts(const float* boxes, const float* angles, const i
  *              workspace (needs pooled_size^2 % 128 == 0: SLN_E_UNSUPPORTED otherwise).
  *   iou      = iou_mean[b] (float64 [B], e.g. the mean_out of sln_layout_cuboid_iou), which is then RESET to 0 for the next
  *              accumulation; NaN when iou_mean is NULL.
+ *   With the mask fields of L set, depth_l1 is the mean over the valid image pixels of the 29 planes (0 when the room has none) and
+ *   the target is not read elsewhere; ce_last follows from the masked labels.
  * scratch: sln_refine_report_scratch_doubles(B) float64.  Fixed summation order. */
 int sln_refine_report(const SlnRefineLoss* L, const float* image, const float* target_depth, const void* workspace, double* scratch,
                       double* iou_mean, float* report_out, void* stream);
