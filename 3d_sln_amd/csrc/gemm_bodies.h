@@ -23,18 +23,12 @@ namespace {
 #ifndef SLN_NT_SCHED
 #define SLN_NT_SCHED 1
 #endif
-#ifndef SLN_TN_SCHED      // 1: the wgrad K loop in a hand-ordered schedule (gemm_tn_body), 0: hipcc's order (lab A/B)
-#define SLN_TN_SCHED 1
-#endif
-#ifndef SLN_TN_ABL        // lab builds only (SLN_HIPCC_EXTRA=-DSLN_TN_ABL=n): leave parts of the wgrad loop out - 1 loads, 2 staging + LDS writes, 4 barrier, 8 fragment reads
-#define SLN_TN_ABL 0
-#endif
 #ifndef SLN_ABL           // tools/lab/gemm_lab.hip only: leave parts of the scheduled loop out (1 loads, 2 LDS writes, 4 barrier, 8 fragment reads)
 #define SLN_ABL 0
 #endif
 
 constexpr int BK = 32;
-constexpr int TN_PAD = 32;     // LDS row padding of the TN (wgrad) tiles, see gemm_tn_body
+constexpr int TN_PAD = 32;     // LDS row padding of the TN (wgrad) fp32 tiles, see TnCoreF32
 
 // Operand loads name the GLOBAL address space.  A pointer that a kernel reads out of device memory (the problem table of the
 // per-pass wgrad launch) has no known address space, hipcc then emits flat_load - which counts on BOTH vmcnt and lgkmcnt: every wait
@@ -1185,9 +1179,9 @@ inline bool nt_wants_small3(const GemmNTArgs& a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// TN kernel (wgrad)
+// TN kernel (wgrad): one workgroup frame (TnFrame), two compute cores (TnCoreF32, TnCoreSplit)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float tn_acc_read(const float& v) {   // see the epilogue of gemm_tn_body
+__device__ __forceinline__ float tn_acc_read(const float& v) {   // see the epilogue of TnFrame::run
   float r;
   asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(r) : "a"(v));
   return r;
@@ -1225,250 +1219,313 @@ __device__ __forceinline__ float4 coef_for_col(const Operand& op, int col) {
   return v;
 }
 
-// XG: the X operand has row-gathered segments (GraphTripleConv input).  Its row indices then run through their own
-// three-stage register pipeline, one tile ahead of the data loads that use them, so that no load waits on another.
-// G (a gradient) is never gathered.
+// The wgrad workgroup: a 64 x 64 tile of dW over one chunk of rows, 256 threads = four wavefronts.
+constexpr int TN_T = 64;                   // tile edge, both ways
+constexpr int TN_TPR = TN_T / 4;           // threads per staged row (a float4 each)
+constexpr int TN_RPP = 256 / TN_TPR;       // rows per staging pass
+constexpr int TN_NP = BK / TN_RPP;         // staging passes per operand and 32-row tile
+static_assert(BK == 32 && TN_NP == 2, "two staging passes per operand and tile");
+
+// The frame: everything of a wgrad workgroup but the matrix products - tile and chunk coordinates, the two coefficient tables, the
+// column selection, the register stages with their loads, the staging pieces (transform, mask, bias sum) and the epilogue.  A core
+// (below) supplies where a staged float4 goes in LDS (putG / putX), the fragment reads and the hand-ordered K loop that issues the
+// frame's pieces behind its MFMAs (run), and the output row an accumulator register stands for (out_row).
 //
-// Round 3 layout of the compute half.  The tiles stay ROW-major in LDS, as the rows arrive ([BK rows][64 columns + pad]: one
-// ds_write_b128 per staged float4, no transposing store).  The four wavefronts of a block no longer own a 32 x 32 quarter of the
-// 64 x 64 output tile each (every operand value fetched with its own ds_read_b32: 32 per wave and tile).  Wave (wr, wc) takes
-// the row half wr of a tile (16 rows = 8 MFMA k-steps) and the column half wc of X, and accumulates a 64 x 32 piece of dW in two
-// 32 x 32 accumulators: a lane reads two ADJACENT G columns with one ds_read_b64 - they become output rows 2i and 2i+1, any fixed
-// permutation of dW's rows is as good as another - and one X value (columns stay lane-contiguous for the atomics); hipcc pairs
-// the reads of two k-steps (ds_read2_b64 / ds_read2_b32): 8 LDS instructions per wave and tile instead of 32.  The two row
-// halves meet in LDS once, behind the loop (each wave hands over one accumulator and finishes the other: 16 KB through the tile
-// buffers), so a block issues the same 64 x 64 atomics as before.  (Four accumulators per wave - the whole 64 x 64 tile, rows
-// split four ways - need 6 LDS instructions per tile but 64 AGPRs: 181-196 registers, two workgroups per CU instead of three.)
+// XG: the X operand has row-gathered segments (GraphTripleConv input).  Its row indices then run through their own register
+// pipeline, one tile ahead of the data loads that use them, so that no load waits on another.  G (a gradient) is never gathered.
+//
+// Wave (wr, wc) takes the row half wr of a tile (16 rows) and the column half wc of X, and accumulates a 64 x 32 piece of dW in two
+// 32 x 32 accumulators (any fixed permutation of dW's rows is as good as another: which rows an accumulator holds is the core's).
+// The two row halves meet in LDS once, behind the loop (each wave hands over one accumulator and finishes the other: 16 KB
+// through the tile buffers), so a block issues 64 x 64 atomics.  (Four accumulators per wave - the whole 64 x 64 tile, rows split
+// four ways - need 64 AGPRs: 181-196 registers, two workgroups per CU instead of three.)
 // The per-column coefficients of the two operands are loop invariants of a thread (its four columns never change): they sit in
 // registers instead of being read from LDS for every staged float4 (16 ds_read_b128 per tile and thread).
-template <int BM, int BN, int WM, int WN, bool G_X2, bool XG>
-__device__ __forceinline__ void gemm_tn_body(const GemmTNArgs& a, const int bx, const int by, char* smem) {
-  static_assert(BM == 64 && BN == 64 && WM * WN == 4, "64 x 64 tile, 4 waves");
-  // row stride = 32 (mod 64) floats: the two rows a wavefront reads per fragment (lanes 0-31 / 32-63) fall into disjoint bank halves
-  constexpr int SA = BM + TN_PAD, SB = BN + TN_PAD;
-  constexpr int TPRA = BM / 4, TPRB = BN / 4;         // threads per row
-  constexpr int RPA = 256 / TPRA, RPB = 256 / TPRB;   // rows per pass
-  constexpr int PA = BK / RPA, PB = BK / RPB;
-  float4* coefG = reinterpret_cast<float4*>(smem);          // [BM]
-  float4* coefX = coefG + BM;                               // [BN]
-  float* As = reinterpret_cast<float*>(coefX + BN);         // [2][BK][SA]
-  float* Bs = As + 2 * BK * SA;                             // [2][BK][SB]
+template <bool G_X2, bool XG, class Core>
+struct TnFrame {
+  using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>;      // register stage tags
+  const GemmTNArgs& a;
+  float* coefGp;                           // G_X2: G's table in planar form (run)
+  int lane, wave, rbeg, rend, ntiles, last;
+  int ca, ra0;                             // this thread's four columns and first row, of both operands
+  ColSel gs, xs;
+  const int* x_ip; const float* g_x2; int g_ld2;
+  float4 g1[2][TN_NP], g2[2][TN_NP], x1[2][TN_NP];     // [register stage, see gemm_nt_body][pass]
+  int xi[2][TN_NP];
+  float4 dbacc;
+  float4 cG[4], cX[4];                     // this thread's coefficients (filled behind the table barrier)
+  f32x16 acc[2];                           // [ja]: output rows n0 + Core::out_row(., ., ja), columns k0 + 32 wc + lane % 32
+  Core core;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles_k = (a.Kin + BN - 1) / BN;
-  const int n0 = (bx / tiles_k) * BM, k0 = (bx % tiles_k) * BN;
-  const int rbeg = by * a.rows_per_block;
-  const int rend = min(a.R, rbeg + a.rows_per_block);
+  __device__ __forceinline__ explicit TnFrame(const GemmTNArgs& a_) : a(a_) {}
 
-  // per-column coefficient tables for this block's column ranges.  The two-source path re-reads G's coefficients from LDS for every
-  // staged tile; as an array of float4 per column a lane's four ds_read_b128 (columns 4 i .. 4 i + 3 of lane i % 16: a 64-byte
-  // stride) ran 4-way bank-conflicted - 64 LDS cycles per wave and tile, half of the kernel's LDS time with three workgroups per
-  // CU.  That table is PLANAR here ([kind][column]): the four coefficients of a kind for a lane's four columns are one aligned
-  // float4, 16 lanes read 256 contiguous bytes.
-  float* coefGp = reinterpret_cast<float*>(coefG);            // G_X2: [4 kinds][BM]
-  // wavefront 0 builds G's table, wavefront 1 X's: one memory round trip instead of two in a row (64 + 64 columns)
-  static_assert(BM == 64 && BN == 64, "one wavefront per table");
-  if (tid < BM) {
-    const int c = tid;
-    const float4 v = coef_for_col(a.G, n0 + c);
-    if (G_X2) { coefGp[c] = v.x; coefGp[BM + c] = v.y; coefGp[2 * BM + c] = v.z; coefGp[3 * BM + c] = v.w; }
-    else coefG[c] = v;
-  } else if (tid < BM + BN) {
-    const int c = tid - BM;
-    coefX[c] = coef_for_col(a.X, k0 + c);
+  // ---- loads: unconditional and clamped (see the note in gemm_nt_body); masking happens in stageG ----
+  __device__ __forceinline__ int row_of(int rt, int p) const { return min(rbeg + rt * BK + ra0 + TN_RPP * p, rend - 1); }
+  template <class St> __device__ __forceinline__ void loadG1(int rt, int p, St) { g1[St::value][p] = ld4(gs.x1 + (size_t)row_of(rt, p) * gs.ld1); }
+  template <class St> __device__ __forceinline__ void loadG2(int rt, int p, St) {
+    if (G_X2) g2[St::value][p] = ld4(g_x2 + (size_t)row_of(rt, p) * g_ld2);
+  }
+  template <class St> __device__ __forceinline__ void loadX(int rt, int p, St) {
+    const int row = row_of(rt, p);
+    const int r = XG ? (xs.which ? xi[St::value][p] : row) : row;
+    x1[St::value][p] = ld4(xs.x1 + (size_t)r * xs.ld1);
+  }
+  template <class St> __device__ __forceinline__ void loadI(int rt, int p, St) { if (XG) xi[St::value][p] = ldi(x_ip + row_of(rt, p)); }
+  // whole register stages, for the prologue: iload - the indices of tile rt; gload - tile rt, and the indices of the tile this
+  // stage will load next
+  template <class St> __device__ void iload(int rt, St st) {
+#pragma unroll
+    for (int p = 0; p < TN_NP; ++p) loadI(rt, p, st);
+  }
+  template <class St> __device__ void gload(int rt, int rt_idx, St st) {
+#pragma unroll
+    for (int p = 0; p < TN_NP; ++p) { loadG1(rt, p, st); loadG2(rt, p, st); }
+#pragma unroll
+    for (int p = 0; p < TN_NP; ++p) loadX(rt, p, st);
+    if (XG) iload(rt_idx, st);
   }
 
-  const int ca = 4 * (tid % TPRA), ra0 = tid / TPRA;
-  const int cb = 4 * (tid % TPRB), rb0 = tid / TPRB;
-  const ColSel gs = pick_col(a.G, n0 + ca);
-  const ColSel xs = pick_col(a.X, k0 + cb);
+  // ---- staging: pass p of tile rt out of its register stage into tile buffer buf ----
+  // rt is NOT clamped: the rows of a surplus tile (rt > last, the loop runs whole pairs of tiles) lie behind rend and are stored as
+  // zeros
+  template <class St> __device__ __forceinline__ void stageG(int rt, int buf, int p, St) {
+    constexpr int S = St::value;
+    // Masks cost matrix-pipe time (8 clocks per v_cndmask, tools/lab/overlap.hip), so only the one that is needed stays: G rows
+    // behind the chunk's end are zeroed - a zero row of G adds nothing to dW or db whatever the (clamped, finite) row of X holds.
+    // Columns behind the operand's width come out as exact zeros by themselves (their coefficient rows are zero), and a segment
+    // without a second source has c.y == 0 and reads x1 twice.
+    const int rl = ra0 + TN_RPP * p;
+    const bool v = (rbeg + rt * BK + rl) < rend;
+    // two-source gradients (BatchNorm backward) keep their coefficients in LDS: with them in registers the dgrad + wgrad kernels
+    // need 172-180 registers and lose the third workgroup per CU
+    float4 t = G_X2 ? xform_planar(g1[S][p], g2[S][p], *reinterpret_cast<const float4*>(coefGp + ca),
+                                   *reinterpret_cast<const float4*>(coefGp + TN_T + ca), *reinterpret_cast<const float4*>(coefGp + 2 * TN_T + ca),
+                                   *reinterpret_cast<const float4*>(coefGp + 3 * TN_T + ca))
+                    : xform1(g1[S][p], cG);
+    t.x = v ? t.x : 0.f; t.y = v ? t.y : 0.f; t.z = v ? t.z : 0.f; t.w = v ? t.w : 0.f;
+    dbacc.x += t.x; dbacc.y += t.y; dbacc.z += t.z; dbacc.w += t.w;
+    core.putG(buf, p, t);
+  }
+  template <class St> __device__ __forceinline__ void stageX(int buf, int p, St) { core.putX(buf, p, xform1(x1[St::value][p], cX)); }
+  // all four passes of a tile (tile 0 of a core that leaves the order of its prologue to hipcc)
+  template <class St> __device__ void stage_tile(int rt, int buf, St st) {
+#pragma unroll
+    for (int p = 0; p < TN_NP; ++p) stageG(rt, buf, p, st);
+#pragma unroll
+    for (int p = 0; p < TN_NP; ++p) stageX(buf, p, st);
+  }
 
-  constexpr int NST = 2;      // register stages, see gemm_nt_body
-  float4 g1[NST][PA], g2[NST][PA], x1[NST][PB];
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  // unconditional, clamped loads (see the note in gemm_nt_body); masking happens in lstore()
-  const int* x_ip = xs.which == 2 ? a.X.idx_b : a.X.idx_a;
-  if (x_ip == nullptr) x_ip = a.X.idx_a ? a.X.idx_a : a.X.idx_b;   // plain-row columns still issue the (unused) index loads
-  const float* g_x2 = gs.x2 ? gs.x2 : gs.x1;
-  const int g_ld2 = gs.x2 ? gs.ld2 : gs.ld1;
-  int xi[NST][PB];
-  auto iload = [&](int rt, auto stage) {
-    constexpr int S = decltype(stage)::value;
-#pragma unroll
-    for (int p = 0; p < PB; ++p) xi[S][p] = ldi(x_ip + min(rbeg + rt * BK + rb0 + RPB * p, rend - 1));
-  };
-  auto gload = [&](int rt, int rt_idx, auto stage) {
-    constexpr int S = decltype(stage)::value;
-    if (SLN_TN_ABL & 1) return;
-#pragma unroll
-    for (int p = 0; p < PA; ++p) {
-      const int row = min(rbeg + rt * BK + ra0 + RPA * p, rend - 1);
-      g1[S][p] = ld4(gs.x1 + (size_t)row * gs.ld1);
-      if (G_X2) g2[S][p] = ld4(g_x2 + (size_t)row * g_ld2);
-    }
-#pragma unroll
-    for (int p = 0; p < PB; ++p) {
-      const int row = min(rbeg + rt * BK + rb0 + RPB * p, rend - 1);
-      const int r = XG ? (xs.which ? xi[S][p] : row) : row;
-      x1[S][p] = ld4(xs.x1 + (size_t)r * xs.ld1);
-    }
-    if (XG) iload(rt_idx, stage);          // indices of the tile this stage will load next
-  };
-  float4 dbacc = z4;
-  float4 cG[4], cX[4];                     // this thread's coefficients (filled behind the table barrier)
-  // rt is NOT clamped here: the rows of a surplus tile (rt > last, the loop runs whole pairs of tiles) lie behind rend and are
-  // stored as zeros
-  auto lstore = [&](int rt, int buf, auto stage) {
-    constexpr int S = decltype(stage)::value;
-    if (SLN_TN_ABL & 2) return;
-#pragma unroll
-    for (int p = 0; p < PA; ++p) {
-      const int rl = ra0 + RPA * p;
-      // Masks cost matrix-pipe time (8 clocks per v_cndmask, tools/lab/overlap.hip), so only the one that is needed stays: G rows
-      // behind the chunk's end are zeroed - a zero row of G adds nothing to dW or db whatever the (clamped, finite) row of X holds.
-      // Columns behind the operand's width come out as exact zeros by themselves (their coefficient rows are zero), and a segment
-      // without a second source has c.y == 0 and reads x1 twice.
-      const bool v = (rbeg + rt * BK + rl) < rend;
-      // two-source gradients (BatchNorm backward) keep their coefficients in LDS: with them in registers the dgrad + wgrad kernels
-      // need 172-180 registers and lose the third workgroup per CU
-      float4 t = G_X2 ? xform_planar(g1[S][p], g2[S][p], *reinterpret_cast<const float4*>(coefGp + ca),
-                                     *reinterpret_cast<const float4*>(coefGp + BM + ca), *reinterpret_cast<const float4*>(coefGp + 2 * BM + ca),
-                                     *reinterpret_cast<const float4*>(coefGp + 3 * BM + ca))
-                      : xform1(g1[S][p], cG);
-      t.x = v ? t.x : 0.f; t.y = v ? t.y : 0.f; t.z = v ? t.z : 0.f; t.w = v ? t.w : 0.f;
-      dbacc.x += t.x; dbacc.y += t.y; dbacc.z += t.z; dbacc.w += t.w;
-      *reinterpret_cast<float4*>(As + buf * BK * SA + rl * SA + ca) = t;
-    }
-#pragma unroll
-    for (int p = 0; p < PB; ++p) {
-      const int rl = rb0 + RPB * p;
-      *reinterpret_cast<float4*>(Bs + buf * BK * SB + rl * SB + cb) = xform1(x1[S][p], cX);
-    }
-  };
-
-  f32x16 acc[2];                           // [ja]: output rows n0 + 2 i + ja, columns k0 + 32 wc + lane % 32
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-  const int ntiles = (rend - rbeg + BK - 1) / BK;
-  using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>;
-  const int last = ntiles - 1;          // ntiles >= 1: every launched block owns at least one row
-  if (XG) { iload(0, S0{}); iload(min(1, last), S1{}); }
-  gload(0, min(2, last), S0{});
-  gload(min(1, last), min(3, last), S1{});
-  __syncthreads();            // coefficient tables visible
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { if (!G_X2) cG[j] = coefG[ca + j]; cX[j] = coefX[cb + j]; }
-  lstore(0, 0, S0{});
-  gload(min(2, last), min(4, last), S0{});
-  __syncthreads();
-  const int lrow = lane & 31, lk = lane >> 5;
-  // fragments of two k-steps (4 rows of the tile) ping-pong between two register sets; set 0 is refilled with the next tile's
-  // first quarter right after the barrier, under the MFMAs of the current tile's last quarter (as in gemm_nt_body)
-  const int wr = wave >> 1, wc = wave & 1;
-  float2 fa[2][2]; float fb[2][2];
-  auto rd = [&](int buf, int quarter, auto set) __attribute__((always_inline)) {
-    constexpr int F = decltype(set)::value;
-    const float* as = As + buf * BK * SA + (16 * wr + 4 * quarter + lk) * SA + 2 * lrow;
-    const float* bs = Bs + buf * BK * SB + (16 * wr + 4 * quarter + lk) * SB + 32 * wc + lrow;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      fa[F][q] = *reinterpret_cast<const float2*>(as + 2 * q * SA);
-      fb[F][q] = bs[2 * q * SB];
-    }
-  };
-  auto mma = [&](auto set) {
-    constexpr int F = decltype(set)::value;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F][q].x, fb[F][q], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F][q].y, fb[F][q], acc[1], 0, 0, 0);
-    }
-  };
-  rd(0, 0, S0{});
-  // same schedule as gemm_nt_body: stage the next tile and refill its register stage first, one straight loop over pairs
-  auto body = [&](int rt, auto stage_next) {
-    const int buf = rt & 1;
-    lstore(rt + 1, buf ^ 1, stage_next);
-    gload(min(rt + 3, last), min(rt + 5, last), stage_next);
+  // ---- the pieces a core's K loop issues while it computes tile rt out of buffer buf: a staging pass of tile rt + 1 into buffer
+  // buf ^ 1 with the reload of its register stage (tile rt + 3) right behind, and the indices of the tile after that ----
+  template <class St> __device__ __forceinline__ void pieceG(int rt, int buf, int p, St st) {
+    stageG(rt + 1, buf ^ 1, p, st);
     __builtin_amdgcn_sched_barrier(0);
-    if (!(SLN_TN_ABL & 8)) rd(buf, 1, S1{});
-    mma(S0{});
-    if (!(SLN_TN_ABL & 8)) rd(buf, 2, S0{});
-    mma(S1{});
-    if (!(SLN_TN_ABL & 8)) rd(buf, 3, S1{});
-    mma(S0{});
-    if (!(SLN_TN_ABL & 4)) __syncthreads();
-    if (!(SLN_TN_ABL & 8)) rd(buf ^ 1, 0, S0{});
-    mma(S1{});
-  };
-#if SLN_TN_SCHED
-  // The same loop with its instruction order written out (as gemm_nt_body's): hipcc issues the tile's four to six global loads and
-  // four LDS writes back to back at the top of the body, and a second memory instruction behind the first stalls the wave at the
-  // issue stage (64 / 52 clocks, tools/lab/overlap.hip) with all its MFMAs queued behind - without the loads the stand-alone
-  // 32 k-row wgrad runs at 100 TF instead of 85 (SLN_TN_ABL).  Here every store / reload pair of a staging pass sits behind its own
-  // MFMA: G passes behind MFMAs 0 .. 3 (the second source one slot later), X passes behind 4 and 5, the row indices of a gathered
-  // X behind 6 and 7; fragment reads a quarter ahead as before.  Same arithmetic, same sums.
-  {
+    loadG1(min(rt + 3, last), p, st);
+  }
+  template <class St> __device__ __forceinline__ void pieceG2(int rt, int p, St st) { loadG2(min(rt + 3, last), p, st); }
+  template <class St> __device__ __forceinline__ void pieceX(int rt, int buf, int p, St st) {
+    stageX(buf ^ 1, p, st);
+    __builtin_amdgcn_sched_barrier(0);
+    loadX(min(rt + 3, last), p, st);
+  }
+  template <class St> __device__ __forceinline__ void pieceI(int rt, int p, St st) { loadI(min(rt + 5, last), p, st); }
+
+  __device__ __forceinline__ void run(const int bx, const int by, char* smem) {
+    float4* coefG = reinterpret_cast<float4*>(smem);          // [64]
+    float4* coefX = coefG + TN_T;                             // [64]
+    char* tiles = reinterpret_cast<char*>(coefX + TN_T);      // the core's two tile buffers (tn_smem_bytes)
+
+    const int tid = threadIdx.x;
+    lane = tid & 63; wave = tid >> 6;
+    const int tiles_k = (a.Kin + TN_T - 1) / TN_T;
+    const int n0 = (bx / tiles_k) * TN_T, k0 = (bx % tiles_k) * TN_T;
+    rbeg = by * a.rows_per_block;
+    rend = min(a.R, rbeg + a.rows_per_block);
+
+    // per-column coefficient tables for this block's column ranges.  The two-source path re-reads G's coefficients from LDS for every
+    // staged tile; as an array of float4 per column a lane's four ds_read_b128 (columns 4 i .. 4 i + 3 of lane i % 16: a 64-byte
+    // stride) ran 4-way bank-conflicted - 64 LDS cycles per wave and tile, half of the kernel's LDS time with three workgroups per
+    // CU.  That table is PLANAR here ([kind][column]): the four coefficients of a kind for a lane's four columns are one aligned
+    // float4, 16 lanes read 256 contiguous bytes.
+    coefGp = reinterpret_cast<float*>(coefG);                 // G_X2: [4 kinds][64]
+    // wavefront 0 builds G's table, wavefront 1 X's: one memory round trip instead of two in a row (64 + 64 columns)
+    if (tid < TN_T) {
+      const int c = tid;
+      const float4 v = coef_for_col(a.G, n0 + c);
+      if (G_X2) { coefGp[c] = v.x; coefGp[TN_T + c] = v.y; coefGp[2 * TN_T + c] = v.z; coefGp[3 * TN_T + c] = v.w; }
+      else coefG[c] = v;
+    } else if (tid < 2 * TN_T) {
+      const int c = tid - TN_T;
+      coefX[c] = coef_for_col(a.X, k0 + c);
+    }
+
+    ca = 4 * (tid % TN_TPR); ra0 = tid / TN_TPR;
+    gs = pick_col(a.G, n0 + ca);
+    xs = pick_col(a.X, k0 + ca);
+    x_ip = xs.which == 2 ? a.X.idx_b : a.X.idx_a;
+    if (x_ip == nullptr) x_ip = a.X.idx_a ? a.X.idx_a : a.X.idx_b;   // plain-row columns still issue the (unused) index loads
+    g_x2 = gs.x2 ? gs.x2 : gs.x1;
+    g_ld2 = gs.x2 ? gs.ld2 : gs.ld1;
+    dbacc = make_float4(0.f, 0.f, 0.f, 0.f);
+    core.init(tiles, ra0, ca);
+
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+
+    ntiles = (rend - rbeg + BK - 1) / BK;
+    last = ntiles - 1;                    // ntiles >= 1: every launched block owns at least one row
+    if (XG) { iload(0, S0{}); iload(min(1, last), S1{}); }
+    gload(0, min(2, last), S0{});
+    gload(min(1, last), min(3, last), S1{});
+    __syncthreads();            // coefficient tables visible
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { if (!G_X2) cG[j] = coefG[ca + j]; cX[j] = coefX[ca + j]; }
+
+    core.run(*this);            // tile 0 out of stage 0, then the K loop over whole pairs of tiles
+
+    // ---- the two row halves meet: wave (wr, wc) finishes accumulator ja = wr of column half wc ----
+    // Accumulators are read out of the AGPRs at their use (v_accvgpr_read through an "a" constraint): left alone hipcc copies all
+    // of them to VGPRs in front of the epilogue and that copy sets the kernel's register count.
+    const int lrow = lane & 31, lk = lane >> 5;
+    const int wr = wave >> 1, wc = wave & 1;
+    __syncthreads();                          // every wave is done with the tile buffers
+    float* red = reinterpret_cast<float*>(tiles);      // [wave 4][16][64] floats = 16 KB of the tile buffers
+    {
+      float* dst = red + (wave * 16) * 64 + lane;
+      if (wr == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dst[r * 64] = tn_acc_read(acc[1][r]);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dst[r * 64] = tn_acc_read(acc[0][r]);
+      }
+    }
+    __syncthreads();
+    {
+      const float* src = red + ((wave ^ 2) * 16) * 64 + lane;      // the partner's copy of the accumulator this wave keeps
+      const float sc = a.sgd_step != nullptr ? -a.sgd_step[0] : 1.f;   // GemmTNArgs::sgd_step (x 1 is exact)
+      const int k = k0 + 32 * wc + lrow;
+      float* dcol = a.dW + min(k, a.Kin - 1);
+      const bool kv = k < a.Kin;
+      // sum order (row half 0) + (row half 1) whichever wave finishes
+      if (wr == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = (tn_acc_read(acc[0][r]) + src[r * 64]) * sc;
+          const int n = n0 + Core::out_row(r, lk, 0);
+          if (kv && n < a.Nout) sln_gatomic_add(dcol + (size_t)n * a.lddw, v);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = (src[r * 64] + tn_acc_read(acc[1][r])) * sc;
+          const int n = n0 + Core::out_row(r, lk, 1);
+          if (kv && n < a.Nout) sln_gatomic_add(dcol + (size_t)n * a.lddw, v);
+        }
+      }
+    }
+
+    if (a.db != nullptr && (bx % tiles_k) == 0) {
+      // threads with equal (tid % TN_TPR) hold partial sums of the same 4 columns
+#pragma unroll
+      for (int off = TN_TPR; off < 64; off <<= 1) {
+        dbacc.x += __shfl_xor(dbacc.x, off, 64); dbacc.y += __shfl_xor(dbacc.y, off, 64);
+        dbacc.z += __shfl_xor(dbacc.z, off, 64); dbacc.w += __shfl_xor(dbacc.w, off, 64);
+      }
+      // the four wavefronts' sums meet in LDS in a fixed order: ONE add per element and block (four atomics - one per wavefront, in
+      // arrival order - made the bias gradient the last order-dependent sum of a single-chunk wgrad)
+      __syncthreads();                          // the accumulator hand-over above is done with `red`
+      float4* dbs = reinterpret_cast<float4*>(red);            // [4 waves][TN_TPR]
+      if (lane < TN_TPR) dbs[wave * TN_TPR + lane] = dbacc;
+      __syncthreads();
+      if (tid < TN_TPR) {
+        const float4 p0 = dbs[tid], p1 = dbs[TN_TPR + tid], p2 = dbs[2 * TN_TPR + tid], p3 = dbs[3 * TN_TPR + tid];
+        const int n = n0 + 4 * tid;
+        const float sb = a.sgd_step != nullptr ? -a.sgd_step[0] : 1.f;
+        if (n + 0 < a.Nout) sln_gatomic_add(a.db + n + 0, (((p0.x + p1.x) + p2.x) + p3.x) * sb);
+        if (n + 1 < a.Nout) sln_gatomic_add(a.db + n + 1, (((p0.y + p1.y) + p2.y) + p3.y) * sb);
+        if (n + 2 < a.Nout) sln_gatomic_add(a.db + n + 2, (((p0.z + p1.z) + p2.z) + p3.z) * sb);
+        if (n + 3 < a.Nout) sln_gatomic_add(a.db + n + 3, (((p0.w + p1.w) + p2.w) + p3.w) * sb);
+      }
+    }
+  }
+};
+
 #define SLN_SB __builtin_amdgcn_sched_barrier(0)
-    auto pieceG = [&](int rt, int buf, int p, auto stage) __attribute__((always_inline)) {       // store pass p of tile rt + 1, reload x1 of tile rt + 3
-      constexpr int S = decltype(stage)::value;
-      const int rl = ra0 + RPA * p;
-      const bool v = (rbeg + (rt + 1) * BK + rl) < rend;
-      float4 t = G_X2 ? xform_planar(g1[S][p], g2[S][p], *reinterpret_cast<const float4*>(coefGp + ca),
-                                     *reinterpret_cast<const float4*>(coefGp + BM + ca), *reinterpret_cast<const float4*>(coefGp + 2 * BM + ca),
-                                     *reinterpret_cast<const float4*>(coefGp + 3 * BM + ca))
-                      : xform1(g1[S][p], cG);
-      t.x = v ? t.x : 0.f; t.y = v ? t.y : 0.f; t.z = v ? t.z : 0.f; t.w = v ? t.w : 0.f;
-      dbacc.x += t.x; dbacc.y += t.y; dbacc.z += t.z; dbacc.w += t.w;
-      *reinterpret_cast<float4*>(As + (buf ^ 1) * BK * SA + rl * SA + ca) = t;
-      SLN_SB;
-      const int row = min(rbeg + min(rt + 3, last) * BK + ra0 + RPA * p, rend - 1);
-      g1[S][p] = ld4(gs.x1 + (size_t)row * gs.ld1);
+
+// The fp32 core: v_mfma_f32_32x32x2_f32, exact fp32 products, 32 MFMAs x 64 clocks per wave and 32-row tile.
+// The tiles stay ROW-major in LDS, as the rows arrive ([BK rows][64 columns + pad]: one ds_write_b128 per staged float4, no
+// transposing store).  A lane reads two ADJACENT G columns with one ds_read_b64 - they become output rows 2 i and 2 i + 1 - and one
+// X value (columns stay lane-contiguous for the atomics); hipcc pairs the reads of two k-steps (ds_read2_b64 / ds_read2_b32): 8 LDS
+// instructions per wave and tile (a 32 x 32 quarter of the output per wave, every operand value fetched with its own ds_read_b32,
+// took 32).
+struct TnCoreF32 {
+  // row stride = 32 (mod 64) floats: the two rows a wavefront reads per fragment (lanes 0-31 / 32-63) fall into disjoint bank halves
+  static constexpr int SA = TN_T + TN_PAD;
+  float* As; float* Bs;                    // [2][BK][SA] each
+  int ra0, ca;
+  __device__ __forceinline__ void init(char* tiles, int ra0_, int ca_) {
+    As = reinterpret_cast<float*>(tiles); Bs = As + 2 * BK * SA; ra0 = ra0_; ca = ca_;
+  }
+  __device__ __forceinline__ void putG(int buf, int p, float4 t) { *reinterpret_cast<float4*>(As + buf * BK * SA + (ra0 + TN_RPP * p) * SA + ca) = t; }
+  __device__ __forceinline__ void putX(int buf, int p, float4 t) { *reinterpret_cast<float4*>(Bs + buf * BK * SA + (ra0 + TN_RPP * p) * SA + ca) = t; }
+  static __device__ __forceinline__ int out_row(int r, int lk, int ja) { return 2 * ((r & 3) + 8 * (r >> 2) + 4 * lk) + ja; }
+
+  template <class F>
+  __device__ __forceinline__ void run(F& f) {
+    using S0 = typename F::S0; using S1 = typename F::S1;
+    const int last = f.last;
+    // tile 0 out of stage 0, then the refill of the stage, in hipcc's order
+    f.stage_tile(0, 0, S0{});
+    f.gload(min(2, last), min(4, last), S0{});
+    __syncthreads();
+    const int lrow = f.lane & 31, lk = f.lane >> 5;
+    // fragments of two k-steps (4 rows of the tile) ping-pong between two register sets; set 0 is refilled with the next tile's
+    // first quarter right after the barrier, under the MFMAs of the current tile's last quarter (as in gemm_nt_body)
+    const int wr = f.wave >> 1, wc = f.wave & 1;
+    float2 fa[2][2]; float fb[2][2];
+    auto rd = [&](int buf, int quarter, auto set) __attribute__((always_inline)) {
+      constexpr int F_ = decltype(set)::value;
+      const float* as = As + buf * BK * SA + (16 * wr + lk) * SA + 4 * quarter * SA + 2 * lrow;
+      const float* bs = Bs + buf * BK * SA + (16 * wr + lk) * SA + 4 * quarter * SA + 32 * wc + lrow;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        fa[F_][q] = *reinterpret_cast<const float2*>(as + 2 * q * SA);
+        fb[F_][q] = bs[2 * q * SA];
+      }
     };
-    auto pieceG2 = [&](int rt, int p, auto stage) __attribute__((always_inline)) {
-      constexpr int S = decltype(stage)::value;
-      const int row = min(rbeg + min(rt + 3, last) * BK + ra0 + RPA * p, rend - 1);
-      if (G_X2) g2[S][p] = ld4(g_x2 + (size_t)row * g_ld2);
-    };
-    auto pieceX = [&](int rt, int buf, int p, auto stage) __attribute__((always_inline)) {
-      constexpr int S = decltype(stage)::value;
-      *reinterpret_cast<float4*>(Bs + (buf ^ 1) * BK * SB + (rb0 + RPB * p) * SB + cb) = xform1(x1[S][p], cX);
-      SLN_SB;
-      const int row = min(rbeg + min(rt + 3, last) * BK + rb0 + RPB * p, rend - 1);
-      const int r = XG ? (xs.which ? xi[S][p] : row) : row;
-      x1[S][p] = ld4(xs.x1 + (size_t)r * xs.ld1);
-    };
-    auto pieceI = [&](int rt, int p, auto stage) __attribute__((always_inline)) {               // indices of the tile this stage loads next
-      constexpr int S = decltype(stage)::value;
-      if (XG) xi[S][p] = ldi(x_ip + min(rbeg + min(rt + 5, last) * BK + rb0 + RPB * p, rend - 1));
-    };
+    rd(0, 0, S0{});
+    // The loop with its instruction order written out (as gemm_nt_body's): hipcc issues the tile's four to six global loads and
+    // four LDS writes back to back at the top of the body, and a second memory instruction behind the first stalls the wave at the
+    // issue stage (64 / 52 clocks, tools/lab/overlap.hip) with all its MFMAs queued behind - without the loads the stand-alone
+    // 32 k-row wgrad runs at 100 TF instead of 85.  Here every store / reload pair of a staging pass sits behind its own
+    // MFMA: G passes behind MFMAs 0 .. 3 (the second source one slot later), X passes behind 4 and 5, the row indices of a gathered
+    // X behind 6 and 7; fragment reads a quarter ahead.
     // the four MFMAs of a quarter (two k-steps x two accumulators), hook(n) behind the n-th
     auto mma4 = [&](auto set, auto&& hook) __attribute__((always_inline)) {
-      constexpr int F = decltype(set)::value;
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F][0].x, fb[F][0], acc[0], 0, 0, 0); SLN_SB; hook(0); SLN_SB;
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F][0].y, fb[F][0], acc[1], 0, 0, 0); SLN_SB; hook(1); SLN_SB;
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F][1].x, fb[F][1], acc[0], 0, 0, 0); SLN_SB; hook(2); SLN_SB;
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F][1].y, fb[F][1], acc[1], 0, 0, 0); SLN_SB; hook(3); SLN_SB;
+      constexpr int F_ = decltype(set)::value;
+      f.acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F_][0].x, fb[F_][0], f.acc[0], 0, 0, 0); SLN_SB; hook(0); SLN_SB;
+      f.acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F_][0].y, fb[F_][0], f.acc[1], 0, 0, 0); SLN_SB; hook(1); SLN_SB;
+      f.acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F_][1].x, fb[F_][1], f.acc[0], 0, 0, 0); SLN_SB; hook(2); SLN_SB;
+      f.acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[F_][1].y, fb[F_][1], f.acc[1], 0, 0, 0); SLN_SB; hook(3); SLN_SB;
     };
-    static_assert(PA == 2 && PB == 2, "two staging passes per operand and tile");
     auto sbody = [&](int rt, auto stage_next) __attribute__((always_inline)) {
       const int buf = rt & 1;
       rd(buf, 1, S1{});
       SLN_SB;
       mma4(S0{}, [&](int n) __attribute__((always_inline)) {
-        if (n == 0) pieceG(rt, buf, 0, stage_next);
-        if (n == 1) pieceG2(rt, 0, stage_next);
-        if (n == 2) pieceG(rt, buf, 1, stage_next);
-        if (n == 3) { pieceG2(rt, 1, stage_next); rd(buf, 2, S0{}); }
+        if (n == 0) f.pieceG(rt, buf, 0, stage_next);
+        if (n == 1) f.pieceG2(rt, 0, stage_next);
+        if (n == 2) f.pieceG(rt, buf, 1, stage_next);
+        if (n == 3) { f.pieceG2(rt, 1, stage_next); rd(buf, 2, S0{}); }
       });
       mma4(S1{}, [&](int n) __attribute__((always_inline)) {
-        if (n == 0) pieceX(rt, buf, 0, stage_next);
-        if (n == 1) pieceX(rt, buf, 1, stage_next);
-        if (n == 2) pieceI(rt, 0, stage_next);
-        if (n == 3) { pieceI(rt, 1, stage_next); rd(buf, 3, S1{}); }
+        if (n == 0) f.pieceX(rt, buf, 0, stage_next);
+        if (n == 1) f.pieceX(rt, buf, 1, stage_next);
+        if (n == 2) f.pieceI(rt, 0, stage_next);
+        if (n == 3) { f.pieceI(rt, 1, stage_next); rd(buf, 3, S1{}); }
       });
       mma4(S0{}, [&](int) __attribute__((always_inline)) {});
       __syncthreads();
@@ -1476,98 +1533,24 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTNArgs& a, const int bx, 
       SLN_SB;
       mma4(S1{}, [&](int) __attribute__((always_inline)) {});
     };
-#undef SLN_SB
-    for (int rt = 0; rt < ntiles; rt += 2) { sbody(rt, S1{}); sbody(rt + 1, S0{}); }
+    for (int rt = 0; rt < f.ntiles; rt += 2) { sbody(rt, S1{}); sbody(rt + 1, S0{}); }
   }
-#else
-  for (int rt = 0; rt < ntiles; rt += 2) { body(rt, S1{}); body(rt + 1, S0{}); }
-#endif
+};
 
-  // ---- the two row halves meet: wave (wr, wc) finishes accumulator ja = wr of column half wc ----
-  // Accumulators are read out of the AGPRs at their use (v_accvgpr_read through an "a" constraint): left alone hipcc copies all
-  // of them to VGPRs in front of the epilogue and that copy sets the kernel's register count.
-  __syncthreads();                          // every wave is done with the tile buffers
-  float* red = As;                          // [wave 4][16][64] floats = 16 KB of the tile buffers
-  {
-    float* dst = red + (wave * 16) * 64 + lane;
-    if (wr == 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r * 64] = tn_acc_read(acc[1][r]);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r * 64] = tn_acc_read(acc[0][r]);
-    }
-  }
-  __syncthreads();
-  {
-    const float* src = red + ((wave ^ 2) * 16) * 64 + lane;      // the partner's copy of the accumulator this wave keeps
-    const float sc = a.sgd_step != nullptr ? -a.sgd_step[0] : 1.f;   // GemmTNArgs::sgd_step (x 1 is exact)
-    const int k = k0 + 32 * wc + lrow;
-    float* dcol = a.dW + min(k, a.Kin - 1);
-    const bool kv = k < a.Kin;
-    // sum order (row half 0) + (row half 1) whichever wave finishes
-    if (wr == 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = (tn_acc_read(acc[0][r]) + src[r * 64]) * sc;
-        const int n = n0 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * lk);
-        if (kv && n < a.Nout) sln_gatomic_add(dcol + (size_t)n * a.lddw, v);
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = (src[r * 64] + tn_acc_read(acc[1][r])) * sc;
-        const int n = n0 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * lk) + 1;
-        if (kv && n < a.Nout) sln_gatomic_add(dcol + (size_t)n * a.lddw, v);
-      }
-    }
-  }
-
-  if (a.db != nullptr && (bx % tiles_k) == 0) {
-    // threads with equal (tid % TPRA) hold partial sums of the same 4 columns
-#pragma unroll
-    for (int off = TPRA; off < 64; off <<= 1) {
-      dbacc.x += __shfl_xor(dbacc.x, off, 64); dbacc.y += __shfl_xor(dbacc.y, off, 64);
-      dbacc.z += __shfl_xor(dbacc.z, off, 64); dbacc.w += __shfl_xor(dbacc.w, off, 64);
-    }
-    // the four wavefronts' sums meet in LDS in a fixed order: ONE add per element and block (four atomics - one per wavefront, in
-    // arrival order - made the bias gradient the last order-dependent sum of a single-chunk wgrad)
-    __syncthreads();                          // the accumulator hand-over above is done with `red`
-    float4* dbs = reinterpret_cast<float4*>(red);            // [4 waves][TPRA]
-    if (lane < TPRA) dbs[wave * TPRA + lane] = dbacc;
-    __syncthreads();
-    if (tid < TPRA) {
-      const float4 p0 = dbs[tid], p1 = dbs[TPRA + tid], p2 = dbs[2 * TPRA + tid], p3 = dbs[3 * TPRA + tid];
-      const int n = n0 + 4 * tid;
-      const float sb = a.sgd_step != nullptr ? -a.sgd_step[0] : 1.f;
-      if (n + 0 < a.Nout) sln_gatomic_add(a.db + n + 0, (((p0.x + p1.x) + p2.x) + p3.x) * sb);
-      if (n + 1 < a.Nout) sln_gatomic_add(a.db + n + 1, (((p0.y + p1.y) + p2.y) + p3.y) * sb);
-      if (n + 2 < a.Nout) sln_gatomic_add(a.db + n + 2, (((p0.z + p1.z) + p2.z) + p3.z) * sb);
-      if (n + 3 < a.Nout) sln_gatomic_add(a.db + n + 3, (((p0.w + p1.w) + p2.w) + p3.w) * sb);
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// TN kernel (wgrad) on the 16-bit matrix pipe: every operand value as three bf16 parts (LAB_NOTES 32)
-// ---------------------------------------------------------------------------------------------
-// gemm_tn_body spends 32 v_mfma_f32_32x32x2_f32 x 64 clocks per wave and 32-row tile.  Here each transformed fp32 value v is split
-// while it is staged: p1 = bf16(v), p2 = bf16(v - p1), p3 = bf16(v - p1 - p2) (round to nearest; both differences are exact in fp32,
-// and bf16 has fp32's exponent range: no scale, no clamp, a gradient of 1e-30 splits like one of 1), and a 16-row k-step is six
-// v_mfma_f32_32x32x16_bf16 per accumulator, smallest first: g1 x3, g3 x1, g2 x2, g1 x2, g2 x1, g1 x1.  The three dropped products are
-// below 2^-24 of g x.  12 MFMAs x 32 clocks per wave and tile.
-// Everything around that is gemm_tn_body's: the tables, the loads and their register stages, the transforms, the fp32 bias sum, the
-// wave split (16 of the tile's 32 rows, 32 of X's columns, two accumulators) and the epilogue - except that accumulator ja holds the
-// output rows n0 + 32 ja + i (the transposed read hands a lane ONE column; any fixed permutation of dW's rows is as good as another).
+// The split core: the 16-bit matrix pipe, every operand value as three bf16 parts (LAB_NOTES 32).
+// Each transformed fp32 value v is split while it is staged: p1 = bf16(v), p2 = bf16(v - p1), p3 = bf16(v - p1 - p2) (round to
+// nearest; both differences are exact in fp32, and bf16 has fp32's exponent range: no scale, no clamp, a gradient of 1e-30 splits
+// like one of 1), and a 16-row k-step is six v_mfma_f32_32x32x16_bf16 per accumulator, smallest first: g1 x3, g3 x1, g2 x2, g1 x2,
+// g2 x1, g1 x1.  The three dropped products are below 2^-24 of g x.  12 MFMAs x 32 clocks per wave and tile, against the fp32
+// core's 32 x 64.  Accumulator ja holds the output rows 32 ja + i: the transposed read hands a lane ONE column.
 // LDS: one row-major bf16 image [32 k rows][64 columns] (128-byte rows, 4 KB) per part, operand and buffer = 48 KB, the size of the
 // fp32 tiles.  A thread writes its four columns of a part with one 8-byte store; fragments come out with ds_read_b64_tr_b16 (4 rows x
 // 16 columns per group of 16 lanes).  The 32 lanes of a half read 4 rows x 64 bytes: at a 128-byte stride rows q and q + 2 would meet
 // on the same banks (2-way), so the 64-byte halves of rows 2, 3 (mod 4) are swapped (byte ^= ((row >> 1) & 1) << 6) - the four rows
 // then cover the four quarters of the 256-byte bank row.  No padding (padded images would not fit three workgroups per CU).
-// Operands that are already broken come out differently from the fp32 body: v = +-inf gives p1 = inf and v - p1 = NaN, and a finite
-// |v| above bf16's largest value less half a step (3.39e38 (1 - 2^-9)) rounds p1 to inf likewise - NaN where the fp32 body gives inf.
-// The transposed read needs EXEC = all ones: the body runs under workgroup-uniform branches only and no lane is ever masked.
+// Operands that are already broken come out differently from the fp32 core: v = +-inf gives p1 = inf and v - p1 = NaN, and a finite
+// |v| above bf16's largest value less half a step (3.39e38 (1 - 2^-9)) rounds p1 to inf likewise - NaN where the fp32 core gives inf.
+// The transposed read needs EXEC = all ones: the frame runs under workgroup-uniform branches only and no lane is ever masked.
 typedef __bf16 sln_bf16x8 __attribute__((ext_vector_type(8)));
 typedef short sln_s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) sln_s16x4* sln_lds_s16x4p;
@@ -1591,234 +1574,91 @@ __device__ __forceinline__ sln_bf16x8 tn_tr_frag(const char* p) {             //
   return __builtin_bit_cast(sln_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-template <bool G_X2, bool XG>
-__device__ __forceinline__ void gemm_tn_split_body(const GemmTNArgs& a, const int bx, const int by, char* smem) {
-  constexpr int BM = 64, BN = 64;
-  constexpr int TPR = 16, RPP = 16;                   // threads per row, rows per staging pass (two passes per operand and tile)
-  constexpr int ROWB = 128, IMG = BK * ROWB, OPB = 3 * IMG, BUFB = 2 * OPB;      // bytes: image row, image, operand (3 parts), buffer (G, X)
-  static_assert(BK == 32 && 2 * BUFB == 2 * BK * (BM + TN_PAD + BN + TN_PAD) * 4, "the bf16 images fill the fp32 tiles' LDS (tn_smem_bytes)");
-  float4* coefG = reinterpret_cast<float4*>(smem);          // [BM]
-  float4* coefX = coefG + BM;                               // [BN]
-  char* img = reinterpret_cast<char*>(coefX + BN);          // [2 buffers][G, X][3 parts][BK rows][128 bytes]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles_k = (a.Kin + BN - 1) / BN;
-  const int n0 = (bx / tiles_k) * BM, k0 = (bx % tiles_k) * BN;
-  const int rbeg = by * a.rows_per_block;
-  const int rend = min(a.R, rbeg + a.rows_per_block);
-
-  float* coefGp = reinterpret_cast<float*>(coefG);            // G_X2: [4 kinds][BM], see gemm_tn_body
-  if (tid < BM) {
-    const int c = tid;
-    const float4 v = coef_for_col(a.G, n0 + c);
-    if (G_X2) { coefGp[c] = v.x; coefGp[BM + c] = v.y; coefGp[2 * BM + c] = v.z; coefGp[3 * BM + c] = v.w; }
-    else coefG[c] = v;
-  } else if (tid < BM + BN) {
-    const int c = tid - BM;
-    coefX[c] = coef_for_col(a.X, k0 + c);
+struct TnCoreSplit {
+  static constexpr int ROWB = 128, IMG = BK * ROWB, OPB = 3 * IMG, BUFB = 2 * OPB;      // bytes: image row, image, operand (3 parts), buffer (G, X)
+  static_assert(2 * BUFB == 2 * BK * (TN_T + TN_PAD + TN_T + TN_PAD) * 4, "the bf16 images fill the fp32 tiles' LDS (tn_smem_bytes)");
+  char* img;                               // [2 buffers][G, X][3 parts][BK rows][128 bytes]
+  int woff;                                // byte offset of this thread's 8 bytes in an image (row ra0, + 16 rows for the second pass: the swapped halves do not move)
+  __device__ __forceinline__ void init(char* tiles, int ra0, int ca) {
+    img = tiles; woff = ra0 * ROWB + ((2 * ca) ^ (((ra0 >> 1) & 1) << 6));
   }
-
-  const int ca = 4 * (tid % TPR), ra0 = tid / TPR;          // this thread's four columns and first row, of both operands
-  const ColSel gs = pick_col(a.G, n0 + ca);
-  const ColSel xs = pick_col(a.X, k0 + ca);
-
-  const int ntiles = (rend - rbeg + BK - 1) / BK;
-  const int last = ntiles - 1;          // ntiles >= 1: every launched block owns at least one row
-  constexpr int NST = 2;
-  float4 g1[NST][2], g2[NST][2], x1[NST][2];
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int* x_ip = xs.which == 2 ? a.X.idx_b : a.X.idx_a;
-  if (x_ip == nullptr) x_ip = a.X.idx_a ? a.X.idx_a : a.X.idx_b;
-  const float* g_x2 = gs.x2 ? gs.x2 : gs.x1;
-  const int g_ld2 = gs.x2 ? gs.ld2 : gs.ld1;
-  int xi[NST][2];
-  auto iload = [&](int rt, auto stage) {
-    constexpr int S = decltype(stage)::value;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) xi[S][p] = ldi(x_ip + min(rbeg + rt * BK + ra0 + RPP * p, rend - 1));
-  };
-  auto gload = [&](int rt, int rt_idx, auto stage) {
-    constexpr int S = decltype(stage)::value;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int row = min(rbeg + rt * BK + ra0 + RPP * p, rend - 1);
-      g1[S][p] = ld4(gs.x1 + (size_t)row * gs.ld1);
-      if (G_X2) g2[S][p] = ld4(g_x2 + (size_t)row * g_ld2);
-    }
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int row = min(rbeg + rt * BK + ra0 + RPP * p, rend - 1);
-      const int r = XG ? (xs.which ? xi[S][p] : row) : row;
-      x1[S][p] = ld4(xs.x1 + (size_t)r * xs.ld1);
-    }
-    if (XG) iload(rt_idx, stage);
-  };
-  float4 dbacc = z4;
-  float4 cG[4], cX[4];
-  // byte offset of this thread's 8 bytes in an image (row ra0, + 16 rows for the second pass: the swapped halves do not move)
-  const int woff = ra0 * ROWB + ((2 * ca) ^ (((ra0 >> 1) & 1) << 6));
-  auto put = [&](char* dst, float4 t) __attribute__((always_inline)) {
+  __device__ __forceinline__ void put(char* dst, float4 t) {
     uint2 q1, q2, q3;
     tn_split2(t.x, t.y, q1.x, q2.x, q3.x);
     tn_split2(t.z, t.w, q1.y, q2.y, q3.y);
     *reinterpret_cast<uint2*>(dst) = q1;
     *reinterpret_cast<uint2*>(dst + IMG) = q2;
     *reinterpret_cast<uint2*>(dst + 2 * IMG) = q3;
-  };
-  // the staging passes, as gemm_tn_body's scheduled loop cuts them: pass p of tile rt + 1 goes to buffer buf ^ 1 and its register
-  // stage is refilled with tile rt + 3.  Rows behind the chunk's end are stored as zeros (G only, see gemm_tn_body).
-  auto pieceG = [&](int rt, int buf, int p, auto stage) __attribute__((always_inline)) {
-    constexpr int S = decltype(stage)::value;
-    const int rl = ra0 + RPP * p;
-    const bool v = (rbeg + (rt + 1) * BK + rl) < rend;
-    float4 t = G_X2 ? xform_planar(g1[S][p], g2[S][p], *reinterpret_cast<const float4*>(coefGp + ca),
-                                   *reinterpret_cast<const float4*>(coefGp + BM + ca), *reinterpret_cast<const float4*>(coefGp + 2 * BM + ca),
-                                   *reinterpret_cast<const float4*>(coefGp + 3 * BM + ca))
-                    : xform1(g1[S][p], cG);
-    t.x = v ? t.x : 0.f; t.y = v ? t.y : 0.f; t.z = v ? t.z : 0.f; t.w = v ? t.w : 0.f;
-    dbacc.x += t.x; dbacc.y += t.y; dbacc.z += t.z; dbacc.w += t.w;
-    put(img + (buf ^ 1) * BUFB + p * RPP * ROWB + woff, t);
-    __builtin_amdgcn_sched_barrier(0);
-    const int row = min(rbeg + min(rt + 3, last) * BK + rl, rend - 1);
-    g1[S][p] = ld4(gs.x1 + (size_t)row * gs.ld1);
-    if (G_X2) g2[S][p] = ld4(g_x2 + (size_t)row * g_ld2);
-  };
-  auto pieceX = [&](int rt, int buf, int p, auto stage) __attribute__((always_inline)) {
-    constexpr int S = decltype(stage)::value;
-    put(img + (buf ^ 1) * BUFB + OPB + p * RPP * ROWB + woff, xform1(x1[S][p], cX));
-    __builtin_amdgcn_sched_barrier(0);
-    const int row = min(rbeg + min(rt + 3, last) * BK + ra0 + RPP * p, rend - 1);
-    const int r = XG ? (xs.which ? xi[S][p] : row) : row;
-    x1[S][p] = ld4(xs.x1 + (size_t)r * xs.ld1);
-  };
-  auto pieceI = [&](int rt, int p, auto stage) __attribute__((always_inline)) {
-    constexpr int S = decltype(stage)::value;
-    if (XG) xi[S][p] = ldi(x_ip + min(rbeg + min(rt + 5, last) * BK + ra0 + RPP * p, rend - 1));
-  };
+  }
+  __device__ __forceinline__ void putG(int buf, int p, float4 t) { put(img + buf * BUFB + p * TN_RPP * ROWB + woff, t); }
+  __device__ __forceinline__ void putX(int buf, int p, float4 t) { put(img + buf * BUFB + OPB + p * TN_RPP * ROWB + woff, t); }
+  static __device__ __forceinline__ int out_row(int r, int lk, int ja) { return 32 * ja + (r & 3) + 8 * (r >> 2) + 4 * lk; }
 
-  f32x16 acc[2];                           // [ja]: output rows n0 + 32 ja + i, columns k0 + 32 wc + lane % 32
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-
-  using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>;
-  if (XG) { iload(0, S0{}); iload(min(1, last), S1{}); }
-  gload(0, min(2, last), S0{});
-  gload(min(1, last), min(3, last), S1{});
-  __syncthreads();            // coefficient tables visible
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { if (!G_X2) cG[j] = coefG[ca + j]; cX[j] = coefX[ca + j]; }
-  // tile 0 out of stage 0 (pieces of "tile -1": they store tile 0 into buffer 0 and refill the stage with tile 2)
-  pieceG(-1, 1, 0, S0{}); pieceG(-1, 1, 1, S0{}); pieceX(-1, 1, 0, S0{}); pieceX(-1, 1, 1, S0{});
-  if (XG) { pieceI(-1, 0, S0{}); pieceI(-1, 1, S0{}); }
-  __syncthreads();
-  const int lrow = lane & 31, lk = lane >> 5;
-  const int wr = wave >> 1, wc = wave & 1;
-  // transposed reads: lane 4 q + p of a 16-lane group gives the address of row q, columns 4 p .. 4 p + 3 of the group's 4 x 16
-  // block and receives column (lane % 16) of the four rows.  Groups 0 / 1 of a half: columns 0-15 / 16-31 of the wave's 32.
-  const int tq = (lane >> 2) & 3, tp = lane & 3;
-  const int rbase = (16 * wr + 8 * lk + tq) * ROWB + 32 * ((lane >> 4) & 1) + 8 * tp;
-  const int aG0 = rbase + 64 * (tq >> 1), aG1 = rbase + 64 * ((tq >> 1) ^ 1), aX = OPB + rbase + 64 * (wc ^ (tq >> 1));
-  sln_bf16x8 fg[3][2], fx[3];
-  // fragments are read as the products come to need them (all eighteen up front are 36 registers: the two-source kernels then
-  // pass 168 and lose the third workgroup per CU): g1 and x3 behind the barrier, g3 and x1 under the first product, g2 and x2 under
-  // the second.  Every read of a buffer is issued before the barrier that ends its tile.
-  using P1 = std::integral_constant<int, 0>; using P2 = std::integral_constant<int, 1>; using P3 = std::integral_constant<int, 2>;
-  auto rdG = [&](int buf, auto part) __attribute__((always_inline)) {
-    constexpr int P = decltype(part)::value;
-    fg[P][0] = tn_tr_frag(img + buf * BUFB + P * IMG + aG0);
-    fg[P][1] = tn_tr_frag(img + buf * BUFB + P * IMG + aG1);
-  };
-  auto rdX = [&](int buf, auto part) __attribute__((always_inline)) {
-    constexpr int P = decltype(part)::value;
-    fx[P] = tn_tr_frag(img + buf * BUFB + P * IMG + aX);
-  };
-  rdG(0, P1{}); rdX(0, P3{});
-#define SLN_SB __builtin_amdgcn_sched_barrier(0)
-  // one product of the six for both accumulators (gp, xp: parts 0 .. 2), hook() behind it - every staging pass sits behind its own
-  // pair of MFMAs, as in gemm_tn_body's scheduled loop
-  auto mma2 = [&](auto gp, auto xp, auto&& hook) __attribute__((always_inline)) {
-    constexpr int GP = decltype(gp)::value, XP = decltype(xp)::value;
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fg[GP][0], fx[XP], acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fg[GP][1], fx[XP], acc[1], 0, 0, 0);
-    SLN_SB; hook(); SLN_SB;
-  };
-  auto sbody = [&](int rt, auto stage_next) __attribute__((always_inline)) {
-    const int buf = rt & 1;
-    rdG(buf, P3{}); rdX(buf, P1{});
-    SLN_SB;
-    mma2(P1{}, P3{}, [&]() __attribute__((always_inline)) { pieceG(rt, buf, 0, stage_next); });
-    mma2(P3{}, P1{}, [&]() __attribute__((always_inline)) { rdG(buf, P2{}); rdX(buf, P2{}); SLN_SB; pieceG(rt, buf, 1, stage_next); });
-    mma2(P2{}, P2{}, [&]() __attribute__((always_inline)) { pieceX(rt, buf, 0, stage_next); });
-    mma2(P1{}, P2{}, [&]() __attribute__((always_inline)) { pieceX(rt, buf, 1, stage_next); });
-    mma2(P2{}, P1{}, [&]() __attribute__((always_inline)) { pieceI(rt, 0, stage_next); pieceI(rt, 1, stage_next); });
-    mma2(P1{}, P1{}, [&]() __attribute__((always_inline)) {});
+  template <class F>
+  __device__ __forceinline__ void run(F& f) {
+    using S0 = typename F::S0; using S1 = typename F::S1;
+    // tile 0 out of stage 0 (pieces of "tile -1": they store tile 0 into buffer 0 and refill the stage with tile 2)
+    f.pieceG(-1, 1, 0, S0{}); f.pieceG2(-1, 0, S0{}); f.pieceG(-1, 1, 1, S0{}); f.pieceG2(-1, 1, S0{});
+    f.pieceX(-1, 1, 0, S0{}); f.pieceX(-1, 1, 1, S0{});
+    f.pieceI(-1, 0, S0{}); f.pieceI(-1, 1, S0{});
     __syncthreads();
-    rdG(buf ^ 1, P1{}); rdX(buf ^ 1, P3{});
-    SLN_SB;
-  };
+    const int lane = f.lane, lk = lane >> 5;
+    const int wr = f.wave >> 1, wc = f.wave & 1;
+    // transposed reads: lane 4 q + p of a 16-lane group gives the address of row q, columns 4 p .. 4 p + 3 of the group's 4 x 16
+    // block and receives column (lane % 16) of the four rows.  Groups 0 / 1 of a half: columns 0-15 / 16-31 of the wave's 32.
+    const int tq = (lane >> 2) & 3, tp = lane & 3;
+    const int rbase = (16 * wr + 8 * lk + tq) * ROWB + 32 * ((lane >> 4) & 1) + 8 * tp;
+    const int aG0 = rbase + 64 * (tq >> 1), aG1 = rbase + 64 * ((tq >> 1) ^ 1), aX = OPB + rbase + 64 * (wc ^ (tq >> 1));
+    sln_bf16x8 fg[3][2], fx[3];
+    // fragments are read as the products come to need them (all eighteen up front are 36 registers: the two-source kernels then
+    // pass 168 and lose the third workgroup per CU): g1 and x3 behind the barrier, g3 and x1 under the first product, g2 and x2 under
+    // the second.  Every read of a buffer is issued before the barrier that ends its tile.
+    using P1 = std::integral_constant<int, 0>; using P2 = std::integral_constant<int, 1>; using P3 = std::integral_constant<int, 2>;
+    auto rdG = [&](int buf, auto part) __attribute__((always_inline)) {
+      constexpr int P = decltype(part)::value;
+      fg[P][0] = tn_tr_frag(img + buf * BUFB + P * IMG + aG0);
+      fg[P][1] = tn_tr_frag(img + buf * BUFB + P * IMG + aG1);
+    };
+    auto rdX = [&](int buf, auto part) __attribute__((always_inline)) {
+      constexpr int P = decltype(part)::value;
+      fx[P] = tn_tr_frag(img + buf * BUFB + P * IMG + aX);
+    };
+    rdG(0, P1{}); rdX(0, P3{});
+    // one product of the six for both accumulators (gp, xp: parts 0 .. 2), hook() behind it - every staging pass sits behind its own
+    // pair of MFMAs; both sources of a G pass are reloaded in one slot
+    auto mma2 = [&](auto gp, auto xp, auto&& hook) __attribute__((always_inline)) {
+      constexpr int GP = decltype(gp)::value, XP = decltype(xp)::value;
+      f.acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fg[GP][0], fx[XP], f.acc[0], 0, 0, 0);
+      f.acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fg[GP][1], fx[XP], f.acc[1], 0, 0, 0);
+      SLN_SB; hook(); SLN_SB;
+    };
+    auto sbody = [&](int rt, auto stage_next) __attribute__((always_inline)) {
+      const int buf = rt & 1;
+      rdG(buf, P3{}); rdX(buf, P1{});
+      SLN_SB;
+      mma2(P1{}, P3{}, [&]() __attribute__((always_inline)) { f.pieceG(rt, buf, 0, stage_next); f.pieceG2(rt, 0, stage_next); });
+      mma2(P3{}, P1{}, [&]() __attribute__((always_inline)) { rdG(buf, P2{}); rdX(buf, P2{}); SLN_SB; f.pieceG(rt, buf, 1, stage_next); f.pieceG2(rt, 1, stage_next); });
+      mma2(P2{}, P2{}, [&]() __attribute__((always_inline)) { f.pieceX(rt, buf, 0, stage_next); });
+      mma2(P1{}, P2{}, [&]() __attribute__((always_inline)) { f.pieceX(rt, buf, 1, stage_next); });
+      mma2(P2{}, P1{}, [&]() __attribute__((always_inline)) { f.pieceI(rt, 0, stage_next); f.pieceI(rt, 1, stage_next); });
+      mma2(P1{}, P1{}, [&]() __attribute__((always_inline)) {});
+      __syncthreads();
+      rdG(buf ^ 1, P1{}); rdX(buf ^ 1, P3{});
+      SLN_SB;
+    };
+    for (int rt = 0; rt < f.ntiles; rt += 2) { sbody(rt, S1{}); sbody(rt + 1, S0{}); }
+  }
+};
 #undef SLN_SB
-  for (int rt = 0; rt < ntiles; rt += 2) { sbody(rt, S1{}); sbody(rt + 1, S0{}); }
 
-  // ---- the two row halves meet: wave (wr, wc) finishes accumulator ja = wr of column half wc (gemm_tn_body's epilogue) ----
-  __syncthreads();                          // every wave is done with the images
-  float* red = reinterpret_cast<float*>(img);      // [wave 4][16][64] floats = 16 KB of the images
-  {
-    float* dst = red + (wave * 16) * 64 + lane;
-    if (wr == 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r * 64] = tn_acc_read(acc[1][r]);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r * 64] = tn_acc_read(acc[0][r]);
-    }
-  }
-  __syncthreads();
-  {
-    const float* src = red + ((wave ^ 2) * 16) * 64 + lane;
-    const float sc = a.sgd_step != nullptr ? -a.sgd_step[0] : 1.f;
-    const int k = k0 + 32 * wc + lrow;
-    float* dcol = a.dW + min(k, a.Kin - 1);
-    const bool kv = k < a.Kin;
-    // sum order (row half 0) + (row half 1) whichever wave finishes
-    if (wr == 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = (tn_acc_read(acc[0][r]) + src[r * 64]) * sc;
-        const int n = n0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-        if (kv && n < a.Nout) sln_gatomic_add(dcol + (size_t)n * a.lddw, v);
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = (src[r * 64] + tn_acc_read(acc[1][r])) * sc;
-        const int n = n0 + 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-        if (kv && n < a.Nout) sln_gatomic_add(dcol + (size_t)n * a.lddw, v);
-      }
-    }
-  }
-
-  if (a.db != nullptr && (bx % tiles_k) == 0) {
-#pragma unroll
-    for (int off = TPR; off < 64; off <<= 1) {
-      dbacc.x += __shfl_xor(dbacc.x, off, 64); dbacc.y += __shfl_xor(dbacc.y, off, 64);
-      dbacc.z += __shfl_xor(dbacc.z, off, 64); dbacc.w += __shfl_xor(dbacc.w, off, 64);
-    }
-    __syncthreads();                          // the accumulator hand-over above is done with `red`
-    float4* dbs = reinterpret_cast<float4*>(red);            // [4 waves][TPR]
-    if (lane < TPR) dbs[wave * TPR + lane] = dbacc;
-    __syncthreads();
-    if (tid < TPR) {
-      const float4 p0 = dbs[tid], p1 = dbs[TPR + tid], p2 = dbs[2 * TPR + tid], p3 = dbs[3 * TPR + tid];
-      const int n = n0 + 4 * tid;
-      const float sb = a.sgd_step != nullptr ? -a.sgd_step[0] : 1.f;
-      if (n + 0 < a.Nout) sln_gatomic_add(a.db + n + 0, (((p0.x + p1.x) + p2.x) + p3.x) * sb);
-      if (n + 1 < a.Nout) sln_gatomic_add(a.db + n + 1, (((p0.y + p1.y) + p2.y) + p3.y) * sb);
-      if (n + 2 < a.Nout) sln_gatomic_add(a.db + n + 2, (((p0.z + p1.z) + p2.z) + p3.z) * sb);
-      if (n + 3 < a.Nout) sln_gatomic_add(a.db + n + 3, (((p0.w + p1.w) + p2.w) + p3.w) * sb);
-    }
-  }
+// a wgrad workgroup on the fp32 matrix pipe / on the 16-bit pipe with three-way split operands
+template <bool G_X2, bool XG>
+__device__ __forceinline__ void gemm_tn_body(const GemmTNArgs& a, const int bx, const int by, char* smem) {
+  TnFrame<G_X2, XG, TnCoreF32>(a).run(bx, by, smem);
+}
+template <bool G_X2, bool XG>
+__device__ __forceinline__ void gemm_tn_split_body(const GemmTNArgs& a, const int bx, const int by, char* smem) {
+  TnFrame<G_X2, XG, TnCoreSplit>(a).run(bx, by, smem);
 }
 
 // whether a problem runs the split body under the split word (sln_common.h: g_sln_tn_split).  A function of the PROBLEM - on the host
@@ -1838,8 +1678,8 @@ __device__ __forceinline__ void gemm_tn_mixed_item(const GemmTNArgs* __restrict_
     else gemm_tn_split_body<G_X2, false>(probs[it.prob], it.tile, it.chunk, smem);
     return;
   }
-  if (it.xg) gemm_tn_body<64, 64, 2, 2, G_X2, true>(probs[it.prob], it.tile, it.chunk, smem);
-  else gemm_tn_body<64, 64, 2, 2, G_X2, false>(probs[it.prob], it.tile, it.chunk, smem);
+  if (it.xg) gemm_tn_body<G_X2, true>(probs[it.prob], it.tile, it.chunk, smem);
+  else gemm_tn_body<G_X2, false>(probs[it.prob], it.tile, it.chunk, smem);
 }
 
 inline bool tn_gathers(const GemmTNArgs& a) {

@@ -15,8 +15,10 @@
 //               64 x 64 tiles with a ragged last round of workgroups (nt16_pick)
 //   gemm_nt_small : 32 x 32 tiles, K split over the four wavefronts (the object-side Linears: 64-128 tiles of 64 x 64 for 256 CUs)
 //
-// NT: k-contiguous LDS tiles ([rows][BK + 4]: one ds_read_b128 feeds four MFMAs); TN: row-major tiles as the rows arrive, the
-// waves split a tile's rows (gemm_bodies.h).  Global->LDS staging goes through registers (the BatchNorm / ReLU / gather
+// NT: k-contiguous LDS tiles ([rows][BK + 4]: one ds_read_b128 feeds four MFMAs); TN: one workgroup frame (gemm_bodies.h: TnFrame -
+// coordinates, coefficient tables, register stages, staging, epilogue) around one of two compute cores: TnCoreF32 (row-major fp32
+// tiles as the rows arrive, the waves split a tile's rows) or TnCoreSplit (operands as three bf16 parts on the 16-bit pipe, the
+// *_split_kernel forms below).  Global->LDS staging goes through registers (the BatchNorm / ReLU / gather
 // transform happens on the way), double-buffered so one barrier per K tile.  The K loops of the 64 x 64 NT tile, of the 16 x 16
 // body and of the wgrad body are written out instruction by instruction (one piece of staging work behind each MFMA): one
 // wavefront per SIMD hides nothing behind its own MFMAs (tools/lab/overlap.hip).  NT kernels with a
@@ -175,10 +177,10 @@ NtRoute nt_route(const GemmNTArgs& a, int epi, int tile) {
   return r;
 }
 
-template <int BM, int BN, int WM, int WN, bool G_X2, bool XG>
+template <bool G_X2, bool XG>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmTNArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemm_tn_body<BM, BN, WM, WN, G_X2, XG>(a, blockIdx.x, blockIdx.y, smem);
+  gemm_tn_body<G_X2, XG>(a, blockIdx.x, blockIdx.y, smem);
 }
 
 // Every wgrad of a backward pass in one grid: workgroup b runs entry b of the item table (problem, output tile, row chunk; see
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(256) void gemm_tn_multi_kernel(const GemmTNArgs* __
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const TnMultiItem it = meta->item[blockIdx.x];
   if (it.prob < 0) return;
-  gemm_tn_body<64, 64, 2, 2, G_X2, XG>(probs[it.prob], it.tile, it.chunk, smem);
+  gemm_tn_body<G_X2, XG>(probs[it.prob], it.tile, it.chunk, smem);
 }
 
 // ... and of a whole iteration, gathered X rows or not, in one grid (sln_gemm.h: TnMixedMeta): the item says which of the two
@@ -219,21 +221,40 @@ __global__ __launch_bounds__(256) void gemm_tn_mixed_split_kernel(const GemmTNAr
   gemm_tn_mixed_item<G_X2, true>(probs, meta->item[blockIdx.x], smem);
 }
 
-template <int BM, int BN, int WM, int WN, bool G_X2>
-int launch_tn(const GemmTNArgs& a, hipStream_t st) {
-  const size_t smem = tn_smem_bytes(BM, BN);
-  const int gx = sln_cdiv(a.Nout, BM) * sln_cdiv(a.Kin, BN);
+// The wgrad kernel variants, known in ONE place: for each launch form a function from (split, x2[, xg]) to the instantiation.  The
+// launchers launch through the pointer it returns and tn_kernels_init walks the same functions over every argument, so an
+// instantiation cannot be launched without its dynamic-LDS limit raised.
+// split: the split word is set and the launch may take the split kernel (sln_common.h: sln_tn_split_launch); x2: G carries a second
+// source; xg: X rows are gathered.
+using TnKernel = void (*)(GemmTNArgs);
+using TnMultiKernel = void (*)(const GemmTNArgs*, const TnMultiMeta*);
+using TnMixedKernel = void (*)(const GemmTNArgs*, const TnMixedMeta*);
+#define SLN_TN_PICK(K) (x2 ? (xg ? &K<true, true> : &K<true, false>) : (xg ? &K<false, true> : &K<false, false>))
+TnKernel tn_kernel(bool split, bool x2, bool xg) { return split ? SLN_TN_PICK(gemm_tn_split_kernel) : SLN_TN_PICK(gemm_tn_kernel); }
+TnMultiKernel tn_multi_kernel(bool split, bool x2, bool xg) { return split ? SLN_TN_PICK(gemm_tn_multi_split_kernel) : SLN_TN_PICK(gemm_tn_multi_kernel); }
+#undef SLN_TN_PICK
+TnMixedKernel tn_mixed_kernel(bool split, bool x2) {
+  if (split) return x2 ? &gemm_tn_mixed_split_kernel<true> : &gemm_tn_mixed_split_kernel<false>;
+  return x2 ? &gemm_tn_mixed_kernel<true> : &gemm_tn_mixed_kernel<false>;
+}
+int tn_kernels_init() {
+  hipError_t e = hipSuccess;
+  auto raise = [&e](auto k) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); };
+  for (int v = 0; v < 8; ++v) {
+    const bool split = v & 4, x2 = v & 2, xg = v & 1;
+    raise(tn_kernel(split, x2, xg)); raise(tn_multi_kernel(split, x2, xg));
+    if (!xg) raise(tn_mixed_kernel(split, x2));
+  }
+  return (int)e;
+}
+
+int launch_tn(const GemmTNArgs& a, bool x2, hipStream_t st) {
+  const size_t smem = tn_smem_bytes(TN_T, TN_T);
+  const int gx = sln_cdiv(a.Nout, TN_T) * sln_cdiv(a.Kin, TN_T);
   const int gy = sln_cdiv(a.R, a.rows_per_block);
   if (gx <= 0 || gy <= 0) return 0;
   if (!tn_supported(a)) return -1;
-  if (sln_tn_split_launch() && tn_split_takes(a)) {
-    if (tn_gathers(a)) hipLaunchKernelGGL((gemm_tn_split_kernel<G_X2, true>), dim3(gx, gy), dim3(256), smem, st, a);
-    else hipLaunchKernelGGL((gemm_tn_split_kernel<G_X2, false>), dim3(gx, gy), dim3(256), smem, st, a);
-    SLN_CHECK_LAUNCH();
-    return 0;
-  }
-  if (tn_gathers(a)) hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, WM, WN, G_X2, true>), dim3(gx, gy), dim3(256), smem, st, a);
-  else hipLaunchKernelGGL((gemm_tn_kernel<BM, BN, WM, WN, G_X2, false>), dim3(gx, gy), dim3(256), smem, st, a);
+  hipLaunchKernelGGL(tn_kernel(sln_tn_split_launch() && tn_split_takes(a), x2, tn_gathers(a)), dim3(gx, gy), dim3(256), smem, st, a);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -295,27 +316,7 @@ int sln_gemm_init() {
   if (!r) r = init_nt_tile<128, 64, 2, 2, SLN_ST_WT>();
   if (!r) r = init_nt_tile<128, 128, 2, 2, SLN_ST_PLAIN>();
   if (!r) r = init_nt_tile<128, 128, 2, 2, SLN_ST_WT>();
-#define SLN_SET_TN(X2, XG)                                                                                        \
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<64, 64, 2, 2, X2, XG>),     \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  SLN_SET_TN(true, true) SLN_SET_TN(true, false) SLN_SET_TN(false, true) SLN_SET_TN(false, false)
-#undef SLN_SET_TN
-#define SLN_SET_TNM(X2, XG)                                                                                       \
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_multi_kernel<X2, XG>),             \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  SLN_SET_TNM(true, true) SLN_SET_TNM(true, false) SLN_SET_TNM(false, true) SLN_SET_TNM(false, false)
-#undef SLN_SET_TNM
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#define SLN_SET_TNS(X2, XG)                                                                                       \
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_split_kernel<X2, XG>),             \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_multi_split_kernel<X2, XG>),       \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  SLN_SET_TNS(true, true) SLN_SET_TNS(true, false) SLN_SET_TNS(false, true) SLN_SET_TNS(false, false)
-#undef SLN_SET_TNS
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_mixed_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (!r) r = tn_kernels_init();
   if (!r) r = sln_gemm_group_init();
   if (!r) r = sln_vae_tail_init();
   done = r == 0;
@@ -413,8 +414,7 @@ int sln_launch_gemm_tn(const GemmTNArgs& a0, hipStream_t st) {
   SlnProfScope prof(SLN_FAM_GEMM_TN, 2.0 * a0.R * a0.Nout * a0.Kin, st);
   GemmTNArgs a = a0;
   const bool x2 = tn_prepare(a);
-  if (x2) return launch_tn<64, 64, 2, 2, true>(a, st);
-  return launch_tn<64, 64, 2, 2, false>(a, st);
+  return launch_tn(a, x2, st);
 }
 
 // The planner of both table launches.  mixed: the one launch of a whole iteration (items carry their problem's gather bit, plain
@@ -479,7 +479,7 @@ static int tn_plan(GemmTNArgs* probs, int n, int max_probs, int max_items, bool 
   int mx = 0;
   for (int x = 0; x < 8; ++x) mx = per_xcd[x] > mx ? per_xcd[x] : mx;
   *nprob = n; *nblocks = 8 * mx;
-  std::memset(item, 0, sizeof(TnMultiItem) * (size_t)(mixed ? 8 * mx : max_items));      // (the mixed table is used by its prefix only)
+  std::memset(item, 0, sizeof(TnMultiItem) * (size_t)(8 * mx));      // (a table is used by its prefix only, sln_gemm.h: TnMeta)
   for (int b = 0; b < 8 * mx; ++b) item[b].prob = -1;
   int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (size_t g = 0; g < groups.size(); ++g) {          // cost order: an XCD starts with its longest groups
@@ -509,18 +509,7 @@ int sln_launch_gemm_tn_multi(const GemmTNArgs* dev_probs, const TnMultiMeta* dev
   SlnProfScope prof(SLN_FAM_GEMM_TN, flops, st);
   const size_t smem = tn_smem_bytes(64, 64);
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
-  if (sln_tn_split_launch() && !all_keep_f32) {
-    if (x2 && xg) hipLaunchKernelGGL((gemm_tn_multi_split_kernel<true, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-    else if (x2) hipLaunchKernelGGL((gemm_tn_multi_split_kernel<true, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-    else if (xg) hipLaunchKernelGGL((gemm_tn_multi_split_kernel<false, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-    else hipLaunchKernelGGL((gemm_tn_multi_split_kernel<false, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-    SLN_CHECK_LAUNCH();
-    return 0;
-  }
-  if (x2 && xg) hipLaunchKernelGGL((gemm_tn_multi_kernel<true, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-  else if (x2) hipLaunchKernelGGL((gemm_tn_multi_kernel<true, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-  else if (xg) hipLaunchKernelGGL((gemm_tn_multi_kernel<false, true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-  else hipLaunchKernelGGL((gemm_tn_multi_kernel<false, false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+  hipLaunchKernelGGL(tn_multi_kernel(sln_tn_split_launch() && !all_keep_f32, x2, xg), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -530,14 +519,7 @@ int sln_launch_gemm_tn_mixed(const GemmTNArgs* dev_probs, const TnMixedMeta* dev
   SlnProfScope prof(SLN_FAM_GEMM_TN, flops, st);
   const size_t smem = tn_smem_bytes(64, 64);
   if (smem > 48 * 1024) { int r = sln_gemm_init(); if (r) return r; }
-  if (sln_tn_split_launch()) {
-    if (x2) hipLaunchKernelGGL((gemm_tn_mixed_split_kernel<true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-    else hipLaunchKernelGGL((gemm_tn_mixed_split_kernel<false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-    SLN_CHECK_LAUNCH();
-    return 0;
-  }
-  if (x2) hipLaunchKernelGGL((gemm_tn_mixed_kernel<true>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
-  else hipLaunchKernelGGL((gemm_tn_mixed_kernel<false>), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
+  hipLaunchKernelGGL(tn_mixed_kernel(sln_tn_split_launch(), x2), dim3(blocks), dim3(256), smem, st, dev_probs, dev_meta);
   SLN_CHECK_LAUNCH();
   return 0;
 }

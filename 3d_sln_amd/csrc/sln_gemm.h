@@ -65,7 +65,9 @@ enum { SLN_TN_MULTI_MAX = 64, SLN_TN_MULTI_ITEMS = 4096 };
 // the same amount of work.  XCDs with fewer items are padded with empty entries (prob < 0).
 // xg: the mixed launch only (below) - this item's problem gathers its X rows and runs the gathering body.
 struct TnMultiItem { int prob, tile, chunk, xg; };
-struct TnMultiMeta { int nprob, nblocks; TnMultiItem item[SLN_TN_MULTI_ITEMS]; };
+// the table of a launch, of item capacity N; only its first nblocks items are ever written, compared, uploaded or indexed
+template <int N> struct TnMeta { int nprob, nblocks; TnMultiItem item[N]; };
+using TnMultiMeta = TnMeta<SLN_TN_MULTI_ITEMS>;
 // The whole iteration's wgrads - gathered X rows or not - as ONE launch: every workgroup picks its body by its item's `xg` bit
 // (block-uniform), so a plain problem never pays the gathering body's index loads.  Same chunking, same XCD dealing and the same
 // atomics as the two per-kind launches it replaces; the table is longer (a 64-graph step: 52 problems, 4 880 items) and has its
@@ -73,7 +75,7 @@ struct TnMultiMeta { int nprob, nblocks; TnMultiItem item[SLN_TN_MULTI_ITEMS]; }
 // refused (the caller then runs the per-kind launches, whose planner lengthens chunks): the row chunks of a problem - and with
 // them its per-element sums - are the same on both routes.
 enum { SLN_TN_MIXED_MAX = 128, SLN_TN_MIXED_ITEMS = 16384 };
-struct TnMixedMeta { int nprob, nblocks; TnMultiItem item[SLN_TN_MIXED_ITEMS]; };
+using TnMixedMeta = TnMeta<SLN_TN_MIXED_ITEMS>;
 // host side: fills rows_per_block of every problem (long chunks: the per-block prologue / 64x64 atomics are paid once per
 // ~1 k rows instead of once per 256; longer still when the launch would not fit the table) and builds the item table.
 // Returns 0, or a negative value when a problem cannot run on the TN body.

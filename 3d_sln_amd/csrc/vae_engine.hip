@@ -138,10 +138,25 @@ struct SlnVae {
   // The problem tables live in device memory.  Set 0 belongs to the captured iterations (filled after the capture ends, before
   // the graph is launched: a capture records, nothing runs), set 1 to eager calls; [which] 0 = decoder pass, 1 = encoder pass;
   // [k] 0 = plain rows, 1 = gathered X rows.
-  struct TnGroup {
-    GemmTNArgs probs[SLN_TN_MULTI_MAX]; TnMultiMeta meta; int n = 0, blocks = 0; bool x2 = false, xg = false; double flops = 0.0;
-    bool dirty = true; GemmTNArgs* dev_probs = nullptr; TnMultiMeta* dev_meta = nullptr;
+  // One table of a launch with its resident device copy, of NP problems and NI items at most.  Only the used prefix of either
+  // array (n problems, meta.nblocks items) is compared, copied and uploaded: nothing indexes behind it.
+  template <int NP, int NI>
+  struct TnTable {
+    using Meta = TnMeta<NI>;
+    GemmTNArgs probs[NP]; Meta meta; int n = 0, blocks = 0; bool x2 = false, xg = false; double flops = 0.0;
+    bool dirty = true; GemmTNArgs* dev_probs = nullptr; Meta* dev_meta = nullptr;
+    size_t probs_bytes() const { return sizeof(GemmTNArgs) * (size_t)n; }
+    size_t meta_bytes() const { return offsetof(Meta, item) + sizeof(TnMultiItem) * (size_t)meta.nblocks; }
+    // takes over a freshly planned table when it differs from this (resident) one, which is then dirty
+    void adopt(const TnTable& t) {
+      if (n == t.n && meta.nblocks == t.meta.nblocks && std::memcmp(probs, t.probs, t.probs_bytes()) == 0 &&
+          std::memcmp(&meta, &t.meta, t.meta_bytes()) == 0) return;
+      std::memcpy(probs, t.probs, t.probs_bytes());
+      std::memcpy(&meta, &t.meta, t.meta_bytes());
+      n = t.n; blocks = t.blocks; x2 = t.x2; xg = t.xg; flops = t.flops; dirty = true;
+    }
   };
+  using TnGroup = TnTable<SLN_TN_MULTI_MAX, SLN_TN_MULTI_ITEMS>;      // a per-kind launch of a pass
   // table slots of the per-pass wgrad launches: three regions of tn_slots / 3 - decoder pass, encoder pass, and (round 6) the ONE flush of
   // a full iteration, whose tables must not share slots with the two-half graphs of the same engine.  Sized from the layer count
   // at creation (per-layer flushing - SLN_TN_PER_LAYER, deterministic mode with shared 'recurrent' weights - takes up to two per
@@ -158,9 +173,9 @@ struct SlnVae {
   std::vector<GemmTNArgs> deferred;
   TnGroup* tn_groups_store = nullptr;            // [2 sets][TN_SLOTS][2], heap (a TnGroup is 50 KB)
   TnGroup& tn_group(int set, int slot, int k) { return tn_groups_store[((size_t)set * tn_slots + slot) * 2 + k]; }
-  int upload_group(TnGroup& g) {
-    hipError_t e = hipMemcpy(g.dev_probs, g.probs, sizeof(GemmTNArgs) * (size_t)g.n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(g.dev_meta, &g.meta, sizeof(TnMultiMeta), hipMemcpyHostToDevice);
+  template <class T> int upload_table(T& g) {     // blocking (after a capture)
+    hipError_t e = hipMemcpy(g.dev_probs, g.probs, g.probs_bytes(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(g.dev_meta, &g.meta, g.meta_bytes(), hipMemcpyHostToDevice);
     g.dirty = e != hipSuccess;
     return (int)e;
   }
@@ -198,9 +213,13 @@ struct SlnVae {
     if (e == hipSuccess) e = hipEventRecord(sl.done, st);
     return (int)e;
   }
-  int upload_group_async(TnGroup& g, hipStream_t st) {
-    const int r = stage_upload(g.dev_probs, g.probs, sizeof(GemmTNArgs) * (size_t)g.n, g.dev_meta, &g.meta,
-                               offsetof(TnMultiMeta, item) + sizeof(TnMultiItem) * (size_t)g.meta.nblocks, st);
+  // A freshly planned table becomes the resident one `g`: adopted when it differs, and then uploaded in stream order (an eager call
+  // with a new problem set - new shape, other BatchNorm mode) or left to upload_pending_tables (while capturing)
+  template <class T> int make_resident(T& g, const T& planned, hipStream_t st) {
+    g.adopt(planned);
+    if (!g.dirty) return 0;
+    if (capturing) { tn_upload_pending = true; return 0; }
+    const int r = stage_upload(g.dev_probs, g.probs, g.probs_bytes(), g.dev_meta, &g.meta, g.meta_bytes(), st);
     if (r == 0) g.dirty = false;
     return r;
   }
@@ -208,19 +227,16 @@ struct SlnVae {
     for (int w = 0; w < tn_slots; ++w)
       for (int k = 0; k < 2; ++k) {
         TnGroup& g = tn_group(0, w, k);
-        if (g.n > 0 && g.dirty) { int r = upload_group(g); if (r) return r; }
+        if (g.n > 0 && g.dirty) { int r = upload_table(g); if (r) return r; }
       }
-    if (tn_mixed_store && tn_mixed_store[0].n > 0 && tn_mixed_store[0].dirty) { int r = upload_mixed(tn_mixed_store[0]); if (r) return r; }
+    if (tn_mixed_store && tn_mixed_store[0].n > 0 && tn_mixed_store[0].dirty) { int r = upload_table(tn_mixed_store[0]); if (r) return r; }
     tn_upload_pending = false;
     return 0;
   }
   // Round 10: a full iteration's ONE flush runs gathered and plain problems as one launch (sln_launch_gemm_tn_mixed) out of a table
   // region of its own - [0] the captured iterations', [1] eager calls', [2] the planner's scratch; carved and allocated only in
   // engines that can take it (tail_merge).  Same upload rules as the per-kind tables above.
-  struct TnMixedGroup {
-    GemmTNArgs probs[SLN_TN_MIXED_MAX]; TnMixedMeta meta; int n = 0, blocks = 0; bool x2 = false; double flops = 0.0;
-    bool dirty = true; GemmTNArgs* dev_probs = nullptr; TnMixedMeta* dev_meta = nullptr;
-  };
+  using TnMixedGroup = TnTable<SLN_TN_MIXED_MAX, SLN_TN_MIXED_ITEMS>;
   TnMixedGroup* tn_mixed_store = nullptr;
   bool tail_merge = true;         // SLN_TN_MIXED=0 at creation: one wgrad launch per kind, as before round 10
   bool it_tail = false;           // this iteration's one flush takes the mixed launch
@@ -228,13 +244,6 @@ struct SlnVae {
   bool it_dec_leaf = false;       // this iteration runs the decoder's assembly backward as a leaf job
   bool tail_leaf = true;          // SLN_TN_MIXED=1 at creation: the leaf jobs keep their own launch in front of it (lab: part by part)
   long tail_launches = 0;         // mixed launches issued by this engine (sln_debug_vae_tail_launches)
-  static size_t mixed_meta_bytes(const TnMixedMeta& m) { return offsetof(TnMixedMeta, item) + sizeof(TnMultiItem) * (size_t)m.nblocks; }
-  int upload_mixed(TnMixedGroup& g) {
-    hipError_t e = hipMemcpy(g.dev_probs, g.probs, sizeof(GemmTNArgs) * (size_t)g.n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(g.dev_meta, &g.meta, mixed_meta_bytes(g.meta), hipMemcpyHostToDevice);
-    g.dirty = e != hipSuccess;
-    return (int)e;
-  }
   // 0: launched; TN_MIXED_NO_FIT: the list does not fit the mixed table (or holds a problem the planner refuses) - the caller runs
   // one launch per kind; anything else: an error
   enum { TN_MIXED_NO_FIT = 1 << 20 };
@@ -252,20 +261,7 @@ struct SlnVae {
     tmp.n = n;
     if (sln_tn_mixed_plan(tmp.probs, n, &tmp.meta, &tmp.blocks, &tmp.x2, &tmp.flops) != 0) return TN_MIXED_NO_FIT;
     TnMixedGroup& g = tn_mixed_store[set];
-    if (g.n != n || g.meta.nblocks != tmp.meta.nblocks || std::memcmp(g.probs, tmp.probs, sizeof(GemmTNArgs) * (size_t)n) != 0 ||
-        std::memcmp(&g.meta, &tmp.meta, mixed_meta_bytes(tmp.meta)) != 0) {
-      std::memcpy(g.probs, tmp.probs, sizeof(GemmTNArgs) * (size_t)n);
-      std::memcpy(&g.meta, &tmp.meta, mixed_meta_bytes(tmp.meta));
-      g.n = n; g.blocks = tmp.blocks; g.x2 = tmp.x2; g.flops = tmp.flops; g.dirty = true;
-    }
-    if (g.dirty) {
-      if (capturing) tn_upload_pending = true;
-      else {
-        const int r = stage_upload(g.dev_probs, g.probs, sizeof(GemmTNArgs) * (size_t)g.n, g.dev_meta, &g.meta, mixed_meta_bytes(g.meta), st);
-        if (r) return r;
-        g.dirty = false;
-      }
-    }
+    { const int r = make_resident(g, tmp, st); if (r) return r; }
     const int r = leaf ? sln_launch_vae_tail(g.dev_probs, g.dev_meta, g.blocks, g.x2, g.flops, *leaf, st)
                        : sln_launch_gemm_tn_mixed(g.dev_probs, g.dev_meta, g.blocks, g.x2, g.flops, st);
     if (r == 0) { ++tail_launches; if (leaf) ++leaf_launches; }
@@ -346,19 +342,8 @@ struct SlnVae {
         next += (size_t)tmp.n;
         const int slot = which * (tn_slots / 3) + tn_slot_next[which]++;
         TnGroup& g = tn_group(set, slot, k);
-        if (g.n != tmp.n || std::memcmp(g.probs, tmp.probs, sizeof(GemmTNArgs) * (size_t)tmp.n) != 0 ||
-            std::memcmp(&g.meta, &tmp.meta, sizeof(TnMultiMeta)) != 0) {
-          std::memcpy(g.probs, tmp.probs, sizeof(GemmTNArgs) * (size_t)tmp.n);
-          g.meta = tmp.meta; g.n = tmp.n; g.blocks = tmp.blocks; g.x2 = tmp.x2; g.xg = tmp.xg; g.flops = tmp.flops;
-          g.dirty = true;
-        }
-        if (g.dirty) {
-          if (capturing) tn_upload_pending = true;
-          else {                      // eager call with a new problem set (new shape, other BatchNorm mode): stream-ordered upload
-            r = upload_group_async(g, st);
-            if (r) { deferred.clear(); return r; }
-          }
-        }
+        r = make_resident(g, tmp, st);
+        if (r) { deferred.clear(); return r; }
         r = sln_launch_gemm_tn_multi(g.dev_probs, g.dev_meta, g.blocks, g.x2, g.xg, g.flops, st);
         if (r) { deferred.clear(); return r; }
       }

@@ -1,6 +1,7 @@
 // Launchers of the non-GEMM kernels of the scene-graph VAE path (see vae_kernels.hip).
 #pragma once
 #include "sln_common.h"
+#include "sln_gemm.h"      // GemmTNArgs, TnMixedMeta (sln_launch_vae_tail)
 
 // ---- graph structure (once per batch) -------------------------------------------------------
 struct GraphCsr {          // device pointers, all int32 unless noted
@@ -176,7 +177,6 @@ int sln_vae_leaf_fits(const VaeLeaf& a);    // 1: every job takes its LDS-table 
 int sln_launch_vae_leaf(const VaeLeaf& a, hipStream_t st);
 // The iteration's tail as ONE launch: the mixed wgrad table (sln_gemm.h: sln_tn_mixed_plan) followed by the leaf jobs as trailing
 // workgroup ranges.  `a` must pass sln_vae_leaf_fits.
-struct GemmTNArgs; struct TnMixedMeta;
 int sln_launch_vae_tail(const GemmTNArgs* dev_probs, const TnMixedMeta* dev_meta, int blocks, bool x2, double flops, const VaeLeaf& a,
                         hipStream_t st);
 int sln_vae_tail_init();   // called by sln_gemm_init

@@ -1585,11 +1585,18 @@ int sln_launch_vae_leaf(const VaeLeaf& v, hipStream_t st) {
   return 0;
 }
 
+// the tail kernel of a launch (split: sln_tn_split_launch; x2: G carries a second source) - launched through this pointer, and
+// sln_vae_tail_init walks the same function: no instantiation is launched without its dynamic-LDS limit raised
+using VaeTailKernel = void (*)(const GemmTNArgs*, const TnMixedMeta*, unsigned int, LeafRanges, LeafArgs);
+static VaeTailKernel vae_tail_pick(bool split, bool x2) {
+  if (split) return x2 ? &vae_tail_split_kernel<true> : &vae_tail_split_kernel<false>;
+  return x2 ? &vae_tail_kernel<true> : &vae_tail_kernel<false>;
+}
+
 int sln_vae_tail_init() {
-  int r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (!r) r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&vae_tail_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  int r = 0;
+  for (int v = 0; v < 4 && !r; ++v)
+    r = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(vae_tail_pick(v & 2, v & 1)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   return r;
 }
 
@@ -1602,14 +1609,8 @@ int sln_launch_vae_tail(const GemmTNArgs* dev_probs, const TnMixedMeta* dev_meta
   if (lds > smem) return -1;                 // (the tables are capped at 40 KB, the wgrad tiles take 50 KB)
   { const int e = sln_gemm_init(); if (e) return e; }       // raises the dynamic-LDS limit of this kernel too
   SlnProfScope prof(SLN_FAM_GEMM_TN, flops, st);
-  if (sln_tn_split_launch()) {
-    if (x2) hipLaunchKernelGGL((vae_tail_split_kernel<true>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
-    else hipLaunchKernelGGL((vae_tail_split_kernel<false>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
-    SLN_CHECK_LAUNCH();
-    return 0;
-  }
-  if (x2) hipLaunchKernelGGL((vae_tail_kernel<true>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
-  else hipLaunchKernelGGL((vae_tail_kernel<false>), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta, (unsigned int)blocks, r, a);
+  hipLaunchKernelGGL(vae_tail_pick(sln_tn_split_launch(), x2), dim3((unsigned int)blocks + tot), dim3(256), smem, st, dev_probs, dev_meta,
+                     (unsigned int)blocks, r, a);
   SLN_CHECK_LAUNCH();
   return 0;
 }

@@ -121,15 +121,22 @@ def test_table_launches(lib, key, route):
         _check(p, out, i, "%s/%s[%d] (%d, %d, %d)" % (route, key, i, p.R, p.Nout, p.Kin))
 
 
-@pytest.mark.parametrize("key", ["rows", "widths"])
+# the single launch alone (a sixth entry: rows_per_block).  'surplus': three 32-row tiles per chunk - the K loop runs whole pairs of
+# tiles, so the rows of a fourth are staged as zeros - in three chunks, the last of 8 rows; two ragged output tiles each way
+SINGLE = dict(LISTS, surplus=[(200, 100, 100, "bwd", "concat", 96)])
+
+
+@pytest.mark.parametrize("key", ["rows", "widths", "surplus"])
 def test_single_launch(lib, key):
     """Widths of a single launch must be whole groups of four (the hook's rule for it): the others go through the tables above."""
-    for i, (Rr, Nout, Kin, gf, xf) in enumerate(LISTS[key]):
+    for i, (Rr, Nout, Kin, gf, xf, *rpb) in enumerate(SINGLE[key]):
         if Nout % 4 or Kin % 4:
             continue
         p = MX._problem("split-single-%s-%d" % (key, i), Rr, Nout, Kin, gf, xf, with_db=(i % 3 != 2))
+        if rpb:
+            p = p.replace(rows_per_block=rpb[0])
         out = _both_words(lib, [p], "single")
-        _check(p, out, 0, "single/%s[%d] %s" % (key, i, LISTS[key][i]))
+        _check(p, out, 0, "single/%s[%d] %s" % (key, i, SINGLE[key][i]))
         if Rr >= 300:            # (a sum over a few rows can round alike in both bodies)
             assert not torch.equal(out[1][0][0], out[0][0][0]), "word 1 gave word 0's bits: the single launch did not take the split body"
 
