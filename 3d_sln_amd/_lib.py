@@ -123,6 +123,11 @@ class SlnDbgNTRoute(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("body", "multi", "amode", "threads")]
 
 
+# What sln_debug_conv_route reports (csrc/spade.hip conv_route), checked against sln_debug_conv_sizes by tests/test_conv_route_host.py
+class SlnDbgConvRoute(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kernel", "bmc", "tile_h", "gk", "blk", "terms", "shares")]
+
+
 # Descriptions of the VAE kernel test hooks (sln_debug_vae_*), checked against sln_debug_vae_sizes by tests/test_vae_ref_host.py
 class SlnDbgCsr(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("s", "p", "o", "deg", "invdeg", "rowptr", "cursor", "ent")] + [("T", C.c_int), ("O", C.c_int)]
@@ -257,6 +262,8 @@ SIGNATURES = {
     "sln_debug_gemm_nt_half": (C.c_int, [C.POINTER(SlnDbgGemmNT), C.c_int, C.c_void_p]),
     "sln_debug_gemm_nt_half_takes": (C.c_int, [C.POINTER(SlnDbgGemmNT)]),
     "sln_debug_gemm_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "sln_debug_conv_route": (C.c_int, [C.c_int] * 10 + [C.POINTER(SlnDbgConvRoute)]),
+    "sln_debug_conv_sizes": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "sln_debug_vae_csr": (C.c_int, [c_i64p, C.c_int, C.c_int, C.c_int, C.POINTER(SlnDbgCsr), C.c_void_p, C.c_void_p]),
     "sln_debug_vae_edge": (C.c_int, [C.POINTER(SlnDbgEdge), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "sln_debug_vae_loss": (C.c_int, [C.POINTER(SlnDbgLoss), C.c_void_p]),

@@ -380,7 +380,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
 #pragma unroll
   for (int j = 0; j < NH; ++j) {
     const int e = tid + 256 * j;
-    h_off[j] = e < CK * HS ? (int)(e / HS * plane + t.source(a, e % HS, KS)) : 0;     // tail slots load a valid address, never stored
+    // tail slots load a valid address, never stored: gload takes them as channel CK - 1 and subtracts that channel again, so their
+    // offset is that channel's plane (with 0 a first chunk of fewer than CK channels read (Cin - CK) planes in front of the sample)
+    h_off[j] = e < CK * HS ? (int)(e / HS * plane + t.source(a, e % HS, KS)) : (int)((CK - 1) * plane);
     h_lds[j] = e;
   }
   float hreg[NH];
@@ -702,8 +704,7 @@ constexpr long CONV_SPLIT_TARGET = 512;     // ... into about this many
 constexpr int CONV_SPLIT_MAX = 32;          // shares at most; SLN_CONV_KSPLIT sets another bound (1: never)
 // shares of a launch of `blocks` workgroups over `chunks` chunks of input channels, at least `least_chunks` each, whose partial
 // images of part_bytes each fit the scratch slot; <= 1: no split
-static int conv_split_shares(long blocks, int chunks, int least_chunks, size_t part_bytes) {
-  static const int split_max = getenv("SLN_CONV_KSPLIT") ? atoi(getenv("SLN_CONV_KSPLIT")) : CONV_SPLIT_MAX;
+static int conv_split_shares(long blocks, int chunks, int least_chunks, size_t part_bytes, int split_max) {
   if (split_max <= 1 || blocks >= CONV_SPLIT_BELOW) return 1;
   const int S = (int)std::min<long>(std::min(split_max, chunks / least_chunks), (CONV_SPLIT_TARGET + blocks - 1) / blocks);
   return (int)std::min<size_t>((size_t)S, CONV_PART_BYTES / part_bytes);
@@ -716,74 +717,7 @@ struct ConvSplitKind {
   bool no_idle_share;     // fewer shares of the same ceil(chunks / S) chunks, so that no workgroup is left without a chunk
 };
 constexpr ConvSplitKind CONV_SPLIT_F32{4, 8, true, false};
-// bmc: rows per workgroup; launch(args with part / part_stride set, S) runs the shares.  *done: the launch was taken.
-template <class Launch>
-int launch_conv_split(const ConvArgs& a, hipStream_t st, int bmc, const ConvSplitKind& k, bool* done, Launch launch) {
-  *done = false;
-  if (k.whole_chunks && a.Cin % k.chunk_cin != 0) return 0;
-  const long blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, TH) * a.B * (a.rows_pad / bmc);
-  const int chunks = sln_cdiv(a.Cin, k.chunk_cin);
-  const size_t one = (size_t)a.B * a.rows * a.H * a.W;
-  int S = conv_split_shares(blocks, chunks, k.least_chunks, one * sizeof(float));
-  if (S <= 1) return 0;
-  if (k.no_idle_share) S = sln_cdiv(chunks, sln_cdiv(chunks, S));
-  float* part = nullptr;
-  *done = true;                                            // from here on the launch is the split one - or an error, never another kernel
-  { const int r = conv_part_scratch(st, &part, true); if (r) return r; }
-  ConvArgs p = a; p.part = part; p.part_stride = (long)one;
-  const int r = launch(p, S);
-  return r ? r : launch_conv_split_finish(a, part, S, (long)one, st);
-}
-
-static bool conv_staged_only() {      // SLN_CONV_STAGED: A/B runs and tests, the Cin >= 512 convolutions included
-  static const bool v = getenv("SLN_CONV_STAGED") != nullptr;
-  return v;
-}
-
-// Blocked accumulation (see conv_mfma_kernel): variants with 64 accumulators per lane.  Blocks of 16 input channels (144
-// products): 2 buffers of 8 channels / 4 buffers of 4 / 2 staged chunks of 8.
-template <int BMC>
-int launch_conv_blocked(const ConvArgs& a, hipStream_t st) {
-  if (a.Cin % 8 != 0 || conv_staged_only()) return launch_conv_staged<BMC, 3, CEPI_BIAS_ACT, 2>(a, st);
-  // 64-row workgroups of 16 x 16 pixels (the halo is DMA'd once per 64 rows instead of once per 128: 1.2x the operand traffic
-  // of the 128-row workgroups; 8 x 16 x 128 rows re-reads the weights per 128 pixels: 1.8x)
-  const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / 64);
-  if (a.H >= 16 && tall_blocks >= 512) return launch_conv_dma<64, 3, CEPI_BIAS_ACT, 16, 8, 2>(a, st);
-  auto launch = [&](const ConvArgs& p, int S) { return launch_conv_dma<BMC, 3, CEPI_BIAS_ACT, TH, 4, 4>(p, st, S); };
-  bool done = false;
-  const int r = launch_conv_split(a, st, BMC, CONV_SPLIT_F32, &done, launch);
-  return done ? r : launch(a, 1);
-}
-
-template <int BMC, int KS, int EPI>
-int launch_conv(const ConvArgs& a, hipStream_t st) {
-  // measured per shape (tools/lab/conv_lab.py, same box): with 8 x 16 pixels per workgroup the DMA kernel wins 2 % on the modulation
-  // convs and loses 2-6 % on the bias/activation convs (twice the barriers of the staged kernel); with 16 x 16 pixels it wins on
-  // every 128-row conv (modulation 9.8 -> 9.15 ms, 1 024 -> 512 channels at 32 x 32 2.34 -> 2.26 ms)
-  static const bool dma_all = getenv("SLN_CONV_DMA") != nullptr;
-  const bool staged_only = conv_staged_only();
-  if constexpr (KS == 3 && EPI == CEPI_BIAS_ACT) { if (a.blocked) return launch_conv_blocked<BMC>(a, st); }
-  if constexpr (EPI == CEPI_BIAS_ACT) {
-    if (!staged_only) {
-      bool done = false;
-      const int r = launch_conv_split(a, st, BMC, CONV_SPLIT_F32, &done,
-                                      [&](const ConvArgs& p, int S) { return launch_conv_dma<BMC, KS, CEPI_BIAS_ACT, TH, 4>(p, st, S); });
-      if (done) return r;
-    }
-  }
-  if (a.Cin % 8 == 0 && !staged_only) {
-    if constexpr (KS == 3) {
-      // 16 x 16 pixels per workgroup where the image has the rows (half the weight DMA per MFMA, twice the MFMAs per barrier)
-      // (not for launches too small to give every CU two of the tall workgroups: batch-1 convs of the one-map-many-z path).
-      // 64-row blocks: buffers of 8 channels (the same 144 MFMAs per wave and barrier; 2 % over the staged kernel at 256 x 256).
-      // 8-channel buffers for the 128-row blocks leave room for one workgroup per CU only: 10.1 ms against 9.06 ms.
-      const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / BMC);
-      if (a.H >= 16 && tall_blocks >= 512) return launch_conv_dma<BMC, 3, EPI, 16, BMC == 128 ? 4 : 8>(a, st);
-    }
-    if (EPI == CEPI_MODULATE || dma_all) return launch_conv_dma<BMC, KS, EPI, TH, 4>(a, st);
-  }
-  return launch_conv_staged<BMC, KS, EPI>(a, st);
-}
+// (the decision itself, conv_route, stands behind the half kernel: it needs that kernel's constants)
 
 // ------------------------------------------------------------------------------------------------
 // fp16-MFMA 3x3 convolution (opt-in precision modes "f16" and "f16x3")
@@ -928,41 +862,155 @@ int launch_conv_f16_k(const ConvArgs& a, const uint16_t* whi, const uint16_t* wl
       sizeof(_Float16) * (size_t)NT * (9 * BMC * FK + ConvTile<BMC, THT>::halo(3) * FK), BMC, THT, a, st, ksplit, whi, wlo);
 }
 
-// Routing of the half modes (every 3x3 launch of the generator): blocked accumulation (Cin >= 512) and the input-channel split of
-// launches of fewer than 192 workgroups as in the fp32 path; 16 x 16-pixel workgroups where the image has the rows and the launch
-// gives every CU two of them, else 8 x 16.  -Rpass-analysis=kernel-resource-usage: no spills and no scratch in any variant; 1-3
-// waves per SIMD (three products, 128 rows: 1).
+// ------------------------------------------------------------------------------------------------
+// Which kernel runs: ONE decision (conv_route), carried out by the two switches below and reported by sln_debug_conv_route
+// ------------------------------------------------------------------------------------------------
+constexpr int CONV_BLOCK_CIN = 512;      // blocked accumulation for the long chains (K = 9 Cin >= 4 608), see conv_mfma_kernel
+static bool conv_blocked(int epi, int ksize, int Cin) { return epi == CEPI_BIAS_ACT && ksize == 3 && Cin >= CONV_BLOCK_CIN; }
+enum { CONV_STAGED = 0, CONV_DMA = 1, CONV_F16 = 2 };      // conv_mfma_kernel, conv_glds_kernel, conv_f16_kernel
+struct ConvRoute {
+  int kernel;      // CONV_STAGED / CONV_DMA / CONV_F16
+  int bmc;         // packed rows per workgroup (64 / 128)
+  int tile_h;      // pixel rows per workgroup (TH = 8 / 16), 16 columns
+  int gk;          // input channels per chunk (CK = 8 staged, 4 / 8 DMA, FK = 16 half)
+  int blk;         // chunks per accumulation block, 0: one chain
+  int terms;       // 0 fp32, 1 / 3 products of the half modes
+  int shares;      // workgroups that share the input channels of a tile (> 1: split + conv_split_finish_kernel)
+};
+// The environment switches, read once per process: SLN_CONV_STAGED (every fp32 conv through the staged kernel, A/B runs and tests,
+// the Cin >= 512 convolutions included), SLN_CONV_DMA (the DMA kernel wherever it can run), SLN_CONV_KSPLIT (see CONV_SPLIT_MAX).
+struct ConvPolicy { bool staged_only, dma_all; int split_max; };
+static const ConvPolicy& conv_policy() {
+  static const ConvPolicy p{getenv("SLN_CONV_STAGED") != nullptr, getenv("SLN_CONV_DMA") != nullptr,
+                            getenv("SLN_CONV_KSPLIT") ? atoi(getenv("SLN_CONV_KSPLIT")) : CONV_SPLIT_MAX};
+  return p;
+}
 constexpr ConvSplitKind CONV_SPLIT_F16{FK, 2, false, true};      // the channel tail is zero padded; a share without a chunk would be a wasted workgroup
-template <int BMC, int EPI, int TERMS>
-int launch_conv_f16(const ConvArgs& a, const uint16_t* whi, const uint16_t* wlo, hipStream_t st) {
-  if constexpr (EPI == CEPI_BIAS_ACT) {
-    auto launch = [&](const ConvArgs& p, int S) {
-      return a.blocked ? launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 1>(p, whi, wlo, st, S)
-                       : launch_conv_f16_k<BMC, CEPI_BIAS_ACT, TH, TERMS, 0>(p, whi, wlo, st, S);
-    };
-    bool done = false;
-    const int r = launch_conv_split(a, st, BMC, CONV_SPLIT_F16, &done, launch);
-    if (done) return r;
-    if (a.blocked) return launch(a, 1);
-  }
-  // (16 x 16 pixels x 128 rows in the three-product form: 512 registers and still 4 spilled - 8 x 16 there)
-  if constexpr (!(TERMS == 3 && BMC == 128)) {
-    const long tall_blocks = (long)sln_cdiv(a.W, TW) * sln_cdiv(a.H, 16) * a.B * (a.rows_pad / BMC);
-    if (a.H >= 16 && tall_blocks >= 512) return launch_conv_f16_k<BMC, EPI, 16, TERMS, 0>(a, whi, wlo, st);
-  }
-  return launch_conv_f16_k<BMC, EPI, TH, TERMS, 0>(a, whi, wlo, st);
+
+// shares of a bias/activation launch in bmc-row workgroups of 8 x 16 pixels; 1: no split
+static int conv_route_shares(int B, int Cin, int H, int W, int rows, int rows_pad, int bmc, const ConvSplitKind& k, const ConvPolicy& pol) {
+  if (k.whole_chunks && Cin % k.chunk_cin != 0) return 1;
+  const long blocks = (long)sln_cdiv(W, TW) * sln_cdiv(H, TH) * B * (rows_pad / bmc);
+  const int chunks = sln_cdiv(Cin, k.chunk_cin);
+  const size_t one = (size_t)B * rows * H * W;
+  int S = conv_split_shares(blocks, chunks, k.least_chunks, one * sizeof(float), pol.split_max);
+  if (S <= 1) return 1;
+  if (k.no_idle_share) S = sln_cdiv(chunks, sln_cdiv(chunks, S));
+  return S;
 }
 
-template <int EPI>
-int launch_conv_f16_any(const ConvArgs& a, const uint16_t* whi, const uint16_t* wlo, hipStream_t st) {
-  const bool big = a.rows_pad % 128 == 0;
-  if (wlo) return big ? launch_conv_f16<128, EPI, 3>(a, whi, wlo, st) : launch_conv_f16<64, EPI, 3>(a, whi, wlo, st);
-  return big ? launch_conv_f16<128, EPI, 1>(a, whi, wlo, st) : launch_conv_f16<64, EPI, 1>(a, whi, wlo, st);
+// terms: 0 fp32, 1 / 3 half; epi: CEPI_*; rows: logical packed rows (Cout, or 2 C of a modulation).  Sizes are the entry points'
+// (checked there).  Every route returned has an instantiation in launch_conv_f32 / launch_conv_f16 below.
+static ConvRoute conv_route(int terms, int epi, int B, int Cin, int H, int W, int rows, int rows_pad, int ksize, const ConvPolicy& pol) {
+  const int bmc = rows_pad % 128 == 0 ? 128 : 64;
+  const bool blocked = conv_blocked(epi, ksize, Cin);
+  // 16 x 16 pixels per workgroup where the image has the rows (half the weight DMA per MFMA, twice the MFMAs per barrier) - not for
+  // launches too small to give every CU two of the tall workgroups: batch-1 convs of the one-map-many-z path
+  auto tall = [&](int rows_per_wg) {
+    return H >= 16 && (long)sln_cdiv(W, TW) * sln_cdiv(H, 16) * B * (rows_pad / rows_per_wg) >= 512;
+  };
+  if (terms != 0) {
+    // the half modes (every 3x3 launch of the generator): blocked accumulation (Cin >= 512) and the input-channel split of launches
+    // of fewer than 192 workgroups as in the fp32 path; 16 x 16-pixel workgroups where the image has the rows and the launch gives
+    // every CU two of them, else 8 x 16.  -Rpass-analysis=kernel-resource-usage: no spills and no scratch in any variant; 1-3
+    // waves per SIMD (three products, 128 rows: 1).
+    if (epi == CEPI_BIAS_ACT) {
+      const int S = conv_route_shares(B, Cin, H, W, rows, rows_pad, bmc, CONV_SPLIT_F16, pol);
+      if (S > 1 || blocked) return ConvRoute{CONV_F16, bmc, TH, FK, blocked ? 1 : 0, terms, S};
+    }
+    // (16 x 16 pixels x 128 rows in the three-product form: 512 registers and still 4 spilled - 8 x 16 there)
+    if (!(terms == 3 && bmc == 128) && tall(bmc)) return ConvRoute{CONV_F16, bmc, 16, FK, 0, terms, 1};
+    return ConvRoute{CONV_F16, bmc, TH, FK, 0, terms, 1};
+  }
+  if (blocked) {
+    // Blocked accumulation (see conv_mfma_kernel): variants with 64 accumulators per lane.  Blocks of 16 input channels (144
+    // products): 2 buffers of 8 channels / 4 buffers of 4 / 2 staged chunks of 8.
+    if (Cin % 8 != 0 || pol.staged_only) return ConvRoute{CONV_STAGED, bmc, TH, CK, 2, 0, 1};
+    // 64-row workgroups of 16 x 16 pixels (the halo is DMA'd once per 64 rows instead of once per 128: 1.2x the operand traffic
+    // of the 128-row workgroups; 8 x 16 x 128 rows re-reads the weights per 128 pixels: 1.8x)
+    if (tall(64)) return ConvRoute{CONV_DMA, 64, 16, 8, 2, 0, 1};
+    return ConvRoute{CONV_DMA, bmc, TH, 4, 4, 0, conv_route_shares(B, Cin, H, W, rows, rows_pad, bmc, CONV_SPLIT_F32, pol)};
+  }
+  // measured per shape (tools/lab/conv_lab.py, same box): with 8 x 16 pixels per workgroup the DMA kernel wins 2 % on the modulation
+  // convs and loses 2-6 % on the bias/activation convs (twice the barriers of the staged kernel); with 16 x 16 pixels it wins on
+  // every 128-row conv (modulation 9.8 -> 9.15 ms, 1 024 -> 512 channels at 32 x 32 2.34 -> 2.26 ms)
+  if (epi == CEPI_BIAS_ACT && !pol.staged_only) {
+    const int S = conv_route_shares(B, Cin, H, W, rows, rows_pad, bmc, CONV_SPLIT_F32, pol);
+    if (S > 1) return ConvRoute{CONV_DMA, bmc, TH, 4, 0, 0, S};
+  }
+  if (Cin % 8 == 0 && !pol.staged_only) {
+    // 64-row blocks: buffers of 8 channels (the same 144 MFMAs per wave and barrier; 2 % over the staged kernel at 256 x 256).
+    // 8-channel buffers for the 128-row blocks leave room for one workgroup per CU only: 10.1 ms against 9.06 ms.
+    if (ksize == 3 && tall(bmc)) return ConvRoute{CONV_DMA, bmc, 16, bmc == 128 ? 4 : 8, 0, 0, 1};
+    if (epi == CEPI_MODULATE || pol.dma_all) return ConvRoute{CONV_DMA, bmc, TH, 4, 0, 0, 1};
+  }
+  return ConvRoute{CONV_STAGED, bmc, TH, CK, 0, 0, 1};
+}
+
+// One instantiated kernel = one key.
+constexpr int conv_key(int kernel, int bmc, int ks, int epi, int tht, int gk, int blk, int terms) {
+  return kernel | (bmc == 128) << 2 | (ks == 3) << 3 | epi << 4 | (tht == 16) << 5 | blk << 6 | terms << 9 | gk << 11;
+}
+// Runs launch(args, shares): as it stands, or with the scratch of an input-channel split and conv_split_finish_kernel behind it.
+// A split launch is the split one - or an error, never another kernel.
+template <class Launch>
+int launch_conv_shares(const ConvArgs& a, const ConvRoute& r, hipStream_t st, Launch launch) {
+  if (r.shares <= 1) return launch(a, 1);
+  const size_t one = (size_t)a.B * a.rows * a.H * a.W;
+  float* part = nullptr;
+  { const int e = conv_part_scratch(st, &part, true); if (e) return e; }
+  ConvArgs p = a; p.part = part; p.part_stride = (long)one;
+  const int e = launch(p, r.shares);
+  return e ? e : launch_conv_split_finish(a, part, r.shares, (long)one, st);
+}
+
+// The fp32 instantiations: 8 staged, 13 DMA.  A route that names none of them is refused.
+int launch_conv_f32(const ConvArgs& a, int epi, int ksize, hipStream_t st) {
+  const ConvRoute r = conv_route(0, epi, a.B, a.Cin, a.H, a.W, a.rows, a.rows_pad, ksize, conv_policy());
+  return launch_conv_shares(a, r, st, [&](const ConvArgs& p, int S) -> int {
+    switch (conv_key(r.kernel, r.bmc, ksize, epi, r.tile_h, r.gk, r.blk, 0)) {
+#define SLN_STG(BMC, KS, EPI, BLK) \
+  case conv_key(CONV_STAGED, BMC, KS, EPI, TH, CK, BLK, 0): return S == 1 ? launch_conv_staged<BMC, KS, EPI, BLK>(p, st) : SLN_E_UNSUPPORTED;
+#define SLN_DMA(BMC, KS, EPI, THT, GK, BLK) \
+  case conv_key(CONV_DMA, BMC, KS, EPI, THT, GK, BLK, 0): return launch_conv_dma<BMC, KS, EPI, THT, GK, BLK>(p, st, S);
+      SLN_STG(64, 3, CEPI_BIAS_ACT, 0) SLN_STG(128, 3, CEPI_BIAS_ACT, 0) SLN_STG(64, 1, CEPI_BIAS_ACT, 0) SLN_STG(128, 1, CEPI_BIAS_ACT, 0)
+      SLN_STG(64, 3, CEPI_BIAS_ACT, 2) SLN_STG(128, 3, CEPI_BIAS_ACT, 2)
+      SLN_STG(64, 3, CEPI_MODULATE, 0) SLN_STG(128, 3, CEPI_MODULATE, 0)
+      SLN_DMA(64, 3, CEPI_BIAS_ACT, TH, 4, 0) SLN_DMA(128, 3, CEPI_BIAS_ACT, TH, 4, 0)
+      SLN_DMA(64, 1, CEPI_BIAS_ACT, TH, 4, 0) SLN_DMA(128, 1, CEPI_BIAS_ACT, TH, 4, 0)
+      SLN_DMA(64, 3, CEPI_BIAS_ACT, TH, 4, 4) SLN_DMA(128, 3, CEPI_BIAS_ACT, TH, 4, 4)
+      SLN_DMA(64, 3, CEPI_BIAS_ACT, 16, 8, 2)
+      SLN_DMA(64, 3, CEPI_BIAS_ACT, 16, 8, 0) SLN_DMA(128, 3, CEPI_BIAS_ACT, 16, 4, 0)
+      SLN_DMA(64, 3, CEPI_MODULATE, TH, 4, 0) SLN_DMA(128, 3, CEPI_MODULATE, TH, 4, 0)
+      SLN_DMA(64, 3, CEPI_MODULATE, 16, 8, 0) SLN_DMA(128, 3, CEPI_MODULATE, 16, 4, 0)
+#undef SLN_STG
+#undef SLN_DMA
+      default: return SLN_E_UNSUPPORTED;
+    }
+  });
+}
+
+// The half instantiations: 18 (no 16 x 16 x 128-row three-product form, no blocked or split modulation).
+int launch_conv_f16(const ConvArgs& a, int epi, const uint16_t* whi, const uint16_t* wlo, hipStream_t st) {
+  const int terms = wlo ? 3 : 1;
+  const ConvRoute r = conv_route(terms, epi, a.B, a.Cin, a.H, a.W, a.rows, a.rows_pad, 3, conv_policy());
+  return launch_conv_shares(a, r, st, [&](const ConvArgs& p, int S) -> int {
+    switch (conv_key(r.kernel, r.bmc, 3, epi, r.tile_h, r.gk, r.blk, terms)) {
+#define SLN_F16(BMC, EPI, THT, TERMS, BLK) \
+  case conv_key(CONV_F16, BMC, 3, EPI, THT, FK, BLK, TERMS): return launch_conv_f16_k<BMC, EPI, THT, TERMS, BLK>(p, whi, wlo, st, S);
+      SLN_F16(64, CEPI_BIAS_ACT, TH, 1, 0) SLN_F16(128, CEPI_BIAS_ACT, TH, 1, 0) SLN_F16(64, CEPI_BIAS_ACT, TH, 3, 0) SLN_F16(128, CEPI_BIAS_ACT, TH, 3, 0)
+      SLN_F16(64, CEPI_BIAS_ACT, TH, 1, 1) SLN_F16(128, CEPI_BIAS_ACT, TH, 1, 1) SLN_F16(64, CEPI_BIAS_ACT, TH, 3, 1) SLN_F16(128, CEPI_BIAS_ACT, TH, 3, 1)
+      SLN_F16(64, CEPI_BIAS_ACT, 16, 1, 0) SLN_F16(128, CEPI_BIAS_ACT, 16, 1, 0) SLN_F16(64, CEPI_BIAS_ACT, 16, 3, 0)
+      SLN_F16(64, CEPI_MODULATE, TH, 1, 0) SLN_F16(128, CEPI_MODULATE, TH, 1, 0) SLN_F16(64, CEPI_MODULATE, TH, 3, 0) SLN_F16(128, CEPI_MODULATE, TH, 3, 0)
+      SLN_F16(64, CEPI_MODULATE, 16, 1, 0) SLN_F16(128, CEPI_MODULATE, 16, 1, 0) SLN_F16(64, CEPI_MODULATE, 16, 3, 0)
+#undef SLN_F16
+      default: return SLN_E_UNSUPPORTED;
+    }
+  });
 }
 
 // The two call shapes of the C entry points, fp32 and half alike (half: wp = the fp16 hi pack for the checks, nullptr in ConvArgs -
 // the packs are kernel arguments of their own - and two more terms in the checks, at the place they had).
-constexpr int CONV_BLOCK_CIN = 512;      // blocked accumulation for the long chains (K = 9 Cin >= 4 608), see conv_mfma_kernel
 int conv_sums_check(const void* x, const void* wp, const void* y, int B, int Cin, int H, int W, int rows, int rows_pad, int ksize, bool half) {
   if (!x || !wp || !y || B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || rows <= 0 || rows_pad % 64 != 0 || rows > rows_pad) return SLN_E_BADARG;
   if (ksize != 3 && (half || ksize != 1)) return SLN_E_UNSUPPORTED;
@@ -975,7 +1023,7 @@ ConvArgs conv_sums_args(const float* x, int B, int Cin, int H, int W, const floa
   ConvArgs a{};
   a.x = x; a.wp = wp; a.bias = bias; a.y = y; a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.rows = rows; a.rows_pad = rows_pad;
   a.act = act; a.slope = slope; a.ln_acc = ln_acc; a.gap_acc = gap_acc;
-  a.blocked = ksize == 3 && Cin >= CONV_BLOCK_CIN;
+  a.blocked = conv_blocked(CEPI_BIAS_ACT, ksize, Cin);      // (a record for who reads the arguments: conv_route decides by itself)
   return a;
 }
 int conv_modulate_check(const void* actv, const void* wp, const void* bias, const void* xin, const void* stats, const void* out, int B, int Cin,
@@ -1571,9 +1619,7 @@ int sln_spade_conv_sums(const float* x, int B, int Cin, int H, int W, const floa
   hipStream_t st = (hipStream_t)stream;
   const ConvArgs a = conv_sums_args(x, B, Cin, H, W, wp, bias, rows, rows_pad, ksize, act, slope, y, ln_acc, gap_acc);
   SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * ksize * ksize * rows, st);
-  const bool big = rows_pad % 128 == 0;
-  if (ksize == 3) return big ? launch_conv<128, 3, CEPI_BIAS_ACT>(a, st) : launch_conv<64, 3, CEPI_BIAS_ACT>(a, st);
-  return big ? launch_conv<128, 1, CEPI_BIAS_ACT>(a, st) : launch_conv<64, 1, CEPI_BIAS_ACT>(a, st);
+  return launch_conv_f32(a, CEPI_BIAS_ACT, ksize, st);
 }
 int sln_spade_prepare(void* stream) {
   float* p = nullptr;
@@ -1596,7 +1642,7 @@ int sln_spade_modulate_up(const float* actv, int B, int Cin, int H, int W, const
   hipStream_t st = (hipStream_t)stream;
   const ConvArgs a = conv_modulate_args(actv, B, Cin, H, W, wp, bias, C, rows_pad, xin, xin_up, stats, act, slope, out);
   SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * 9 * 2 * C, st);
-  return rows_pad % 128 == 0 ? launch_conv<128, 3, CEPI_MODULATE>(a, st) : launch_conv<64, 3, CEPI_MODULATE>(a, st);
+  return launch_conv_f32(a, CEPI_MODULATE, 3, st);
 }
 int sln_spade_modulate(const float* actv, int B, int Cin, int H, int W, const float* wp, const float* bias, int C, int rows_pad,
                        const float* xin, const float* stats, int act, float slope, float* out, void* stream) {
@@ -1611,7 +1657,7 @@ int sln_spade_conv_sums_f16(const float* x, int B, int Cin, int H, int W, const 
   hipStream_t st = (hipStream_t)stream;
   const ConvArgs a = conv_sums_args(x, B, Cin, H, W, nullptr, bias, rows, rows_pad, ksize, act, slope, y, ln_acc, gap_acc);
   SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * 9 * rows, st);
-  return launch_conv_f16_any<CEPI_BIAS_ACT>(a, wp_hi, wp_lo, st);
+  return launch_conv_f16(a, CEPI_BIAS_ACT, wp_hi, wp_lo, st);
 }
 int sln_spade_conv_f16(const float* x, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
                        int rows, int rows_pad, int ksize, int act, float slope, float* y, void* stream) {
@@ -1624,11 +1670,36 @@ int sln_spade_modulate_up_f16(const float* actv, int B, int Cin, int H, int W, c
   hipStream_t st = (hipStream_t)stream;
   const ConvArgs a = conv_modulate_args(actv, B, Cin, H, W, nullptr, bias, C, rows_pad, xin, xin_up, stats, act, slope, out);
   SlnProfScope prof(SLN_FAM_CONV, 2.0 * B * H * W * (double)Cin * 9 * 2 * C, st);
-  return launch_conv_f16_any<CEPI_MODULATE>(a, wp_hi, wp_lo, st);
+  return launch_conv_f16(a, CEPI_MODULATE, wp_hi, wp_lo, st);
 }
 int sln_spade_modulate_f16(const float* actv, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
                            int C, int rows_pad, const float* xin, const float* stats, int act, float slope, float* out, void* stream) {
   return sln_spade_modulate_up_f16(actv, B, Cin, H, W, wp_hi, wp_lo, bias, C, rows_pad, xin, 0, stats, act, slope, out, stream);
+}
+
+// Host only: the route conv_route takes (see include/sln_hip.h).  No HIP call.
+int sln_debug_conv_route(int terms, int epi, int B, int Cin, int H, int W, int rows, int rows_pad, int ksize, int force, SlnDbgConvRoute* out) {
+  static_assert(sizeof(SlnDbgConvRoute) == sizeof(ConvRoute), "SlnDbgConvRoute mirrors ConvRoute");
+  if (!out || (terms != 0 && terms != 1 && terms != 3) || (epi != CEPI_BIAS_ACT && epi != CEPI_MODULATE) || force < -1 || force > 2)
+    return SLN_E_BADARG;
+  const void* some = out;      // the checks look at pointers only for NULL
+  if (epi == CEPI_BIAS_ACT) {
+    if (const int r = conv_sums_check(some, some, some, B, Cin, H, W, rows, rows_pad, ksize, terms != 0)) return r;
+  } else {
+    if (ksize != 3) return SLN_E_UNSUPPORTED;
+    if (const int r = conv_modulate_check(some, some, some, some, some, some, B, Cin, H, W, rows, rows_pad, 0, terms != 0)) return r;
+  }
+  ConvPolicy pol = conv_policy();
+  if (force >= 0) pol = ConvPolicy{force == 1, force == 2, CONV_SPLIT_MAX};
+  const ConvRoute r = conv_route(terms, epi, B, Cin, H, W, epi == CEPI_MODULATE ? 2 * rows : rows, rows_pad, ksize, pol);
+  *out = SlnDbgConvRoute{r.kernel, r.bmc, r.tile_h, r.gk, r.blk, r.terms, r.shares};
+  return 0;
+}
+int sln_debug_conv_sizes(int* out, int max) {
+  const int sizes[] = {(int)sizeof(SlnDbgConvRoute)};
+  const int n = (int)(sizeof(sizes) / sizeof(sizes[0]));
+  for (int i = 0; out && i < n && i < max; ++i) out[i] = sizes[i];
+  return n;
 }
 
 // stats[b] from sums a conv epilogue / block tail accumulated (acc [B][16] doubles: sum, sum of squares over n_acc values,

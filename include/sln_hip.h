@@ -815,6 +815,19 @@ int sln_spade_modulate_f16(const float* actv, int B, int Cin, int H, int W, cons
 int sln_spade_modulate_up_f16(const float* actv, int B, int Cin, int H, int W, const uint16_t* wp_hi, const uint16_t* wp_lo, const float* bias,
                               int C, int rows_pad, const float* xin, int xin_up, const float* stats, int act, float slope, float* out,
                               void* stream);
+/* TEST HOOK, host only (no HIP call): which convolution kernel the four entry points above launch for a problem - the decision of
+ * csrc/spade.hip's conv_route, the one place where it is taken.  terms: 0 fp32, 1 / 3 the half modes (wp_lo NULL / given); epi: 0
+ * bias + activation (sln_spade_conv*), 1 modulation (sln_spade_modulate*; ksize must be 3); rows: the entry point's Cout, or C.
+ * force: -1 the process's own switches (SLN_CONV_STAGED, SLN_CONV_DMA, SLN_CONV_KSPLIT, read once per process), 0 no switch,
+ * 1 SLN_CONV_STAGED alone, 2 SLN_CONV_DMA alone.  Returns 0, or what the entry point's size checks return for the problem
+ * (SLN_E_BADARG also for a NULL out or a terms / epi / force value outside the lists above).
+ * kernel: 0 conv_mfma_kernel (operands staged through registers), 1 conv_glds_kernel (DMA into LDS), 2 conv_f16_kernel; bmc: packed
+ * rows per workgroup (64 / 128); tile_h: pixel rows per workgroup (8 / 16, by 16 columns); gk: input channels per chunk; blk: chunks
+ * per accumulation block (0: one chain); shares: workgroups sharing the input channels of a tile (> 1: the input-channel split). */
+typedef struct SlnDbgConvRoute { int kernel, bmc, tile_h, gk, blk, terms, shares; } SlnDbgConvRoute;
+int sln_debug_conv_route(int terms, int epi, int B, int Cin, int H, int W, int rows, int rows_pad, int ksize, int force, SlnDbgConvRoute* out);
+/* sizeof of SlnDbgConvRoute; returns how many sizes there are. */
+int sln_debug_conv_sizes(int* out, int max);
 /* Tail of SPADEResnetBlock4.forward (:1492-1493) and the nn.Upsample after it (:1585-1600) in one pass:
  *   out = up(xs + dx * sigmoid(W2 relu(W0 GAP(dx)))),  stats = LayerNorm2D statistics of the next block's input.
  * xs [B,C,H,W] (xs_up = 1: [B,C,H/2,W/2] read through nearest x2); gap_sums = the gap_acc of sln_spade_conv_sums or NULL;
