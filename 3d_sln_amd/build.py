@@ -30,6 +30,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # mesh_split: marks, midpoints and the diagonal choice are held to the numpy restatement for equality (host/mesh_prep.py)
 # (shade_view.hip takes the default flags: its placement and projection are held to a tolerance, not to bits, and contraction stays on)
 # (observed_reproject.hip likewise: unprojection, pose and projection to a tolerance; its compose step only copies bits and bytes)
+# (observed_fuse.hip: copies bits and bytes; its one float decision, the agreement test, is written with __fsub_rn / __fmul_rn)
 PER_FILE = {"raster.hip": ["-ffp-contract=off"], "graph_build.hip": ["-ffp-contract=off"], "placement.hip": ["-ffp-contract=off"],
             "layout_iou.hip": ["-ffp-contract=off"], "spade_input.hip": ["-ffp-contract=off"], "layout_plot.hip": ["-ffp-contract=off"],
             "scene_pictures.hip": ["-ffp-contract=off"], "mesh_retrieve.hip": ["-ffp-contract=off"],

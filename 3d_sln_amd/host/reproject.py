@@ -8,12 +8,16 @@ pixel out of the rasterizer's maps.
 
   * ``ObservedReprojector``   static buffers, three steps of launches (faces, raster, compose), nothing read back;
   * ``reproject_torch``       the definition in torch ops with the caller's rasterizer: the yardstick of the tests and the CPU route;
+  * ``ObservedFuser``         V frames per room: faces and raster over R * V frames, then ONE fused compose (csrc/observed_fuse.hip) that
+    gives every target pixel to the frame with the nearest surface there - the z-buffer rule - and says which frame won, how many
+    frames saw the pixel and how many of them agree with the winner's depth; ``fuse_torch`` / ``reproject_views_torch`` restate it
+    (DESIGN §4 "Several observed frames per room");
   * ``relative_pose``, ``refine_view``, ``scene_as_source``   the cameras: source -> target pose from two world poses, the refinement
     view of a room row, and the source intrinsics under which a scene tensor's own planes are a frame of their own camera.
 
-A target pixel no face covers - a disocclusion, a cut at a depth step, the frame's border - reads "no reading" (-1, label 0); the
-refinement loss has no validity mask, so ``hits`` is the caller's signal.  There is no pre-filter when the frame is finer than the
-target, and one frame per room: fusing several is not done here.
+A target pixel no face covers - a disocclusion, a cut at a depth step, the frame's border - reads "no reading" (-1, label 0);
+``RefineBatch(mask="readings")`` keeps such pixels out of the loss, and further frames of the room fill them (``ObservedFuser``).  There
+is no pre-filter when a frame is finer than the target; labels are never blended or voted, and V is ragged only by ``fx = 0`` padding.
 """
 import numpy as np
 import torch
@@ -27,6 +31,7 @@ NO_READING = -1.0
 MAX_FACES = 1 << 24
 MAX_S = 4096
 MAX_B = 65535
+MAX_V = 255
 # corner -> (row, column) offset inside the cell, per slot: (a, b, c) and (d, c, b)
 _DI = ((0, 1, 0), (1, 0, 1))
 _DJ = ((0, 0, 1), (1, 1, 0))
@@ -120,9 +125,10 @@ def faces_torch(depth_src, k_src, pose, K_tgt, orig_size, near=0.1, gap=0.05, dt
     return faces.reshape(B, n_faces(Hs, Ws), 3, 3).contiguous()
 
 
-def compose_torch(face_index, weight, raster_depth, labels_src):
-    """csrc/observed_reproject.hip's compose in torch ops: maps [B, S, S] in raster order and ``labels_src`` [B, Hs, Ws] uint8 ->
-    (depth [B, S, S] float32, labels [B, S, S] uint8) in the planes' row order, hits [B] int64"""
+def _hit_and_label(face_index, weight, labels_src):
+    """compose's rule per frame, in raster order: -> hit [B, S, S] bool (``face_index`` in [0, F), no NaN among the three weights) and
+    the byte of ``labels_src`` at the face's corner of largest weight, ties to the lower corner number ([B, S, S] uint8; meaningless
+    where there is no hit)"""
     B, Hs, Ws = labels_src.shape
     Wc, F = Ws - 1, n_faces(Hs, Ws)
     dev = face_index.device
@@ -137,10 +143,56 @@ def compose_torch(face_index, weight, raster_depth, labels_src):
     corner = torch.where(w[..., 2] > torch.where(first, w[..., 1], w[..., 0]), torch.full_like(corner, 2), corner)
     di, dj = torch.tensor(_DI, device=dev)[which, corner], torch.tensor(_DJ, device=dev)[which, corner]
     frame = torch.arange(B, device=dev)[:, None, None]
-    lab = labels_src[frame, ci + di, cj + dj]
+    return hit, labels_src[frame, ci + di, cj + dj]
+
+
+def compose_torch(face_index, weight, raster_depth, labels_src):
+    """csrc/observed_reproject.hip's compose in torch ops: maps [B, S, S] in raster order and ``labels_src`` [B, Hs, Ws] uint8 ->
+    (depth [B, S, S] float32, labels [B, S, S] uint8) in the planes' row order, hits [B] int64"""
+    dev = face_index.device
+    hit, lab = _hit_and_label(face_index, weight, labels_src)
     labels = torch.where(hit, lab, torch.zeros((), dtype=torch.uint8, device=dev))
     depth = torch.where(hit, raster_depth.float(), torch.full((), NO_READING, dtype=torch.float32, device=dev))
     return torch.flip(depth, [1]).contiguous(), torch.flip(labels, [1]).contiguous(), hit.sum(dim=(1, 2))
+
+
+def fuse_torch(face_index, weight, raster_depth, labels_src, V, gap=0.05):
+    """The fusion of V frames per room in torch ops (DESIGN §4 "Several observed frames per room"): the rasterizer's maps [R * V, S, S(, 3)]
+    in raster order, frame ``r * V + v``, and ``labels_src`` [R * V, Hs, Ws] uint8 -> dict, in the planes' row order:
+
+      depth  [R, S, S] float32  the depth of the WINNER: of the contributing frames (a hit by compose's rule whose depth is no NaN) the one
+                                with the smallest depth, equal depths to the lowest v; -1 where no frame contributes
+      labels [R, S, S] uint8    the winner's label by compose's rule (a 0 of the winner stays 0); 0 without a winner
+      source [R, S, S] uint8    1 + v of the winner, 0 without one
+      count  [R, S, S] uint8    contributing frames
+      agree  [R, S, S] uint8    contributing frames with ``!((d_v - dmin) > gap * dmin)`` in float32 (the winner among them)
+      hits [R], wins [R, V] int64   pixels with a winner, pixels per winning frame"""
+    B, Hs, Ws = labels_src.shape
+    V = int(V)
+    if V < 1 or V > MAX_V or B % V or not gap >= 0:
+        raise ValueError("V in [1, 255] that divides the %d frames and gap >= 0 expected, got V = %r, gap = %r" % (B, V, gap))
+    R, S = B // V, int(face_index.shape[1])
+    dev = face_index.device
+    hit, lab = _hit_and_label(face_index, weight, labels_src)
+    d = raster_depth.float().reshape(R, V, S, S)
+    contributes = (hit.reshape(R, V, S, S) & ~torch.isnan(d))
+    lab = lab.reshape(R, V, S, S)
+    best = torch.full((R, S, S), -1, dtype=torch.long, device=dev)
+    dmin = torch.full((R, S, S), NO_READING, dtype=torch.float32, device=dev)
+    labels = torch.zeros((R, S, S), dtype=torch.uint8, device=dev)
+    for v in range(V):                                               # v upwards, a strict <: the z-buffer rule
+        take = contributes[:, v] & ((best < 0) | (d[:, v] < dmin))
+        dmin = torch.where(take, d[:, v], dmin)
+        labels = torch.where(take, lab[:, v], labels)
+        best = torch.where(take, torch.full_like(best, v), best)
+    edge = torch.tensor(gap, dtype=torch.float32, device=dev) * dmin  # one float32 product ...
+    near = ~((d - dmin[:, None]) > edge[:, None])                     # ... against one float32 difference
+    count = contributes.sum(1)
+    agree = (contributes & near).sum(1)
+    wins = torch.stack([(best == v).sum(dim=(1, 2)) for v in range(V)], 1)
+    flip = lambda x, dt: torch.flip(x, [1]).to(dt).contiguous()
+    return dict(depth=flip(dmin, torch.float32), labels=flip(labels, torch.uint8), source=flip(best + 1, torch.uint8),
+                count=flip(count, torch.uint8), agree=flip(agree, torch.uint8), hits=(best >= 0).sum(dim=(1, 2)), wins=wins)
 
 
 def reproject_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near=0.1, far=100.0, gap=0.05, dtype=torch.float64):
@@ -158,6 +210,36 @@ def reproject_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, ras
     fi, w, dep = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (fi, w, dep))
     depth, labels, hits = compose_torch(fi, w, dep, labels_src)
     return dict(depth=depth, labels=labels, hits=hits, faces_xyz=fxyz, face_index=fi, weight=w)
+
+
+def _check_views(R, V, Hs, Ws, S):
+    if R < 1 or V < 1 or V > MAX_V:
+        raise ValueError("rooms >= 1 and views in [1, 255] expected, got rooms = %r, views = %r" % (R, V))
+    _check_sizes(R * V, Hs, Ws, S)
+
+
+def reproject_views_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near=0.1, far=100.0, gap=0.05,
+                          dtype=torch.float64):
+    """The route of ``ObservedFuser`` in torch ops on the tensors' device, in ``dtype``: ``reproject_torch``'s counterpart for V frames
+    per room.  ``depth_src`` [R, V, Hs, Ws] float, ``labels_src`` [R, V, Hs, Ws] uint8, ``k_src`` [R, V, 4], ``pose`` [R, V, 3, 4],
+    ``K_tgt`` [R, 3, 3] (the room's); ``rasterize`` as in ``reproject_torch``.  -> the dict of ``fuse_torch`` plus faces_xyz
+    [R * V, F, 3, 3] in ``dtype`` and the maps face_index, weight, raster_depth [R * V, S, S(, 3)]"""
+    if depth_src.dim() != 4 or labels_src.shape != depth_src.shape or labels_src.dtype != torch.uint8:
+        raise ValueError("depth_src [R, V, Hs, Ws] float and labels_src [R, V, Hs, Ws] uint8 expected")
+    R, V, Hs, Ws = depth_src.shape
+    _check_views(R, V, Hs, Ws, int(S))
+    if tuple(k_src.shape) != (R, V, 4) or tuple(pose.shape) != (R, V, 3, 4) or tuple(K_tgt.shape) != (R, 3, 3):
+        raise ValueError("k_src [R, V, 4], pose [R, V, 3, 4] and K_tgt [R, 3, 3] expected")
+    dev = depth_src.device
+    B = R * V
+    lab = labels_src.reshape(B, Hs, Ws)
+    fxyz = faces_torch(depth_src.reshape(B, Hs, Ws), k_src.reshape(B, 4), pose.reshape(B, 3, 4), K_tgt.repeat_interleave(V, 0), orig_size,
+                       near, gap, dtype)
+    fi, w, dep = rasterize(fxyz.float().cpu().numpy(), int(S), float(near), float(far))
+    fi, w, dep = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (fi, w, dep))
+    out = fuse_torch(fi, w, dep, lab, V, gap)
+    out.update(faces_xyz=fxyz, face_index=fi, weight=w, raster_depth=dep)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -237,3 +319,88 @@ class ObservedReprojector:
                 "sln_raster_forward")
         compose(self.face_index, self.weight, self.raster_depth, labels_src, self.depth, self.labels, self.hits)
         return self.depth, self.labels, self.hits
+
+
+def fuse(face_index, weight, raster_depth, labels_src, V, gap, depth_out, labels_out, hits, source_out=None, count_out=None, agree_out=None,
+         wins=None):
+    """the bare ``sln_reproject_fuse`` call over the caller's buffers (maps and ``labels_src`` of R * V frames); the last four are optional"""
+    B, Hs, Ws = (int(x) for x in labels_src.shape)
+    V = int(V)
+    if V < 1 or B % V:
+        raise ValueError("V >= 1 that divides the %d frames expected, got %r" % (B, V))
+    L.check(L.lib().sln_reproject_fuse(L.ptr(face_index), L.ptr(weight), L.ptr(raster_depth), L.ptr(labels_src), B // V, V, Hs, Ws,
+                                       int(face_index.shape[1]), float(gap), L.ptr(depth_out), L.ptr(labels_out), L.ptr(source_out),
+                                       L.ptr(count_out), L.ptr(agree_out), L.ptr(hits), L.ptr(wins), _stream(depth_out)),
+            "sln_reproject_fuse")
+
+
+class ObservedFuser:
+    """``views`` frames per room of ``rooms`` rooms, each ``Hs`` x ``Ws``, fused into one target view of ``S`` x ``S`` per room on the
+    device: where several frames see a target pixel, the one with the nearest surface there has it (the z-buffer rule).
+
+        fu = ObservedFuser(480, 640, 256, rooms=16, views=4)
+        depth, labels, source = fu(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
+        rb = RefineBatch(model, rooms, observed=(depth, labels), mask=fu.valid(), image_size=256, ...)      # or mask="readings"
+        corroborated = (fu.agree >= 2).to(torch.uint8)          # pixels two frames agree on, for mask= - built by the caller
+
+    ``depth_src`` [R, V, Hs, Ws] float32, ``labels_src`` [R, V, Hs, Ws] uint8, ``k_src`` [R, V, 4] float32, ``pose`` [R, V, 3, 4] float32
+    - per frame, as ``ObservedReprojector`` takes them; a room with fewer frames pads with frames whose ``k_src`` has fx = 0 -, ``K_tgt``
+    [R, 3, 3] float32 and ``orig_size`` per room (``refine_view``).  -> ``depth`` [R, S, S] float32 (-1 without a winner), ``labels``
+    [R, S, S] uint8, ``source`` [R, S, S] uint8 (1 + v of the winning frame, 0 without one); ``count``, ``agree`` [R, S, S] uint8
+    (frames that see the pixel; those within ``gap`` of the winner's depth, itself included), ``hits`` [R] and ``wins`` [R, V] int64
+    are attributes.  All are the instance's static buffers: the next call overwrites them.  A call spreads ``K_tgt`` over the frames
+    with one ``copy_`` and makes three steps of launches (faces and raster over R * V frames, the fused compose) on the current stream,
+    allocates nothing and reads nothing back: legal under a graph capture.  Tensors of another dtype, device or shape are refused
+    before anything is launched."""
+
+    def __init__(self, Hs, Ws, S, rooms=1, views=1, near=0.1, far=100.0, gap=0.05, device="cuda"):
+        self.Hs, self.Ws, self.S, self.rooms, self.views = int(Hs), int(Ws), int(S), int(rooms), int(views)
+        self.near, self.far, self.gap = float(near), float(far), float(gap)
+        _check_views(self.rooms, self.views, self.Hs, self.Ws, self.S)
+        _check_scalars(1.0, self.near, self.gap)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.SlnError("ObservedFuser runs on the MI355X only (no CPU fallback); reproject_views_torch restates it for CPU tensors")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        R, V, S, dev = self.rooms, self.views, self.S, self.device
+        B = self.batch = R * V
+        self.F = n_faces(self.Hs, self.Ws)
+        self.K_frames = torch.zeros(B, 3, 3, dtype=torch.float32, device=dev)
+        self.faces_xyz = torch.zeros(B, self.F, 3, 3, dtype=torch.float32, device=dev)
+        self.face_index = torch.empty(B, S, S, dtype=torch.int32, device=dev)
+        self.weight = torch.empty(B, S, S, 3, dtype=torch.float32, device=dev)
+        self.raster_depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+        self._raster_ws = torch.empty(int(L.lib().sln_raster_workspace_bytes(B, self.F)), dtype=torch.uint8, device=dev)
+        self.depth = torch.empty(R, S, S, dtype=torch.float32, device=dev)
+        self.labels, self.source, self.count, self.agree, self._valid = (torch.empty(R, S, S, dtype=torch.uint8, device=dev) for _ in range(5))
+        self.hits = torch.zeros(R, dtype=torch.int64, device=dev)
+        self.wins = torch.zeros(R, V, dtype=torch.int64, device=dev)
+
+    def check(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
+        """raises ValueError before anything is launched; reads the instance's sizes, scalars and device only"""
+        R, V, dev = self.rooms, self.views, self.device
+        for t, dt, shape, what in ((depth_src, torch.float32, (R, V, self.Hs, self.Ws), "depth_src"), (labels_src, torch.uint8, (R, V, self.Hs, self.Ws), "labels_src"),
+                                   (k_src, torch.float32, (R, V, 4), "k_src"), (pose, torch.float32, (R, V, 3, 4), "pose"), (K_tgt, torch.float32, (R, 3, 3), "K_tgt")):
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != dev:
+                raise ValueError("%s: a %s tensor on %s expected" % (what, str(dt).replace("torch.", ""), dev))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s: shape %s is not a contiguous %s" % (what, tuple(t.shape), list(shape)))
+        _check_scalars(float(orig_size), self.near, self.gap)
+
+    def __call__(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
+        self.check(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
+        R, V, B = self.rooms, self.views, self.batch
+        self.K_frames.view(R, V, 3, 3).copy_(K_tgt[:, None])
+        lab = labels_src.view(B, self.Hs, self.Ws)
+        faces(depth_src.view(B, self.Hs, self.Ws), k_src.view(B, 4), pose.view(B, 3, 4), self.K_frames, orig_size, self.near, self.gap, self.faces_xyz)
+        L.check(L.lib().sln_raster_forward(L.ptr(self.faces_xyz), B, self.F, self.S, self.near, self.far, L.ptr(self._raster_ws),
+                                           L.ptr(self.face_index), L.ptr(self.weight), L.ptr(self.raster_depth), L.current_stream_ptr()),
+                "sln_raster_forward")
+        fuse(self.face_index, self.weight, self.raster_depth, lab, V, self.gap, self.depth, self.labels, self.hits, self.source, self.count,
+             self.agree, self.wins)
+        return self.depth, self.labels, self.source
+
+    def valid(self):
+        """``source > 0`` as uint8 [R, S, S] in a static buffer: the tensor ``RefineBatch(mask=)`` takes (no allocation, nothing read back)"""
+        return self._valid.copy_(self.source).clamp_(max=1)

@@ -1185,6 +1185,36 @@ int sln_reproject_faces(const SlnReproject* d, float* faces_xyz, void* stream);
  * 8-byte aligned. */
 int sln_reproject_compose(const int32_t* face_index, const float* weight, const float* raster_depth, const unsigned char* labels_src, int B,
                           int Hs, int Ws, int S, float* depth_out, unsigned char* labels_out, int64_t* hits, void* stream);
+/* Several observed frames per room (csrc/observed_fuse.hip; DESIGN §4 "Several observed frames per room").  R rooms, V frames per
+ * room: frame b = r * V + v is reprojected as above - sln_reproject_faces over B = R * V frames with a k_src, pose and labels_src of its
+ * own and the room's K_tgt, then sln_raster_forward with B = R * V.  From the rasterizer's maps (raster order) of the V frames of a
+ * room, per target pixel, into the planes' row order (sln_reproject_compose's row flip):
+ *   frame v CONTRIBUTES iff it is a hit by sln_reproject_compose's rule (face_index in [0, F), no NaN among the three weights) and its
+ *   rasterizer depth d_v is not a NaN.  The WINNER is the contributing frame of smallest d_v, walking v upwards with a strict <: equal
+ *   depths go to the lowest v.  This is the z-buffer rule: of several surfaces on one ray the target view sees the nearest; a frame that
+ *   saw a farther one looked past the nearer from elsewhere - it is occluded, not wrong.
+ *   depth_out  [R, S, S] float32  the winner's depth, bits untouched; -1.0f where no frame contributes
+ *   labels_out [R, S, S] uint8    the byte of the winner's labels_src at the winning face's corner of largest weight (ties: the lower
+ *                                 corner number - sln_reproject_compose's rule); 0 where no frame contributes.  A byte of 0 in the
+ *                                 winning frame stays 0: no other frame lends a label
+ *   source_out [R, S, S] uint8    1 + v of the winner, 0 without one
+ *   count_out  [R, S, S] uint8    the number of contributing frames
+ *   agree_out  [R, S, S] uint8    the number of contributing frames with !((d_v - dmin) > gap * dmin), dmin the winner's depth: one
+ *                                 float32 difference against one float32 product, sln_reproject_faces' depth-step test with the same
+ *                                 gap.  The winner counts itself
+ *   hits       [R] int64          the pixels with a winner
+ *   wins       [R, V] int64       the pixels each frame wins; their sum over v is hits
+ * hits and wins are integer sums: the same from call to call under either deterministic setting.  A room with fewer than V frames pads
+ * with frames whose k_src has fx = 0: they yield nothing.  With V = 1, depth_out, labels_out and hits are sln_reproject_compose's bit
+ * for bit.  source_out, count_out, agree_out and wins are optional (NULL: not computed, nothing written).  The weights of a frame are
+ * loaded only when it would become the nearest so far, and - for count_out / agree_out - for the NaN rule of the other in-range
+ * candidates.  Two or three launches (hits and wins are cleared first), no allocation, synchronisation, read-back or floating-point
+ * atomic: legal inside a stream capture.  Every index read from a map is compared with its range before it addresses anything.
+ * SLN_E_BADARG, nothing launched and nothing written: a null required pointer, R < 1, V < 1, V > 255, R * V > 65535, Hs < 2, Ws < 2,
+ * S < 1, S > 4096, F > 2^24, !(gap >= 0), hits or wins not 8-byte aligned, depth_out not 4-byte aligned. */
+int sln_reproject_fuse(const int32_t* face_index, const float* weight, const float* raster_depth, const unsigned char* labels_src, int R,
+                       int V, int Hs, int Ws, int S, float gap, float* depth_out, unsigned char* labels_out, unsigned char* source_out,
+                       unsigned char* count_out, unsigned char* agree_out, int64_t* hits, int64_t* wins, void* stream);
 
 /* =============================================================================================
  * The --draw_3d picture (render/render_room_color.py::render_test): a lit colour picture with hard shadows of the view the viewpoint
