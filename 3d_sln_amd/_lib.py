@@ -391,6 +391,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p]),
     "sln_reproject_fuse": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sln_observed_prefilter": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, C.c_void_p, c_f32p,
+                                         C.c_void_p, C.c_void_p]),
     "sln_draw3d_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "sln_draw3d": (C.c_int, [C.POINTER(SlnDraw3D), C.c_void_p, C.c_void_p, c_f32p, C.c_void_p]),
     "sln_mesh_split_mark": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -28,13 +28,15 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # mesh_retrieve: an argmin over float64 distances of float32 quotients - every product, difference and quotient rounds as numpy's
 # observed_target: the depth-hot planes of an observed target are meant to be the scene pass's bits (raster.hip's compose expressions)
 # mesh_split: marks, midpoints and the diagonal choice are held to the numpy restatement for equality (host/mesh_prep.py)
+# observed_prefilter: the harmonic mean of a block is a chain of double operations that round one by one, as torch's do
 # (shade_view.hip takes the default flags: its placement and projection are held to a tolerance, not to bits, and contraction stays on)
 # (observed_reproject.hip likewise: unprojection, pose and projection to a tolerance; its compose step only copies bits and bytes)
 # (observed_fuse.hip: copies bits and bytes; its one float decision, the agreement test, is written with __fsub_rn / __fmul_rn)
 PER_FILE = {"raster.hip": ["-ffp-contract=off"], "graph_build.hip": ["-ffp-contract=off"], "placement.hip": ["-ffp-contract=off"],
             "layout_iou.hip": ["-ffp-contract=off"], "spade_input.hip": ["-ffp-contract=off"], "layout_plot.hip": ["-ffp-contract=off"],
             "scene_pictures.hip": ["-ffp-contract=off"], "mesh_retrieve.hip": ["-ffp-contract=off"],
-            "observed_target.hip": ["-ffp-contract=off"], "mesh_split.hip": ["-ffp-contract=off"]}
+            "observed_target.hip": ["-ffp-contract=off"], "mesh_split.hip": ["-ffp-contract=off"],
+            "observed_prefilter.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -16,8 +16,10 @@ pixel out of the rasterizer's maps.
     view of a room row, and the source intrinsics under which a scene tensor's own planes are a frame of their own camera.
 
 A target pixel no face covers - a disocclusion, a cut at a depth step, the frame's border - reads "no reading" (-1, label 0);
-``RefineBatch(mask="readings")`` keeps such pixels out of the loss, and further frames of the room fill them (``ObservedFuser``).  There
-is no pre-filter when a frame is finer than the target; labels are never blended or voted, and V is ragged only by ``fx = 0`` padding.
+``RefineBatch(mask="readings")`` keeps such pixels out of the loss, and further frames of the room fill them (``ObservedFuser``).  A
+frame finer than the target is decimated in front of the route by an integer factor (``prefilter=``, ``ObservedPrefilter``,
+``prefilter_torch``, ``prefilter_factor``; csrc/observed_prefilter.hip; DESIGN §4 "Observed frames finer than the target"): depths and
+labels of two surfaces are never blended, and V is ragged only by ``fx = 0`` padding.
 """
 import numpy as np
 import torch
@@ -32,6 +34,7 @@ MAX_FACES = 1 << 24
 MAX_S = 4096
 MAX_B = 65535
 MAX_V = 255
+MAX_PREFILTER = 8
 # corner -> (row, column) offset inside the cell, per slot: (a, b, c) and (d, c, b)
 _DI = ((0, 1, 0), (1, 0, 1))
 _DJ = ((0, 0, 1), (1, 1, 0))
@@ -86,9 +89,81 @@ def scene_as_source(K_tgt, orig_size, S):
     return (torch.stack((K[..., 0, 0], K[..., 1, 1], K[..., 0, 2], K[..., 1, 2]), -1) * s).float().contiguous()
 
 
+def prefilter_factor(k_src, K_tgt, orig_size, S, fmax=MAX_PREFILTER):
+    """The largest decimation factor at which a coarse source pixel still subtends no more than a target pixel on the optical axis:
+    ``floor(min over frames of min(fx, fy) * orig_size / (S * max over rooms of max(K00, K11)))`` in float64, clamped to [1, fmax].
+    ``k_src`` [..., 4] (frames with fx <= 0 are padding and skipped), ``K_tgt`` [..., 3, 3].  The pose is not looked at: a camera much
+    nearer to a surface than the target view sees it finer still, and the caller may pass a larger factor."""
+    if not orig_size > 0 or int(S) < 1 or int(fmax) < 1 or int(fmax) > MAX_PREFILTER:
+        raise ValueError("orig_size > 0, S >= 1 and fmax in [1, %d] expected, got %r, %r, %r" % (MAX_PREFILTER, orig_size, S, fmax))
+    k = torch.as_tensor(k_src).detach().double().cpu().reshape(-1, 4)
+    K = torch.as_tensor(K_tgt).detach().double().cpu().reshape(-1, 3, 3)
+    k = k[k[:, 0] > 0]
+    if k.shape[0] == 0:
+        return 1
+    src = float(torch.minimum(k[:, 0], k[:, 1]).min())
+    tgt = float(torch.maximum(K[:, 0, 0], K[:, 1, 1]).max())
+    ratio = src * float(orig_size) / (float(int(S)) * tgt)
+    if not ratio >= 1.0:                                             # (a NaN, a coarser frame, a focal length that is not positive)
+        return 1
+    return int(min(float(int(fmax)), np.floor(ratio)))
+
+
+def _check_prefilter(f, Hs, Ws, gap=0.0):
+    if int(f) != f or f < 1 or f > MAX_PREFILTER or Hs < f or Ws < f or not gap >= 0:
+        raise ValueError("an integer factor in [1, %d], a frame of at least f x f pixels and gap >= 0 expected, got f = %r, Hs = %r, Ws = %r, "
+                         "gap = %r" % (MAX_PREFILTER, f, Hs, Ws, gap))
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # the definition in torch ops
 # ------------------------------------------------------------------------------------------------------------------------------
+def prefilter_torch(depth_src, labels_src, k_src, f, gap=0.05):
+    """csrc/observed_prefilter.hip in torch ops on the tensors' device (DESIGN §4 "Observed frames finer than the target"):
+    ``depth_src`` [B, Hs, Ws] float, ``labels_src`` [B, Hs, Ws] uint8, ``k_src`` [B, 4] -> (depth [B, Hs // f, Ws // f] float32, labels
+    uint8, k_out [B, 4] float32, counts [B, 3] int64: coarse pixels whose block is all members, with a reading but fewer members,
+    without a reading)."""
+    if depth_src.dim() != 3 or labels_src.shape != depth_src.shape or labels_src.dtype != torch.uint8 or tuple(k_src.shape) != (depth_src.shape[0], 4):
+        raise ValueError("depth_src [B, Hs, Ws] float, labels_src [B, Hs, Ws] uint8 and k_src [B, 4] expected")
+    B, Hs, Ws = depth_src.shape
+    _check_prefilter(f, Hs, Ws, gap)
+    f = int(f)
+    Hd, Wd, n = Hs // f, Ws // f, f * f
+    dev = depth_src.device
+    blocks = lambda t: t[:, :f * Hd, :f * Wd].reshape(B, Hd, f, Wd, f).permute(0, 1, 3, 2, 4).reshape(B, Hd, Wd, n)   # row-major inside the block
+    d, lab = blocks(depth_src.float()), blocks(labels_src).long()
+    reading = (d > 0) & (d <= FAR)
+    r = reading.sum(-1)
+    has = 2 * r >= n
+    inf = torch.full((), float("inf"), dtype=torch.float32, device=dev)
+    ranked = torch.sort(torch.where(reading, d, inf), -1).values                                  # the readings in ascending order, then inf
+    dref = torch.gather(ranked, -1, ((r - 1).clamp(min=0) // 2)[..., None])                       # the lower median
+    hi, lo = torch.maximum(d, dref), torch.minimum(d, dref)
+    member = reading & ~((hi - lo) > torch.tensor(gap, dtype=torch.float32, device=dev) * lo)      # float32, the face kernel's test
+    m = member.sum(-1)
+    total = torch.zeros(B, Hd, Wd, dtype=torch.float64, device=dev)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    for t in range(n):                                               # row-major order of the block, one rounded addition each
+        total = total + torch.where(member[..., t], 1.0 / d[..., t].double(), zero)
+    depth = torch.where(has, (m.double() / total).float(), torch.zeros((), dtype=torch.float32, device=dev))
+    votes = torch.zeros(B, Hd, Wd, n, dtype=torch.long, device=dev)
+    for u in range(n):                                               # votes[t]: the members that carry pixel t's byte
+        votes += (member[..., u, None] & (lab[..., u, None] == lab)).long()
+    key = torch.where(member, votes * 256 + (255 - lab), torch.full((), -1, dtype=torch.long, device=dev))    # most votes, then the smallest byte
+    labels = torch.where(has, 255 - key.max(-1).values % 256, torch.zeros((), dtype=torch.long, device=dev)).to(torch.uint8)
+    counts = torch.stack(((has & (m == n)).sum(dim=(1, 2)), (has & (m < n)).sum(dim=(1, 2)), (~has).sum(dim=(1, 2))), 1)
+    k_out = k_src.float() / torch.tensor(float(f), dtype=torch.float32, device=k_src.device)
+    return depth.contiguous(), labels.contiguous(), k_out.contiguous(), counts
+
+
+def _prefiltered(depth_src, labels_src, k_src, prefilter, gap):
+    """the frames a torch route goes on with: themselves at ``prefilter`` 1 (not filtered: non-readings pass to the face step as they are)"""
+    _check_prefilter(prefilter, *depth_src.shape[-2:])
+    if int(prefilter) == 1:
+        return depth_src, labels_src, k_src
+    return prefilter_torch(depth_src, labels_src, k_src, prefilter, gap)[:3]
+
+
 def faces_torch(depth_src, k_src, pose, K_tgt, orig_size, near=0.1, gap=0.05, dtype=torch.float64):
     """csrc/observed_reproject.hip's first kernel in torch ops, in ``dtype``: -> faces_xyz [B, F, 3, 3].  The two decisions on the
     source depths (reading, depth step) are float32 operations in either precision: they are part of the definition."""
@@ -195,13 +270,16 @@ def fuse_torch(face_index, weight, raster_depth, labels_src, V, gap=0.05):
                 count=flip(count, torch.uint8), agree=flip(agree, torch.uint8), hits=(best >= 0).sum(dim=(1, 2)), wins=wins)
 
 
-def reproject_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near=0.1, far=100.0, gap=0.05, dtype=torch.float64):
+def reproject_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near=0.1, far=100.0, gap=0.05, dtype=torch.float64,
+                    prefilter=1):
     """The route of ``ObservedReprojector`` in torch ops on the tensors' device, in ``dtype``.  ``rasterize(faces float32 numpy
     [B, F, 3, 3], image_size, near, far) -> (face_index, weight, depth)`` numpy maps in raster order is the caller's rasterizer (the
     tests pass the C restatement the rasterizer kernels are held to).  -> dict(depth [B, S, S] float32, labels [B, S, S] uint8,
-    hits [B] int64, faces_xyz [B, F, 3, 3] in ``dtype``, face_index, weight)"""
+    hits [B] int64, faces_xyz [B, F, 3, 3] in ``dtype``, face_index, weight).  With ``prefilter`` f > 1 the frames go through
+    ``prefilter_torch`` first and everything else runs on the coarse frames: F is that of Hs // f x Ws // f."""
     if depth_src.dim() != 3 or labels_src.shape != depth_src.shape or labels_src.dtype != torch.uint8:
         raise ValueError("depth_src [B, Hs, Ws] float and labels_src [B, Hs, Ws] uint8 expected")
+    depth_src, labels_src, k_src = _prefiltered(depth_src, labels_src, k_src, prefilter, gap)
     B, Hs, Ws = depth_src.shape
     _check_sizes(B, Hs, Ws, int(S))
     dev = depth_src.device
@@ -219,22 +297,26 @@ def _check_views(R, V, Hs, Ws, S):
 
 
 def reproject_views_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near=0.1, far=100.0, gap=0.05,
-                          dtype=torch.float64):
+                          dtype=torch.float64, prefilter=1):
     """The route of ``ObservedFuser`` in torch ops on the tensors' device, in ``dtype``: ``reproject_torch``'s counterpart for V frames
     per room.  ``depth_src`` [R, V, Hs, Ws] float, ``labels_src`` [R, V, Hs, Ws] uint8, ``k_src`` [R, V, 4], ``pose`` [R, V, 3, 4],
     ``K_tgt`` [R, 3, 3] (the room's); ``rasterize`` as in ``reproject_torch``.  -> the dict of ``fuse_torch`` plus faces_xyz
-    [R * V, F, 3, 3] in ``dtype`` and the maps face_index, weight, raster_depth [R * V, S, S(, 3)]"""
+    [R * V, F, 3, 3] in ``dtype`` and the maps face_index, weight, raster_depth [R * V, S, S(, 3)].  ``prefilter`` as in
+    ``reproject_torch``."""
     if depth_src.dim() != 4 or labels_src.shape != depth_src.shape or labels_src.dtype != torch.uint8:
         raise ValueError("depth_src [R, V, Hs, Ws] float and labels_src [R, V, Hs, Ws] uint8 expected")
-    R, V, Hs, Ws = depth_src.shape
-    _check_views(R, V, Hs, Ws, int(S))
+    R, V = depth_src.shape[:2]
     if tuple(k_src.shape) != (R, V, 4) or tuple(pose.shape) != (R, V, 3, 4) or tuple(K_tgt.shape) != (R, 3, 3):
         raise ValueError("k_src [R, V, 4], pose [R, V, 3, 4] and K_tgt [R, 3, 3] expected")
+    if R < 1 or V < 1:
+        raise ValueError("rooms >= 1 and views in [1, 255] expected, got rooms = %r, views = %r" % (R, V))
     dev = depth_src.device
     B = R * V
-    lab = labels_src.reshape(B, Hs, Ws)
-    fxyz = faces_torch(depth_src.reshape(B, Hs, Ws), k_src.reshape(B, 4), pose.reshape(B, 3, 4), K_tgt.repeat_interleave(V, 0), orig_size,
-                       near, gap, dtype)
+    flat, lab, k_flat = _prefiltered(depth_src.reshape(B, *depth_src.shape[2:]), labels_src.reshape(B, *depth_src.shape[2:]), k_src.reshape(B, 4),
+                                     prefilter, gap)
+    Hs, Ws = flat.shape[1:]
+    _check_views(R, V, Hs, Ws, int(S))
+    fxyz = faces_torch(flat, k_flat, pose.reshape(B, 3, 4), K_tgt.repeat_interleave(V, 0), orig_size, near, gap, dtype)
     fi, w, dep = rasterize(fxyz.float().cpu().numpy(), int(S), float(near), float(far))
     fi, w, dep = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (fi, w, dep))
     out = fuse_torch(fi, w, dep, lab, V, gap)
@@ -267,6 +349,67 @@ def compose(face_index, weight, raster_depth, labels_src, depth_out, labels_out,
             "sln_reproject_compose")
 
 
+def prefilter(depth_src, labels_src, k_src, f, gap, depth_out, labels_out, k_out, counts=None):
+    """the bare ``sln_observed_prefilter`` call over the caller's buffers (contiguous, on the device); ``counts`` [B, 3] int64 is optional"""
+    B, Hs, Ws = (int(x) for x in depth_src.shape)
+    L.check(L.lib().sln_observed_prefilter(L.ptr(depth_src), L.ptr(labels_src), L.ptr(k_src), B, Hs, Ws, int(f), float(gap), L.ptr(depth_out),
+                                           L.ptr(labels_out), L.ptr(k_out), L.ptr(counts), _stream(depth_out)), "sln_observed_prefilter")
+
+
+class ObservedPrefilter:
+    """``batch`` frames of ``Hs`` x ``Ws`` decimated by the integer factor ``f`` on the device, in front of the reprojection (DESIGN §4
+    "Observed frames finer than the target"; ``prefilter_factor`` chooses ``f``).
+
+        pf = ObservedPrefilter(480, 640, 2, batch=16)
+        depth, labels, k_out = pf(depth_src, labels_src, k_src)          # [16, 240, 320], [16, 240, 320], [16, 4]
+
+    A coarse pixel takes the harmonic mean of the readings of its f x f block that lie on the surface of the block's lower median
+    depth, and those readings' most frequent label; it has no reading (0.0, label 0) when fewer than half the block's pixels have one.
+    ``counts`` [B, 3] int64 (blocks that are all one surface, blocks with a reading otherwise, blocks without) is an attribute.  The
+    outputs are the instance's static buffers.  A call is two launches on the current stream, allocates nothing and reads nothing
+    back: legal under a graph capture.  Tensors of another dtype, device or shape are refused before anything is launched."""
+
+    def __init__(self, Hs, Ws, f, batch=1, gap=0.05, device="cuda"):
+        self.Hs, self.Ws, self.batch, self.gap = int(Hs), int(Ws), int(batch), float(gap)
+        _check_prefilter(f, self.Hs, self.Ws, self.gap)
+        self.f = int(f)
+        if self.batch < 1 or self.batch > MAX_B:
+            raise ValueError("batch in [1, 65535] expected, got %r" % (batch,))
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.SlnError("ObservedPrefilter runs on the MI355X only (no CPU fallback); prefilter_torch restates it for CPU tensors")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        B, dev = self.batch, self.device
+        self.Hd, self.Wd = self.Hs // self.f, self.Ws // self.f
+        self.depth = torch.empty(B, self.Hd, self.Wd, dtype=torch.float32, device=dev)
+        self.labels = torch.empty(B, self.Hd, self.Wd, dtype=torch.uint8, device=dev)
+        self.k_out = torch.empty(B, 4, dtype=torch.float32, device=dev)
+        self.counts = torch.zeros(B, 3, dtype=torch.int64, device=dev)
+
+    def check(self, depth_src, labels_src, k_src):
+        """raises ValueError before anything is launched; reads the instance's sizes and device only"""
+        B, dev = self.batch, self.device
+        for t, dt, shape, what in ((depth_src, torch.float32, (B, self.Hs, self.Ws), "depth_src"), (labels_src, torch.uint8, (B, self.Hs, self.Ws), "labels_src"),
+                                   (k_src, torch.float32, (B, 4), "k_src")):
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != dev:
+                raise ValueError("%s: a %s tensor on %s expected" % (what, str(dt).replace("torch.", ""), dev))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s: shape %s is not a contiguous %s" % (what, tuple(t.shape), list(shape)))
+
+    def __call__(self, depth_src, labels_src, k_src):
+        self.check(depth_src, labels_src, k_src)
+        prefilter(depth_src, labels_src, k_src, self.f, self.gap, self.depth, self.labels, self.k_out, self.counts)
+        return self.depth, self.labels, self.k_out
+
+
+def _coarse(prefilter_, Hs, Ws):
+    """the size of the frames the face step sees under ``prefilter=``: -> (f, Hd, Wd)"""
+    _check_prefilter(prefilter_, Hs, Ws)
+    f = int(prefilter_)
+    return f, Hs // f, Ws // f
+
+
 class ObservedReprojector:
     """Frames of ``batch`` rooms, each ``Hs`` x ``Ws``, brought into target views of ``S`` x ``S`` on the device.
 
@@ -280,18 +423,24 @@ class ObservedReprojector:
     ``K_tgt`` [B, 3, 3] float32 and ``orig_size`` (``refine_view``).  -> ``depth`` [B, S, S] float32 (-1 where no face was hit),
     ``labels`` [B, S, S] uint8, ``hits`` [B] int64 (hit pixels per frame).  These are the instance's static buffers: the next call
     overwrites them.  A call makes three steps of launches (faces, raster, compose) on the current stream, allocates nothing and reads
-    nothing back: legal under a graph capture.  Tensors of another dtype, device or shape are refused before anything is launched."""
+    nothing back: legal under a graph capture.  Tensors of another dtype, device or shape are refused before anything is launched.
 
-    def __init__(self, Hs, Ws, S, batch=1, near=0.1, far=100.0, gap=0.05, device="cuda"):
+    ``prefilter`` f > 1 (``prefilter_factor``) puts an ``ObservedPrefilter`` in front, as ``self.pre``: the three steps then run on
+    frames of ``Hs // f`` x ``Ws // f`` (at least 2 x 2) with f * f times fewer faces, and ``labels`` are gathered from the coarse
+    labels.  With 1, the default, the filter is not run."""
+
+    def __init__(self, Hs, Ws, S, batch=1, near=0.1, far=100.0, gap=0.05, device="cuda", prefilter=1):
         self.Hs, self.Ws, self.S, self.batch = int(Hs), int(Ws), int(S), int(batch)
         self.near, self.far, self.gap = float(near), float(far), float(gap)
-        _check_sizes(self.batch, self.Hs, self.Ws, self.S)
+        self.prefilter, self.Hd, self.Wd = _coarse(prefilter, self.Hs, self.Ws)
+        _check_sizes(self.batch, self.Hd, self.Wd, self.S)
         _check_scalars(1.0, self.near, self.gap)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise L.SlnError("ObservedReprojector runs on the MI355X only (no CPU fallback); reproject_torch restates it for CPU tensors")
         B, S, dev = self.batch, self.S, self.device
-        self.F = n_faces(self.Hs, self.Ws)
+        self.pre = ObservedPrefilter(self.Hs, self.Ws, self.prefilter, B, self.gap, dev) if self.prefilter > 1 else None
+        self.F = n_faces(self.Hd, self.Wd)
         self.faces_xyz = torch.zeros(B, self.F, 3, 3, dtype=torch.float32, device=dev)
         self.face_index = torch.empty(B, S, S, dtype=torch.int32, device=dev)
         self.weight = torch.empty(B, S, S, 3, dtype=torch.float32, device=dev)
@@ -313,6 +462,8 @@ class ObservedReprojector:
 
     def __call__(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
         self.check(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
+        if self.pre is not None:
+            depth_src, labels_src, k_src = self.pre(depth_src, labels_src, k_src)
         faces(depth_src, k_src, pose, K_tgt, orig_size, self.near, self.gap, self.faces_xyz)
         L.check(L.lib().sln_raster_forward(L.ptr(self.faces_xyz), self.batch, self.F, self.S, self.near, self.far, L.ptr(self._raster_ws),
                                            L.ptr(self.face_index), L.ptr(self.weight), L.ptr(self.raster_depth), L.current_stream_ptr()),
@@ -351,12 +502,14 @@ class ObservedFuser:
     are attributes.  All are the instance's static buffers: the next call overwrites them.  A call spreads ``K_tgt`` over the frames
     with one ``copy_`` and makes three steps of launches (faces and raster over R * V frames, the fused compose) on the current stream,
     allocates nothing and reads nothing back: legal under a graph capture.  Tensors of another dtype, device or shape are refused
-    before anything is launched."""
+    before anything is launched.  ``prefilter`` f > 1 as in ``ObservedReprojector``: one ``ObservedPrefilter`` over the R * V frames
+    (``self.pre``) in front, everything else on frames of ``Hs // f`` x ``Ws // f``."""
 
-    def __init__(self, Hs, Ws, S, rooms=1, views=1, near=0.1, far=100.0, gap=0.05, device="cuda"):
+    def __init__(self, Hs, Ws, S, rooms=1, views=1, near=0.1, far=100.0, gap=0.05, device="cuda", prefilter=1):
         self.Hs, self.Ws, self.S, self.rooms, self.views = int(Hs), int(Ws), int(S), int(rooms), int(views)
         self.near, self.far, self.gap = float(near), float(far), float(gap)
-        _check_views(self.rooms, self.views, self.Hs, self.Ws, self.S)
+        self.prefilter, self.Hd, self.Wd = _coarse(prefilter, self.Hs, self.Ws)
+        _check_views(self.rooms, self.views, self.Hd, self.Wd, self.S)
         _check_scalars(1.0, self.near, self.gap)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -365,7 +518,8 @@ class ObservedFuser:
             self.device = torch.device("cuda", torch.cuda.current_device())
         R, V, S, dev = self.rooms, self.views, self.S, self.device
         B = self.batch = R * V
-        self.F = n_faces(self.Hs, self.Ws)
+        self.pre = ObservedPrefilter(self.Hs, self.Ws, self.prefilter, B, self.gap, dev) if self.prefilter > 1 else None
+        self.F = n_faces(self.Hd, self.Wd)
         self.K_frames = torch.zeros(B, 3, 3, dtype=torch.float32, device=dev)
         self.faces_xyz = torch.zeros(B, self.F, 3, 3, dtype=torch.float32, device=dev)
         self.face_index = torch.empty(B, S, S, dtype=torch.int32, device=dev)
@@ -392,8 +546,10 @@ class ObservedFuser:
         self.check(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
         R, V, B = self.rooms, self.views, self.batch
         self.K_frames.view(R, V, 3, 3).copy_(K_tgt[:, None])
-        lab = labels_src.view(B, self.Hs, self.Ws)
-        faces(depth_src.view(B, self.Hs, self.Ws), k_src.view(B, 4), pose.view(B, 3, 4), self.K_frames, orig_size, self.near, self.gap, self.faces_xyz)
+        dep, lab, k = depth_src.view(B, self.Hs, self.Ws), labels_src.view(B, self.Hs, self.Ws), k_src.view(B, 4)
+        if self.pre is not None:
+            dep, lab, k = self.pre(dep, lab, k)
+        faces(dep, k, pose.view(B, 3, 4), self.K_frames, orig_size, self.near, self.gap, self.faces_xyz)
         L.check(L.lib().sln_raster_forward(L.ptr(self.faces_xyz), B, self.F, self.S, self.near, self.far, L.ptr(self._raster_ws),
                                            L.ptr(self.face_index), L.ptr(self.weight), L.ptr(self.raster_depth), L.current_stream_ptr()),
                 "sln_raster_forward")

@@ -1215,6 +1215,29 @@ int sln_reproject_compose(const int32_t* face_index, const float* weight, const 
 int sln_reproject_fuse(const int32_t* face_index, const float* weight, const float* raster_depth, const unsigned char* labels_src, int R,
                        int V, int Hs, int Ws, int S, float gap, float* depth_out, unsigned char* labels_out, unsigned char* source_out,
                        unsigned char* count_out, unsigned char* agree_out, int64_t* hits, int64_t* wins, void* stream);
+/* An observed frame finer than the target, decimated by an integer factor f in [1, 8] in front of sln_reproject_faces
+ * (csrc/observed_prefilter.hip; DESIGN §4 "Observed frames finer than the target").  B frames, all device pointers: depth_src
+ * [B, Hs, Ws] float32 (a READING iff 0 < d <= 15), labels_src [B, Hs, Ws] uint8 (any byte), k_src [B, 4].  Hd = Hs / f, Wd = Ws / f
+ * (integer division); coarse pixel (I, J) owns the n = f * f source pixels [f I, f I + f) x [f J, f J + f); the rows and columns
+ * behind f Hd, f Wd are not read.  With r the number of readings of the block:
+ *   2 r < n:   depth_out = 0.0f, labels_out = 0 (no reading: the majority of the area says nothing).  Otherwise
+ *   dref       the lower median of the block's readings, rank (r - 1) / 2 in ascending order
+ *   MEMBERS    the readings d with !((max(d, dref) - min(d, dref)) > gap * min(d, dref)): one float32 difference against one float32
+ *              product, sln_reproject_faces' depth-step test; m >= 1 of them
+ *   depth_out  [B, Hd, Wd] float32  (float)((double)m / sum), sum adding 1.0 / (double)d over the members in row-major order of the
+ *                                   block, every operation a correctly rounded double operation: the harmonic mean - exact at the
+ *                                   block's centre on a plane, never a blend of two surfaces
+ *   labels_out [B, Hd, Wd] uint8    the most frequent byte among the members, ties to the smallest byte; 0 competes like any other
+ *   k_out      [B, 4] float32       k_src / (float)f, four float32 divisions: the exact pinhole of the coarse grid
+ *   counts     [B, 3] int64         coarse pixels with m == n, with a reading and m < n, without a reading; or NULL
+ * With f = 1 a reading keeps its bits and everything else becomes 0.0f with label 0.  One launch, and a zero-fill launch in front when
+ * counts is given; counts are integer sums: the same from call to call under either deterministic setting.  No allocation,
+ * synchronisation, read-back or floating-point atomic: legal inside a stream capture.  Every index is formed from the sizes given
+ * here.  SLN_E_BADARG, nothing launched and nothing written: a null required pointer, B < 1, B > 65535, f < 1, f > 8, Hs < f, Ws < f,
+ * !(gap >= 0), counts not 8-byte aligned, depth_src, depth_out, k_src or k_out not 4-byte aligned, more than 2^31 - 1 tiles of
+ * 32 x 2 coarse pixels in a frame. */
+int sln_observed_prefilter(const float* depth_src, const unsigned char* labels_src, const float* k_src, int B, int Hs, int Ws, int f,
+                           float gap, float* depth_out, unsigned char* labels_out, float* k_out, int64_t* counts, void* stream);
 
 /* =============================================================================================
  * The --draw_3d picture (render/render_room_color.py::render_test): a lit colour picture with hard shadows of the view the viewpoint
