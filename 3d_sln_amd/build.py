@@ -31,7 +31,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # observed_prefilter: the harmonic mean of a block is a chain of double operations that round one by one, as torch's do
 # (shade_view.hip takes the default flags: its placement and projection are held to a tolerance, not to bits, and contraction stays on)
 # (observed_reproject.hip likewise: unprojection, pose and projection to a tolerance; its compose step only copies bits and bytes)
-# (observed_fuse.hip: copies bits and bytes; its one float decision, the agreement test, is written with __fsub_rn / __fmul_rn)
+# (observed_fuse.hip: copies bits and bytes; its one float decision, the agreement test, is observed_rules.h's depth-step test)
+# (observed_rules.h is included by units of either setting: its float decisions are written with __fsub_rn / __fmul_rn, single rounded
+# operations whatever the flag)
 PER_FILE = {"raster.hip": ["-ffp-contract=off"], "graph_build.hip": ["-ffp-contract=off"], "placement.hip": ["-ffp-contract=off"],
             "layout_iou.hip": ["-ffp-contract=off"], "spade_input.hip": ["-ffp-contract=off"], "layout_plot.hip": ["-ffp-contract=off"],
             "scene_pictures.hip": ["-ffp-contract=off"], "mesh_retrieve.hip": ["-ffp-contract=off"],

@@ -14,23 +14,21 @@
 //                              `agree` are defined over CONTRIBUTING frames the weights of every in-range candidate other than the
 //                              winner are loaded here for the NaN rule - the one place a losing frame's weights are read.
 //
-// hits: ballot + popcount per wavefront, one 64-bit integer atomic per workgroup, as reproject_compose_kernel.  wins: an LDS array of V
+// hits: observed_rules.h's workgroup count, as reproject_compose_kernel; so are the hit rule and the label gather.  wins: an LDS array of V
 // integer counters per workgroup, one 64-bit integer atomic per non-zero counter.  Integer sums only: the same from call to call.  No
 // allocation, synchronisation, read-back or floating-point atomic.  Every index read from a map is compared with its range before it
-// addresses anything.  The agreement test is the face kernel's depth-step test, one rounded difference against one rounded product
-// (__fsub_rn / __fmul_rn: contraction cannot fuse them); everything else copies bits and bytes, so the unit takes the default flags.
+// addresses anything.  The agreement test is the face kernel's depth-step test (observed_rules.h: one rounded difference against one
+// rounded product, which contraction cannot fuse); everything else copies bits and bytes, so the unit takes the default flags.
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "observed_rules.h"
 #include "sln_common.h"
 #include "sln_hip.h"
 
 namespace {
 
 constexpr int IN_FLIGHT = 4;               // frames whose face_index and depth are loaded before the first of them is looked at
-constexpr int MAX_V = 255;                 // `source` is a byte: 1 + v
-
-__device__ __forceinline__ bool any_nan(float a, float b, float c) { return a != a || b != b || c != c; }
 
 __global__ __launch_bounds__(256) void reproject_fuse_kernel(const int32_t* __restrict__ fi, const float* __restrict__ weight,
                                                              const float* __restrict__ depth, const unsigned char* __restrict__ labels_src,
@@ -38,12 +36,11 @@ __global__ __launch_bounds__(256) void reproject_fuse_kernel(const int32_t* __re
                                                              unsigned char* __restrict__ lout, unsigned char* __restrict__ src,
                                                              unsigned char* __restrict__ cnt, unsigned char* __restrict__ agr,
                                                              unsigned long long* __restrict__ hits, unsigned long long* __restrict__ wins) {
-  __shared__ int wcnt[MAX_V + 1];
-  __shared__ int red[4];
+  __shared__ int wcnt[OBS_MAX_VIEWS + 1];
   const int r = blockIdx.y;
   const long n = (long)S * S;
   const long room = (long)r * V * n;                               // the room's first frame in the maps
-  const int Wc = Ws - 1, F = 2 * (Hs - 1) * Wc;
+  const int F = obs_n_faces(Hs, Ws);
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (wins)
     for (int v = threadIdx.x; v < V; v += 256) wcnt[v] = 0;
@@ -65,11 +62,11 @@ __global__ __launch_bounds__(256) void reproject_fuse_kernel(const int32_t* __re
       }
 #pragma unroll
       for (int j = 0; j < IN_FLIGHT; ++j) {
-        if (k[j] < 0 || k[j] >= F || d[j] != d[j]) continue;
+        if (!obs_face_in_range(k[j], F) || d[j] != d[j]) continue;
         if (best >= 0 && !(d[j] < dmin)) continue;                 // strict: equal depths stay with the lower v
         const float* w = weight + 3 * (room + (long)(v0 + j) * n + p);
         const float a = w[0], b = w[1], c = w[2];
-        if (any_nan(a, b, c)) continue;                            // not a hit: the previous best stands
+        if (obs_any_nan(a, b, c)) continue;                        // not a hit: the previous best stands
         best = v0 + j; dmin = d[j]; kbest = k[j]; w0 = a; w1 = b; w2 = c;
       }
     }
@@ -77,17 +74,10 @@ __global__ __launch_bounds__(256) void reproject_fuse_kernel(const int32_t* __re
     float z = -1.0f;
     int count = 0, agree = 0;
     if (best >= 0) {
-      int corner = w1 > w0 ? 1 : 0;                                // ties go to the lower corner number
-      if (w2 > (corner ? w1 : w0)) corner = 2;
-      const int cell = kbest >> 1, which = kbest & 1;
-      const int ci = cell / Wc, cj = cell - ci * Wc;               // kbest < F: ci < Hs - 1, cj < Ws - 1
-      // slot 0: a (0, 0), b (1, 0), c (0, 1); slot 1: d (1, 1), c (0, 1), b (1, 0)
-      const int di = which ? (corner == 1 ? 0 : 1) : (corner == 1 ? 1 : 0);
-      const int dj = which ? (corner == 2 ? 0 : 1) : (corner == 2 ? 1 : 0);
-      lab = labels_src[(((long)r * V + best) * Hs + ci + di) * Ws + cj + dj];
+      lab = labels_src[obs_label_index((long)r * V + best, kbest, w0, w1, w2, Hs, Ws)];
       z = dmin;
       if (cnt || agr) {
-        const float edge = __fmul_rn(gap, dmin);
+        const float edge = obs_step_edge(gap, dmin);
         for (int v0 = 0; v0 < V; v0 += IN_FLIGHT) {
           int k[IN_FLIGHT];
           float d[IN_FLIGHT];
@@ -100,13 +90,13 @@ __global__ __launch_bounds__(256) void reproject_fuse_kernel(const int32_t* __re
           }
 #pragma unroll
           for (int j = 0; j < IN_FLIGHT; ++j) {
-            if (k[j] < 0 || k[j] >= F || d[j] != d[j]) continue;
+            if (!obs_face_in_range(k[j], F) || d[j] != d[j]) continue;
             if (v0 + j != best) {                                  // the NaN rule of a candidate that did not win
               const float* w = weight + 3 * (room + (long)(v0 + j) * n + p);
-              if (any_nan(w[0], w[1], w[2])) continue;
+              if (obs_any_nan(w[0], w[1], w[2])) continue;
             }
             ++count;
-            agree += !(__fsub_rn(d[j], dmin) > edge) ? 1 : 0;
+            agree += !(obs_step_rise(d[j], dmin) > edge) ? 1 : 0;
           }
         }
       }
@@ -119,13 +109,7 @@ __global__ __launch_bounds__(256) void reproject_fuse_kernel(const int32_t* __re
     if (agr) agr[q] = (unsigned char)agree;
     if (wins && best >= 0) atomicAdd(&wcnt[best], 1);
   }
-  const int c = __popcll(__ballot(best >= 0));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int s = red[0] + red[1] + red[2] + red[3];
-    if (s) atomicAdd(hits + r, (unsigned long long)s);             // (integers: the total does not depend on the order)
-  }
+  obs_count_flags(best >= 0, hits + r);                            // (its barrier also orders the wcnt updates before the reads below)
   if (wins)
     for (int v = threadIdx.x; v < V; v += 256)
       if (wcnt[v]) atomicAdd(wins + (long)r * V + v, (unsigned long long)wcnt[v]);
@@ -139,8 +123,7 @@ int sln_reproject_fuse(const int32_t* face_index, const float* weight, const flo
                        int V, int Hs, int Ws, int S, float gap, float* depth_out, unsigned char* labels_out, unsigned char* source_out,
                        unsigned char* count_out, unsigned char* agree_out, int64_t* hits, int64_t* wins, void* stream) {
   if (!face_index || !weight || !raster_depth || !labels_src || !depth_out || !labels_out || !hits) return SLN_E_BADARG;
-  if (R < 1 || V < 1 || V > MAX_V || (long)R * V > 65535 || Hs < 2 || Ws < 2 || S < 1 || S > 4096) return SLN_E_BADARG;
-  if (2L * (Hs - 1) * (Ws - 1) > (1L << 24)) return SLN_E_BADARG;
+  if (R < 1 || !obs_views_ok(V) || obs_check_frames((long)R * V, Hs, Ws) || !obs_target_ok(S)) return SLN_E_BADARG;
   if (!(gap >= 0.f)) return SLN_E_BADARG;
   if ((reinterpret_cast<uintptr_t>(hits) & 7) || (reinterpret_cast<uintptr_t>(wins) & 7) || (reinterpret_cast<uintptr_t>(depth_out) & 3))
     return SLN_E_BADARG;

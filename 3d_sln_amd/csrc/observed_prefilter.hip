@@ -20,18 +20,17 @@
 // k_out: lanes 0 .. 3 of the frame's first workgroup.  counts: ballots and popcounts, one 64-bit integer atomic per workgroup and
 // non-zero counter.  No allocation, synchronisation, read-back or floating-point atomic; every index is formed from the launch's own
 // sizes - no address depends on data.  Built with -ffp-contract=off: the harmonic mean is a chain of correctly rounded double
-// operations; the member test is written with __fsub_rn / __fmul_rn besides.
+// operations; the member test is observed_rules.h's depth-step test, which rounds each operation under either flag.
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "observed_rules.h"
 #include "sln_common.h"
 #include "sln_hip.h"
 
 namespace {
 
 constexpr int TW = 32, TH = 2, LANES = TW * TH;   // coarse pixels per workgroup: one wavefront
-constexpr float FAR_READING = 15.0f;               // observe.FAR
-constexpr int MAX_F = 8;
 
 template <int F>
 __global__ __launch_bounds__(LANES) void observed_prefilter_kernel(const float* __restrict__ depth_src, const unsigned char* __restrict__ labels_src,
@@ -79,7 +78,9 @@ __global__ __launch_bounds__(LANES) void observed_prefilter_kernel(const float* 
       if (cc < 0 || cc >= cols) continue;
       const int tx = cc / F, j = cc - tx * F;
       const int to = (i * F + j) * LANES + ty * TW + tx;
-      sd[to] = (d[t] > 0.f && d[t] <= FAR_READING) ? d[t] : 0.f;     // (a NaN fails both comparisons)
+      // obs_reading(d[t]), spelled out: through the helper hipcc selects on the inverted condition - other code for the same work,
+      // which would have to be timed again; written here the kernels keep their code (LAB_NOTES §37)
+      sd[to] = (d[t] > 0.f && d[t] <= OBS_FAR) ? d[t] : 0.f;
       sl[to] = l[t];
     }
   }
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(LANES) void observed_prefilter_kernel(const float* 
         const float d = my_d[t * LANES];
         if (!(d > 0.f)) continue;
         const float hi = fmaxf(d, dref), lo = fminf(d, dref);
-        if (__fsub_rn(hi, lo) > __fmul_rn(gap, lo)) continue;        // the face kernel's depth-step test: another surface
+        if (obs_depth_step(hi, lo, gap)) continue;                   // another surface
         member |= 1ull << t;
         sum += 1.0 / (double)d;
         ++m;
@@ -163,7 +164,7 @@ extern "C" {
 int sln_observed_prefilter(const float* depth_src, const unsigned char* labels_src, const float* k_src, int B, int Hs, int Ws, int f, float gap,
                            float* depth_out, unsigned char* labels_out, float* k_out, int64_t* counts, void* stream) {
   if (!depth_src || !labels_src || !k_src || !depth_out || !labels_out || !k_out) return SLN_E_BADARG;
-  if (B < 1 || B > 65535 || f < 1 || f > MAX_F || Hs < f || Ws < f) return SLN_E_BADARG;
+  if (!obs_batch_ok(B) || f < 1 || f > OBS_MAX_PREFILTER || Hs < f || Ws < f) return SLN_E_BADARG;
   if (!(gap >= 0.f)) return SLN_E_BADARG;
   if ((reinterpret_cast<uintptr_t>(counts) & 7) || (reinterpret_cast<uintptr_t>(depth_out) & 3) || (reinterpret_cast<uintptr_t>(depth_src) & 3) ||
       (reinterpret_cast<uintptr_t>(k_src) & 3) || (reinterpret_cast<uintptr_t>(k_out) & 3))

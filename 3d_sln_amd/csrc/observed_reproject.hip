@@ -19,13 +19,13 @@
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "observed_rules.h"
 #include "sln_common.h"
 #include "sln_hip.h"
 
 namespace {
 
 constexpr float PROJ_EPS = 1e-9f;          // sln_project_faces' eps as host/neural_renderer.py passes it
-constexpr float READING_FAR = 15.0f;       // host/observe.py: FAR
 constexpr int TILE = 16;                   // cells per tile edge; TILE + 1 vertices
 constexpr int TV = TILE + 1;
 constexpr int CELL_FLOATS = 18;            // two slots of three corners
@@ -50,7 +50,7 @@ __device__ __forceinline__ Frame load_frame(const SlnReproject& d, int b) {
 
 // (x_ndc, y_ndc, z_cam, source depth) of the vertex at pixel (i, j); w = 0 marks a pixel without a reading
 __device__ __forceinline__ float4 make_vertex(const Frame& f, int i, int j, float dep) {
-  const bool reading = dep > 0.f && dep <= READING_FAR;          // (a NaN has none)
+  const bool reading = obs_reading(dep);
   const float xs = ((float)j + 0.5f - f.cx) / f.fx * dep;
   const float ys = ((float)i + 0.5f - f.cy) / f.fy * dep;
   const float x = xs * f.P[0] + ys * f.P[1] + dep * f.P[2] + f.P[3];
@@ -66,7 +66,7 @@ __device__ __forceinline__ float4 make_vertex(const Frame& f, int i, int j, floa
 __device__ __forceinline__ void make_slot(const Frame& f, const float4& p, const float4& q, const float4& r, float* out) {
   const float dmin = fminf(p.w, fminf(q.w, r.w)), dmax = fmaxf(p.w, fmaxf(q.w, r.w));
   bool cull = !f.ok || !(dmin > 0.f);
-  cull = cull || __fsub_rn(dmax, dmin) > __fmul_rn(f.gap, dmin);
+  cull = cull || obs_depth_step(dmax, dmin, f.gap);
   cull = cull || !(p.z >= f.near) || !(q.z >= f.near) || !(r.z >= f.near);          // (a NaN depth is culled too)
   out[0] = cull ? 0.f : p.x; out[1] = cull ? 0.f : p.y; out[2] = cull ? 0.f : p.z;
   out[3] = cull ? 0.f : q.x; out[4] = cull ? 0.f : q.y; out[5] = cull ? 0.f : q.z;
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void reproject_compose_kernel(const int32_t* _
                                                                 unsigned char* __restrict__ lout, unsigned long long* __restrict__ hits) {
   const int b = blockIdx.y;
   const long n = (long)S * S, base = (long)b * n;
-  const int Wc = Ws - 1, F = 2 * (Hs - 1) * Wc;
+  const int F = obs_n_faces(Hs, Ws);
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   bool hit = false;
   if (p < n) {
@@ -121,38 +121,18 @@ __global__ __launch_bounds__(256) void reproject_compose_kernel(const int32_t* _
     const int k = fi[base + p];
     const float* w = weight + 3 * (base + p);
     const float w0 = w[0], w1 = w[1], w2 = w[2];
-    hit = k >= 0 && k < F && !(w0 != w0 || w1 != w1 || w2 != w2);
+    hit = obs_hit(k, F, w0, w1, w2);
     unsigned char lab = 0;
     float z = -1.0f;
     if (hit) {
-      int corner = w1 > w0 ? 1 : 0;                                // ties go to the lower corner number
-      if (w2 > (corner ? w1 : w0)) corner = 2;
-      const int cell = k >> 1, which = k & 1;
-      const int ci = cell / Wc, cj = cell - ci * Wc;               // k < F: ci < Hs - 1, cj < Ws - 1
-      // slot 0: a (0, 0), b (1, 0), c (0, 1); slot 1: d (1, 1), c (0, 1), b (1, 0)
-      const int di = which ? (corner == 1 ? 0 : 1) : (corner == 1 ? 1 : 0);
-      const int dj = which ? (corner == 2 ? 0 : 1) : (corner == 2 ? 1 : 0);
-      lab = labels_src[((long)b * Hs + ci + di) * Ws + cj + dj];
+      lab = labels_src[obs_label_index(b, k, w0, w1, w2, Hs, Ws)];
       z = depth[base + p];
     }
     const long q = base + (long)(S - 1 - y) * S + x;             // the planes' rows run downwards
     lout[q] = lab;
     dout[q] = z;
   }
-  __shared__ int red[4];
-  const int c = __popcll(__ballot(hit));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int s = red[0] + red[1] + red[2] + red[3];
-    if (s) atomicAdd(hits + b, (unsigned long long)s);             // (integers: the total does not depend on the order)
-  }
-}
-
-int check_shape(int B, int Hs, int Ws) {
-  if (B < 1 || B > 65535 || Hs < 2 || Ws < 2) return SLN_E_BADARG;
-  if (2L * (Hs - 1) * (Ws - 1) > (1L << 24)) return SLN_E_BADARG;
-  return 0;
+  obs_count_flags(hit, hits + b);
 }
 
 }  // namespace
@@ -161,7 +141,7 @@ extern "C" {
 
 int sln_reproject_faces(const SlnReproject* d, float* faces_xyz, void* stream) {
   if (!d || !faces_xyz || !d->depth_src || !d->k_src || !d->pose || !d->K_tgt) return SLN_E_BADARG;
-  if (check_shape(d->B, d->Hs, d->Ws)) return SLN_E_BADARG;
+  if (obs_check_frames(d->B, d->Hs, d->Ws)) return SLN_E_BADARG;
   if (!(d->orig_size > 0.f) || !(d->gap >= 0.f) || !(d->near > 0.f)) return SLN_E_BADARG;
   if (reinterpret_cast<uintptr_t>(faces_xyz) & 7) return SLN_E_BADARG;
   const int Hc = d->Hs - 1, Wc = d->Ws - 1;
@@ -174,7 +154,7 @@ int sln_reproject_faces(const SlnReproject* d, float* faces_xyz, void* stream) {
 int sln_reproject_compose(const int32_t* face_index, const float* weight, const float* raster_depth, const unsigned char* labels_src, int B,
                           int Hs, int Ws, int S, float* depth_out, unsigned char* labels_out, int64_t* hits, void* stream) {
   if (!face_index || !weight || !raster_depth || !labels_src || !depth_out || !labels_out || !hits) return SLN_E_BADARG;
-  if (check_shape(B, Hs, Ws) || S < 1 || S > 4096) return SLN_E_BADARG;
+  if (obs_check_frames(B, Hs, Ws) || !obs_target_ok(S)) return SLN_E_BADARG;
   if (reinterpret_cast<uintptr_t>(hits) & 7) return SLN_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   const int e = sln_zero_async(hits, sizeof(int64_t) * (size_t)B, st);

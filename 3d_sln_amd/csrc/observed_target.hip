@@ -30,6 +30,7 @@
 
 #include <cstdint>
 
+#include "observed_rules.h"
 #include "sln_common.h"
 #include "sln_hip.h"
 
@@ -53,8 +54,6 @@ struct OtTabs {                      // derived from chan / dch on the host
   int32_t wall_label;                // chan[0] + 1
 };
 
-__device__ __forceinline__ bool ot_reading(float d) { return d > 0.f && d <= 15.f; }
-
 __global__ void __launch_bounds__(OT_T) observed_stats(const float* __restrict__ depth, const unsigned char* __restrict__ labels, int64_t n,
                                                       unsigned long long known, OtRoom* __restrict__ ws) {
   __shared__ unsigned long long s_sum[OT_T];
@@ -73,7 +72,7 @@ __global__ void __launch_bounds__(OT_T) observed_stats(const float* __restrict__
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const unsigned y = (w >> (8 * i)) & 0xffu;
-        const bool rd = ot_reading(d[i]);
+        const bool rd = obs_reading(d[i]);
         if (y > (unsigned)OT_LAB) f |= 1;
         else if (y > 0u) f |= rd ? (((known >> y) & 1ull) ? 0 : 2) : 8;
       }
@@ -99,7 +98,7 @@ __global__ void __launch_bounds__(OT_T) observed_stats(const float* __restrict__
     const float d[4] = {d4.x, d4.y, d4.z, d4.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      if (hit[i] && ot_reading(d[i])) {
+      if (hit[i] && obs_reading(d[i])) {
         sum += (unsigned long long)(long long)rint((double)d[i] * 4294967296.0);
         cnt += 1;
         mx = fmaxf(mx, d[i]);
@@ -155,7 +154,7 @@ __global__ void __launch_bounds__(OT_T) observed_compose(const float* __restrict
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const unsigned y = (w >> (8 * i)) & 0xffu;
-    const bool rd = ot_reading(d[i]);
+    const bool rd = obs_reading(d[i]);
     d0[i] = rd ? d[i] : -1.f;
     l[i] = (rd && y <= (unsigned)OT_LAB) ? (int)y : 0;
     dq[i] = d0[i] / wall_max;
@@ -181,13 +180,13 @@ __global__ void __launch_bounds__(OT_T) observed_compose(const float* __restrict
 }  // namespace
 
 extern "C" int64_t sln_observed_target_workspace_bytes(int B, int S) {
-  if (S < 4 || S % 4 != 0 || S > 4096 || B < 1 || B > 65535) return SLN_E_UNSUPPORTED;
+  if (S < 4 || S % 4 != 0 || S > OBS_MAX_S || !obs_batch_ok(B)) return SLN_E_UNSUPPORTED;
   return (int64_t)B * (int64_t)sizeof(OtRoom);
 }
 
 extern "C" int sln_observed_target(const float* depth, const unsigned char* labels, int B, int S, int NC, const int32_t* chan,
                                    const int32_t* dch, int nch, void* workspace, float* out, int32_t* status, void* stream) {
-  if (S < 4 || S % 4 != 0 || S > 4096 || B < 1 || B > 65535 || NC < 1 || NC > 64 || nch < OT_DEP0 || nch > OT_DEP0 + OT_MAX_DCH)
+  if (S < 4 || S % 4 != 0 || S > OBS_MAX_S || !obs_batch_ok(B) || NC < 1 || NC > 64 || nch < OT_DEP0 || nch > OT_DEP0 + OT_MAX_DCH)
     return SLN_E_UNSUPPORTED;
   if (!depth || !labels || !chan || !dch || !workspace || !out || !status) return SLN_E_BADARG;
   int owned = 0;

@@ -113,11 +113,8 @@ class ObservedTarget:
     @staticmethod
     def check_tensors(depth, labels, shape, device):
         """``depth`` float32 and ``labels`` uint8, both of ``shape`` = (batch, S, S) on the CUDA ``device`` (a tensor's ``.device``)"""
-        for t, dt, what in ((depth, torch.float32, "depth"), (labels, torch.uint8, "labels")):
-            if not torch.is_tensor(t) or t.dtype != dt or t.device.type != "cuda" or t.device != device:
-                raise ValueError("%s: a %s tensor on %s expected" % (what, str(dt).replace("torch.", ""), device))
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError("%s: shape %s is not %s" % (what, tuple(t.shape), list(shape)))
+        from .reproject import check_tensors                    # (reproject imports this module: FAR)
+        check_tensors(((depth, torch.float32, shape, "depth"), (labels, torch.uint8, shape, "labels")), device, contiguous=False, cuda=True)
 
     def check(self, depth, labels):
         self.check_tensors(depth, labels, (self.batch, self.S, self.S), self.target.device)

@@ -44,15 +44,36 @@ def n_faces(Hs, Ws):
     return 2 * (int(Hs) - 1) * (int(Ws) - 1)
 
 
+def _reading(d32):
+    """a float32 depth is a reading when 0 < d <= 15 (a NaN has none): csrc/observed_rules.h, obs_reading"""
+    return (d32 > 0) & (d32 <= FAR)
+
+
 def _check_sizes(B, Hs, Ws, S):
+    """the limits of csrc/observed_rules.h for B frames as the face step sees them"""
     if B < 1 or B > MAX_B or Hs < 2 or Ws < 2 or S < 1 or S > MAX_S or n_faces(Hs, Ws) > MAX_FACES:
         raise ValueError("batch in [1, 65535], a frame of at least 2 x 2 pixels and at most 2^24 faces, S in [1, 4096] expected, got "
                          "batch = %r, Hs = %r, Ws = %r, S = %r" % (B, Hs, Ws, S))
 
 
+def _check_views(R, V):
+    if R < 1 or V < 1 or V > MAX_V:
+        raise ValueError("rooms >= 1 and views in [1, 255] expected, got rooms = %r, views = %r" % (R, V))
+
+
 def _check_scalars(orig_size, near, gap):
     if not orig_size > 0 or not gap >= 0 or not near > 0:
         raise ValueError("orig_size > 0, gap >= 0 and near > 0 expected, got %r, %r, %r" % (orig_size, gap, near))
+
+
+def check_tensors(specs, device, contiguous=True, cuda=False):
+    """``specs``: (tensor, dtype, shape, name) per argument.  Raises ValueError for what is no tensor of that dtype on ``device`` (with
+    ``cuda``: on a GPU at all), or not of that shape (with ``contiguous``: and contiguous).  Reads nothing but the tensors' metadata."""
+    for t, dt, shape, what in specs:
+        if not torch.is_tensor(t) or t.dtype != dt or t.device != device or (cuda and not t.is_cuda):
+            raise ValueError("%s: a %s tensor on %s expected" % (what, str(dt).replace("torch.", ""), device))
+        if tuple(t.shape) != tuple(shape) or (contiguous and not t.is_contiguous()):
+            raise ValueError("%s: shape %s is not %s%s" % (what, tuple(t.shape), "a contiguous " if contiguous else "", list(shape)))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -132,7 +153,7 @@ def prefilter_torch(depth_src, labels_src, k_src, f, gap=0.05):
     dev = depth_src.device
     blocks = lambda t: t[:, :f * Hd, :f * Wd].reshape(B, Hd, f, Wd, f).permute(0, 1, 3, 2, 4).reshape(B, Hd, Wd, n)   # row-major inside the block
     d, lab = blocks(depth_src.float()), blocks(labels_src).long()
-    reading = (d > 0) & (d <= FAR)
+    reading = _reading(d)
     r = reading.sum(-1)
     has = 2 * r >= n
     inf = torch.full((), float("inf"), dtype=torch.float32, device=dev)
@@ -156,14 +177,6 @@ def prefilter_torch(depth_src, labels_src, k_src, f, gap=0.05):
     return depth.contiguous(), labels.contiguous(), k_out.contiguous(), counts
 
 
-def _prefiltered(depth_src, labels_src, k_src, prefilter, gap):
-    """the frames a torch route goes on with: themselves at ``prefilter`` 1 (not filtered: non-readings pass to the face step as they are)"""
-    _check_prefilter(prefilter, *depth_src.shape[-2:])
-    if int(prefilter) == 1:
-        return depth_src, labels_src, k_src
-    return prefilter_torch(depth_src, labels_src, k_src, prefilter, gap)[:3]
-
-
 def faces_torch(depth_src, k_src, pose, K_tgt, orig_size, near=0.1, gap=0.05, dtype=torch.float64):
     """csrc/observed_reproject.hip's first kernel in torch ops, in ``dtype``: -> faces_xyz [B, F, 3, 3].  The two decisions on the
     source depths (reading, depth step) are float32 operations in either precision: they are part of the definition."""
@@ -171,7 +184,7 @@ def faces_torch(depth_src, k_src, pose, K_tgt, orig_size, near=0.1, gap=0.05, dt
     d32 = depth_src.float()
     B, Hs, Ws = d32.shape
     dev = d32.device
-    reading = (d32 > 0) & (d32 <= FAR)
+    reading = _reading(d32)
     d = d32.to(dtype)
     k, P, K = k_src.to(dtype), pose.to(dtype), K_tgt.to(dtype)
     fx, fy, cx, cy = (k[:, e, None, None] for e in range(4))
@@ -270,6 +283,21 @@ def fuse_torch(face_index, weight, raster_depth, labels_src, V, gap=0.05):
                 count=flip(count, torch.uint8), agree=flip(agree, torch.uint8), hits=(best >= 0).sum(dim=(1, 2)), wins=wins)
 
 
+def _route_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near, far, gap, dtype, prefilter):
+    """What the two torch routes share, over B frames [B, Hs, Ws] with a ``K_tgt`` each: the filter (not run at ``prefilter`` 1:
+    non-readings pass to the face step as they are), ``faces_torch``, the caller's rasterizer and the way back from numpy -> (the
+    labels the last step gathers from, faces_xyz, face_index, weight, raster_depth)"""
+    _check_prefilter(prefilter, *depth_src.shape[-2:])
+    if int(prefilter) > 1:
+        depth_src, labels_src, k_src = prefilter_torch(depth_src, labels_src, k_src, prefilter, gap)[:3]
+    B, Hs, Ws = depth_src.shape
+    _check_sizes(B, Hs, Ws, int(S))
+    fxyz = faces_torch(depth_src, k_src, pose, K_tgt, orig_size, near, gap, dtype)
+    maps = rasterize(fxyz.float().cpu().numpy(), int(S), float(near), float(far))
+    fi, w, dep = (torch.from_numpy(np.ascontiguousarray(x)).to(depth_src.device) for x in maps)
+    return labels_src, fxyz, fi, w, dep
+
+
 def reproject_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near=0.1, far=100.0, gap=0.05, dtype=torch.float64,
                     prefilter=1):
     """The route of ``ObservedReprojector`` in torch ops on the tensors' device, in ``dtype``.  ``rasterize(faces float32 numpy
@@ -279,21 +307,9 @@ def reproject_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, ras
     ``prefilter_torch`` first and everything else runs on the coarse frames: F is that of Hs // f x Ws // f."""
     if depth_src.dim() != 3 or labels_src.shape != depth_src.shape or labels_src.dtype != torch.uint8:
         raise ValueError("depth_src [B, Hs, Ws] float and labels_src [B, Hs, Ws] uint8 expected")
-    depth_src, labels_src, k_src = _prefiltered(depth_src, labels_src, k_src, prefilter, gap)
-    B, Hs, Ws = depth_src.shape
-    _check_sizes(B, Hs, Ws, int(S))
-    dev = depth_src.device
-    fxyz = faces_torch(depth_src, k_src, pose, K_tgt, orig_size, near, gap, dtype)
-    fi, w, dep = rasterize(fxyz.float().cpu().numpy(), int(S), float(near), float(far))
-    fi, w, dep = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (fi, w, dep))
-    depth, labels, hits = compose_torch(fi, w, dep, labels_src)
+    lab, fxyz, fi, w, dep = _route_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near, far, gap, dtype, prefilter)
+    depth, labels, hits = compose_torch(fi, w, dep, lab)
     return dict(depth=depth, labels=labels, hits=hits, faces_xyz=fxyz, face_index=fi, weight=w)
-
-
-def _check_views(R, V, Hs, Ws, S):
-    if R < 1 or V < 1 or V > MAX_V:
-        raise ValueError("rooms >= 1 and views in [1, 255] expected, got rooms = %r, views = %r" % (R, V))
-    _check_sizes(R * V, Hs, Ws, S)
 
 
 def reproject_views_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, S, rasterize, near=0.1, far=100.0, gap=0.05,
@@ -308,17 +324,10 @@ def reproject_views_torch(depth_src, labels_src, k_src, pose, K_tgt, orig_size, 
     R, V = depth_src.shape[:2]
     if tuple(k_src.shape) != (R, V, 4) or tuple(pose.shape) != (R, V, 3, 4) or tuple(K_tgt.shape) != (R, 3, 3):
         raise ValueError("k_src [R, V, 4], pose [R, V, 3, 4] and K_tgt [R, 3, 3] expected")
-    if R < 1 or V < 1:
-        raise ValueError("rooms >= 1 and views in [1, 255] expected, got rooms = %r, views = %r" % (R, V))
-    dev = depth_src.device
-    B = R * V
-    flat, lab, k_flat = _prefiltered(depth_src.reshape(B, *depth_src.shape[2:]), labels_src.reshape(B, *depth_src.shape[2:]), k_src.reshape(B, 4),
-                                     prefilter, gap)
-    Hs, Ws = flat.shape[1:]
-    _check_views(R, V, Hs, Ws, int(S))
-    fxyz = faces_torch(flat, k_flat, pose.reshape(B, 3, 4), K_tgt.repeat_interleave(V, 0), orig_size, near, gap, dtype)
-    fi, w, dep = rasterize(fxyz.float().cpu().numpy(), int(S), float(near), float(far))
-    fi, w, dep = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (fi, w, dep))
+    _check_views(R, V)
+    B, frame = R * V, depth_src.shape[2:]
+    lab, fxyz, fi, w, dep = _route_torch(depth_src.reshape(B, *frame), labels_src.reshape(B, *frame), k_src.reshape(B, 4), pose.reshape(B, 3, 4),
+                                         K_tgt.repeat_interleave(V, 0), orig_size, S, rasterize, near, far, gap, dtype, prefilter)
     out = fuse_torch(fi, w, dep, lab, V, gap)
     out.update(faces_xyz=fxyz, face_index=fi, weight=w, raster_depth=dep)
     return out
@@ -356,6 +365,20 @@ def prefilter(depth_src, labels_src, k_src, f, gap, depth_out, labels_out, k_out
                                            L.ptr(labels_out), L.ptr(k_out), L.ptr(counts), _stream(depth_out)), "sln_observed_prefilter")
 
 
+def _device(who, device, torch_name):
+    """the device of ``who``'s static buffers: a CUDA device, ``cuda`` normalised to the current index (what a tensor's ``.device`` says)"""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise L.SlnError("%s runs on the MI355X only (no CPU fallback); %s restates it for CPU tensors" % (type(who).__name__, torch_name))
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _frame_specs(lead, Hs, Ws, depth_src, labels_src, k_src):
+    """``check_tensors``' specs of the per-frame inputs; ``lead`` is (B,) or (R, V)"""
+    return [(depth_src, torch.float32, lead + (Hs, Ws), "depth_src"), (labels_src, torch.uint8, lead + (Hs, Ws), "labels_src"),
+            (k_src, torch.float32, lead + (4,), "k_src")]
+
+
 class ObservedPrefilter:
     """``batch`` frames of ``Hs`` x ``Ws`` decimated by the integer factor ``f`` on the device, in front of the reprojection (DESIGN §4
     "Observed frames finer than the target"; ``prefilter_factor`` chooses ``f``).
@@ -375,13 +398,8 @@ class ObservedPrefilter:
         self.f = int(f)
         if self.batch < 1 or self.batch > MAX_B:
             raise ValueError("batch in [1, 65535] expected, got %r" % (batch,))
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.SlnError("ObservedPrefilter runs on the MI355X only (no CPU fallback); prefilter_torch restates it for CPU tensors")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        B, dev = self.batch, self.device
-        self.Hd, self.Wd = self.Hs // self.f, self.Ws // self.f
+        B, dev = self.batch, _device(self, device, "prefilter_torch")
+        self.device, self.Hd, self.Wd = dev, self.Hs // self.f, self.Ws // self.f
         self.depth = torch.empty(B, self.Hd, self.Wd, dtype=torch.float32, device=dev)
         self.labels = torch.empty(B, self.Hd, self.Wd, dtype=torch.uint8, device=dev)
         self.k_out = torch.empty(B, 4, dtype=torch.float32, device=dev)
@@ -389,13 +407,7 @@ class ObservedPrefilter:
 
     def check(self, depth_src, labels_src, k_src):
         """raises ValueError before anything is launched; reads the instance's sizes and device only"""
-        B, dev = self.batch, self.device
-        for t, dt, shape, what in ((depth_src, torch.float32, (B, self.Hs, self.Ws), "depth_src"), (labels_src, torch.uint8, (B, self.Hs, self.Ws), "labels_src"),
-                                   (k_src, torch.float32, (B, 4), "k_src")):
-            if not torch.is_tensor(t) or t.dtype != dt or t.device != dev:
-                raise ValueError("%s: a %s tensor on %s expected" % (what, str(dt).replace("torch.", ""), dev))
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s: shape %s is not a contiguous %s" % (what, tuple(t.shape), list(shape)))
+        check_tensors(_frame_specs((self.batch,), self.Hs, self.Ws, depth_src, labels_src, k_src), self.device)
 
     def __call__(self, depth_src, labels_src, k_src):
         self.check(depth_src, labels_src, k_src)
@@ -403,14 +415,54 @@ class ObservedPrefilter:
         return self.depth, self.labels, self.k_out
 
 
-def _coarse(prefilter_, Hs, Ws):
-    """the size of the frames the face step sees under ``prefilter=``: -> (f, Hd, Wd)"""
-    _check_prefilter(prefilter_, Hs, Ws)
-    f = int(prefilter_)
-    return f, Hs // f, Ws // f
+class _ObservedRoute:
+    """What ``ObservedReprojector`` and ``ObservedFuser`` share: ``batch`` frames of ``Hs`` x ``Ws`` through (the filter,) the face step and
+    the rasterizer into maps of ``S`` x ``S``.  Owns the size and scalar checks, the device, ``pre`` (the ``ObservedPrefilter``, or None),
+    ``Hd`` x ``Wd`` (the frames the face step sees), ``F`` and the buffers faces_xyz, face_index, weight, raster_depth; a subclass adds
+    its outputs and its last step."""
+
+    def __init__(self, torch_name, Hs, Ws, S, batch, near, far, gap, device, prefilter):
+        self.Hs, self.Ws, self.S, self.batch = int(Hs), int(Ws), int(S), int(batch)
+        self.near, self.far, self.gap = float(near), float(far), float(gap)
+        _check_prefilter(prefilter, self.Hs, self.Ws)
+        self.prefilter = int(prefilter)
+        self.Hd, self.Wd = self.Hs // self.prefilter, self.Ws // self.prefilter
+        _check_sizes(self.batch, self.Hd, self.Wd, self.S)
+        _check_scalars(1.0, self.near, self.gap)
+        self.device = dev = _device(self, device, torch_name)
+        B, S = self.batch, self.S
+        self.pre = ObservedPrefilter(self.Hs, self.Ws, self.prefilter, B, self.gap, dev) if self.prefilter > 1 else None
+        self.F = n_faces(self.Hd, self.Wd)
+        self.faces_xyz = torch.zeros(B, self.F, 3, 3, dtype=torch.float32, device=dev)
+        self.face_index = torch.empty(B, S, S, dtype=torch.int32, device=dev)
+        self.weight = torch.empty(B, S, S, 3, dtype=torch.float32, device=dev)
+        self.raster_depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+        self._raster_ws = torch.empty(int(L.lib().sln_raster_workspace_bytes(B, self.F)), dtype=torch.uint8, device=dev)
+
+    def raster(self):
+        """``sln_raster_forward`` over ``faces_xyz`` into the maps, on the current stream"""
+        L.check(L.lib().sln_raster_forward(L.ptr(self.faces_xyz), self.batch, self.F, self.S, self.near, self.far, L.ptr(self._raster_ws),
+                                           L.ptr(self.face_index), L.ptr(self.weight), L.ptr(self.raster_depth), L.current_stream_ptr()),
+                "sln_raster_forward")
+
+    def _maps(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
+        """(filter,) faces and raster over the ``batch`` flat frames; -> the labels the last step gathers from"""
+        if self.pre is not None:
+            depth_src, labels_src, k_src = self.pre(depth_src, labels_src, k_src)
+        faces(depth_src, k_src, pose, K_tgt, orig_size, self.near, self.gap, self.faces_xyz)
+        self.raster()
+        return labels_src
 
 
-class ObservedReprojector:
+def _check_route(me, lead, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
+    """the ``check`` of both routes: raises ValueError before anything is launched; reads ``me``'s sizes, scalars and device only.
+    ``lead`` is (B,) or (R, V): the leading sizes of the per-frame tensors, whose first is that of ``K_tgt``"""
+    check_tensors(_frame_specs(lead, me.Hs, me.Ws, depth_src, labels_src, k_src) +
+                  [(pose, torch.float32, lead + (3, 4), "pose"), (K_tgt, torch.float32, lead[:1] + (3, 3), "K_tgt")], me.device)
+    _check_scalars(float(orig_size), me.near, me.gap)
+
+
+class ObservedReprojector(_ObservedRoute):
     """Frames of ``batch`` rooms, each ``Hs`` x ``Ws``, brought into target views of ``S`` x ``S`` on the device.
 
         rp = ObservedReprojector(480, 640, 256, batch=16)
@@ -430,45 +482,19 @@ class ObservedReprojector:
     labels.  With 1, the default, the filter is not run."""
 
     def __init__(self, Hs, Ws, S, batch=1, near=0.1, far=100.0, gap=0.05, device="cuda", prefilter=1):
-        self.Hs, self.Ws, self.S, self.batch = int(Hs), int(Ws), int(S), int(batch)
-        self.near, self.far, self.gap = float(near), float(far), float(gap)
-        self.prefilter, self.Hd, self.Wd = _coarse(prefilter, self.Hs, self.Ws)
-        _check_sizes(self.batch, self.Hd, self.Wd, self.S)
-        _check_scalars(1.0, self.near, self.gap)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.SlnError("ObservedReprojector runs on the MI355X only (no CPU fallback); reproject_torch restates it for CPU tensors")
+        super().__init__("reproject_torch", Hs, Ws, S, batch, near, far, gap, device, prefilter)
         B, S, dev = self.batch, self.S, self.device
-        self.pre = ObservedPrefilter(self.Hs, self.Ws, self.prefilter, B, self.gap, dev) if self.prefilter > 1 else None
-        self.F = n_faces(self.Hd, self.Wd)
-        self.faces_xyz = torch.zeros(B, self.F, 3, 3, dtype=torch.float32, device=dev)
-        self.face_index = torch.empty(B, S, S, dtype=torch.int32, device=dev)
-        self.weight = torch.empty(B, S, S, 3, dtype=torch.float32, device=dev)
-        self.raster_depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
-        self._raster_ws = torch.empty(int(L.lib().sln_raster_workspace_bytes(B, self.F)), dtype=torch.uint8, device=dev)
         self.depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
         self.labels = torch.empty(B, S, S, dtype=torch.uint8, device=dev)
         self.hits = torch.zeros(B, dtype=torch.int64, device=dev)
 
     def check(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
-        B, dev = self.batch, self.depth.device
-        for t, dt, shape, what in ((depth_src, torch.float32, (B, self.Hs, self.Ws), "depth_src"), (labels_src, torch.uint8, (B, self.Hs, self.Ws), "labels_src"),
-                                   (k_src, torch.float32, (B, 4), "k_src"), (pose, torch.float32, (B, 3, 4), "pose"), (K_tgt, torch.float32, (B, 3, 3), "K_tgt")):
-            if not torch.is_tensor(t) or t.dtype != dt or t.device != dev:
-                raise ValueError("%s: a %s tensor on %s expected" % (what, str(dt).replace("torch.", ""), dev))
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s: shape %s is not a contiguous %s" % (what, tuple(t.shape), list(shape)))
-        _check_scalars(float(orig_size), self.near, self.gap)
+        _check_route(self, (self.batch,), depth_src, labels_src, k_src, pose, K_tgt, orig_size)
 
     def __call__(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
         self.check(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
-        if self.pre is not None:
-            depth_src, labels_src, k_src = self.pre(depth_src, labels_src, k_src)
-        faces(depth_src, k_src, pose, K_tgt, orig_size, self.near, self.gap, self.faces_xyz)
-        L.check(L.lib().sln_raster_forward(L.ptr(self.faces_xyz), self.batch, self.F, self.S, self.near, self.far, L.ptr(self._raster_ws),
-                                           L.ptr(self.face_index), L.ptr(self.weight), L.ptr(self.raster_depth), L.current_stream_ptr()),
-                "sln_raster_forward")
-        compose(self.face_index, self.weight, self.raster_depth, labels_src, self.depth, self.labels, self.hits)
+        lab = self._maps(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
+        compose(self.face_index, self.weight, self.raster_depth, lab, self.depth, self.labels, self.hits)
         return self.depth, self.labels, self.hits
 
 
@@ -485,7 +511,7 @@ def fuse(face_index, weight, raster_depth, labels_src, V, gap, depth_out, labels
             "sln_reproject_fuse")
 
 
-class ObservedFuser:
+class ObservedFuser(_ObservedRoute):
     """``views`` frames per room of ``rooms`` rooms, each ``Hs`` x ``Ws``, fused into one target view of ``S`` x ``S`` per room on the
     device: where several frames see a target pixel, the one with the nearest surface there has it (the z-buffer rule).
 
@@ -506,26 +532,11 @@ class ObservedFuser:
     (``self.pre``) in front, everything else on frames of ``Hs // f`` x ``Ws // f``."""
 
     def __init__(self, Hs, Ws, S, rooms=1, views=1, near=0.1, far=100.0, gap=0.05, device="cuda", prefilter=1):
-        self.Hs, self.Ws, self.S, self.rooms, self.views = int(Hs), int(Ws), int(S), int(rooms), int(views)
-        self.near, self.far, self.gap = float(near), float(far), float(gap)
-        self.prefilter, self.Hd, self.Wd = _coarse(prefilter, self.Hs, self.Ws)
-        _check_views(self.rooms, self.views, self.Hd, self.Wd, self.S)
-        _check_scalars(1.0, self.near, self.gap)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise L.SlnError("ObservedFuser runs on the MI355X only (no CPU fallback); reproject_views_torch restates it for CPU tensors")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        R, V, S, dev = self.rooms, self.views, self.S, self.device
-        B = self.batch = R * V
-        self.pre = ObservedPrefilter(self.Hs, self.Ws, self.prefilter, B, self.gap, dev) if self.prefilter > 1 else None
-        self.F = n_faces(self.Hd, self.Wd)
-        self.K_frames = torch.zeros(B, 3, 3, dtype=torch.float32, device=dev)
-        self.faces_xyz = torch.zeros(B, self.F, 3, 3, dtype=torch.float32, device=dev)
-        self.face_index = torch.empty(B, S, S, dtype=torch.int32, device=dev)
-        self.weight = torch.empty(B, S, S, 3, dtype=torch.float32, device=dev)
-        self.raster_depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
-        self._raster_ws = torch.empty(int(L.lib().sln_raster_workspace_bytes(B, self.F)), dtype=torch.uint8, device=dev)
+        R, V = self.rooms, self.views = int(rooms), int(views)
+        _check_views(R, V)
+        super().__init__("reproject_views_torch", Hs, Ws, S, R * V, near, far, gap, device, prefilter)
+        S, dev = self.S, self.device
+        self.K_frames = torch.zeros(R * V, 3, 3, dtype=torch.float32, device=dev)
         self.depth = torch.empty(R, S, S, dtype=torch.float32, device=dev)
         self.labels, self.source, self.count, self.agree, self._valid = (torch.empty(R, S, S, dtype=torch.uint8, device=dev) for _ in range(5))
         self.hits = torch.zeros(R, dtype=torch.int64, device=dev)
@@ -533,26 +544,14 @@ class ObservedFuser:
 
     def check(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
         """raises ValueError before anything is launched; reads the instance's sizes, scalars and device only"""
-        R, V, dev = self.rooms, self.views, self.device
-        for t, dt, shape, what in ((depth_src, torch.float32, (R, V, self.Hs, self.Ws), "depth_src"), (labels_src, torch.uint8, (R, V, self.Hs, self.Ws), "labels_src"),
-                                   (k_src, torch.float32, (R, V, 4), "k_src"), (pose, torch.float32, (R, V, 3, 4), "pose"), (K_tgt, torch.float32, (R, 3, 3), "K_tgt")):
-            if not torch.is_tensor(t) or t.dtype != dt or t.device != dev:
-                raise ValueError("%s: a %s tensor on %s expected" % (what, str(dt).replace("torch.", ""), dev))
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s: shape %s is not a contiguous %s" % (what, tuple(t.shape), list(shape)))
-        _check_scalars(float(orig_size), self.near, self.gap)
+        _check_route(self, (self.rooms, self.views), depth_src, labels_src, k_src, pose, K_tgt, orig_size)
 
     def __call__(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
         self.check(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
         R, V, B = self.rooms, self.views, self.batch
         self.K_frames.view(R, V, 3, 3).copy_(K_tgt[:, None])
-        dep, lab, k = depth_src.view(B, self.Hs, self.Ws), labels_src.view(B, self.Hs, self.Ws), k_src.view(B, 4)
-        if self.pre is not None:
-            dep, lab, k = self.pre(dep, lab, k)
-        faces(dep, k, pose.view(B, 3, 4), self.K_frames, orig_size, self.near, self.gap, self.faces_xyz)
-        L.check(L.lib().sln_raster_forward(L.ptr(self.faces_xyz), B, self.F, self.S, self.near, self.far, L.ptr(self._raster_ws),
-                                           L.ptr(self.face_index), L.ptr(self.weight), L.ptr(self.raster_depth), L.current_stream_ptr()),
-                "sln_raster_forward")
+        lab = self._maps(depth_src.view(B, self.Hs, self.Ws), labels_src.view(B, self.Hs, self.Ws), k_src.view(B, 4), pose.view(B, 3, 4),
+                         self.K_frames, orig_size)
         fuse(self.face_index, self.weight, self.raster_depth, lab, V, self.gap, self.depth, self.labels, self.hits, self.source, self.count,
              self.agree, self.wins)
         return self.depth, self.labels, self.source

@@ -15,7 +15,6 @@ import numpy as np
 import torch
 
 import observed_reproject_cases as OC
-from conftest import pkg
 
 _CACHE = {}
 NAMES = ["split_plane_18x34_s32", "near_wins_18x34_s32", "two_rooms_18x34_s32", "nothing_3x5_s16", "one_view_48x64_s64"]
@@ -100,13 +99,7 @@ def frames(c):
 
 def torch_route(c, dtype):
     """``reproject_views_torch`` of a case with the rasterizer's C restatement, computed once per (case, dtype) and never modified"""
-    key = (c["name"], dtype)
-    if key not in _CACHE:
-        from oracle import raster_ref
-        RP = pkg("host.reproject")
-        _CACHE[key] = RP.reproject_views_torch(c["depth_src"], c["labels_src"], c["k_src"], c["pose"], c["K_tgt"], c["orig_size"], c["S"],
-                                               raster_ref.nmr_forward, near=c["near"], far=c["far"], gap=c["gap"], dtype=dtype)
-    return _CACHE[key]
+    return OC.torch_route(c, dtype, "reproject_views_torch")
 
 
 def whole_route(c, dtype):
@@ -203,6 +196,4 @@ def maps():
 
 def junk(R, V, S, device="cpu"):
     """the seven outputs, pre-filled with values no result holds"""
-    u8 = lambda v: torch.full((R, S, S), v, dtype=torch.uint8, device=device)
-    return dict(depth=torch.full((R, S, S), 7.5, device=device), labels=u8(9), source=u8(201), count=u8(202), agree=u8(203),
-                hits=torch.full((R,), -3, dtype=torch.int64, device=device), wins=torch.full((R, V), -5, dtype=torch.int64, device=device))
+    return OC.junk(dict(depth=(R, S, S), labels=(R, S, S), source=(R, S, S), count=(R, S, S), agree=(R, S, S), hits=(R,), wins=(R, V)), device)

@@ -151,16 +151,9 @@ ROUTE_NAMES = ["plane_37x70_f2", "frames_48x64_f4", "plane_64x96_f8"]
 
 def torch_route(c, dtype):
     """``reproject_torch(prefilter=f)`` of a case with the rasterizer's C restatement, once per (case, dtype)"""
-    key = (c["name"], dtype)
-    if key not in _CACHE:
-        from oracle import raster_ref
-        RP = pkg("host.reproject")
-        _CACHE[key] = RP.reproject_torch(c["depth_src"], c["labels_src"], c["k_src"], c["pose"], c["K_tgt"], c["orig_size"], c["S"],
-                                         raster_ref.nmr_forward, near=c["near"], far=c["far"], gap=c["gap"], dtype=dtype, prefilter=c["f"])
-    return _CACHE[key]
+    return OC.torch_route(c, dtype, prefilter=c["f"])
 
 
 def junk(B, Hd, Wd, device="cpu"):
     """the four outputs, pre-filled with values no result holds"""
-    return dict(depth=torch.full((B, Hd, Wd), 7.5, device=device), labels=torch.full((B, Hd, Wd), 9, dtype=torch.uint8, device=device),
-                k_out=torch.full((B, 4), -2.5, device=device), counts=torch.full((B, 3), -3, dtype=torch.int64, device=device))
+    return OC.junk(dict(depth=(B, Hd, Wd), labels=(B, Hd, Wd), k_out=(B, 4), counts=(B, 3)), device)

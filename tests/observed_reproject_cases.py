@@ -131,15 +131,27 @@ def case(name):
     return [c for c in cases() if c["name"] == name][0]
 
 
-def torch_route(c, dtype):
-    """``reproject_torch`` of a case with the rasterizer's C restatement, computed once per (case, dtype) and never modified"""
-    key = (c["name"], dtype)
+def torch_route(c, dtype, route="reproject_torch", **more):
+    """host/reproject.py's ``route`` (``reproject_torch``, ``reproject_views_torch``) of a case of this module's layout, of
+    observed_fuse_cases' or of observed_prefilter_cases', with the rasterizer's C restatement: computed once per (route, case, dtype)
+    and never modified"""
+    key = (route, c["name"], dtype)
     if key not in _CACHE:
         from oracle import raster_ref
-        RP = pkg("host.reproject")
-        _CACHE[key] = RP.reproject_torch(c["depth_src"], c["labels_src"], c["k_src"], c["pose"], c["K_tgt"], c["orig_size"], c["S"],
-                                         raster_ref.nmr_forward, near=c["near"], far=c["far"], gap=c["gap"], dtype=dtype)
+        fn = getattr(pkg("host.reproject"), route)
+        _CACHE[key] = fn(c["depth_src"], c["labels_src"], c["k_src"], c["pose"], c["K_tgt"], c["orig_size"], c["S"], raster_ref.nmr_forward,
+                         near=c["near"], far=c["far"], gap=c["gap"], dtype=dtype, **more)
     return _CACHE[key]
+
+
+# outputs pre-filled with values no result holds, by the name of the output: (value, dtype)
+JUNK = dict(depth=(7.5, torch.float32), labels=(9, torch.uint8), source=(201, torch.uint8), count=(202, torch.uint8), agree=(203, torch.uint8),
+            hits=(-3, torch.int64), wins=(-5, torch.int64), k_out=(-2.5, torch.float32), counts=(-3, torch.int64))
+
+
+def junk(shapes, device="cpu"):
+    """name -> shape: a tensor per output, filled with its value of ``JUNK``"""
+    return {k: torch.full(tuple(s), JUNK[k][0], dtype=JUNK[k][1], device=device) for k, s in shapes.items()}
 
 
 def face_error(got, want):

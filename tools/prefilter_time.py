@@ -21,7 +21,6 @@ import importlib
 import os
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,27 +28,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 L = importlib.import_module("3d_sln_amd._lib")
 RP = importlib.import_module("3d_sln_amd.host.reproject")
-from reproject_time import HS, WS, S, ITERS, frame, window            # noqa: E402  (the same frame, the same windows)
-
-ROOM = [0.0, 0.0, 0.0, 4.0, 2.7, 5.0]
-
-
-def _raster(o):
-    lib, P = L.lib(), L.ptr
-    return lambda: L.check(lib.sln_raster_forward(P(o.faces_xyz), o.batch, o.F, S, o.near, o.far, P(o._raster_ws), P(o.face_index), P(o.weight),
-                                                  P(o.raster_depth), L.current_stream_ptr()), "sln_raster_forward")
-
-
-def _steps(o, whole, dep, lab, k, pose, K, orig, last_name, last):
-    """the variants of one setting: the whole call and its steps on what the call left; dep, lab, k are the flat unfiltered frames"""
-    v = [("whole call", whole)]
-    if o.pre is not None:
-        v.append(("sln_observed_prefilter", lambda src=(dep, lab, k): o.pre(*src)))
-        dep, lab, k = o.pre.depth, o.pre.labels, o.pre.k_out
-    v.append(("sln_reproject_faces", lambda: RP.faces(dep, k, pose, K, orig, o.near, o.gap, o.faces_xyz)))
-    v.append(("sln_raster_forward", _raster(o)))
-    v.append((last_name, lambda: last(o, lab)))
-    return v
+# the same frame, cameras, windows and steps of the route
+from reproject_time import HS, WS, S, ITERS, ROOM, frame, window, pose_of, view_poses, steps, compose_step, fuse_step   # noqa: E402
 
 
 def _run(title, settings, repeats, auto):
@@ -83,22 +63,16 @@ def _run(title, settings, repeats, auto):
             auto, max(best) < min(base), max(best) * 1e6, min(base) * 1e6, sorted(base)[len(base) // 2] / sorted(best)[len(best) // 2]), flush=True)
 
 
-def _pose(B):
-    c, s = np.cos(0.05), np.sin(0.05)
-    return torch.tensor([[c, 0.0, s, 0.1], [0.0, 1.0, 0.0, -0.05], [-s, 0.0, c, 0.2]], dtype=torch.float32)[None].repeat(B, 1, 1).cuda()
-
-
 def measure(B, repeats):
     depth, labels, k_src = (t.cuda() for t in frame(B))
     K, _, _, orig = RP.refine_view(ROOM, S)
     auto = RP.prefilter_factor(k_src, K, orig, S)
-    pose, K = _pose(B), K[None].repeat(B, 1, 1).cuda()
+    pose, K = pose_of(B), K[None].repeat(B, 1, 1).cuda()
     settings = []
     for f in sorted({1, 2, 4, auto}):
         rp = RP.ObservedReprojector(HS, WS, S, batch=B, prefilter=f)
         whole = (lambda rp: lambda: rp(depth, labels, k_src, pose, K, orig))(rp)
-        last = lambda o, lab: RP.compose(o.face_index, o.weight, o.raster_depth, lab, o.depth, o.labels, o.hits)
-        settings.append((f, rp, _steps(rp, whole, depth, labels, k_src, pose, K, orig, "sln_reproject_compose", last)))
+        settings.append((f, rp, steps(rp, "whole call", whole, depth, labels, k_src, pose, K, orig, "sln_reproject_compose", compose_step)))
     _run("ObservedReprojector: %d frame(s) of %d x %d into %d x %d" % (B, WS, HS, S, S), settings, repeats, auto)
 
 
@@ -107,21 +81,15 @@ def measure_fuser(R, V, repeats):
     depth, labels, k_src = (t.cuda() for t in frame(B))
     K, _, _, orig = RP.refine_view(ROOM, S)
     auto = RP.prefilter_factor(k_src, K, orig, S)
-    poses = []
-    for v in range(V):                                               # view v looks a few degrees to the side of the others
-        a = 0.05 + 0.06 * (v - 0.5 * (V - 1))
-        c, s = np.cos(a), np.sin(a)
-        poses.append([[c, 0.0, s, 0.1 - 0.15 * (v - 0.5 * (V - 1))], [0.0, 1.0, 0.0, -0.05], [-s, 0.0, c, 0.2]])
-    pose = torch.tensor(poses, dtype=torch.float32)[None].repeat(R, 1, 1, 1).contiguous().cuda()
+    pose = view_poses(R, V)
     K = K[None].repeat(R, 1, 1).cuda()
     d4, l4, k4 = depth.view(R, V, HS, WS), labels.view(R, V, HS, WS), k_src.view(R, V, 4)
     settings = []
     for f in sorted({1, 2, 4, auto}):
         fu = RP.ObservedFuser(HS, WS, S, rooms=R, views=V, prefilter=f)
         whole = (lambda fu: lambda: fu(d4, l4, k4, pose, K, orig))(fu)
-        last = lambda o, lab: RP.fuse(o.face_index, o.weight, o.raster_depth, lab, V, o.gap, o.depth, o.labels, o.hits, o.source, o.count, o.agree, o.wins)
         whole()                                                      # (spreads K_tgt over the frames: the face step alone reads K_frames)
-        settings.append((f, fu, _steps(fu, whole, depth, labels, k_src, pose.view(B, 3, 4), fu.K_frames, orig, "sln_reproject_fuse", last)))
+        settings.append((f, fu, steps(fu, "whole call", whole, depth, labels, k_src, pose.view(B, 3, 4), fu.K_frames, orig, "sln_reproject_fuse", fuse_step)))
     _run("ObservedFuser: %d rooms x %d views of %d x %d into %d x %d" % (R, V, WS, HS, S, S), settings, repeats, auto)
 
 

@@ -70,24 +70,56 @@ def window(fn):
     return a.elapsed_time(b) / ITERS * 1e-3
 
 
+ROOM = [0.0, 0.0, 0.0, 4.0, 2.7, 5.0]
+
+
+def pose_of(B):
+    """[B, 3, 4] on the device: the small rotation and translation of the one-frame route"""
+    c, s = np.cos(0.05), np.sin(0.05)
+    return torch.tensor([[c, 0.0, s, 0.1], [0.0, 1.0, 0.0, -0.05], [-s, 0.0, c, 0.2]], dtype=torch.float32)[None].repeat(B, 1, 1).cuda()
+
+
+def view_poses(R, V):
+    """[R, V, 3, 4] on the device: view v looks a few degrees to the side of the others"""
+    poses = []
+    for v in range(V):
+        a = 0.05 + 0.06 * (v - 0.5 * (V - 1))
+        c, s = np.cos(a), np.sin(a)
+        poses.append([[c, 0.0, s, 0.1 - 0.15 * (v - 0.5 * (V - 1))], [0.0, 1.0, 0.0, -0.05], [-s, 0.0, c, 0.2]])
+    return torch.tensor(poses, dtype=torch.float32)[None].repeat(R, 1, 1, 1).contiguous().cuda()
+
+
+def compose_step(o, lab):
+    RP.compose(o.face_index, o.weight, o.raster_depth, lab, o.depth, o.labels, o.hits)
+
+
+def fuse_step(o, lab):
+    RP.fuse(o.face_index, o.weight, o.raster_depth, lab, o.views, o.gap, o.depth, o.labels, o.hits, o.source, o.count, o.agree, o.wins)
+
+
+def steps(o, whole_name, whole, dep, lab, k, pose, K, orig, last_name, last):
+    """the variants of one route object: the whole call and its steps on what the call left; dep, lab, k, pose, K are the flat frames
+    as the face step takes them without a filter (prefilter_time.py times the same steps per setting)"""
+    v = [(whole_name, whole)]
+    if o.pre is not None:
+        v.append(("sln_observed_prefilter", lambda src=(dep, lab, k): o.pre(*src)))
+        dep, lab, k = o.pre.depth, o.pre.labels, o.pre.k_out
+    v.append(("sln_reproject_faces", lambda: RP.faces(dep, k, pose, K, orig, o.near, o.gap, o.faces_xyz)))
+    v.append(("sln_raster_forward", o.raster))
+    v.append((last_name, lambda: last(o, lab)))
+    return v
+
+
 def measure(B, repeats):
     depth, labels, k_src = (t.cuda() for t in frame(B))
-    K, R, t, orig = RP.refine_view([0.0, 0.0, 0.0, 4.0, 2.7, 5.0], S)
-    c, s = np.cos(0.05), np.sin(0.05)
-    pose = torch.tensor([[c, 0.0, s, 0.1], [0.0, 1.0, 0.0, -0.05], [-s, 0.0, c, 0.2]], dtype=torch.float32)[None].repeat(B, 1, 1).cuda()
+    K, R, t, orig = RP.refine_view(ROOM, S)
+    pose = pose_of(B)
     K = K[None].repeat(B, 1, 1).cuda()
     rp = RP.ObservedReprojector(HS, WS, S, batch=B)
-    lib, P, st = L.lib(), L.ptr, L.current_stream_ptr
-
-    def raster():
-        L.check(lib.sln_raster_forward(P(rp.faces_xyz), B, rp.F, S, rp.near, rp.far, P(rp._raster_ws), P(rp.face_index), P(rp.weight), P(rp.raster_depth),
-                                       st()), "sln_raster_forward")
-    variants = [("ObservedReprojector", lambda: rp(depth, labels, k_src, pose, K, orig)),
-                ("sln_reproject_faces", lambda: RP.faces(depth, k_src, pose, K, orig, rp.near, rp.gap, rp.faces_xyz)),
-                ("sln_raster_forward", raster),
-                ("sln_reproject_compose", lambda: RP.compose(rp.face_index, rp.weight, rp.raster_depth, labels, rp.depth, rp.labels, rp.hits)),
-                ("torch: faces", lambda: RP.faces_torch(depth, k_src, pose, K, orig, rp.near, rp.gap, torch.float32)),
-                ("torch: compose", lambda: RP.compose_torch(rp.face_index, rp.weight, rp.raster_depth, labels))]
+    variants = steps(rp, "ObservedReprojector", lambda: rp(depth, labels, k_src, pose, K, orig), depth, labels, k_src, pose, K, orig,
+                     "sln_reproject_compose", compose_step)
+    variants += [("torch: faces", lambda: RP.faces_torch(depth, k_src, pose, K, orig, rp.near, rp.gap, torch.float32)),
+                 ("torch: compose", lambda: RP.compose_torch(rp.face_index, rp.weight, rp.raster_depth, labels))]
     for _, fn in variants:
         for _ in range(2):
             fn()
@@ -114,13 +146,8 @@ def report(variants, times):
 def measure_views(R, V, Hs, Ws, repeats):
     B = R * V
     depth, labels, k_src = (t.cuda() for t in frame(B, HS=Hs, WS=Ws))
-    K, _, _, orig = RP.refine_view([0.0, 0.0, 0.0, 4.0, 2.7, 5.0], S)
-    poses = []
-    for v in range(V):                                               # view v looks a few degrees to the side of the others
-        a = 0.05 + 0.06 * (v - 0.5 * (V - 1))
-        c, s = np.cos(a), np.sin(a)
-        poses.append([[c, 0.0, s, 0.1 - 0.15 * (v - 0.5 * (V - 1))], [0.0, 1.0, 0.0, -0.05], [-s, 0.0, c, 0.2]])
-    pose = torch.tensor(poses, dtype=torch.float32)[None].repeat(R, 1, 1, 1).contiguous().cuda()
+    K, _, _, orig = RP.refine_view(ROOM, S)
+    pose = view_poses(R, V)
     K = K[None].repeat(R, 1, 1).cuda()
     depth, labels, k_src = depth.view(R, V, Hs, Ws), labels.view(R, V, Hs, Ws), k_src.view(R, V, 4)
     fu = RP.ObservedFuser(Hs, Ws, S, rooms=R, views=V)
@@ -128,8 +155,7 @@ def measure_views(R, V, Hs, Ws, repeats):
     c_depth, c_labels = torch.empty(B, S, S, device="cuda"), torch.empty(B, S, S, dtype=torch.uint8, device="cuda")
     c_hits = torch.zeros(B, dtype=torch.int64, device="cuda")
     variants = [("ObservedFuser", lambda: fu(depth, labels, k_src, pose, K, orig)),
-                ("sln_reproject_fuse", lambda: RP.fuse(fu.face_index, fu.weight, fu.raster_depth, flat_labels, V, fu.gap, fu.depth, fu.labels, fu.hits,
-                                                       fu.source, fu.count, fu.agree, fu.wins)),
+                ("sln_reproject_fuse", lambda: fuse_step(fu, flat_labels)),
                 ("sln_reproject_compose", lambda: RP.compose(fu.face_index, fu.weight, fu.raster_depth, flat_labels, c_depth, c_labels, c_hits))]
     if V == 1:
         rp = RP.ObservedReprojector(Hs, Ws, S, batch=R)
