@@ -569,11 +569,20 @@ def check_mask(mask, shape, device, observed):
         raise ValueError("mask: a tensor on %s expected, got one on %s" % (device, mask.device))
 
 
-def _valid_of(mask, target):
-    """uint8 [B, S, S] of a checked ``mask``: 'readings' - where plane 0 of the built target (the cleaned depth) has a reading"""
-    if isinstance(mask, str):
-        return (target[:, 0] >= 0).to(torch.uint8).contiguous()
-    return (mask != 0).to(torch.uint8).contiguous()
+def check_observed(observed, shape, device, cuda=True, choice=False):
+    """the ``observed=`` argument of the refinement entry points, refused before anything is launched: None, or the pair (depth, uint8 labels),
+    both tensors of ``shape`` = (rooms, S, S) on ``device``.  ``cuda``: the pair feeds ``ObservedTarget``, whose own check it passes (float32
+    depth, a GPU); otherwise ``observed_target_torch``: any depth dtype, any device.  ``choice``: the caller asks for retrieved meshes."""
+    if observed is None:
+        return
+    if choice:
+        raise ValueError("observed targets show no meshes to retrieve: observed combines neither with retrieve=True nor with a bank that leaves a choice")
+    if not isinstance(observed, (tuple, list)) or len(observed) != 2 or not all(torch.is_tensor(t) for t in observed):
+        raise ValueError("observed is (depth %s float32, labels likewise uint8)" % (list(shape),))
+    if cuda:
+        OB.ObservedTarget.check_tensors(observed[0], observed[1], tuple(shape), device)
+    elif any(tuple(t.shape) != tuple(shape) or t.device != torch.device(device) for t in observed) or observed[1].dtype != torch.uint8:
+        raise ValueError("observed: depth and uint8 labels of shape %s on %s expected" % (list(shape), device))
 
 
 class _RefineLossFn(torch.autograd.Function):
@@ -787,7 +796,7 @@ class RefineScene:
     diff_render.py:76-159 turned into ONE batched tensor expression over the visible objects, and fixed tensor shapes:
     the near-plane cull (:346-356) degenerates the culled faces (all three corners collapse to a point, so they never
     cover a pixel) instead of compacting the face list.  Nothing in ``render`` synchronises with the host, which is what
-    lets a whole refinement iteration be captured into one hipGraph (``finetune_vae(..., capture=True)``).
+    lets a whole refinement iteration be captured into one hipGraph (``finetune_vae_fast(..., capture=True)``).
     Built once per room: the room box is frozen (:55-60) and so are K, R, t."""
 
     def __init__(self, class_names, bank, room_box, image_size=DR.final_out, models=None, shell=None):
@@ -898,6 +907,122 @@ class RefineScene:
         return img, size_loss, size
 
 
+def room_start(model, room, noise_seed, iters, device, fp32=False):
+    """A room's start as every loop draws it (test_render_refine.py:274-279, 304): the encoder (``model`` in eval mode), then on ONE CPU generator seeded
+    with ``noise_seed`` (torch.manual_seed(13) in front of every trial) ``randn(mu.shape)`` for ``z0 = mu + randn * exp(0.5 logvar)`` and ``iters``
+    times ``randn(n)`` - the soft-argmax noise of the iterations in the reference's order, up front so that a loop uploads it once.
+    ``room``: dict with ``objs, triples, boxes, angles, attributes``; ``fp32``: the encoder's GEMMs in fp32 whatever ``model.gemm_precision``
+    says.  -> (z0 [n, E] on ``device``, detached and the caller's own; noise rows [iters, n] on the host)"""
+    with _precision(model, "fp32" if fp32 else None), torch.no_grad():
+        mu, logvar = model.encoder(room["objs"], room["triples"], room["boxes"], room["angles"], room["attributes"])
+    gen = torch.Generator(device="cpu").manual_seed(noise_seed)
+    z0 = (mu + torch.randn(mu.shape, generator=gen).to(device) * torch.exp(0.5 * logvar)).detach()
+    rows = [torch.randn(mu.shape[0], generator=gen) for _ in range(iters)]
+    return z0, (torch.stack(rows) if rows else torch.zeros(0, mu.shape[0]))
+
+
+def _shared_class_tables(scenes):
+    """(chan, dch) of the scenes of one batch, which must share them"""
+    chan, dch = scenes[0].chan, scenes[0].dch
+    for sc in scenes[1:]:
+        if not (torch.equal(sc.chan, chan) and torch.equal(sc.dch, dch)):
+            raise _lib.SlnError("rooms of one batch must share the class tables")
+    return chan, dch
+
+
+def room_target(room, bank, image_size, models=None, shell=None, observed=False):
+    """A room's target for the device loops: the scene of the ground-truth rows (``models`` / ``shell``: what ``retrieve_choice`` picked for them)
+    and its render.  ``observed``: the caller builds the targets of its rooms with one ``ObservedTarget`` call - then only the placement
+    runs, for the sizes.  -> (scene, target [1, C, S, S] or None, sizes [n_vis, 3] of the caller's own)"""
+    scene = RefineScene(room["class_names"], bank, room["boxes"][-1].detach().clone(), image_size, models=models, shell=shell)
+    with torch.no_grad():
+        if observed:
+            target, (_, _, sizes) = None, _PlaceFn.apply(room["boxes"], room["angles"].float(), scene, None)
+        else:
+            target, _, sizes = scene.render(room["boxes"], room["angles"].float())
+    return scene, target, sizes.detach().clone().contiguous()
+
+
+def valid_and_labels(mask, target, labels=True):
+    """A checked ``mask`` and the built ``target`` [B, C, S, S] -> (valid uint8 [B, S, S] - 'readings': where plane 0, the cleaned depth, has a
+    reading - or None without a mask; the per-scale labels of the target cleaned under it, None with ``labels`` off: ``RefineLoss`` derives its own)"""
+    valid = None
+    if mask is not None:
+        valid = ((target[:, 0] >= 0) if isinstance(mask, str) else (mask != 0)).to(torch.uint8).contiguous()
+    if not labels:
+        return valid, None
+    return valid, target_labels(target if valid is None else torch.where(valid[:, None] != 0, target, torch.zeros_like(target)))
+
+
+def parse_schedule(spec, iters, name):
+    """The iterations a per-iteration extra (``report``, ``pictures``) runs in: ``spec`` None, "ends" (0 and the last), "all" or an
+    iterable of iteration numbers in [0, max(iters, 1)) -> None, or (sorted tuple of iteration numbers, is it "all")."""
+    if spec is None:
+        return None
+    n = max(int(iters), 1)
+    named = {"all": range(n), "ends": (0, n - 1)}
+    if isinstance(spec, str) and spec not in named:
+        raise ValueError("%s is None, 'ends', 'all' or an iterable of iteration numbers" % name)
+    at = tuple(sorted(set(named[spec] if isinstance(spec, str) else [int(k) for k in spec])))
+    if any(k < 0 or k >= n for k in at):
+        raise ValueError("%s names an iteration outside [0, %d)" % (name, iters))
+    return at, isinstance(spec, str) and spec == "all"
+
+
+class GraphStep:
+    """One step of a loop as a hipGraph.  ``run(step)``: the first call runs ``step()`` on a side stream (the warm-up outside the capture:
+    allocator, lazy kernel attributes), then records a second ``step()`` into the graph; every later call replays it.  -> what the
+    step returned: the warm-up's the first time, the recorded call's (the graph's static outputs) from then on."""
+    graph = out = None
+
+    def run(self, step):
+        if self.graph is not None:
+            self.graph.replay()
+            return self.out
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            out = step()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = step()
+        return out
+
+
+def cut_ranges(ranges, offsets=None, lengths=None):
+    """``ranges`` [(offset, length)] of a flat float buffer minus the tensors at ``offsets`` of ``lengths`` -> what is left, in order.  A length
+    is padded up to 64 floats when every offset is a multiple of 64 (the flat parameter layout pads every tensor to 64 floats, nothing lives
+    in the pad), otherwise to 4.  A cut must start on a multiple of 4 (16 bytes) and not before the position reached inside its range."""
+    if not offsets:
+        return list(ranges)
+    al = 64 if all(o % 64 == 0 for o in offsets) else 4
+    cut = sorted((int(o), -(-int(n) // al) * al) for o, n in zip(offsets, lengths))
+    out = []
+    for a, n in ranges:
+        pos, end = a, a + n
+        for c0, cn in cut:
+            if c0 + cn <= pos or c0 >= end:
+                continue
+            if c0 % 4 or c0 < pos:
+                raise _lib.SlnError("a fused parameter tensor does not start on a 16-byte boundary of the decoder run")
+            if c0 > pos:
+                out.append((pos, c0 - pos))
+            pos = c0 + cn
+        if pos < end:
+            out.append((pos, end - pos))
+    return out
+
+
+def _one_room_arguments(observed, mask, S, dev, cuda, bank=None):
+    """``observed`` / ``mask`` of the one-room loops, brought from [S, S] to [1, S, S] and checked before anything is launched"""
+    lift = lambda t: t[None] if torch.is_tensor(t) and t.dim() == 2 else t
+    observed, mask = tuple(lift(t) for t in observed) if isinstance(observed, (tuple, list)) else observed, lift(mask)
+    check_observed(observed, (1, S, S), dev, cuda, choice=bank is not None and bank.has_choice())
+    check_mask(mask, (1, S, S), dev, observed)
+    return observed, mask
+
+
 def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, bank=None, learning_rate=1e-4,
                       noise_seed=13, image_size=256, capture=False, log=None, fused_loss=True, fused_head=True, observed=None, mask=None):
     """``finetune_vae`` with the batched ``RefineScene`` and no per-iteration python optimiser objects: the reference builds a
@@ -906,67 +1031,50 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
     (lr ``learning_rate``/10).  ``fused_loss``: the PSP-pool / L1 / cross-entropy block runs as ``RefineLoss`` (two C calls)
     instead of torch ops; ``fused_head``: the soft-argmax / noise / concatenation glue and the two gradient hooks as one launch
     each way (``_HeadFn``) and both parameter updates plus the gradient zero-fill as one launch (``sln_refine_sgd``).
-    ``capture=True`` records one iteration (decoder, placement, fused render, PSP losses,
-    backward, both updates) into a hipGraph and replays it; the noise of the angle soft-argmax is then drawn on the device.
+    ``capture=True`` records one iteration (decoder, placement, fused render, PSP losses, backward, both updates) into a hipGraph and
+    replays it (``GraphStep``).
     ``observed``: None, or ``(depth [S, S] or [1, S, S] float32, labels likewise uint8)`` on the device - the target is built from this
     observation with one ``ObservedTarget`` call on the room's class tables instead of rendered from ``boxes_gt`` (``RefineBatch``'s
     ``observed``, for one room).  ``mask``: None, "readings" or a uint8 / bool tensor [S, S] or [1, S, S] - the loss under a validity mask
     (``RefineBatch``'s ``mask``).
-    Returns (losses [iters] tensor on the device, (boxes_pred, angle_idx))."""
-    dev = boxes_gt.device
-    observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, cuda=True)
-    if observed is not None and bank is not None and bank.has_choice():
-        raise ValueError("observed targets show no meshes to retrieve: observed does not combine with a bank that leaves a choice")
+    Returns (losses [iters] tensor on the device, (boxes_pred, angle_idx)).  ``log``: called once per iteration, the captured one included."""
+    dev, S = boxes_gt.device, int(image_size)
+    observed, mask = _one_room_arguments(observed, mask, S, dev, True, bank)
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
+    room = dict(objs=objs, triples=triples, boxes=boxes_gt, angles=angles_gt, attributes=attributes, class_names=class_names)
     model.eval()
-    with torch.no_grad():
-        mu, logvar = model.encoder(objs, triples, boxes_gt, angles_gt, attributes)
-    gen = torch.Generator(device="cpu").manual_seed(noise_seed)
-    z = (mu + torch.randn(mu.shape, generator=gen).to(dev) * torch.exp(0.5 * logvar)).detach().clone().requires_grad_(True)
-    room_box = boxes_gt[-1].detach().clone()
+    # the soft-argmax noise of every iteration is uploaded once: a per-iteration host-to-device copy would block the host and leave
+    # the GPU idle between two iterations
+    z, noise_all = room_start(model, room, noise_seed, iters, dev)
+    z, noise_all = z.requires_grad_(True), noise_all.to(dev)
     # the target shows the meshes retrieved for the ground-truth boxes (test_render_refine.py:319), the iterates those retrieved for
     # iteration 0's boxes (:324-326) - two scenes when the bank leaves a choice
     models_gt, shell = None, None
     if bank.has_choice():
         models_gt, shells = retrieve_choice(bank, boxes_gt, class_names)
         models_gt, shell = models_gt.cpu().tolist(), (shells[0] if shells is not None else None)
-    target_scene = scene = RefineScene(class_names, bank, room_box, image_size, models=models_gt, shell=shell)
-    with torch.no_grad():
-        if observed is None:
-            target, _, sizes = target_scene.render(boxes_gt, angles_gt.float())
-        else:                            # the placement alone, for the sizes; the target from the observation (csrc/observed_target.hip)
-            _, _, sizes = _PlaceFn.apply(boxes_gt, angles_gt.float(), target_scene, None)
-            built, _ = OB.ObservedTarget(target_scene.chan, target_scene.dch, int(image_size), batch=1, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)
-            target = built.clone()
-    valid = _valid_of(mask, target) if mask is not None else None
-    labels = target_labels(torch.where(valid[:, None] != 0, target, torch.zeros_like(target)) if valid is not None else target)
+    target_scene, target, size_target = room_target(room, bank, S, models_gt, shell, observed is not None)      # (size_target: a buffer, filled below)
+    scene = target_scene
+    if observed is not None:                                           # the target from the observation (csrc/observed_target.hip)
+        target = OB.ObservedTarget(scene.chan, scene.dch, S, batch=1, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)[0]
+    valid, labels = valid_and_labels(mask, target, labels=not fused_loss)
     fused = RefineLoss(target, valid=valid) if fused_loss else None    # the PSP / L1 / cross-entropy block as two C calls
-    size_target = sizes.detach().clone()                           # (a buffer: filled with the FIRST iterate's sizes below)
-    n = boxes_gt.shape[0]
-    noise = torch.zeros(n, device=dev)
-    # the soft-argmax noise of every iteration, drawn in the reference's order (one randn(n) per iteration) but uploaded once:
-    # a per-iteration host-to-device copy would block the host and leave the GPU idle between two iterations
-    noise_all = torch.stack([torch.randn(n, generator=gen) for _ in range(iters)]).to(dev) if iters > 0 else torch.zeros(0, n, device=dev)
+    noise = torch.zeros(boxes_gt.shape[0], device=dev)
     losses = torch.zeros(iters, device=dev)
-    flat, flat_grad = model.flat_params, model.flat_grads
-    state = {}
-
-    box_last = boxes_gt[-1].detach().float().contiguous()
-    angle_last = angles_gt[-1:].detach().float().contiguous()
+    flat, flat_grad, state = model.flat_params, model.flat_grads, {}
+    box_last, angle_last = boxes_gt[-1].detach().float().contiguous(), angles_gt[-1:].detach().float().contiguous()
     if fused_head:
         flat_grad.zero_()                                  # from here on the update kernel leaves the gradient buffer zeroed
     if iters > 0 and scene.n_vis:
-        # the size penalty holds the objects to the sizes of the FIRST iterate (test_render_refine.py:319-327: size_infos is what the
-        # first mesh_render_func call on boxes_pred returns; the target render's sizes are discarded): one decoder + placement pass
-        # with iteration 0's z, parameters and noise row.  Iteration 0 then measures its own sizes against themselves - a size loss
-        # of exactly 0 with zero gradient, which is the reference's ``size_loss = 0.0`` of the first call.
+        # the size penalty holds the objects to the sizes of the FIRST iterate (see ``RefineBatch._first_iterate_sizes``): one decoder +
+        # placement pass with iteration 0's z, parameters and noise row
         with torch.no_grad():
             bp0, ap0 = model.decoder(z, objs, triples, attributes)
             b0 = torch.cat([bp0[:-1], boxes_gt[-1:]], 0)
             i0 = torch.cat([(softargmax(ap0, sum_dim=1) + noise_all[0] / 10.0)[:-1], angles_gt[-1:].float()], 0)
             size_target.copy_(_PlaceFn.apply(b0, i0, target_scene, None)[2])              # (sizes do not depend on the model)
             if bank.has_choice():
-                scene = RefineScene(class_names, bank, room_box, image_size, models=retrieve_choice(bank, b0, class_names)[0].cpu().tolist(),
+                scene = RefineScene(class_names, bank, target_scene.room, S, models=retrieve_choice(bank, b0, class_names)[0].cpu().tolist(),
                                     shell=shell)
 
     def iteration():
@@ -1002,26 +1110,10 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
         state["boxes"], state["idx"] = boxes_full.detach(), idx.detach()
         return loss.detach()
 
-    graph = None
+    graph = GraphStep()
     for k in range(iters):
-        if capture:
-            noise.copy_(noise_all[k])
-            if graph is None:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):                      # warm-up outside the capture (allocator, lazy init)
-                    state["loss"] = iteration()
-                torch.cuda.current_stream().wait_stream(side)
-                losses[k] = state["loss"]
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    state["loss"] = iteration()
-                continue
-            graph.replay()
-            losses[k] = state["loss"]
-        else:
-            noise.copy_(noise_all[k])
-            losses[k] = iteration()
+        noise.copy_(noise_all[k])
+        losses[k] = graph.run(iteration) if capture else iteration()
         if log:
             log("iter %d: loss %.4f" % (k, float(losses[k])))
     return losses, (state["boxes"], state["idx"])
@@ -1083,126 +1175,106 @@ class RefineBatch:
 
     def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
                  retrieve=False, observed=None, mask=None):
-        L = _lib.lib()
-        self.model, self.R, self.iters, self.lr = model, len(rooms), int(iters), float(learning_rate)
-        R = self.R
-        if R < 1:
-            raise ValueError("RefineBatch needs at least one room")
+        self.model, self.R, self.iters, self.lr, self.S = model, len(rooms), int(iters), float(learning_rate), int(image_size)
         dev = model.flat_params.device
-        if observed is not None:                                # refused here, in front of the first launch
-            if retrieve:
-                raise ValueError("observed targets show no meshes to retrieve: observed and retrieve=True do not combine")
-            if not isinstance(observed, (tuple, list)) or len(observed) != 2:
-                raise ValueError("observed is (depth [R, S, S] float32, labels [R, S, S] uint8)")
-            OB.ObservedTarget.check_tensors(observed[0], observed[1], (R, int(image_size), int(image_size)), dev)
-        check_mask(mask, (R, int(image_size), int(image_size)), dev, observed)
-        names_all = set(n for rm in rooms for n in rm["class_names"])
-        bank = bank or MeshBank([n for n in names_all if n not in DO_NOT_VIS and n != "__room__"], dev)
-        model.eval()
-        E, na, S = model.embedding_dim, model.Nangle, int(image_size)
+        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev)      # every refusal, in front of the first launch
+        self._bank = bank or MeshBank([n for n in set(n for rm in rooms for n in rm["class_names"]) if n not in DO_NOT_VIS and n != "__room__"], dev)
+        self._retrieve, self._class_names = bool(retrieve), [list(rm["class_names"]) for rm in rooms]
         self.rows = [int(rm["objs"].shape[0]) for rm in rooms]
-        self.row0 = [0]
-        for n in self.rows[:-1]:
-            self.row0.append(self.row0[-1] + n)
-        N = sum(self.rows)
-        self.N = N
-        f32 = dict(dtype=torch.float32, device=dev)
-        # ---- per room: encoder (the checkpoint model), z draw, noise of every iteration, scene, target render ----
-        z = torch.empty(N, E, **f32)
-        noise = torch.zeros(max(self.iters, 1), N)
-        scenes, targets, size_targets = [], [], []
-        # ---- retrieve=True: the targets' meshes from ONE retrieval launch over all rooms' ground-truth rows (read back: this is set-up) ----
-        self._retrieve, self._bank, self._class_names = bool(retrieve), bank, [list(rm["class_names"]) for rm in rooms]
-        self.target_models = self.models = None
-        tm, self._shells = None, None
-        if self._retrieve:
-            if any(len(nm) != n for nm, n in zip(self._class_names, self.rows)):
-                raise ValueError("class_names must name every row of a room")
-            gt = torch.cat([rm["boxes"].detach().float() for rm in rooms]).to(dev)
-            self.target_models, self._shells = retrieve_choice(bank, gt, [n for nm in self._class_names for n in nm], self.rows)
-            tm = self.target_models.cpu().tolist()
-        box_last, angle_last = torch.empty(R, 6, **f32), torch.empty(R, **f32)
-        for r, rm in enumerate(rooms):
-            # (fp32 whatever model.gemm_precision says: the refinement loop's room engines are fp32 only, and so is its starting point)
-            with _precision(model, "fp32"), torch.no_grad():
-                mu, logvar = model.encoder(rm["objs"], rm["triples"], rm["boxes"], rm["angles"], rm["attributes"])
-            gen = torch.Generator(device="cpu").manual_seed(noise_seed)          # torch.manual_seed(13) in front of every trial (:274-275)
-            a, n = self.row0[r], self.rows[r]
-            z[a:a + n] = mu + torch.randn(mu.shape, generator=gen).to(dev) * torch.exp(0.5 * logvar)
-            if self.iters > 0:           # one randn(n) per iteration, as the reference draws them (:304); one strided copy into the table
-                noise[:self.iters, a:a + n] = torch.stack([torch.randn(n, generator=gen) for _ in range(self.iters)])
-            sc = RefineScene(rm["class_names"], bank, rm["boxes"][-1].detach().clone(), S, models=tm[a:a + n] if tm is not None else None,
-                             shell=self._shells[r] if self._shells is not None else None)
-            with torch.no_grad():
-                if observed is None:
-                    tgt, _, sizes = sc.render(rm["boxes"], rm["angles"].float())
-                else:                   # the placement alone, for the sizes: the target is not rendered from the room's boxes
-                    tgt = None
-                    _, _, sizes = _PlaceFn.apply(rm["boxes"], rm["angles"].float(), sc, None)
-            scenes.append(sc); targets.append(tgt); size_targets.append(sizes.detach().clone().contiguous())
-            box_last[r] = rm["boxes"][-1].detach().float(); angle_last[r] = rm["angles"][-1].detach().float()
-        self.target_status = None
-        if observed is not None:
-            # ---- all R targets from ONE ObservedTarget call on the batch's class tables (csrc/observed_target.hip) ----
-            for sc in scenes[1:]:
-                if not (torch.equal(sc.chan, scenes[0].chan) and torch.equal(sc.dch, scenes[0].dch)):
-                    raise _lib.SlnError("rooms of one batch must share the class tables")
-            built, status = OB.ObservedTarget(scenes[0].chan, scenes[0].dch, S, batch=R, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)
-            targets = [built[r:r + 1] for r in range(R)]
-            self.target_status = status.clone()
-        self.z, self.scenes, self.target_scenes = z, scenes, scenes
-        self._report_all = report == "all"
-        if report is None:
-            self._report_at = None
-        else:
-            last = max(self.iters - 1, 0)
-            at = range(self.iters) if report == "all" else ((0, last) if report == "ends" else [int(k) for k in report])
-            if isinstance(report, str) and report not in ("all", "ends"):
-                raise ValueError("report is None, 'ends', 'all' or an iterable of iteration numbers")
-            self._report_at = frozenset(at)
-            if any(k < 0 or k >= max(self.iters, 1) for k in self._report_at):
-                raise ValueError("report names an iteration outside [0, %d)" % self.iters)
-            # the ground truth of the IoU (all rooms' rows), the full-resolution depth-hot planes of the targets (not null-filled, :332)
-            self._gt_boxes = torch.cat([rm["boxes"].detach().float() for rm in rooms]).to(dev).contiguous()
-            self._gt_angles = torch.cat([rm["angles"].detach().float() for rm in rooms]).to(dev).contiguous()
-            self._visible = torch.tensor([nm not in DO_NOT_VIS for rm in rooms for nm in rm["class_names"]], dtype=torch.uint8, device=dev)
-            if self._visible.numel() != N:
-                raise ValueError("class_names must name every row of a room")
-            self._target_depth = torch.cat([t[:, 41:] for t in targets], 0).contiguous()
-            self._iou_mean = torch.zeros(R, dtype=torch.float64, device=dev)
-            self._report_ws = torch.empty(int(L.sln_refine_report_scratch_doubles(R)), dtype=torch.float64, device=dev)
-            self.report = torch.full((max(self.iters, 1), R, 3), float("nan"), **f32)
-        self._pictures_all = isinstance(pictures, str) and pictures == "all"
-        if pictures is None:
-            self._pictures_at = None
-        else:
-            if isinstance(pictures, str) and pictures not in ("all", "ends"):
-                raise ValueError("pictures is None, 'ends', 'all' or an iterable of iteration numbers")
-            last = max(self.iters - 1, 0)
-            at = range(max(self.iters, 1)) if pictures == "all" else ((0, last) if pictures == "ends" else [int(k) for k in pictures])
-            at = sorted(set(at))
-            if any(k < 0 or k >= max(self.iters, 1) for k in at):
-                raise ValueError("pictures names an iteration outside [0, %d)" % self.iters)
-            self._pictures_at = {k: j for j, k in enumerate(at)}
-            self._pics = SP.ScenePictures(S, batch=R, channels=DR.N_SCENE_CHANNELS, device=dev)
-            u8 = dict(dtype=torch.uint8, device=dev)
-            n_pic = len(at)
-            self.pictures = PictureSet(torch.zeros(n_pic, R, S, S, **u8), torch.zeros(n_pic, R, S, S, **u8), torch.zeros(n_pic, R, S, S, 3, **u8),
-                                       torch.zeros(n_pic, R, dtype=torch.int32, device=dev), tuple(at))
-            t = self._pics(torch.cat(targets, 0).contiguous())                     # (:320: the target as rendered, every plane written)
-            self.target_pictures = SP.Pictures(t.depth8.clone(), t.labels.clone(), t.rgb.clone(), None, t.status.clone())
-        self.noise_all = noise.to(dev)
-        self.box_last, self.angle_last = box_last, angle_last
-        # ---- the loss of all rooms: one descriptor, per-room normalisation ----
-        all_targets = torch.cat(targets, 0)
-        self.loss = RefineLoss(all_targets, per_room=True, valid=_valid_of(mask, all_targets) if mask is not None else None)
+        self.row0 = [sum(self.rows[:r]) for r in range(self.R)]
+        self.N, self.n_max = sum(self.rows), max(self.rows)
+        model.eval()
+        targets = self._start_rooms(rooms, noise_seed, observed, dev)
+        if self._report_at is not None:
+            self._report_buffers(rooms, targets, dev)
+        if self._pictures_at is not None:
+            self._picture_buffers(targets, dev)
+        all_targets = torch.cat(targets, 0)                   # the loss of all rooms: one descriptor, per-room normalisation
+        self.loss = RefineLoss(all_targets, per_room=True, valid=valid_and_labels(mask, all_targets, labels=False)[0])
         self.mask_status = self.loss.mask_status
         del targets, all_targets
-        # ---- R parameter copies, R engines, one launch program ----
-        nflat = model.flat_params.numel()
+        self._create_group(rooms, dev)
+        self._head_and_placement_buffers(dev)
+        self._bind_scenes(self.scenes)
+        self._image_and_loss_buffers(dev)
+        self._sgd_ranges()
+        self.noise = torch.zeros(self.N, dtype=torch.float32, device=dev)
+        self._graph, self._graph_out, self.k = GraphStep(), None, 0
+        # the side stream of the wgrads / the scene backward's depth chain is PROBED for real overlap with the caller's stream, which
+        # synchronises that stream: here, at set-up, not inside the first iteration's asynchronous calls (csrc/streams.hip)
+        if not torch.cuda.is_current_stream_capturing():
+            _lib.lib().sln_side_stream_prepare(_lib.current_stream_ptr())
+
+    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev):
+        """refuses what cannot run; leaves ``_report_at`` (frozenset) and ``_pictures_at`` ({iteration: slot}), None when not asked for, + "all" flags"""
+        if self.R < 1:
+            raise ValueError("RefineBatch needs at least one room")
+        check_observed(observed, (self.R, self.S, self.S), dev, cuda=True, choice=retrieve)
+        check_mask(mask, (self.R, self.S, self.S), dev, observed)
+        at, self._report_all = parse_schedule(report, self.iters, "report") or (None, False)
+        self._report_at = None if at is None else frozenset(at)
+        at, self._pictures_all = parse_schedule(pictures, self.iters, "pictures") or (None, False)
+        self._pictures_at = None if at is None else {k: j for j, k in enumerate(at)}
+        if (retrieve or report is not None) and any(len(rm["class_names"]) != int(rm["objs"].shape[0]) for rm in rooms):
+            raise ValueError("class_names must name every row of a room")
+
+    def _start_rooms(self, rooms, noise_seed, observed, dev):
+        """per room: the start (``room_start``), the target scene, the target and the frozen room row -> the R targets [1, C, S, S]"""
+        R, S, bank, f32 = self.R, self.S, self._bank, dict(dtype=torch.float32, device=dev)
+        self.z = torch.empty(self.N, self.model.embedding_dim, **f32)
+        noise = torch.zeros(max(self.iters, 1), self.N)
+        # all rooms' ground-truth rows: what retrieve=True retrieves the targets' meshes for and what the report's IoU measures against
+        self._gt_boxes = None
+        if self._retrieve or self._report_at is not None:
+            self._gt_boxes = torch.cat([rm["boxes"].detach().float() for rm in rooms]).to(dev).contiguous()
+        self.target_models = self.models = self._shells = tm = None
+        if self._retrieve:               # the targets' meshes from ONE retrieval launch over those rows (read back: this is set-up)
+            self.target_models, self._shells = retrieve_choice(bank, self._gt_boxes, [n for nm in self._class_names for n in nm], self.rows)
+            tm = self.target_models.cpu().tolist()
+        self.box_last, self.angle_last = torch.empty(R, 6, **f32), torch.empty(R, **f32)
+        scenes, targets, self._size_targets = [], [], []
+        for r, rm in enumerate(rooms):
+            a, n = self.row0[r], self.rows[r]
+            # (fp32 whatever model.gemm_precision says: the refinement loop's room engines are fp32 only, and so is its starting point)
+            self.z[a:a + n], noise[:self.iters, a:a + n] = room_start(self.model, rm, noise_seed, self.iters, dev, fp32=True)
+            sc, tgt, sizes = room_target(rm, bank, S, tm[a:a + n] if tm is not None else None, self._shells[r] if self._shells is not None else None,
+                                         observed is not None)
+            scenes.append(sc); targets.append(tgt); self._size_targets.append(sizes)
+            self.box_last[r] = rm["boxes"][-1].detach().float(); self.angle_last[r] = rm["angles"][-1].detach().float()
+        self.target_status = None
+        if observed is not None:         # all R targets from ONE ObservedTarget call on the batch's class tables (csrc/observed_target.hip)
+            built, status = OB.ObservedTarget(*_shared_class_tables(scenes), S, batch=R, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)
+            targets, self.target_status = [built[r:r + 1] for r in range(R)], status.clone()
+        self.scenes = self.target_scenes = scenes
+        self.noise_all = noise.to(dev)
+        return targets
+
+    def _report_buffers(self, rooms, targets, dev):
+        """report: the IoU's ground truth, the targets' full-resolution depth-hot planes (not null-filled, :332), the IoU means, ``report``"""
+        R = self.R
+        self._gt_angles = torch.cat([rm["angles"].detach().float() for rm in rooms]).to(dev).contiguous()
+        self._visible = torch.tensor([nm not in DO_NOT_VIS for rm in rooms for nm in rm["class_names"]], dtype=torch.uint8, device=dev)
+        self._target_depth = torch.cat([t[:, 41:] for t in targets], 0).contiguous()
+        self._iou_mean = torch.zeros(R, dtype=torch.float64, device=dev)
+        self._report_ws = torch.empty(int(_lib.lib().sln_refine_report_scratch_doubles(R)), dtype=torch.float64, device=dev)
+        self.report = torch.full((max(self.iters, 1), R, 3), float("nan"), dtype=torch.float32, device=dev)
+
+    def _picture_buffers(self, targets, dev):
+        """pictures: one slot per pictured iteration, and ``target_pictures`` of the targets as built (:320: every plane written)"""
+        R, S, n_pic = self.R, self.S, len(self._pictures_at)
+        self._pics = SP.ScenePictures(S, batch=R, channels=DR.N_SCENE_CHANNELS, device=dev)
+        u8 = dict(dtype=torch.uint8, device=dev)
+        self.pictures = PictureSet(torch.zeros(n_pic, R, S, S, **u8), torch.zeros(n_pic, R, S, S, **u8), torch.zeros(n_pic, R, S, S, 3, **u8),
+                                   torch.zeros(n_pic, R, dtype=torch.int32, device=dev), tuple(self._pictures_at))
+        t = self._pics(torch.cat(targets, 0).contiguous())
+        self.target_pictures = SP.Pictures(t.depth8.clone(), t.labels.clone(), t.rgb.clone(), None, t.status.clone())
+
+    def _create_group(self, rooms, dev):
+        """R parameter copies, R engines with their room bound, one launch program over them (``_group``)"""
+        L, R, N, model, f32 = _lib.lib(), self.R, self.N, self.model, dict(dtype=torch.float32, device=dev)
         self.params = model.flat_params.detach().unsqueeze(0).repeat(R, 1).contiguous()
-        self.grads = torch.zeros(R, nflat, **f32)
-        self._engines = model.room_engines(self.params, self.grads, max(self.rows), max(int(rm["triples"].shape[0]) for rm in rooms))
+        self.grads = torch.zeros(R, model.flat_params.numel(), **f32)
+        self._engines = model.room_engines(self.params, self.grads, self.n_max, max(int(rm["triples"].shape[0]) for rm in rooms))
         st = _lib.current_stream_ptr()
         self._keep = []
         for (h, _ws, _arr), rm in zip(self._engines, rooms):
@@ -1214,13 +1286,12 @@ class RefineBatch:
             b.O, b.T = n, int(tri.shape[0])
             _lib.check(L.sln_vae_set_batch(h, C.byref(b), st), "sln_vae_set_batch")
             self._keep.append((objs, tri, attrs, zb, za))
-        self.boxes_pred, self.angles_pred = torch.empty(N, model.box_dim, **f32), torch.empty(N, na, **f32)
-        self.d_boxes_pred, self.d_angles_pred = torch.zeros(N, 8, **f32), torch.empty(N, na, **f32)
-        self.dz = torch.empty(N, E, **f32)
+        self.boxes_pred, self.angles_pred = torch.empty(N, model.box_dim, **f32), torch.empty(N, model.Nangle, **f32)
+        self.d_boxes_pred, self.d_angles_pred = torch.zeros(N, 8, **f32), torch.empty(N, model.Nangle, **f32)
+        self.dz = torch.empty(N, model.embedding_dim, **f32)
         io = _lib.SlnVaeGroupIO()
-        io.rows_total = N
         self._row0_c = (C.c_int * R)(*self.row0)
-        io.row0_host = self._row0_c
+        io.rows_total, io.row0_host = N, self._row0_c
         io.z, io.boxes_pred, io.angles_pred = self.z.data_ptr(), self.boxes_pred.data_ptr(), self.angles_pred.data_ptr()
         io.d_boxes_pred, io.d_angles_pred, io.dz = self.d_boxes_pred.data_ptr(), self.d_angles_pred.data_ptr(), self.dz.data_ptr()
         # SGD of the Linear weights / biases in the epilogue of their wgrads (one pass over the R parameter copies instead of the
@@ -1228,39 +1299,38 @@ class RefineBatch:
         self._step = torch.full((1,), (self.lr / 10.0) * 1.1, **f32)
         if not os.environ.get("SLN_REFINE_SEPARATE_SGD"):
             io.sgd_step = self._step.data_ptr()
-        harr = (C.c_void_p * R)(*[e[0] for e in self._engines])
-        g = C.c_void_p()
+        harr, g = (C.c_void_p * R)(*[e[0] for e in self._engines]), C.c_void_p()
         torch.cuda.current_stream(dev).synchronize()          # the tables of the program are uploaded with blocking copies
         _lib.check(L.sln_vae_group_create(harr, R, C.byref(io), C.byref(g)), "sln_vae_group_create")
         self._group = g
-        # ---- head / placement tables ----
+
+    def _head_and_placement_buffers(self, dev):
+        """everything per row or per room that the head and the placement read and write, whatever the scenes (``_bind_scenes``)"""
+        R, N, f32 = self.R, self.N, dict(dtype=torch.float32, device=dev)
         self.room_of_row = torch.cat([torch.full((n,), r, dtype=torch.int32) for r, n in enumerate(self.rows)]).to(dev)
         self.last_row = torch.tensor([a + n - 1 for a, n in zip(self.row0, self.rows)], dtype=torch.int32, device=dev)
         if self._report_at is not None or self._retrieve:
             self._room_row = self.last_row[self.room_of_row.long()].contiguous()         # [N]: every row's room row
         self.boxes, self.idx = torch.empty(N, 6, **f32), torch.empty(N, **f32)
         self.g_boxes, self.g_idx = torch.empty(N, 6, **f32), torch.empty(N, **f32)
-        self.n_max = max(self.rows)
-        self.sizes = torch.zeros(R, max(max(sc.n_vis for sc in scenes), 1), 3, **f32)
+        self.sizes = torch.zeros(R, max(max(sc.n_vis for sc in self.scenes), 1), 3, **f32)
         self.size_loss = torch.zeros(R, **f32)
         self.g_size_loss = torch.full((1,), 2.0, **f32)               # loss = ... + 2 * size_loss (test_render_refine.py:350-352)
-        self._size_targets = size_targets
-        # the soft-argmax / noise / frozen-row glue inside the two placement launches (SlnPlacementRoom's head fields; the noise of
-        # iteration k is row k of noise_all, k a device counter the backward launch advances)
-        self._fused_head = max(self.rows) <= 128 and not os.environ.get("SLN_REFINE_SEPARATE_HEAD")
+        # the head inside the two placement launches (SlnPlacementRoom's head fields; iteration k's noise: row k of noise_all, k a device counter)
+        self._fused_head = self.n_max <= 128 and not os.environ.get("SLN_REFINE_SEPARATE_HEAD")
         self._noise_step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.S = S
-        self._bind_scenes(scenes)
-        self.image = torch.zeros(R, DR.N_SCENE_CHANNELS, S, S, **f32)         # (planes flagged dead are never written, nor read)
-        self.g_image = torch.zeros(R, DR.N_SCENE_CHANNELS, S, S, **f32)
+
+    def _image_and_loss_buffers(self, dev):
+        """the image and its gradient, the loss outputs and the live-plane flags the loss and the scene pass share"""
+        R, S, f32 = self.R, self.S, dict(dtype=torch.float32, device=dev)
+        self.image, self.g_image = (torch.zeros(R, DR.N_SCENE_CHANNELS, S, S, **f32) for _ in range(2))       # (planes flagged dead: never touched)
         self.loss_out = torch.empty(R, 3, **f32)
         # the semantic planes of classes without a visible pixel are zeros, and the scene pass never reads their gradients nor
         # those of such classes' depth-hot planes: the loss skips them (SlnRefineLoss::live_planes, refreshed after every scene pass)
         self.live = torch.full((R, DR.N_SCENE_CHANNELS), 3, dtype=torch.uint8, device=dev)
         self.null_mask = None
-        # (only when the loss takes the flags for this geometry - image sizes below the pooled size do not: it would read planes
-        #  the sparse scene pass leaves unwritten)
-        if not os.environ.get("SLN_REFINE_ALL_PLANES") and L.sln_refine_loss_live_ok(C.byref(self.loss.desc)):
+        # (only when the loss takes the flags for this geometry: below the pooled size it would read planes the sparse scene pass leaves unwritten)
+        if not os.environ.get("SLN_REFINE_ALL_PLANES") and _lib.lib().sln_refine_loss_live_ok(C.byref(self.loss.desc)):
             self.loss.desc.live_planes = self.live.data_ptr()
             self.null_mask = torch.zeros(R, S, S, dtype=torch.uint8, device=dev)
             self.loss.desc.null_mask = self.null_mask.data_ptr()
@@ -1268,61 +1338,40 @@ class RefineBatch:
             self.loss.desc.pooled_ones = self._pooled_ones.data_ptr()
         self.one = torch.ones(1, **f32)
         self.losses = torch.zeros(max(self.iters, 1), R, **f32)
-        rg = model.decoder_param_ranges()
+
+    def _sgd_ranges(self):
+        """what the stand-alone SGD launch steps: the decoder's parameter runs minus the tensors the wgrad launches step themselves"""
+        L = _lib.lib()
         nf = int(L.sln_vae_group_fused_params(self._group, None, None, 0))
-        if nf > 0:                                                   # ... minus the tensors the wgrad launches step themselves
-            ptrs, lens = (C.c_void_p * nf)(), (C.c_int64 * nf)()
+        ptrs, lens = (C.c_void_p * nf)(), (C.c_int64 * nf)()
+        if nf > 0:
             L.sln_vae_group_fused_params(self._group, ptrs, lens, nf)
-            base = self.params.data_ptr()
-            offs = [(int(ptrs[i]) - base) // 4 for i in range(nf)]
-            al = 64 if all(o % 64 == 0 for o in offs) else 4         # the flat layout pads every tensor to 64 floats (nothing lives in the pad)
-            cut = sorted((o, -(-int(lens[i]) // al) * al) for i, o in enumerate(offs))
-            out = []
-            for a, n in rg:
-                pos, end = a, a + n
-                for c0, cn in cut:
-                    if c0 + cn <= pos or c0 >= end:
-                        continue
-                    if c0 % 4 or c0 < pos:
-                        raise _lib.SlnError("a fused parameter tensor does not start on a 16-byte boundary of the decoder run")
-                    if c0 > pos:
-                        out.append((pos, c0 - pos))
-                    pos = c0 + cn
-                if pos < end:
-                    out.append((pos, end - pos))
-            rg = out
+        base = self.params.data_ptr()
+        rg = cut_ranges(self.model.decoder_param_ranges(), [(int(ptrs[i]) - base) // 4 for i in range(nf)], [int(lens[i]) for i in range(nf)])
         self._sgd_off = (C.c_int64 * len(rg))(*[a for a, _ in rg])
         self._sgd_len = (C.c_int64 * len(rg))(*[b for _, b in rg])
         self._n_rg = len(rg)
-        self.noise = torch.zeros(N, **f32)
-        self._graph = None
-        self.k = 0
-        # the side stream of the wgrads / the scene backward's depth chain is PROBED for real overlap with the caller's stream, which
-        # synchronises that stream: here, at set-up, not inside the first iteration's asynchronous calls (csrc/streams.hip)
-        if not torch.cuda.is_current_stream_capturing():
-            L.sln_side_stream_prepare(st)
 
     def _bind_scenes(self, scenes):
         """Everything of the launch program that follows the rooms' SCENES (their models' vertices and face lists): the padded face
         buffers, the class table of the faces, the placement table and the scene pass's workspace.  Called at construction with the
         target scenes and, with retrieve=True, once more by the first ``run()`` with the scenes of the iterates' meshes (which may
         change F2); the size targets, the head's buffers and everything per row stay where they are."""
-        L = _lib.lib()
         R, N, na, dev = self.R, self.N, self.model.Nangle, self.boxes.device
         f32 = dict(dtype=torch.float32, device=dev)
         self.scenes = scenes
+        self.chan, self.dch = _shared_class_tables(scenes)
         self.F2 = 2 * max(sc.desc.F for sc in scenes)
         self.faces = torch.zeros(R, self.F2, 3, 3, **f32)             # rows beyond a room's 2 F stay degenerate triangles of no class
         self.g_faces = torch.empty(R, self.F2, 3, 3, **f32)
-        cls = torch.full((R, self.F2), -1, dtype=torch.int32, device=dev)
-        size_targets = self._size_targets
+        self.cls = cls = torch.full((R, self.F2), -1, dtype=torch.int32, device=dev)
         tab = (_lib.SlnPlacementRoom * R)()
         for r, sc in enumerate(scenes):
             cls[r, :2 * sc.desc.F] = sc.cls2[0]
             e, a = tab[r], self.row0[r]
             e.P = sc.desc
             e.boxes, e.angles = self.boxes.data_ptr() + 24 * a, self.idx.data_ptr() + 4 * a
-            e.size_target = size_targets[r].data_ptr() if sc.n_vis else None
+            e.size_target = self._size_targets[r].data_ptr() if sc.n_vis else None
             e.faces_out, e.sizes, e.size_loss = self.faces[r].data_ptr(), self.sizes[r].data_ptr(), self.size_loss.data_ptr() + 4 * r
             e.grad_faces, e.grad_size_loss = self.g_faces[r].data_ptr(), self.g_size_loss.data_ptr()
             e.grad_boxes, e.grad_angles = self.g_boxes.data_ptr() + 24 * a, self.g_idx.data_ptr() + 4 * a
@@ -1333,12 +1382,7 @@ class RefineBatch:
                 e.grad_boxes_pred, e.grad_angles_pred = self.d_boxes_pred.data_ptr() + 32 * a, self.d_angles_pred.data_ptr() + 4 * na * a
                 e.n_angle, e.ld_gb, e.beta = na, 8, 2.0
         self._place_tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
-        self.cls = cls
-        self.chan, self.dch = scenes[0].chan, scenes[0].dch
-        for sc in scenes[1:]:
-            if not (torch.equal(sc.chan, self.chan) and torch.equal(sc.dch, self.dch)):
-                raise _lib.SlnError("rooms of one batch must share the class tables")
-        self.scene_ws = torch.empty(int(L.sln_scene_workspace_bytes(R, self.F2, self.S)), dtype=torch.uint8, device=dev)
+        self.scene_ws = torch.empty(int(_lib.lib().sln_scene_workspace_bytes(R, self.F2, self.S)), dtype=torch.uint8, device=dev)
 
     def _retrieve_iterates(self):
         """retrieve=True: the iterates' meshes are those retrieved for the FIRST iterate's boxes (testing/test_render_refine.py:324-326:
@@ -1352,11 +1396,8 @@ class RefineBatch:
         host = self.models.cpu().tolist()
         if host == self.target_models.cpu().tolist():
             return
-        scenes = []
-        for r, sc in enumerate(self.target_scenes):
-            a, n = self.row0[r], self.rows[r]
-            scenes.append(RefineScene(self._class_names[r], self._bank, sc.room, self.S, models=host[a:a + n], shell=sc.shell))
-        self._bind_scenes(scenes)
+        self._bind_scenes([RefineScene(names, self._bank, sc.room, self.S, models=host[a:a + n], shell=sc.shell)
+                           for names, sc, a, n in zip(self._class_names, self.target_scenes, self.row0, self.rows)])
 
     def model_ids(self, target=False):
         """[[id per row, None where nothing is retrieved (room rows, classes without a model)] per room] of the iterates' meshes
@@ -1365,10 +1406,18 @@ class RefineBatch:
         if models is None:
             raise ValueError("no retrieval yet: RefineBatch(retrieve=True), and run() for the iterates' meshes")
         table, host = self._bank.table, models.cpu().tolist()
-        out = []
-        for names, a in zip(self._class_names, self.row0):
-            out.append([table.id_of(table.vocab.index(n), host[a + i]) if host[a + i] >= 0 else None for i, n in enumerate(names)])
-        return out
+        return [[table.id_of(table.vocab.index(n), host[a + i]) if host[a + i] >= 0 else None for i, n in enumerate(names)]
+                for names, a in zip(self._class_names, self.row0)]
+
+    def _forward_to_placement(self, noise):
+        """decoder of all rooms, the head (``noise`` [N]; its own launch unless the placement launch holds it) and the placement"""
+        L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
+        _lib.check(L.sln_vae_group_decoder(self._group, st), "sln_vae_group_decoder")
+        if not self._fused_head:
+            _lib.check(L.sln_refine_head_forward_rooms(self.N, self.model.Nangle, P(self.room_of_row), P(self.last_row), P(self.boxes_pred),
+                                                       P(self.angles_pred), P(noise), P(self.box_last), P(self.angle_last), 2.0, P(self.boxes),
+                                                       P(self.idx), st), "sln_refine_head_forward_rooms")
+        _lib.check(L.sln_place_forward_rooms(P(self._place_tab), self.R, self.F2 // 2, st), "sln_place_forward_rooms")
 
     def _first_iterate_sizes(self):
         """The size penalty holds every object to the size of the FIRST iterate (testing/test_render_refine.py:319-327: ``size_infos`` is
@@ -1377,13 +1426,7 @@ class RefineBatch:
         rooms' targets.  Iteration 0 then measures its own sizes against themselves: a size loss of exactly 0 with zero gradient - the
         reference's ``size_loss = 0.0`` of a first call.  Run by ``run()`` in front of iteration 0 (eagerly, outside any capture), so
         that edits of ``z`` or ``params`` between construction and the first ``run()`` are the first iterate's; frozen from then on."""
-        L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
-        _lib.check(L.sln_vae_group_decoder(self._group, st), "sln_vae_group_decoder")
-        if not self._fused_head:
-            _lib.check(L.sln_refine_head_forward_rooms(self.N, self.model.Nangle, P(self.room_of_row), P(self.last_row), P(self.boxes_pred),
-                                                       P(self.angles_pred), P(self.noise_all[0]), P(self.box_last), P(self.angle_last), 2.0,
-                                                       P(self.boxes), P(self.idx), st), "sln_refine_head_forward_rooms")
-        _lib.check(L.sln_place_forward_rooms(P(self._place_tab), self.R, self.F2 // 2, st), "sln_place_forward_rooms")
+        self._forward_to_placement(self.noise_all[0])
         for r, sc in enumerate(self.scenes):
             if sc.n_vis:
                 self._size_targets[r].copy_(self.sizes[r, :sc.n_vis])
@@ -1398,22 +1441,15 @@ class RefineBatch:
         [R, 3] (a reported iteration) the report, ``pictures_out`` (a pictured iteration) = (depth8, labels, rgb, status) of one slot"""
         L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
         N, R, na, S = self.N, self.R, self.model.Nangle, self.S
-        _lib.check(L.sln_vae_group_decoder(self._group, st), "sln_vae_group_decoder")
-        if not self._fused_head:
-            _lib.check(L.sln_refine_head_forward_rooms(N, na, P(self.room_of_row), P(self.last_row), P(self.boxes_pred), P(self.angles_pred), P(noise),
-                                                       P(self.box_last), P(self.angle_last), 2.0, P(self.boxes), P(self.idx), st),
-                       "sln_refine_head_forward_rooms")
-        _lib.check(L.sln_place_forward_rooms(P(self._place_tab), R, self.F2 // 2, st), "sln_place_forward_rooms")
+        self._forward_to_placement(noise)
         if report_out is not None:      # (the fused head lives in the placement launch: boxes / idx of this iterate exist from here on)
             _lib.check(L.sln_layout_cuboid_iou(P(self.boxes), P(self.idx), P(self._gt_boxes), P(self._gt_angles), P(self._room_row), P(self._visible),
                                                P(self.room_of_row), R, 1, N, None, P(self._iou_mean), st), "sln_layout_cuboid_iou")
         rl = self.loss
-        if rl.desc.live_planes:
-            _lib.check(L.sln_scene_forward_live(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 0.1, 0.001, 100.0,
-                                                1e-3, P(self.scene_ws), P(self.image), P(self.live), P(self.null_mask), st), "sln_scene_forward_live")
-        else:
-            _lib.check(L.sln_scene_forward(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 0.1, 0.001, 100.0,
-                                           1e-3, P(self.scene_ws), P(self.image), st), "sln_scene_forward")
+        live = (P(self.live), P(self.null_mask)) if rl.desc.live_planes else ()        # the scene pass refreshes the live-plane flags
+        forward = L.sln_scene_forward_live if live else L.sln_scene_forward
+        _lib.check(forward(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 0.1, 0.001, 100.0, 1e-3,
+                           P(self.scene_ws), P(self.image), *live, st), "sln_scene_forward_live" if live else "sln_scene_forward")
         _lib.check(L.sln_refine_loss_forward(rl.desc, P(self.image), P(rl.target_depth), P(rl.labels), P(rl.inv_count), P(rl.ws), P(self.loss_out), st),
                    "sln_refine_loss_forward")
         torch.add(self.loss_out[:, 0], self.size_loss, alpha=2.0, out=out)
@@ -1421,8 +1457,7 @@ class RefineBatch:
             _lib.check(L.sln_refine_report(rl.desc, P(self.image), P(self._target_depth), P(rl.ws), P(self._report_ws), P(self._iou_mean), P(report_out),
                                            st), "sln_refine_report")
         if pictures_out is not None:    # the iterate as the loss saw it: the planes `live` flags dead are not read
-            d8, lab, rgb, stat = pictures_out
-            self._pics.into(self.image, self.live, d8, lab, rgb, None, stat)
+            self._pics.into(self.image, self.live, *pictures_out[:3], None, pictures_out[3])
         _lib.check(L.sln_refine_loss_backward(rl.desc, P(rl.ws), P(self.one), P(self.g_image), st), "sln_refine_loss_backward")
         _lib.check(L.sln_scene_backward(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 1e-3, P(self.scene_ws),
                                         P(self.g_image), P(self.g_faces), st), "sln_scene_backward")
@@ -1443,46 +1478,31 @@ class RefineBatch:
         n = (self.iters - self.k) if iters is None else int(iters)
         if self.k + n > self.iters:
             raise ValueError("RefineBatch was built for %d iterations (the noise of every iteration is drawn at construction)" % self.iters)
-        if capture and self._report_at is not None and not self._report_all:
-            raise ValueError("run(capture=True) replays one graph for every iteration: report must be 'all' or None")
-        if capture and self._pictures_at is not None and not self._pictures_all:
-            raise ValueError("run(capture=True) replays one graph for every iteration: pictures must be 'all' or None")
-        scratch = self.loss_out.new_empty(self.R)
-        rep_scratch = self.loss_out.new_empty(self.R, 3) if capture and self._report_all and self._graph is None else None
-        pic_scratch = None
-        if capture and self._pictures_all and self._graph is None:                # the graph's slot: copied to the iteration's after a replay
-            pic_scratch = tuple(torch.empty_like(t[0]) for t in self.pictures[:4])
+        for name, at, is_all in (("report", self._report_at, self._report_all), ("pictures", self._pictures_at, self._pictures_all)):
+            if capture and at is not None and not is_all:
+                raise ValueError("run(capture=True) replays one graph for every iteration: %s must be 'all' or None" % name)
+        if capture and self._graph_out is None:       # what the graph writes: copied to the iteration's own rows after every captured step
+            self._graph_out = (self.loss_out.new_empty(self.R), self.loss_out.new_empty(self.R, 3) if self._report_all else None,
+                               tuple(torch.empty_like(t[0]) for t in self.pictures[:4]) if self._pictures_all else None)
         if n > 0 and self.k == 0:
             self._first_iterate_sizes()
             if self._retrieve and self.models is None:
                 self._retrieve_iterates()
+        step = lambda: self._iteration(self.noise, *self._graph_out)
         for _ in range(n):
             k = self.k
             rep = self.report[k] if self._report_at is not None and k in self._report_at else None
-            pic = None
-            if self._pictures_at is not None and k in self._pictures_at:
-                pic = tuple(t[self._pictures_at[k]] for t in self.pictures[:4])
+            slot = None if self._pictures_at is None else self._pictures_at.get(k)
+            pic = None if slot is None else tuple(t[slot] for t in self.pictures[:4])
             if capture:
                 if not self._fused_head:
                     self.noise.copy_(self.noise_all[k])
-                if self._graph is None:
-                    side = torch.cuda.Stream()
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):                  # warm-up outside the capture (lazy kernel attributes)
-                        self._iteration(self.noise, self.losses[k], rep, pic)
-                    torch.cuda.current_stream().wait_stream(side)
-                    self._graph = torch.cuda.CUDAGraph()
-                    self._graph_out, self._graph_report, self._graph_pictures = scratch, rep_scratch, pic_scratch
-                    with torch.cuda.graph(self._graph):
-                        self._iteration(self.noise, self._graph_out, self._graph_report, self._graph_pictures)
-                else:
-                    self._graph.replay()
-                    self.losses[k].copy_(self._graph_out)
-                    if rep is not None:
-                        rep.copy_(self._graph_report)
-                    if pic is not None:
-                        for dst, src in zip(pic, self._graph_pictures):
-                            dst.copy_(src)
+                self._graph.run(step)
+                self.losses[k].copy_(self._graph_out[0])
+                if rep is not None:
+                    rep.copy_(self._graph_out[1])
+                for dst, src in zip(pic or (), self._graph_out[2] or ()):
+                    dst.copy_(src)
             else:
                 self._iteration(self.noise_all[k], self.losses[k], rep, pic)
             self.k += 1
@@ -1528,39 +1548,19 @@ def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-
     return out
 
 
-def _one_room_arguments(observed, mask, S, dev, cuda):
-    """``observed`` / ``mask`` of the one-room loops, checked before anything is launched and brought to [1, S, S]"""
-    if observed is not None:
-        if not isinstance(observed, (tuple, list)) or len(observed) != 2 or not all(torch.is_tensor(t) for t in observed):
-            raise ValueError("observed is (depth [S, S] or [1, S, S] float32, labels likewise uint8)")
-        observed = tuple(t[None] if t.dim() == 2 else t for t in observed)
-        if cuda:
-            OB.ObservedTarget.check_tensors(observed[0], observed[1], (1, S, S), dev)
-        elif any(tuple(t.shape) != (1, S, S) or t.device != dev for t in observed) or observed[1].dtype != torch.uint8:
-            raise ValueError("observed: depth and uint8 labels of shape [%d, %d] on %s expected" % (S, S, dev))
-    if torch.is_tensor(mask) and mask.dim() == 2:
-        mask = mask[None]
-    check_mask(mask, (1, S, S), dev, observed)
-    return observed, mask
-
-
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,
                  learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None):
     """finetune_VAE's inner loop for ONE room (test_render_refine.py:265-359) on synthetic meshes.
     ``observed`` / ``mask``: as ``finetune_vae_fast``'s, on the boxes' device whichever it is - the target from ``observed_target_torch`` on
     the room's class tables, the loss from ``refinement_loss_masked``.
     Returns the list of per-iteration losses and the final (boxes_pred, angles_idx)."""
-    render_fn = render_fn or DR.scene_render
-    dev = boxes_gt.device
-    observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, cuda=False)
-    if observed is not None and bank is not None and bank.has_choice():
-        raise ValueError("observed targets show no meshes to retrieve: observed does not combine with a bank that leaves a choice")
+    render_fn, dev = render_fn or DR.scene_render, boxes_gt.device
+    observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, False, bank)
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
     model.eval()
-    with torch.no_grad():
-        mu, logvar = model.encoder(objs, triples, boxes_gt, angles_gt, attributes)
-    gen = torch.Generator(device="cpu").manual_seed(noise_seed)
-    z = (mu + torch.randn(mu.shape, generator=gen).to(dev) * torch.exp(0.5 * logvar)).detach().requires_grad_(True)
+    # (the noise rows: one randn(n) per iteration behind the z draw, which is the stream the reference draws inside its loop, :304)
+    z, noise_rows = room_start(model, dict(objs=objs, triples=triples, boxes=boxes_gt, angles=angles_gt, attributes=attributes), noise_seed, iters, dev)
+    z.requires_grad_(True)
     room_box = boxes_gt[-1].detach().clone()
     # target: the meshes retrieved for the ground truth (test_render_refine.py:319); iterates: those of iteration 0's boxes (:324-326)
     choose, models_gt, models_it, shell = bank.has_choice(), None, None, None
@@ -1574,10 +1574,8 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         else:
             _, chan, dch = DR.class_tables(ranges.keys())
             target, _ = OB.observed_target_torch(observed[0], observed[1], chan, dch, nch=DR.N_SCENE_CHANNELS)
-    valid = _valid_of(mask, target) if mask is not None else None
-    labels = target_labels(torch.where(valid[:, None] != 0, target, torch.zeros_like(target)) if valid is not None else target)
-    size_target = None                   # the sizes of the FIRST iterate, not the target's (test_render_refine.py:319-327: the target render's
-    #                                      sizes are "unused_sizes"; size_infos is what the first render of boxes_pred returns)
+    valid, labels = valid_and_labels(mask, target)
+    size_target = None                   # the sizes of the FIRST iterate (:319-327: size_infos), not the target's (its sizes are "unused_sizes")
     losses = []
     for k in range(iters):
         opt = torch.optim.SGD([{'params': [z]}, {'params': list(model.parameters()), 'lr': learning_rate / 10.0}], lr=2e-4,
@@ -1585,7 +1583,7 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         boxes_pred, angles_pred = model.decoder(z, objs, triples, attributes)
         boxes_pred.register_hook(fix_grad)
         boxes_pred = torch.cat([boxes_pred[:-1], boxes_gt[-1:]], 0)
-        idx = softargmax(angles_pred, sum_dim=1) + torch.randn(angles_pred.shape[0], generator=gen).to(dev) / 10.0
+        idx = softargmax(angles_pred, sum_dim=1) + noise_rows[k].to(dev) / 10.0
         idx.register_hook(quad_grad)
         idx = torch.cat([idx[:-1], angles_gt[-1:].float()], 0)
         if choose and models_it is None:
