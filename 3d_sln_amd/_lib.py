@@ -341,6 +341,8 @@ SIGNATURES = {
     "sln_layout_cuboid_iou": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f32p,
                                         C.c_void_p, C.c_void_p]),
     "sln_layout_overlap": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, c_i64p, C.c_void_p]),
+    "sln_layout_overlap_penalty": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                             C.c_void_p, c_f32p, c_f32p, C.c_void_p]),
     "sln_layout_plot": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "sln_layout_footprint_counts": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -9,7 +9,8 @@
   * ``measure_acc_l1_std`` - the whole mode: the nine figures the reference prints, read back once at the end;
   * ``cuboid_iou``    - the rotated-cuboid 3-D IoU of S layouts against the ground truth (testing/test_render_refine.py:78-116,360-368,
     testing/test_utils.py:7-40) with per-room means (sln_layout_cuboid_iou) - the figure of the refinement table;
-  * ``layout_overlap`` - how much of a layout's furniture interpenetrates: intersection volume and pair count (sln_layout_overlap).
+  * ``layout_overlap`` - how much of a layout's furniture interpenetrates: intersection volume and pair count (sln_layout_overlap);
+  * ``overlap_penalty`` - that volume per room as a differentiable loss term (sln_layout_overlap_penalty).
 
 The ``*_torch`` functions restate each kernel in torch ops for CPU tensors (the host-side tests), as ``sampling.layout_heatmap``
 does for the heat-map kernel.
@@ -205,6 +206,71 @@ def layout_overlap(boxes, angles, room_of_row, visible, thresh=0.0, vol=None, pa
     return vol, pairs
 
 
+def collide_rows(objs, vocab_names, room_cls):
+    """[O] bool: the rows whose interpenetration ``overlap_penalty`` counts by default - the class is not in DO_NOT_VIS and the row is
+    not a room row (``visible_rows`` keeps room rows; a room row's cuboid is the room itself)"""
+    return visible_rows(objs, vocab_names) & (objs.to(torch.int64) != int(room_cls))
+
+
+def _check_penalty_arguments(boxes, angles, room_of_row, collide):
+    _check_layouts(boxes)
+    S, O, _ = boxes.shape
+    if angles.shape != (S, O) or collide.shape != (O,):
+        raise ValueError("angles must be [S, O], collide [O]")
+    r = _check_rooms(room_of_row, O)
+    if O and int(torch.bincount(r).max()) > MAX_ROOM_ROWS:
+        raise ValueError("a room of more than %d rows" % MAX_ROOM_ROWS)
+
+
+def overlap_penalty_launch(boxes, angles, room_of_row, collide, room_id, n_rooms, weight=1.0, accumulate=False, penalty=None, grad_boxes=None,
+                           grad_angles=None):
+    """the one sln_layout_overlap_penalty launch on prepared device tensors (float32 contiguous layouts, int32 tables, uint8 ``collide``)
+    -> (penalty [S, n_rooms] float64 written, grad_boxes [S, O, 6], grad_angles [S, O] = weight * d penalty, written or added onto)"""
+    S, O, _ = boxes.shape
+    dev = boxes.device
+    penalty = torch.empty(S, int(n_rooms), dtype=torch.float64, device=dev) if penalty is None else penalty
+    if grad_boxes is None:
+        grad_boxes, grad_angles = torch.empty(S, O, 6, dtype=torch.float32, device=dev), torch.empty(S, O, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().sln_layout_overlap_penalty(_lib.ptr(boxes), _lib.ptr(angles), _lib.ptr(room_of_row), _lib.ptr(collide), _lib.ptr(room_id),
+                                                     int(n_rooms), S, O, float(weight), int(bool(accumulate)), _lib.ptr(penalty), _lib.ptr(grad_boxes),
+                                                     _lib.ptr(grad_angles), _lib.current_stream_ptr()), "sln_layout_overlap_penalty")
+    return penalty, grad_boxes, grad_angles
+
+
+class _OverlapPenaltyFn(torch.autograd.Function):
+    """penalty [S, n_rooms] float64 of boxes [S, O, 6] / angles [S, O]: the forward computes the gradients too (one launch on the device,
+    the torch restatement on CPU tensors), the backward scales every row by its room's incoming gradient"""
+
+    @staticmethod
+    def forward(ctx, boxes, angles, room_of_row, collide, room_id, n_rooms):
+        if boxes.is_cuda:
+            b, a = boxes.detach().float().contiguous(), angles.detach().float().contiguous()
+            pen, gb, ga = overlap_penalty_launch(b, a, room_of_row.to(torch.int32).contiguous(), collide.to(torch.uint8).contiguous(),
+                                                 room_id.to(torch.int32).contiguous(), n_rooms)
+        else:
+            pen, gb, ga = overlap_penalty_torch(boxes.detach(), angles.detach(), room_of_row, collide, room_id=room_id, n_rooms=n_rooms)
+        ctx.save_for_backward(gb, ga, room_id.to(torch.int64))
+        ctx.dtypes = (boxes.dtype, angles.dtype)
+        return pen
+
+    @staticmethod
+    def backward(ctx, gout):
+        gb, ga, rid = ctx.saved_tensors
+        up = gout[:, rid].to(gb.dtype)                                                   # [S, O]: the row's room's upstream gradient
+        return (gb * up[..., None]).to(ctx.dtypes[0]), (ga * up).to(ctx.dtypes[1]), None, None, None, None
+
+
+def overlap_penalty(boxes, angles, room_of_row, collide, room_id=None, n_rooms=None):
+    """boxes [S, O, 6], angles [S, O] (float bins) -> penalty [S, n_rooms] float64, differentiable in both: per room the summed
+    intersection volume of the pairs of rows with ``collide`` != 0 - what ``layout_overlap`` reports, as a loss term.  The
+    room rows' extents are constants and a room row's gradient is 0.  One sln_layout_overlap_penalty launch on the device;
+    ``overlap_penalty_torch`` on CPU tensors."""
+    _check_penalty_arguments(boxes, angles, room_of_row, collide)
+    if room_id is None:
+        room_id, n_rooms = _room_ids(room_of_row)
+    return _OverlapPenaltyFn.apply(boxes, angles, room_of_row, collide, room_id, int(n_rooms))
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # torch restatements (CPU tensors)
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -306,6 +372,83 @@ def layout_overlap_torch(boxes, angles, room_of_row, visible, thresh=0.0, dtype=
     i, j = i[ok], j[ok]
     iou, inter = _pair_iou(ring[:, i], h0[:, i], h1[:, i], ring[:, j], h0[:, j], h1[:, j])
     return inter.sum(1), (iou > thresh).sum(1), iou
+
+
+def quad_area_grad_torch(a, b):
+    """d quad_intersection_area(a, b) / d a [..., 4, 2], b fixed (quad_area_grad of csrc/layout_iou.hip): of the boundary of a ^ b only
+    the pieces of a's edges inside b move with a's vertices to first order.  Both rings in counter-clockwise order as the area
+    function brings them; edge p -> q of a (d = q - p) clipped to [s0, s1] of [0, 1] by b's four half planes (the inside rule >= 0),
+    w = (s1^2 - s0^2) / 2: dA/dp += (d.y, -d.x) ((s1 - s0) - w), dA/dq += (d.y, -d.x) w.  No quotient is formed where it is not used."""
+    a, b = torch.broadcast_tensors(a, b)
+    perm = [0, 3, 2, 1]
+    fa = (_shoelace(a) < 0)[..., None, None]
+    p = torch.where(fa, a[..., perm, :], a)
+    b0 = torch.where((_shoelace(b) < 0)[..., None, None], b[..., perm, :], b)
+    q, ed = torch.roll(p, -1, -2), torch.roll(b0, -1, -2) - b0
+    edge = lambda v: ed[..., None, :, 0] * (v[..., :, None, 1] - b0[..., None, :, 1]) - ed[..., None, :, 1] * (v[..., :, None, 0] - b0[..., None, :, 0])
+    f0, f1 = edge(p), edge(q)                                                            # [..., edge of a, edge of b]
+    in0, in1 = f0 >= 0, f1 >= 0
+    cross = (in0 != in1) & ~torch.isnan(f0) & ~torch.isnan(f1)
+    one, zero = torch.ones_like(f0), torch.zeros_like(f0)
+    t = torch.where(cross, f0, zero) / torch.where(cross, f0 - f1, one)
+    s1 = torch.where(cross & in0, t, one).min(-1).values
+    s0 = torch.where(cross & ~in0, t, zero).max(-1).values
+    live = ~(~(in0 & in1) & ~cross).any(-1) & (s1 > s0)
+    w = (s1 * s1 - s0 * s0) / 2
+    d = q - p
+    n = torch.stack([d[..., 1], -d[..., 0]], -1)
+    off = torch.zeros_like(w)
+    g = n * torch.where(live, (s1 - s0) - w, off)[..., None] + torch.roll(n * torch.where(live, w, off)[..., None], 1, -2)
+    return torch.where(fa, g[..., perm, :], g)
+
+
+def overlap_penalty_torch(boxes, angles, room_of_row, collide, dtype=torch.float64, room_id=None, n_rooms=None):
+    """The definition of ``overlap_penalty`` in torch ops on CPU tensors -> (penalty [S, n_rooms], grad_boxes [S, O, 6],
+    grad_angles [S, O]) in ``dtype``, NaN-safe: V_ij = A(ring_i, ring_j) * max(0, min(h1) - max(h0)) over the pairs of colliding rows of
+    one room; d A by ``quad_area_grad_torch``; the height factor's derivative with one half per row on an exact tie; a pair whose height
+    overlap is <= 0 contributes nothing; the chain through get_boxes' expressions with the room row's extent a constant."""
+    _check_penalty_arguments(boxes, angles, room_of_row, collide)
+    S, O, _ = boxes.shape
+    if room_id is None:
+        room_id, n_rooms = _room_ids(room_of_row)
+    b, ang = boxes.detach().to(dtype), angles.detach().to(dtype)
+    rr, rid = room_of_row.to(torch.int64), room_id.to(torch.int64)
+    ring, h0, h1 = cuboids_torch(b, ang, rr, dtype)
+    on = collide.bool()
+    i, j = torch.meshgrid(torch.arange(O), torch.arange(O), indexing="ij")
+    ok = (i != j) & (rr[i] == rr[j]) & on[i] & on[j]
+    i, j = i[ok], j[ok]                                                                  # ordered pairs: row i against its partner j
+    area = quad_intersection_area_torch(ring[:, i], ring[:, j])
+    hov = torch.minimum(h1[:, i], h1[:, j]) - torch.maximum(h0[:, i], h0[:, j])
+    live = hov > 0
+    hov = torch.where(live, hov, torch.zeros_like(hov))
+    area = torch.where(live, area, torch.zeros_like(area))
+    penalty = torch.zeros(S, int(n_rooms), dtype=dtype)
+    behind = j > i
+    penalty.index_add_(1, rid[i[behind]], (area * hov)[:, behind])
+    half = lambda x, y: torch.where(x < y, torch.ones_like(x), torch.where(x == y, torch.full_like(x, 0.5), torch.zeros_like(x)))
+    g_h1 = torch.zeros(S, O, dtype=dtype).index_add_(1, i, area * half(h1[:, i], h1[:, j]))
+    g_h0 = torch.zeros(S, O, dtype=dtype).index_add_(1, i, -area * half(h0[:, j], h0[:, i]))
+    gv = torch.zeros(S, O, 4, 2, dtype=dtype).index_add_(1, i, quad_area_grad_torch(ring[:, i], ring[:, j]) * hov[..., None, None])
+    # vertices and heights -> box[0:6], angle: vertex = R(theta) (+- half size) + centre, theta = -angle * float32(2 pi / 24)
+    k24 = float(np.float32(2.0 * float(np.pi) / 24.0))
+    ext = b[:, rr, 3:6]
+    theta = -ang * k24
+    c, s = torch.cos(theta)[..., None], torch.sin(theta)[..., None]
+    hx, hz = (b[..., 3] * ext[..., 0] - b[..., 0] * ext[..., 0]) / 2, (b[..., 5] * ext[..., 2] - b[..., 2] * ext[..., 2]) / 2
+    xs, zs = torch.stack([-hx, -hx, hx, hx], -1), torch.stack([-hz, hz, hz, -hz], -1)
+    gx, gy = gv[..., 0], gv[..., 1]
+    gxs, gzs = c * gx - s * gy, s * gx + c * gy
+    gcx, gcz = gx.sum(-1), gy.sum(-1)
+    gth = (gx * (-s * xs + c * zs) - gy * (c * xs + s * zs)).sum(-1)
+    gmnx, gmxx, gmnz, gmxz = gxs[..., 0] + gxs[..., 1], gxs[..., 2] + gxs[..., 3], gzs[..., 0] + gzs[..., 3], gzs[..., 1] + gzs[..., 2]
+    gb = torch.stack([ext[..., 0] * ((gmnx - gmxx + gcx) / 2), ext[..., 1] * g_h0, ext[..., 2] * ((gmnz - gmxz + gcz) / 2),
+                      ext[..., 0] * ((gmxx - gmnx + gcx) / 2), ext[..., 1] * g_h1, ext[..., 2] * ((gmxz - gmnz + gcz) / 2)], -1)
+    ga = -k24 * gth
+    room_row = (rr == torch.arange(O))
+    gb = torch.where(room_row[None, :, None], torch.zeros_like(gb), gb)
+    ga = torch.where(room_row[None], torch.zeros_like(ga), ga)
+    return penalty, gb, ga
 
 
 # (the restatements of the --measure_acc_l1_std kernels)

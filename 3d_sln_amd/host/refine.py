@@ -28,6 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from . import diff_render as DR
+from . import evaluate as EV
 from . import mesh_prep as MP
 from . import observe as OB
 from . import retrieve as RT
@@ -585,6 +586,53 @@ def check_observed(observed, shape, device, cuda=True, choice=False):
         raise ValueError("observed: depth and uint8 labels of shape %s on %s expected" % (list(shape), device))
 
 
+def check_overlap(overlap_weight, overlap_rows, rooms):
+    """the ``overlap_weight=`` / ``overlap_rows=`` arguments of the refinement entry points, refused before anything is launched.  ``rooms``:
+    [(rows, class_names)] per room; ``overlap_rows``: None, or per room None or a bool sequence over the room's rows.  -> None with the weight at
+    0 (nothing of the penalty exists), else per room the list of rows that collide: ``overlap_rows``' where given, otherwise the rows whose class
+    is neither in DO_NOT_VIS nor the room's (``evaluate.collide_rows``); the room row - the last one - never collides."""
+    w = float(overlap_weight)
+    if not w >= 0.0:
+        raise ValueError("overlap_weight must be >= 0, got %r" % (overlap_weight,))
+    if overlap_rows is not None and len(overlap_rows) != len(rooms):
+        raise ValueError("overlap_rows: one entry per room expected (None: the default rows of that room)")
+    out = []
+    for r, (n, names) in enumerate(rooms):
+        rows = overlap_rows[r] if overlap_rows is not None else None
+        if rows is not None:
+            rows = [bool(v) for v in (rows.tolist() if torch.is_tensor(rows) else rows)]
+            if len(rows) != n:
+                raise ValueError("overlap_rows: room %d has %d rows, got %d flags" % (r, n, len(rows)))
+        elif w > 0.0 and len(names) != n:
+            raise ValueError("overlap_weight > 0 needs class_names that name every row of a room, or overlap_rows")
+        elif w > 0.0:
+            rows = [nm not in DO_NOT_VIS and nm != "__room__" for nm in names]
+        if w > 0.0 and n > EV.MAX_ROOM_ROWS:
+            raise ValueError("overlap_weight > 0: a room of more than %d rows" % EV.MAX_ROOM_ROWS)
+        if rows:
+            rows[-1] = False
+        out.append(rows)
+    return out if w > 0.0 else None
+
+
+def _one_room_overlap(overlap_weight, overlap_rows, class_names, n, dev):
+    """the one-room loops' checked penalty arguments -> None (weight 0), or the tensors of ``_overlap_term``: (collide uint8 [n], room_of_row
+    int32 [n], room_id int32 [n]) on ``dev``"""
+    rows = check_overlap(overlap_weight, None if overlap_rows is None else [overlap_rows], [(n, list(class_names))])
+    if rows is None:
+        return None
+    return (torch.tensor(rows[0], dtype=torch.uint8, device=dev), torch.full((n,), n - 1, dtype=torch.int32, device=dev),
+            torch.zeros(n, dtype=torch.int32, device=dev))
+
+
+def _overlap_term(boxes_full, idx, tables, overlap_weight):
+    """overlap_weight * penalty of one room's layout as a float32 scalar that autograd follows into ``boxes_full`` [n, 6] and ``idx`` [n]
+    (``evaluate.overlap_penalty`` on checked tables: nothing is read back)"""
+    collide, room_of_row, room_id = tables
+    pen = EV._OverlapPenaltyFn.apply(boxes_full[None], idx[None], room_of_row, collide, room_id, 1)[0, 0]
+    return (pen * float(overlap_weight)).float()
+
+
 class _RefineLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, rl):
@@ -1024,7 +1072,8 @@ def _one_room_arguments(observed, mask, S, dev, cuda, bank=None):
 
 
 def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, bank=None, learning_rate=1e-4,
-                      noise_seed=13, image_size=256, capture=False, log=None, fused_loss=True, fused_head=True, observed=None, mask=None):
+                      noise_seed=13, image_size=256, capture=False, log=None, fused_loss=True, fused_head=True, observed=None, mask=None,
+                      overlap_weight=0.0, overlap_rows=None):
     """``finetune_vae`` with the batched ``RefineScene`` and no per-iteration python optimiser objects: the reference builds a
     NEW SGD(momentum=0.1, nesterov) every iteration (test_render_refine.py:286-292), so its step is exactly
     ``p -= lr * (1 + momentum) * grad``; that closed form is applied to ``z`` (lr 2e-4) and to the flat parameter buffer
@@ -1036,10 +1085,12 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
     ``observed``: None, or ``(depth [S, S] or [1, S, S] float32, labels likewise uint8)`` on the device - the target is built from this
     observation with one ``ObservedTarget`` call on the room's class tables instead of rendered from ``boxes_gt`` (``RefineBatch``'s
     ``observed``, for one room).  ``mask``: None, "readings" or a uint8 / bool tensor [S, S] or [1, S, S] - the loss under a validity mask
-    (``RefineBatch``'s ``mask``).
+    (``RefineBatch``'s ``mask``).  ``overlap_weight`` / ``overlap_rows`` (a bool sequence over the rows): ``RefineBatch``'s, for one room - the loss
+    gains ``overlap_weight * evaluate.overlap_penalty`` of the iterate, followed by autograd.
     Returns (losses [iters] tensor on the device, (boxes_pred, angle_idx)).  ``log``: called once per iteration, the captured one included."""
     dev, S = boxes_gt.device, int(image_size)
     observed, mask = _one_room_arguments(observed, mask, S, dev, True, bank)
+    overlap = _one_room_overlap(overlap_weight, overlap_rows, class_names, int(boxes_gt.shape[0]), dev)
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
     room = dict(objs=objs, triples=triples, boxes=boxes_gt, angles=angles_gt, attributes=attributes, class_names=class_names)
     model.eval()
@@ -1094,6 +1145,8 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
             loss, _, _ = refinement_loss_masked(image, target, labels, size_loss, valid)
         else:
             loss, _, _ = refinement_loss(image, target, labels, size_loss)
+        if overlap is not None:
+            loss = loss + _overlap_term(boxes_full, idx, overlap, overlap_weight)
         z.grad = None
         if not fused_head:
             flat_grad.zero_()
@@ -1171,13 +1224,24 @@ class RefineBatch:
     are not), or a uint8 / bool tensor [R, S, S] on the device (non-zero: valid; works with rendered targets too).  The loss then runs
     under the validity mask (``RefineLoss(valid=)``): the depth term and its gradient over the valid pooled pixels only, the
     labels of the others ignored, ``report``'s depth_l1 over the valid image pixels.  ``mask_status`` [R] int32 (None without a mask):
-    bit 0 - the room has no valid pooled pixel (its depth term is 0), bit 1 - one of its scales keeps no label."""
+    bit 0 - the room has no valid pooled pixel (its depth term is 0), bit 1 - one of its scales keeps no label.
+
+    ``overlap_weight``: 0.0 (default: nothing below exists, the launches are those above), or a weight > 0 - the loss of a room becomes
+    ``... + 2 size_loss + overlap_weight * penalty`` with ``penalty`` the summed intersection volume of the room's colliding furniture
+    (``evaluate.overlap_penalty``): what keeps an object whose hidden side the target does not show out of its neighbour.  The head
+    then runs in launches of its own (the route of rooms above 128 rows) and one sln_layout_overlap_penalty call over all rooms' rows adds the
+    penalty's gradient onto the placement's in front of the head's backward (the ``fix_grad`` / ``quad_grad`` hooks see it); ``overlap``
+    [iters, R] float64 holds the unweighted penalty of every iteration (None with the weight at 0).  ``overlap_rows``: None, or per room None
+    or a bool sequence over the room's rows that replaces the default choice of colliding rows (the class is not in DO_NOT_VIS; needs
+    ``class_names`` that name every row) - to exempt a lamp that a graph places "inside" a shelf; a room row never collides."""
 
     def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
-                 retrieve=False, observed=None, mask=None):
+                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None):
         self.model, self.R, self.iters, self.lr, self.S = model, len(rooms), int(iters), float(learning_rate), int(image_size)
         dev = model.flat_params.device
         self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev)      # every refusal, in front of the first launch
+        self.overlap_weight = float(overlap_weight)
+        self._collide_rows = check_overlap(overlap_weight, overlap_rows, [(int(rm["objs"].shape[0]), list(rm["class_names"])) for rm in rooms])
         self._bank = bank or MeshBank([n for n in set(n for rm in rooms for n in rm["class_names"]) if n not in DO_NOT_VIS and n != "__room__"], dev)
         self._retrieve, self._class_names = bool(retrieve), [list(rm["class_names"]) for rm in rooms]
         self.rows = [int(rm["objs"].shape[0]) for rm in rooms]
@@ -1309,7 +1373,7 @@ class RefineBatch:
         R, N, f32 = self.R, self.N, dict(dtype=torch.float32, device=dev)
         self.room_of_row = torch.cat([torch.full((n,), r, dtype=torch.int32) for r, n in enumerate(self.rows)]).to(dev)
         self.last_row = torch.tensor([a + n - 1 for a, n in zip(self.row0, self.rows)], dtype=torch.int32, device=dev)
-        if self._report_at is not None or self._retrieve:
+        if self._report_at is not None or self._retrieve or self._collide_rows is not None:
             self._room_row = self.last_row[self.room_of_row.long()].contiguous()         # [N]: every row's room row
         self.boxes, self.idx = torch.empty(N, 6, **f32), torch.empty(N, **f32)
         self.g_boxes, self.g_idx = torch.empty(N, 6, **f32), torch.empty(N, **f32)
@@ -1317,7 +1381,13 @@ class RefineBatch:
         self.size_loss = torch.zeros(R, **f32)
         self.g_size_loss = torch.full((1,), 2.0, **f32)               # loss = ... + 2 * size_loss (test_render_refine.py:350-352)
         # the head inside the two placement launches (SlnPlacementRoom's head fields; iteration k's noise: row k of noise_all, k a device counter)
-        self._fused_head = self.n_max <= 128 and not os.environ.get("SLN_REFINE_SEPARATE_HEAD")
+        # (the penalty's gradient joins g_boxes / g_idx between the placement backward and the head's: the head in launches of its own)
+        self._fused_head = self.n_max <= 128 and not os.environ.get("SLN_REFINE_SEPARATE_HEAD") and self._collide_rows is None
+        self.overlap = None
+        if self._collide_rows is not None:
+            self._collide = torch.tensor([v for rows in self._collide_rows for v in rows], dtype=torch.uint8, device=dev)
+            self.overlap = torch.zeros(max(self.iters, 1), R, dtype=torch.float64, device=dev)
+            self._overlap_w64, self._overlap_w32 = torch.zeros(R, dtype=torch.float64, device=dev), torch.zeros(R, **f32)
         self._noise_step = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def _image_and_loss_buffers(self, dev):
@@ -1436,9 +1506,10 @@ class RefineBatch:
         _lib.check(_lib.lib().sln_vae_group_launches(self._group, C.byref(f), C.byref(b), C.byref(s1)), "sln_vae_group_launches")
         return dict(decoder_forward=f.value, decoder_backward=b.value, single_room_fallbacks=s1.value)
 
-    def _iteration(self, noise, out, report_out=None, pictures_out=None):
+    def _iteration(self, noise, out, report_out=None, pictures_out=None, overlap_out=None):
         """one iteration of every room on the current stream; ``noise`` [N], ``out`` [R] receives the rooms' losses, ``report_out``
-        [R, 3] (a reported iteration) the report, ``pictures_out`` (a pictured iteration) = (depth8, labels, rgb, status) of one slot"""
+        [R, 3] (a reported iteration) the report, ``pictures_out`` (a pictured iteration) = (depth8, labels, rgb, status) of one slot,
+        ``overlap_out`` [R] float64 (with the penalty on) the rooms' unweighted penalties"""
         L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
         N, R, na, S = self.N, self.R, self.model.Nangle, self.S
         self._forward_to_placement(noise)
@@ -1462,6 +1533,15 @@ class RefineBatch:
         _lib.check(L.sln_scene_backward(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 1e-3, P(self.scene_ws),
                                         P(self.g_image), P(self.g_faces), st), "sln_scene_backward")
         _lib.check(L.sln_place_backward_rooms(P(self._place_tab), R, self.n_max, st), "sln_place_backward_rooms")
+        if overlap_out is not None:
+            # all rooms' rows as ONE layout of R rooms; += onto the gradients the placement backward has just written (every row of every room,
+            # zeros for rows without a visible object: csrc/placement.hip place_backward_body), in front of the head's backward and its two hooks
+            _lib.check(L.sln_layout_overlap_penalty(P(self.boxes), P(self.idx), P(self._room_row), P(self._collide), P(self.room_of_row), R, 1, N,
+                                                    self.overlap_weight, 1, P(overlap_out), P(self.g_boxes), P(self.g_idx), st),
+                       "sln_layout_overlap_penalty")
+            torch.mul(overlap_out, self.overlap_weight, out=self._overlap_w64)            # loss = ... + 2 size_loss + float32(weight * penalty)
+            self._overlap_w32.copy_(self._overlap_w64)
+            out.add_(self._overlap_w32)
         if not self._fused_head:
             _lib.check(L.sln_refine_head_backward_rooms(N, na, P(self.room_of_row), P(self.last_row), P(self.angles_pred), P(self.g_boxes), P(self.g_idx),
                                                         2.0, P(self.d_boxes_pred), 8, P(self.d_angles_pred), st), "sln_refine_head_backward_rooms")
@@ -1483,7 +1563,8 @@ class RefineBatch:
                 raise ValueError("run(capture=True) replays one graph for every iteration: %s must be 'all' or None" % name)
         if capture and self._graph_out is None:       # what the graph writes: copied to the iteration's own rows after every captured step
             self._graph_out = (self.loss_out.new_empty(self.R), self.loss_out.new_empty(self.R, 3) if self._report_all else None,
-                               tuple(torch.empty_like(t[0]) for t in self.pictures[:4]) if self._pictures_all else None)
+                               tuple(torch.empty_like(t[0]) for t in self.pictures[:4]) if self._pictures_all else None,
+                               torch.empty_like(self.overlap[0]) if self.overlap is not None else None)
         if n > 0 and self.k == 0:
             self._first_iterate_sizes()
             if self._retrieve and self.models is None:
@@ -1503,8 +1584,10 @@ class RefineBatch:
                     rep.copy_(self._graph_out[1])
                 for dst, src in zip(pic or (), self._graph_out[2] or ()):
                     dst.copy_(src)
+                if self.overlap is not None:
+                    self.overlap[k].copy_(self._graph_out[3])
             else:
-                self._iteration(self.noise_all[k], self.losses[k], rep, pic)
+                self._iteration(self.noise_all[k], self.losses[k], rep, pic, self.overlap[k] if self.overlap is not None else None)
             self.k += 1
         return self.losses[:self.k]
 
@@ -1530,13 +1613,13 @@ class RefineBatch:
 
 
 def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None,
-                            pictures=None, retrieve=False, observed=None, mask=None):
+                            pictures=None, retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
     noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
     ``report`` is given, the report [iters, R, 3] as a further element; only when ``pictures`` is given, the pair
-    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask``: as ``RefineBatch``'s."""
+    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask`` / ``overlap_weight`` / ``overlap_rows``: as ``RefineBatch``'s."""
     rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report,
-                     pictures=pictures, retrieve=retrieve, observed=observed, mask=mask)
+                     pictures=pictures, retrieve=retrieve, observed=observed, mask=mask, overlap_weight=overlap_weight, overlap_rows=overlap_rows)
     try:
         out = (rb.run(capture=capture).clone(), [(b.clone(), i.clone()) for b, i in rb.results()])
         if report is not None:
@@ -1549,13 +1632,15 @@ def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-
 
 
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,
-                 learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None):
+                 learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None):
     """finetune_VAE's inner loop for ONE room (test_render_refine.py:265-359) on synthetic meshes.
     ``observed`` / ``mask``: as ``finetune_vae_fast``'s, on the boxes' device whichever it is - the target from ``observed_target_torch`` on
-    the room's class tables, the loss from ``refinement_loss_masked``.
+    the room's class tables, the loss from ``refinement_loss_masked``.  ``overlap_weight`` / ``overlap_rows``: as ``finetune_vae_fast``'s (on CPU
+    tensors the penalty is ``evaluate.overlap_penalty_torch``).
     Returns the list of per-iteration losses and the final (boxes_pred, angles_idx)."""
     render_fn, dev = render_fn or DR.scene_render, boxes_gt.device
     observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, False, bank)
+    overlap = _one_room_overlap(overlap_weight, overlap_rows, class_names, int(boxes_gt.shape[0]), dev)
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
     model.eval()
     # (the noise rows: one randn(n) per iteration behind the z draw, which is the stream the reference draws inside its loop, :304)
@@ -1596,6 +1681,8 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
             loss, dl, sl = refinement_loss_masked(image, target, labels, size_loss, valid)
         else:
             loss, dl, sl = refinement_loss(image, target, labels, size_loss)
+        if overlap is not None:
+            loss = loss + _overlap_term(boxes_pred, idx, overlap, overlap_weight)
         opt.zero_grad()
         loss.backward()
         opt.step()

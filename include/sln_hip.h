@@ -968,6 +968,28 @@ int sln_layout_cuboid_iou(const float* boxes, const float* angles, const float* 
  * of whole rooms; a room of more than 1024 rows (or a room_of_row table that is not as described above) gives vol_out = NaN. */
 int sln_layout_overlap(const float* boxes, const float* angles, const int32_t* room_of_row, const unsigned char* visible, int S, int O,
                        float thresh, double* vol_out, int64_t* pairs_out, void* stream);
+/* The same quantity as a loss term with a gradient: penalty_out[s][room_id[room row]] (float64 [S, n_rooms], WRITTEN) = the sum over
+ * the unordered pairs (i < j) of rows of one room with collide[row] != 0 (uint8 [O]) of V_ij = A(ring_i, ring_j) * max(0, min(h1) -
+ * max(h0)) - the intersection volumes sln_layout_overlap sums, cuboids (testing/test_render_refine.py:90-110), room_of_row and room_id
+ * as in sln_layout_cuboid_iou - and grad_boxes [S, O, 6] / grad_angles [S, O] = weight * d penalty / d (boxes, angles).  The extent
+ * (the room row's [3:6]) is a constant: the gradient of a room row and of a row that does not collide is exactly 0.  d A / d ring_a
+ * with ring b fixed: both rings in counter-clockwise order, every edge p -> q of a (d = q - p) clipped to [s0, s1] of [0, 1] by b's
+ * four half planes (the inside rule of the area function), w = (s1^2 - s0^2) / 2: dA/dp += (d.y, -d.x) ((s1 - s0) - w), dA/dq +=
+ * (d.y, -d.x) w.  Heights: the derivative of max(0, min(.,.) - max(.,.)), one half to each row on an exact tie (torch.minimum /
+ * torch.maximum); nothing from a pair whose height overlap is <= 0.  Then through the corner expressions to box[0:6] and angle.
+ * accumulate = 0 writes every element of the two gradients (zeros for rows that take no part), 1 adds onto what is there with one
+ * float32 add per element.  One launch in the frame of sln_layout_overlap (cuboids staged in LDS in tiles of whole rooms; the tiles
+ * of a layout are dealt to several workgroups): a row walks all colliding partners of its room - four adjacent lanes split the list
+ * and meet in a fixed butterfly - and one lane owns its seven values (no atomics); the value comes from the partners behind the
+ * row, the per-room sum runs in fp64 in row order with one writer per (layout, room): bit-identical from call to call, and a room's
+ * bits do not depend on the rooms around it.  No allocation, no synchronisation: legal inside a capture.  A room of more than 1024
+ * rows (or a broken room_of_row table) gives a NaN penalty - for it and the rooms behind it - and zero gradients.  Finite input gives
+ * finite gradients; a NaN input may give
+ * NaN in its own room's outputs only.  SLN_E_BADARG: a null pointer, a negative size, n_rooms < 1, !(weight >= 0), accumulate not
+ * 0 or 1. */
+int sln_layout_overlap_penalty(const float* boxes, const float* angles, const int32_t* room_of_row, const unsigned char* collide,
+                               const int32_t* room_id, int n_rooms, int S, int O, float weight, int accumulate, double* penalty_out,
+                               float* grad_boxes, float* grad_angles, void* stream);
 /* The top-down picture of testing/test_plot2d.py:9-141 (plot2d) for S layouts x n_rooms rooms in one launch.  boxes [S, O, 6], angles
  * [S, O], room_of_row and room_id (int32 [O]) as in sln_layout_cuboid_iou.  A row's ring is the (x, z) corners of the cuboid above
  * (:88-110 are the statements of get_boxes).  rank (int32 [O]) is the class's index in nyu_class_order (:25-29, at most 127), < 0 for
