@@ -12,6 +12,8 @@
 // where / flip and their autograd nodes), a third of the iteration.  Here: one kernel each way.  Backward runs one workgroup
 // per object over that object's faces (the face list is grouped by object), reduces d centre (3) and d A (3x3) in
 // registers / LDS and applies the chain rule to the box row and the angle - no atomics, deterministic.
+// The *_views kernels project one room's placement through V cameras (several target views per room): a face is placed once and
+// projected, culled and stored per view; the views' adjoints sum in world space into the same twelve accumulators.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -54,19 +56,22 @@ __device__ __forceinline__ ObjXform object_xform(const SlnPlacement& P, const fl
 
 struct Corner { float u, v, z; float x, y; };      // ndc + camera-space coordinates
 
-__device__ __forceinline__ Corner project(const SlnPlacement& P, const float p[3]) {
+// `K`, `R`, `t`: the camera - the descriptor's own (sln_place_*), or one row of a SlnPlacementCamera table (sln_place_*_views)
+__device__ __forceinline__ Corner project(const SlnPlacement& P, const float* __restrict__ K, const float* __restrict__ R,
+                                          const float* __restrict__ t, const float p[3]) {
   Corner c;
-  c.x = p[0] * P.R[0] + p[1] * P.R[1] + p[2] * P.R[2] + P.t[0];
-  c.y = p[0] * P.R[3] + p[1] * P.R[4] + p[2] * P.R[5] + P.t[1];
-  c.z = p[0] * P.R[6] + p[1] * P.R[7] + p[2] * P.R[8] + P.t[2];
+  c.x = p[0] * R[0] + p[1] * R[1] + p[2] * R[2] + t[0];
+  c.y = p[0] * R[3] + p[1] * R[4] + p[2] * R[5] + t[1];
+  c.z = p[0] * R[6] + p[1] * R[7] + p[2] * R[8] + t[2];
   const float os = P.orig_size;
   const float xh = c.x / (c.z + P.proj_eps), yh = c.y / (c.z + P.proj_eps);
-  float u = xh * P.K[0] + yh * P.K[1] + P.K[2];
-  float v = os - (xh * P.K[3] + yh * P.K[4] + P.K[5]);
+  float u = xh * K[0] + yh * K[1] + K[2];
+  float v = os - (xh * K[3] + yh * K[4] + K[5]);
   c.u = 2.f * (u - os / 2.f) / os;
   c.v = 2.f * (v - os / 2.f) / os;
   return c;
 }
+__device__ __forceinline__ Corner project(const SlnPlacement& P, const float p[3]) { return project(P, P.K, P.R, P.t, p); }
 
 __device__ __forceinline__ int object_of_face(const SlnPlacement& P, int f) {
   int k = 0;                                        // n_vis is a dozen: linear search over the range table
@@ -74,10 +79,32 @@ __device__ __forceinline__ int object_of_face(const SlnPlacement& P, int f) {
   return k;                                         // == n_vis: room shell
 }
 
-__device__ __forceinline__ void place_forward_body(const SlnPlacement& P, const float* __restrict__ boxes, const float* __restrict__ angles,
-                                                   const float* __restrict__ size_target, float* __restrict__ fxyz,
-                                                   float* __restrict__ sizes, float* __restrict__ size_loss) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+// corner `vi` of a face of object k (k == n_vis: the room shell, whose vertices are in room coordinates already) in world space
+__device__ __forceinline__ void place_corner(const SlnPlacement& P, const ObjXform& x, int k, int vi, float p[3]) {
+  if (k < P.n_vis) {
+    const float* m = P.model_v + 3L * vi;             // vi indexes the flattened [n_vis * Vm] model table
+#pragma unroll
+    for (int j = 0; j < 3; ++j) p[j] = x.A[3 * j] * m[0] + x.A[3 * j + 1] * m[1] + x.A[3 * j + 2] * m[2] + x.tr[j];
+  } else {
+    const float* m = P.shell_v + 3L * (vi - P.n_vis * P.Vm);
+    p[0] = m[0]; p[1] = m[1]; p[2] = m[2];
+  }
+}
+
+// a projected face and its fill_back copy (corners (2, 1, 0)) into a [2F, 3, 3] face buffer; a culled face collapses to (0, 0, 0)
+__device__ __forceinline__ void store_face(const SlnPlacement& P, const Corner c[3], bool cull, int f, float* __restrict__ fxyz) {
+  float* o0 = fxyz + 9L * f;
+  float* o1 = fxyz + 9L * (P.F + f);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const float u = cull ? 0.f : c[q].u, v = cull ? 0.f : c[q].v, z = cull ? 0.f : c[q].z;
+    o0[3 * q] = u; o0[3 * q + 1] = v; o0[3 * q + 2] = z;
+    o1[3 * (2 - q)] = u; o1[3 * (2 - q) + 1] = v; o1[3 * (2 - q) + 2] = z;
+  }
+}
+
+__device__ __forceinline__ void place_sizes(const SlnPlacement& P, const float* __restrict__ boxes, const float* __restrict__ angles,
+                                            const float* __restrict__ size_target, float* __restrict__ sizes, float* __restrict__ size_loss) {
   if (blockIdx.x == 0 && threadIdx.x < 64) {        // sizes and the size loss: one wavefront
     float l = 0.f;
     for (int k = threadIdx.x; k < P.n_vis; k += 64) {
@@ -93,6 +120,13 @@ __device__ __forceinline__ void place_forward_body(const SlnPlacement& P, const 
     for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, 64);
     if (threadIdx.x == 0) size_loss[0] = l;
   }
+}
+
+__device__ __forceinline__ void place_forward_body(const SlnPlacement& P, const float* __restrict__ boxes, const float* __restrict__ angles,
+                                                   const float* __restrict__ size_target, float* __restrict__ fxyz,
+                                                   float* __restrict__ sizes, float* __restrict__ size_loss) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  place_sizes(P, boxes, angles, size_target, sizes, size_loss);
   if (f >= P.F) return;
   const int k = object_of_face(P, f);
   ObjXform x;
@@ -101,26 +135,41 @@ __device__ __forceinline__ void place_forward_body(const SlnPlacement& P, const 
   bool cull = false;
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
-    const int vi = P.faces[3 * f + q];
     float p[3];
-    if (k < P.n_vis) {
-      const float* m = P.model_v + 3L * vi;           // vi indexes the flattened [n_vis * Vm] model table
-#pragma unroll
-      for (int j = 0; j < 3; ++j) p[j] = x.A[3 * j] * m[0] + x.A[3 * j + 1] * m[1] + x.A[3 * j + 2] * m[2] + x.tr[j];
-    } else {
-      const float* m = P.shell_v + 3L * (vi - P.n_vis * P.Vm);
-      p[0] = m[0]; p[1] = m[1]; p[2] = m[2];
-    }
+    place_corner(P, x, k, P.faces[3 * f + q], p);
     c[q] = project(P, p);
     cull = cull || c[q].z < P.cull_eps;
   }
-  float* o0 = fxyz + 9L * f;
-  float* o1 = fxyz + 9L * (P.F + f);
+  store_face(P, c, cull, f, fxyz);
+}
+
+// Several target views per room: image b = room * V + view.  A lane places its face once - the placement does not depend on the
+// view - and walks the views upwards: project through the view's camera (workgroup-uniform, read from the table), cull, store
+// into the view's face buffer, `view_stride` floats behind the previous one.  No head here: `boxes` / `angles` are read.
+__global__ __launch_bounds__(256) void place_forward_views_kernel(const SlnPlacementRoom* __restrict__ rooms,
+                                                                  const SlnPlacementCamera* __restrict__ cams, int V, long view_stride) {
+  const SlnPlacementRoom& r = rooms[blockIdx.y];
+  const SlnPlacement& P = r.P;
+  if ((int)blockIdx.x * 256 >= P.F && blockIdx.x != 0) return;
+  place_sizes(P, r.boxes, r.angles, r.size_target, r.sizes, r.size_loss);
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= P.F) return;
+  const int k = object_of_face(P, f);
+  ObjXform x;
+  if (k < P.n_vis) x = object_xform(P, r.boxes, r.angles, k);
+  float p[3][3];
 #pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const float u = cull ? 0.f : c[q].u, v = cull ? 0.f : c[q].v, z = cull ? 0.f : c[q].z;
-    o0[3 * q] = u; o0[3 * q + 1] = v; o0[3 * q + 2] = z;
-    o1[3 * (2 - q)] = u; o1[3 * (2 - q) + 1] = v; o1[3 * (2 - q) + 2] = z;
+  for (int q = 0; q < 3; ++q) place_corner(P, x, k, P.faces[3 * f + q], p[q]);
+  const SlnPlacementCamera* cam = cams + (long)blockIdx.y * V;
+  for (int v = 0; v < V; ++v) {
+    Corner c[3];
+    bool cull = false;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      c[q] = project(P, cam[v].K, cam[v].R, cam[v].t, p[q]);
+      cull = cull || c[q].z < P.cull_eps;
+    }
+    store_face(P, c, cull, f, r.faces_out + v * view_stride);
   }
 }
 
@@ -166,19 +215,57 @@ __global__ __launch_bounds__(256) void place_forward_rooms_kernel(const SlnPlace
   place_forward_body(r.P, boxes, angles, r.size_target, r.faces_out, r.sizes, r.size_loss);
 }
 
+// the row's visible object, -1 for a row without one: its gradients are zeros, written here
+__device__ __forceinline__ int object_of_row(const SlnPlacement& P, int row, float* __restrict__ g_boxes, float* __restrict__ g_angles) {
+  int k = -1;
+  for (int q = 0; q < P.n_vis; ++q) k = P.vis[q] == row ? q : k;
+  if (k < 0) {
+    if (threadIdx.x < 6) g_boxes[6 * row + threadIdx.x] = 0.f;
+    if (threadIdx.x == 6) g_angles[row] = 0.f;
+  }
+  return k;
+}
+
+// adjoint of one visible face of object k seen through the camera (K, R): corners 0..2 of `gf` [2F, 3, 3] (the face and its fill_back
+// copy) back through project() into world space - where the cameras of several views meet - and on into d centre (3), d A (3x3)
+__device__ __forceinline__ void face_adjoint(const SlnPlacement& P, const float* __restrict__ K, const float* __restrict__ R, const Corner c[3],
+                                             const float* __restrict__ gf, int f, const float* __restrict__ mc, float s2, float acc[12]) {
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const float* a = gf + 9L * f + 3 * q;
+    const float* b = gf + 9L * (P.F + f) + 3 * (2 - q);
+    const float gu = a[0] + b[0], gv = a[1] + b[1], gz = a[2] + b[2];
+    const float iz = 1.f / (c[q].z + P.proj_eps);
+    const float gxh = s2 * (gu * K[0] - gv * K[3]);
+    const float gyh = s2 * (gu * K[1] - gv * K[4]);
+    const float gx = gxh * iz, gy = gyh * iz;
+    const float gzc = gz - (gxh * c[q].x + gyh * c[q].y) * iz * iz;
+    float gp[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gp[j] = gx * R[j] + gy * R[3 + j] + gzc * R[6 + j];
+    const float* m = P.model_v + 3L * P.faces[3 * f + q];
+    const float d[3] = {m[0] - mc[0], m[1] - mc[1], m[2] - mc[2]};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      acc[j] += gp[j];
+#pragma unroll
+      for (int e = 0; e < 3; ++e) acc[3 + 3 * j + e] += gp[j] * d[e];
+    }
+  }
+}
+
+__device__ __forceinline__ void place_backward_reduce(const SlnPlacement& P, const ObjXform& x, int k, int row, const float acc[12],
+                                                      const float* __restrict__ size_target, const float* __restrict__ g_size_loss,
+                                                      float* __restrict__ g_boxes, float* __restrict__ g_angles);
+
 // one workgroup per row of `boxes`; rows without a visible object get zero gradients
 __device__ __forceinline__ void place_backward_body(const SlnPlacement& P, const float* __restrict__ boxes, const float* __restrict__ angles,
                                                     const float* __restrict__ size_target, const float* __restrict__ gf,
                                                     const float* __restrict__ g_size_loss, float* __restrict__ g_boxes,
                                                     float* __restrict__ g_angles) {
   const int row = blockIdx.x;
-  int k = -1;
-  for (int q = 0; q < P.n_vis; ++q) k = P.vis[q] == row ? q : k;
-  if (k < 0) {
-    if (threadIdx.x < 6) g_boxes[6 * row + threadIdx.x] = 0.f;
-    if (threadIdx.x == 6) g_angles[row] = 0.f;
-    return;
-  }
+  const int k = object_of_row(P, row, g_boxes, g_angles);
+  if (k < 0) return;
   const ObjXform x = object_xform(P, boxes, angles, k);
   float acc[12];                                     // d centre (3), d A (3x3, row-major)
 #pragma unroll
@@ -190,36 +277,56 @@ __device__ __forceinline__ void place_backward_body(const SlnPlacement& P, const
     bool cull = false;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      const float* m = P.model_v + 3L * P.faces[3 * f + q];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) p[q][j] = x.A[3 * j] * m[0] + x.A[3 * j + 1] * m[1] + x.A[3 * j + 2] * m[2] + x.tr[j];
+      place_corner(P, x, k, P.faces[3 * f + q], p[q]);
       c[q] = project(P, p[q]);
       cull = cull || c[q].z < P.cull_eps;
     }
     if (cull) continue;
+    face_adjoint(P, P.K, P.R, c, gf, f, mc, s2, acc);
+  }
+  place_backward_reduce(P, x, k, row, acc, size_target, g_size_loss, g_boxes, g_angles);
+}
+
+// Several target views per room (see place_forward_views_kernel): the adjoints of the views' cameras sum in world space, into the same
+// twelve accumulators - per face the corners are placed once, then the views in ascending order, a view that culls the face skipped.
+__global__ __launch_bounds__(256) void place_backward_views_kernel(const SlnPlacementRoom* __restrict__ rooms,
+                                                                   const SlnPlacementCamera* __restrict__ cams, int V, long view_stride) {
+  const SlnPlacementRoom& r = rooms[blockIdx.y];
+  const SlnPlacement& P = r.P;
+  if ((int)blockIdx.x >= P.n) return;
+  const int row = blockIdx.x;
+  const int k = object_of_row(P, row, r.grad_boxes, r.grad_angles);
+  if (k < 0) return;
+  const ObjXform x = object_xform(P, r.boxes, r.angles, k);
+  float acc[12];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const float* a = gf + 9L * f + 3 * q;
-      const float* b = gf + 9L * (P.F + f) + 3 * (2 - q);
-      const float gu = a[0] + b[0], gv = a[1] + b[1], gz = a[2] + b[2];
-      const float iz = 1.f / (c[q].z + P.proj_eps);
-      const float gxh = s2 * (gu * P.K[0] - gv * P.K[3]);
-      const float gyh = s2 * (gu * P.K[1] - gv * P.K[4]);
-      const float gx = gxh * iz, gy = gyh * iz;
-      const float gzc = gz - (gxh * c[q].x + gyh * c[q].y) * iz * iz;
-      float gp[3];
+  for (int j = 0; j < 12; ++j) acc[j] = 0.f;
+  const float* mc = P.mcenter + 3 * k;
+  const float s2 = 2.f / P.orig_size;
+  const SlnPlacementCamera* cam = cams + (long)blockIdx.y * V;
+  for (int f = P.obj_face_ptr[k] + threadIdx.x; f < P.obj_face_ptr[k + 1]; f += 256) {
+    float p[3][3];
 #pragma unroll
-      for (int j = 0; j < 3; ++j) gp[j] = gx * P.R[j] + gy * P.R[3 + j] + gzc * P.R[6 + j];
-      const float* m = P.model_v + 3L * P.faces[3 * f + q];
-      const float d[3] = {m[0] - mc[0], m[1] - mc[1], m[2] - mc[2]};
+    for (int q = 0; q < 3; ++q) place_corner(P, x, k, P.faces[3 * f + q], p[q]);
+    for (int v = 0; v < V; ++v) {
+      Corner c[3];
+      bool cull = false;
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        acc[j] += gp[j];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) acc[3 + 3 * j + e] += gp[j] * d[e];
+      for (int q = 0; q < 3; ++q) {
+        c[q] = project(P, cam[v].K, cam[v].R, cam[v].t, p[q]);
+        cull = cull || c[q].z < P.cull_eps;
       }
+      if (cull) continue;
+      face_adjoint(P, cam[v].K, cam[v].R, c, r.grad_faces + v * view_stride, f, mc, s2, acc);
     }
   }
+  place_backward_reduce(P, x, k, row, acc, r.size_target, r.grad_size_loss, r.grad_boxes, r.grad_angles);
+}
+
+// the workgroup's twelve sums (shuffle, then LDS) and the chain rule to the box row and the angle: one writer per row
+__device__ __forceinline__ void place_backward_reduce(const SlnPlacement& P, const ObjXform& x, int k, int row, const float acc[12],
+                                                      const float* __restrict__ size_target, const float* __restrict__ g_size_loss,
+                                                      float* __restrict__ g_boxes, float* __restrict__ g_angles) {
   __shared__ float red[4][12];
 #pragma unroll
   for (int j = 0; j < 12; ++j) {
@@ -444,6 +551,23 @@ int sln_place_forward_rooms(const SlnPlacementRoom* rooms, int R, int F_max, voi
 int sln_place_backward_rooms(const SlnPlacementRoom* rooms, int R, int n_max, void* stream) {
   if (!rooms || R <= 0 || n_max <= 0) return SLN_E_BADARG;
   hipLaunchKernelGGL(place_backward_rooms_kernel, dim3(n_max, R), dim3(256), 0, (hipStream_t)stream, rooms);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_place_forward_views(const SlnPlacementRoom* rooms, const SlnPlacementCamera* cams, int R, int V, int F_max, int64_t view_stride,
+                            void* stream) {
+  if (!rooms || !cams || R < 1 || V < 1 || V > SLN_PLACE_MAX_VIEWS || F_max < 1 || view_stride < 18) return SLN_E_BADARG;
+  hipLaunchKernelGGL(place_forward_views_kernel, dim3(sln_cdiv(F_max, 256), R), dim3(256), 0, (hipStream_t)stream, rooms, cams, V,
+                     (long)view_stride);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_place_backward_views(const SlnPlacementRoom* rooms, const SlnPlacementCamera* cams, int R, int V, int n_max, int64_t view_stride,
+                             void* stream) {
+  if (!rooms || !cams || R < 1 || V < 1 || V > SLN_PLACE_MAX_VIEWS || n_max < 1 || view_stride < 18) return SLN_E_BADARG;
+  hipLaunchKernelGGL(place_backward_views_kernel, dim3(n_max, R), dim3(256), 0, (hipStream_t)stream, rooms, cams, V, (long)view_stride);
   SLN_CHECK_LAUNCH();
   return 0;
 }

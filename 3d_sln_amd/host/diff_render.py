@@ -110,11 +110,15 @@ def cull_and_classify(vertices_buf, face_buf, class_ranges, R, t):
     return face_buf[:, valid, :].detach(), cls.to(dev)[valid], classes, chan, dch
 
 
-def scene_render(vertices_buf, face_buf, class_ranges, room_box, image_size=final_out, near=0.001):
+def scene_render(vertices_buf, face_buf, class_ranges, room_box, image_size=final_out, near=0.001, camera=None):
     """diff_render.py:344-434 in one fused HIP pass.  vertices_buf [1,V,3] (grad flows), face_buf [1,F,3] int32,
-    class_ranges {class: [[a,b],...]}, room_box = boxes[-1].  Returns final [1,70,is,is]."""
+    class_ranges {class: [[a,b],...]}, room_box = boxes[-1].  Returns final [1,70,is,is].
+    ``camera``: None (``get_cam_mat(room_box)``), or (K [3,3], R [3,3], t [3]) in its convention - another view of the room."""
     dev = vertices_buf.device
-    K, R, t = get_cam_mat(room_box, dev)
+    if camera is None:
+        K, R, t = get_cam_mat(room_box, dev)
+    else:
+        K, R, t = (torch.as_tensor(x, dtype=torch.float32).to(dev).reshape(s) for x, s in zip(camera, ((1, 3, 3), (1, 3, 3), (1, 1, 3))))
     faces, cls, classes, chan, dch = cull_and_classify(vertices_buf, face_buf, class_ranges, R, t)
     faces = torch.cat((faces, faces[:, :, [2, 1, 0]]), dim=1)                 # fill_back
     cls = torch.cat((cls, cls))[None].contiguous()

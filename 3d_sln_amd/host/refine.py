@@ -19,6 +19,7 @@ What is replaced
 ``render_fn`` is injectable so that the tests can run the very same loss graph on the CPU oracle.
 """
 import collections
+import copy
 import ctypes as C
 import math
 import os
@@ -615,6 +616,46 @@ def check_overlap(overlap_weight, overlap_rows, rooms):
     return out if w > 0.0 else None
 
 
+MAX_VIEWS = 64           # SLN_PLACE_MAX_VIEWS of include/sln_hip.h
+
+
+def check_views(views, rooms=None, observed=None, mask=None, report=None, pictures=None, retrieve=False):
+    """the ``views=`` argument of the refinement entry points, refused before anything is launched.  ``views``: None, or the cameras
+    ``(K [R, V, 3, 3], Rm [R, V, 3, 3], t [R, V, 3])`` of V target views per room in ``get_cam_mat``'s convention, host or device tensors (or
+    anything ``torch.as_tensor`` takes); ``rooms``: R, or None for the one-room form ``(K [V, 3, 3], Rm [V, 3, 3], t [V, 3])``.  -> None, or the
+    three as contiguous float32 host tensors with the room axis.  Refused: anything else in shape, V > 64, a non-finite entry, tensors in
+    ``observed`` or ``mask`` without the V axis (``[R, V, S, S]``; ``[V, S, S]`` in the one-room form), and ``report``, ``pictures`` or
+    ``retrieve=True``, which do not combine with views."""
+    if views is None:
+        return None
+    if not isinstance(views, (tuple, list)) or len(views) != 3:
+        raise ValueError("views is (K [R, V, 3, 3], Rm [R, V, 3, 3], t [R, V, 3])")
+    try:
+        K, Rm, t = (torch.as_tensor(x).detach().to("cpu", torch.float32).contiguous() for x in views)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError("views: three arrays of numbers expected (%s)" % e)
+    lead = () if rooms is None else (int(rooms),)
+    V = int(K.shape[len(lead)]) if K.dim() == len(lead) + 3 else -1
+    want = [lead + (V, 3, 3), lead + (V, 3, 3), lead + (V, 3)]
+    if V < 1 or [tuple(x.shape) for x in (K, Rm, t)] != want:
+        raise ValueError("views: shapes %s are not K %s, Rm likewise, t %s with V >= 1 views" %
+                         ([tuple(x.shape) for x in (K, Rm, t)], list(lead) + ["V", 3, 3], list(lead) + ["V", 3]))
+    if V > MAX_VIEWS:
+        raise ValueError("views: %d views per room, at most %d" % (V, MAX_VIEWS))
+    if not all(bool(torch.isfinite(x).all()) for x in (K, Rm, t)):
+        raise ValueError("views: a camera with a non-finite entry")
+    for name, on in (("report", report is not None), ("pictures", pictures is not None), ("retrieve=True", bool(retrieve))):
+        if on:
+            raise ValueError("views does not combine with %s" % name)
+    tensors = [("observed", x) for x in (observed if isinstance(observed, (tuple, list)) else ())] + [("mask", mask)]
+    for name, x in tensors:
+        if torch.is_tensor(x) and (x.dim() != len(lead) + 3 or tuple(x.shape[:len(lead) + 1]) != lead + (V,)):
+            raise ValueError("%s: with views the V axis is needed, %s expected, got %s" % (name, list(lead) + [V, "S", "S"], tuple(x.shape)))
+    if rooms is None:
+        K, Rm, t = K[None], Rm[None], t[None]
+    return K.contiguous(), Rm.contiguous(), t.contiguous()
+
+
 def _one_room_overlap(overlap_weight, overlap_rows, class_names, n, dev):
     """the one-room loops' checked penalty arguments -> None (weight 0), or the tensors of ``_overlap_term``: (collide uint8 [n], room_of_row
     int32 [n], room_id int32 [n]) on ``dev``"""
@@ -882,6 +923,19 @@ class RefineScene:
             setattr(d, name, (type(getattr(d, name)))(*[float(x) for x in vals]))
         d.orig_size, d.proj_eps, d.cull_eps = float(DR.inter_out), 1e-9, float(DR.CULL_EPS)
         self.desc = d
+
+    def with_view(self, K, R, t):
+        """This scene seen through another camera (K [3, 3], R [3, 3], t [3] in ``get_cam_mat``'s convention, host or device): a shallow copy
+        that shares every buffer, with ``K`` / ``R`` / ``t`` and the descriptor's camera replaced (``reproject.look_at_view``)."""
+        dev = self.K.device
+        Kc, Rc, tc = (torch.as_tensor(x, dtype=torch.float32).detach().cpu().reshape(s) for x, s in zip((K, R, t), ((1, 3, 3), (1, 3, 3), (1, 1, 3))))
+        sc = copy.copy(self)
+        sc.K, sc.R, sc.t = Kc.to(dev), Rc.to(dev), tc.to(dev)
+        d = type(self.desc).from_buffer_copy(self.desc)
+        for name, vals in (("K", Kc), ("R", Rc), ("t", tc)):
+            setattr(d, name, (type(getattr(d, name)))(*[float(x) for x in vals.reshape(-1).tolist()]))
+        sc.desc = d
+        return sc
 
     @staticmethod
     def _static_part(class_names, bank, dev, choice=None, shell=None):
@@ -1233,13 +1287,28 @@ class RefineBatch:
     penalty's gradient onto the placement's in front of the head's backward (the ``fix_grad`` / ``quad_grad`` hooks see it); ``overlap``
     [iters, R] float64 holds the unweighted penalty of every iteration (None with the weight at 0).  ``overlap_rows``: None, or per room None
     or a bool sequence over the room's rows that replaces the default choice of colliding rows (the class is not in DO_NOT_VIS; needs
-    ``class_names`` that name every row) - to exempt a lamp that a graph places "inside" a shelf; a room row never collides."""
+    ``class_names`` that name every row) - to exempt a lamp that a graph places "inside" a shelf; a room row never collides.
+
+    ``views``: None (default: every room is refined against its one refinement view, the launches are those above), or the cameras
+    ``(K [R, V, 3, 3], Rm [R, V, 3, 3], t [R, V, 3])`` of V target views per room, host or device, in ``get_cam_mat``'s convention
+    (``reproject.refine_view`` / ``look_at_view``; DESIGN §4 "Several target views per room").  The views REPLACE the room's camera: view 0
+    need not be ``get_cam_mat``'s.  Image ``b = r * V + v``: the placement is done once per room and projected through its V cameras
+    (sln_place_forward_views / sln_place_backward_views instead of the ``_rooms`` pair, the head in launches of its own), the scene pass and
+    the loss run over R * V images, and a room's loss is ``mean_v L[r, v] + 2 size_loss`` (``+ overlap_weight * penalty``) - every image's
+    gradient is scaled by float32(1 / V).  The targets are the renders of ``rm["boxes"]`` through each view's camera
+    (``RefineScene.with_view``), or ``observed`` frames: ``observed`` and a tensor ``mask`` are then ``[R, V, S, S]``, ``target_status`` and
+    ``mask_status`` ``[R, V]``.  A room with fewer than V views passes an all-zero ``mask`` for the missing ones - the divisor stays V;
+    there is no other ragged form.  The camera table is uploaded once at set-up.  Out of scope, and refused: ``report``, ``pictures`` and
+    ``retrieve=True`` together with ``views``."""
 
     def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
-                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None):
+                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None):
         self.model, self.R, self.iters, self.lr, self.S = model, len(rooms), int(iters), float(learning_rate), int(image_size)
         dev = model.flat_params.device
-        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev)      # every refusal, in front of the first launch
+        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev, views)      # every refusal, in front of the first launch
+        if self._views is not None:      # from here on an image is b = r * V + v: observed frames and a mask tensor lose their room axis
+            fold = lambda x: x.reshape(self.R * self.V, self.S, self.S) if torch.is_tensor(x) else x
+            observed, mask = None if observed is None else tuple(fold(x) for x in observed), fold(mask)
         self.overlap_weight = float(overlap_weight)
         self._collide_rows = check_overlap(overlap_weight, overlap_rows, [(int(rm["objs"].shape[0]), list(rm["class_names"])) for rm in rooms])
         self._bank = bank or MeshBank([n for n in set(n for rm in rooms for n in rm["class_names"]) if n not in DO_NOT_VIS and n != "__room__"], dev)
@@ -1256,6 +1325,8 @@ class RefineBatch:
         all_targets = torch.cat(targets, 0)                   # the loss of all rooms: one descriptor, per-room normalisation
         self.loss = RefineLoss(all_targets, per_room=True, valid=valid_and_labels(mask, all_targets, labels=False)[0])
         self.mask_status = self.loss.mask_status
+        if self._views is not None and self.mask_status is not None:
+            self.mask_status = self.mask_status.view(self.R, self.V)
         del targets, all_targets
         self._create_group(rooms, dev)
         self._head_and_placement_buffers(dev)
@@ -1269,12 +1340,16 @@ class RefineBatch:
         if not torch.cuda.is_current_stream_capturing():
             _lib.lib().sln_side_stream_prepare(_lib.current_stream_ptr())
 
-    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev):
-        """refuses what cannot run; leaves ``_report_at`` (frozenset) and ``_pictures_at`` ({iteration: slot}), None when not asked for, + "all" flags"""
+    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev, views=None):
+        """refuses what cannot run; leaves ``_report_at`` (frozenset) and ``_pictures_at`` ({iteration: slot}), None when not asked for, + "all" flags,
+        ``_views`` (``check_views``: the cameras on the host, or None) and ``V``"""
         if self.R < 1:
             raise ValueError("RefineBatch needs at least one room")
-        check_observed(observed, (self.R, self.S, self.S), dev, cuda=True, choice=retrieve)
-        check_mask(mask, (self.R, self.S, self.S), dev, observed)
+        self._views = check_views(views, self.R, observed, mask, report, pictures, retrieve)
+        self.V = 1 if self._views is None else int(self._views[0].shape[1])
+        shape = (self.R, self.S, self.S) if self._views is None else (self.R, self.V, self.S, self.S)
+        check_observed(observed, shape, dev, cuda=True, choice=retrieve)
+        check_mask(mask, shape, dev, observed)
         at, self._report_all = parse_schedule(report, self.iters, "report") or (None, False)
         self._report_at = None if at is None else frozenset(at)
         at, self._pictures_all = parse_schedule(pictures, self.iters, "pictures") or (None, False)
@@ -1302,13 +1377,21 @@ class RefineBatch:
             # (fp32 whatever model.gemm_precision says: the refinement loop's room engines are fp32 only, and so is its starting point)
             self.z[a:a + n], noise[:self.iters, a:a + n] = room_start(self.model, rm, noise_seed, self.iters, dev, fp32=True)
             sc, tgt, sizes = room_target(rm, bank, S, tm[a:a + n] if tm is not None else None, self._shells[r] if self._shells is not None else None,
-                                         observed is not None)
+                                         observed is not None or self._views is not None)
+            if self._views is not None and observed is None:
+                # a room's V targets: the same ground-truth rows through each view's camera, on the single-view path (``with_view``)
+                with torch.no_grad():
+                    tgt = torch.cat([sc.with_view(*(x[r, v] for x in self._views)).render(rm["boxes"], rm["angles"].float())[0]
+                                     for v in range(self.V)], 0)
             scenes.append(sc); targets.append(tgt); self._size_targets.append(sizes)
             self.box_last[r] = rm["boxes"][-1].detach().float(); self.angle_last[r] = rm["angles"][-1].detach().float()
         self.target_status = None
-        if observed is not None:         # all R targets from ONE ObservedTarget call on the batch's class tables (csrc/observed_target.hip)
-            built, status = OB.ObservedTarget(*_shared_class_tables(scenes), S, batch=R, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)
-            targets, self.target_status = [built[r:r + 1] for r in range(R)], status.clone()
+        if observed is not None:         # all targets from ONE ObservedTarget call on the batch's class tables (csrc/observed_target.hip)
+            B = R * self.V
+            built, status = OB.ObservedTarget(*_shared_class_tables(scenes), S, batch=B, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)
+            targets, self.target_status = [built[b:b + 1] for b in range(B)], status.clone()
+            if self._views is not None:
+                self.target_status = self.target_status.view(R, self.V)
         self.scenes = self.target_scenes = scenes
         self.noise_all = noise.to(dev)
         return targets
@@ -1382,7 +1465,9 @@ class RefineBatch:
         self.g_size_loss = torch.full((1,), 2.0, **f32)               # loss = ... + 2 * size_loss (test_render_refine.py:350-352)
         # the head inside the two placement launches (SlnPlacementRoom's head fields; iteration k's noise: row k of noise_all, k a device counter)
         # (the penalty's gradient joins g_boxes / g_idx between the placement backward and the head's: the head in launches of its own)
-        self._fused_head = self.n_max <= 128 and not os.environ.get("SLN_REFINE_SEPARATE_HEAD") and self._collide_rows is None
+        # (the view placement reads boxes / idx and has no head of its own: with views the head runs in launches of its own as well)
+        self._fused_head = (self.n_max <= 128 and not os.environ.get("SLN_REFINE_SEPARATE_HEAD") and self._collide_rows is None
+                            and self._views is None)
         self.overlap = None
         if self._collide_rows is not None:
             self._collide = torch.tensor([v for rows in self._collide_rows for v in rows], dtype=torch.uint8, device=dev)
@@ -1393,20 +1478,24 @@ class RefineBatch:
     def _image_and_loss_buffers(self, dev):
         """the image and its gradient, the loss outputs and the live-plane flags the loss and the scene pass share"""
         R, S, f32 = self.R, self.S, dict(dtype=torch.float32, device=dev)
-        self.image, self.g_image = (torch.zeros(R, DR.N_SCENE_CHANNELS, S, S, **f32) for _ in range(2))       # (planes flagged dead: never touched)
-        self.loss_out = torch.empty(R, 3, **f32)
+        B = R * self.V                                                 # images: b = r * V + v
+        self.image, self.g_image = (torch.zeros(B, DR.N_SCENE_CHANNELS, S, S, **f32) for _ in range(2))       # (planes flagged dead: never touched)
+        self.loss_out = torch.empty(B, 3, **f32)
         # the semantic planes of classes without a visible pixel are zeros, and the scene pass never reads their gradients nor
         # those of such classes' depth-hot planes: the loss skips them (SlnRefineLoss::live_planes, refreshed after every scene pass)
-        self.live = torch.full((R, DR.N_SCENE_CHANNELS), 3, dtype=torch.uint8, device=dev)
+        self.live = torch.full((B, DR.N_SCENE_CHANNELS), 3, dtype=torch.uint8, device=dev)
         self.null_mask = None
         # (only when the loss takes the flags for this geometry: below the pooled size it would read planes the sparse scene pass leaves unwritten)
         if not os.environ.get("SLN_REFINE_ALL_PLANES") and _lib.lib().sln_refine_loss_live_ok(C.byref(self.loss.desc)):
             self.loss.desc.live_planes = self.live.data_ptr()
-            self.null_mask = torch.zeros(R, S, S, dtype=torch.uint8, device=dev)
+            self.null_mask = torch.zeros(B, S, S, dtype=torch.uint8, device=dev)
             self.loss.desc.null_mask = self.null_mask.data_ptr()
             self._pooled_ones = self.loss.pooled_ones()
             self.loss.desc.pooled_ones = self._pooled_ones.data_ptr()
         self.one = torch.ones(1, **f32)
+        # a room's loss is the mean of its views' (+ 2 size_loss): every image's gradient is scaled by float32(1 / V)
+        self.grad_scale = self.one if self._views is None else torch.full((1,), 1.0 / self.V, **f32)
+        self._view_mean = None if self._views is None else torch.empty(R, **f32)
         self.losses = torch.zeros(max(self.iters, 1), R, **f32)
 
     def _sgd_ranges(self):
@@ -1427,23 +1516,24 @@ class RefineBatch:
         buffers, the class table of the faces, the placement table and the scene pass's workspace.  Called at construction with the
         target scenes and, with retrieve=True, once more by the first ``run()`` with the scenes of the iterates' meshes (which may
         change F2); the size targets, the head's buffers and everything per row stay where they are."""
-        R, N, na, dev = self.R, self.N, self.model.Nangle, self.boxes.device
+        R, V, N, na, dev = self.R, self.V, self.N, self.model.Nangle, self.boxes.device
         f32 = dict(dtype=torch.float32, device=dev)
         self.scenes = scenes
         self.chan, self.dch = _shared_class_tables(scenes)
         self.F2 = 2 * max(sc.desc.F for sc in scenes)
-        self.faces = torch.zeros(R, self.F2, 3, 3, **f32)             # rows beyond a room's 2 F stay degenerate triangles of no class
-        self.g_faces = torch.empty(R, self.F2, 3, 3, **f32)
-        self.cls = cls = torch.full((R, self.F2), -1, dtype=torch.int32, device=dev)
+        # (with views: image b = r * V + v; a room's table entry points at its view 0, view v lies 9 * F2 floats behind it)
+        self.faces = torch.zeros(R * V, self.F2, 3, 3, **f32)         # rows beyond a room's 2 F stay degenerate triangles of no class
+        self.g_faces = torch.empty(R * V, self.F2, 3, 3, **f32)
+        self.cls = cls = torch.full((R * V, self.F2), -1, dtype=torch.int32, device=dev)
         tab = (_lib.SlnPlacementRoom * R)()
         for r, sc in enumerate(scenes):
-            cls[r, :2 * sc.desc.F] = sc.cls2[0]
+            cls[r * V:(r + 1) * V, :2 * sc.desc.F] = sc.cls2[0]
             e, a = tab[r], self.row0[r]
             e.P = sc.desc
             e.boxes, e.angles = self.boxes.data_ptr() + 24 * a, self.idx.data_ptr() + 4 * a
             e.size_target = self._size_targets[r].data_ptr() if sc.n_vis else None
-            e.faces_out, e.sizes, e.size_loss = self.faces[r].data_ptr(), self.sizes[r].data_ptr(), self.size_loss.data_ptr() + 4 * r
-            e.grad_faces, e.grad_size_loss = self.g_faces[r].data_ptr(), self.g_size_loss.data_ptr()
+            e.faces_out, e.sizes, e.size_loss = self.faces[r * V].data_ptr(), self.sizes[r].data_ptr(), self.size_loss.data_ptr() + 4 * r
+            e.grad_faces, e.grad_size_loss = self.g_faces[r * V].data_ptr(), self.g_size_loss.data_ptr()
             e.grad_boxes, e.grad_angles = self.g_boxes.data_ptr() + 24 * a, self.g_idx.data_ptr() + 4 * a
             if self._fused_head:
                 e.boxes_pred, e.angles_pred = self.boxes_pred.data_ptr() + 24 * a, self.angles_pred.data_ptr() + 4 * na * a
@@ -1452,7 +1542,10 @@ class RefineBatch:
                 e.grad_boxes_pred, e.grad_angles_pred = self.d_boxes_pred.data_ptr() + 32 * a, self.d_angles_pred.data_ptr() + 4 * na * a
                 e.n_angle, e.ld_gb, e.beta = na, 8, 2.0
         self._place_tab = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
-        self.scene_ws = torch.empty(int(_lib.lib().sln_scene_workspace_bytes(R, self.F2, self.S)), dtype=torch.uint8, device=dev)
+        if self._views is not None and getattr(self, "_cams", None) is None:
+            # the camera table [R * V] of SlnPlacementCamera (K[9], R[9], t[3]), uploaded once
+            self._cams = torch.cat([x.reshape(R * V, -1) for x in self._views], 1).contiguous().to(dev)
+        self.scene_ws = torch.empty(int(_lib.lib().sln_scene_workspace_bytes(R * V, self.F2, self.S)), dtype=torch.uint8, device=dev)
 
     def _retrieve_iterates(self):
         """retrieve=True: the iterates' meshes are those retrieved for the FIRST iterate's boxes (testing/test_render_refine.py:324-326:
@@ -1487,7 +1580,10 @@ class RefineBatch:
             _lib.check(L.sln_refine_head_forward_rooms(self.N, self.model.Nangle, P(self.room_of_row), P(self.last_row), P(self.boxes_pred),
                                                        P(self.angles_pred), P(noise), P(self.box_last), P(self.angle_last), 2.0, P(self.boxes),
                                                        P(self.idx), st), "sln_refine_head_forward_rooms")
-        _lib.check(L.sln_place_forward_rooms(P(self._place_tab), self.R, self.F2 // 2, st), "sln_place_forward_rooms")
+        if self._views is not None:
+            _lib.check(L.sln_place_forward_views(P(self._place_tab), P(self._cams), self.R, self.V, self.F2 // 2, 9 * self.F2, st), "sln_place_forward_views")
+        else:
+            _lib.check(L.sln_place_forward_rooms(P(self._place_tab), self.R, self.F2 // 2, st), "sln_place_forward_rooms")
 
     def _first_iterate_sizes(self):
         """The size penalty holds every object to the size of the FIRST iterate (testing/test_render_refine.py:319-327: ``size_infos`` is
@@ -1511,7 +1607,7 @@ class RefineBatch:
         [R, 3] (a reported iteration) the report, ``pictures_out`` (a pictured iteration) = (depth8, labels, rgb, status) of one slot,
         ``overlap_out`` [R] float64 (with the penalty on) the rooms' unweighted penalties"""
         L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
-        N, R, na, S = self.N, self.R, self.model.Nangle, self.S
+        N, R, na, S, B = self.N, self.R, self.model.Nangle, self.S, self.R * self.V
         self._forward_to_placement(noise)
         if report_out is not None:      # (the fused head lives in the placement launch: boxes / idx of this iterate exist from here on)
             _lib.check(L.sln_layout_cuboid_iou(P(self.boxes), P(self.idx), P(self._gt_boxes), P(self._gt_angles), P(self._room_row), P(self._visible),
@@ -1519,20 +1615,27 @@ class RefineBatch:
         rl = self.loss
         live = (P(self.live), P(self.null_mask)) if rl.desc.live_planes else ()        # the scene pass refreshes the live-plane flags
         forward = L.sln_scene_forward_live if live else L.sln_scene_forward
-        _lib.check(forward(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 0.1, 0.001, 100.0, 1e-3,
+        _lib.check(forward(P(self.faces), P(self.cls), B, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 0.1, 0.001, 100.0, 1e-3,
                            P(self.scene_ws), P(self.image), *live, st), "sln_scene_forward_live" if live else "sln_scene_forward")
         _lib.check(L.sln_refine_loss_forward(rl.desc, P(self.image), P(rl.target_depth), P(rl.labels), P(rl.inv_count), P(rl.ws), P(self.loss_out), st),
                    "sln_refine_loss_forward")
-        torch.add(self.loss_out[:, 0], self.size_loss, alpha=2.0, out=out)
+        if self._views is not None:     # a room's loss: the mean of its views' losses (exact for V = 1)
+            torch.mean(self.loss_out[:, 0].view(R, self.V), 1, out=self._view_mean)
+            torch.add(self._view_mean, self.size_loss, alpha=2.0, out=out)
+        else:
+            torch.add(self.loss_out[:, 0], self.size_loss, alpha=2.0, out=out)
         if report_out is not None:      # reads the image and the loss forward's partial sums, consumes (and re-arms) the IoU means
             _lib.check(L.sln_refine_report(rl.desc, P(self.image), P(self._target_depth), P(rl.ws), P(self._report_ws), P(self._iou_mean), P(report_out),
                                            st), "sln_refine_report")
         if pictures_out is not None:    # the iterate as the loss saw it: the planes `live` flags dead are not read
             self._pics.into(self.image, self.live, *pictures_out[:3], None, pictures_out[3])
-        _lib.check(L.sln_refine_loss_backward(rl.desc, P(rl.ws), P(self.one), P(self.g_image), st), "sln_refine_loss_backward")
-        _lib.check(L.sln_scene_backward(P(self.faces), P(self.cls), R, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 1e-3, P(self.scene_ws),
+        _lib.check(L.sln_refine_loss_backward(rl.desc, P(rl.ws), P(self.grad_scale), P(self.g_image), st), "sln_refine_loss_backward")
+        _lib.check(L.sln_scene_backward(P(self.faces), P(self.cls), B, self.F2, S, self.chan.numel(), P(self.chan), P(self.dch), 1e-3, P(self.scene_ws),
                                         P(self.g_image), P(self.g_faces), st), "sln_scene_backward")
-        _lib.check(L.sln_place_backward_rooms(P(self._place_tab), R, self.n_max, st), "sln_place_backward_rooms")
+        if self._views is not None:     # the views' adjoints meet in world space: one launch, one writer per row
+            _lib.check(L.sln_place_backward_views(P(self._place_tab), P(self._cams), R, self.V, self.n_max, 9 * self.F2, st), "sln_place_backward_views")
+        else:
+            _lib.check(L.sln_place_backward_rooms(P(self._place_tab), R, self.n_max, st), "sln_place_backward_rooms")
         if overlap_out is not None:
             # all rooms' rows as ONE layout of R rooms; += onto the gradients the placement backward has just written (every row of every room,
             # zeros for rows without a visible object: csrc/placement.hip place_backward_body), in front of the head's backward and its two hooks
@@ -1613,13 +1716,15 @@ class RefineBatch:
 
 
 def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None,
-                            pictures=None, retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None):
+                            pictures=None, retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
     noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
     ``report`` is given, the report [iters, R, 3] as a further element; only when ``pictures`` is given, the pair
-    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask`` / ``overlap_weight`` / ``overlap_rows``: as ``RefineBatch``'s."""
+    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask`` / ``overlap_weight`` / ``overlap_rows`` /
+    ``views``: as ``RefineBatch``'s (``views`` combines with neither ``report``, ``pictures`` nor ``retrieve=True``)."""
     rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report,
-                     pictures=pictures, retrieve=retrieve, observed=observed, mask=mask, overlap_weight=overlap_weight, overlap_rows=overlap_rows)
+                     pictures=pictures, retrieve=retrieve, observed=observed, mask=mask, overlap_weight=overlap_weight, overlap_rows=overlap_rows,
+                     views=views)
     try:
         out = (rb.run(capture=capture).clone(), [(b.clone(), i.clone()) for b, i in rb.results()])
         if report is not None:
@@ -1632,14 +1737,25 @@ def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-
 
 
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,
-                 learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None):
+                 learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None,
+                 views=None):
     """finetune_VAE's inner loop for ONE room (test_render_refine.py:265-359) on synthetic meshes.
     ``observed`` / ``mask``: as ``finetune_vae_fast``'s, on the boxes' device whichever it is - the target from ``observed_target_torch`` on
     the room's class tables, the loss from ``refinement_loss_masked``.  ``overlap_weight`` / ``overlap_rows``: as ``finetune_vae_fast``'s (on CPU
     tensors the penalty is ``evaluate.overlap_penalty_torch``).
+    ``views``: None, or ``(K [V, 3, 3], Rm [V, 3, 3], t [V, 3])`` - ``RefineBatch``'s ``views`` for one room, in autograd: every view is
+    rendered with ``render_fn(..., camera=(K, Rm, t))``, the loss is ``mean_v L_v + 2 size_loss`` with ``L_v`` the view's depth and semantic
+    terms over its own image; ``observed`` and a tensor ``mask`` are then ``[V, S, S]``.  The yardstick of the view kernels' loop.
     Returns the list of per-iteration losses and the final (boxes_pred, angles_idx)."""
     render_fn, dev = render_fn or DR.scene_render, boxes_gt.device
-    observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, False, bank)
+    cams = check_views(views, None, observed, mask)
+    if cams is None:
+        observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, False, bank)
+    else:
+        cams = [tuple(x[0, v] for x in cams) for v in range(int(cams[0].shape[1]))]
+        shape = (len(cams), int(image_size), int(image_size))
+        check_observed(observed, shape, dev, False, choice=bank is not None and bank.has_choice())
+        check_mask(mask, shape, dev, observed)
     overlap = _one_room_overlap(overlap_weight, overlap_rows, class_names, int(boxes_gt.shape[0]), dev)
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
     model.eval()
@@ -1654,7 +1770,9 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         models_gt, shell = models_gt.cpu().tolist(), (shells[0] if shells is not None else None)
     v, f, ranges, sizes, _ = assemble_scene(boxes_gt, angles_gt.float(), class_names, bank, room_box, models=models_gt, shell=shell)
     with torch.no_grad():
-        if observed is None:
+        if observed is None and cams is not None:
+            target = torch.cat([render_fn(v, f, ranges, room_box, image_size=image_size, camera=cam) for cam in cams], 0)
+        elif observed is None:
             target = render_fn(v, f, ranges, room_box, image_size=image_size)
         else:
             _, chan, dch = DR.class_tables(ranges.keys())
@@ -1676,11 +1794,23 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         v, f, ranges, sizes_k, size_loss = assemble_scene(boxes_pred, idx, class_names, bank, room_box, size_target, models=models_it, shell=shell)
         if size_target is None:
             size_target = [s.clone() for s in sizes_k]
-        image = render_fn(v, f, ranges, room_box, image_size=image_size)
-        if valid is not None:
-            loss, dl, sl = refinement_loss_masked(image, target, labels, size_loss, valid)
+        if cams is not None:            # mean over the views of each view's own loss, the size loss once
+            per_view = []
+            for vi, cam in enumerate(cams):
+                image = render_fn(v, f, ranges, room_box, image_size=image_size, camera=cam)
+                tgt, lab = target[vi:vi + 1], [t[vi:vi + 1] for t in labels]
+                if valid is not None:
+                    per_view.append(refinement_loss_masked(image, tgt, lab, 0.0, valid[vi:vi + 1]))
+                else:
+                    per_view.append(refinement_loss(image, tgt, lab, 0.0))
+            loss, dl, sl = (torch.stack([p[j] for p in per_view]).mean() for j in range(3))
+            loss = loss + size_loss * 2.0
         else:
-            loss, dl, sl = refinement_loss(image, target, labels, size_loss)
+            image = render_fn(v, f, ranges, room_box, image_size=image_size)
+            if valid is not None:
+                loss, dl, sl = refinement_loss_masked(image, target, labels, size_loss, valid)
+            else:
+                loss, dl, sl = refinement_loss(image, target, labels, size_loss)
         if overlap is not None:
             loss = loss + _overlap_term(boxes_pred, idx, overlap, overlap_weight)
         opt.zero_grad()

@@ -12,8 +12,9 @@ pixel out of the rasterizer's maps.
     gives every target pixel to the frame with the nearest surface there - the z-buffer rule - and says which frame won, how many
     frames saw the pixel and how many of them agree with the winner's depth; ``fuse_torch`` / ``reproject_views_torch`` restate it
     (DESIGN §4 "Several observed frames per room");
-  * ``relative_pose``, ``refine_view``, ``scene_as_source``   the cameras: source -> target pose from two world poses, the refinement
-    view of a room row, and the source intrinsics under which a scene tensor's own planes are a frame of their own camera.
+  * ``relative_pose``, ``refine_view``, ``look_at_view``, ``scene_as_source``   the cameras: source -> target pose from two world poses,
+    the refinement view of a room row, a further view of the room from an eye and a point it looks at (``RefineBatch(views=)``), and the
+    source intrinsics under which a scene tensor's own planes are a frame of their own camera.
 
 A target pixel no face covers - a disocclusion, a cut at a depth step, the frame's border - reads "no reading" (-1, label 0);
 ``RefineBatch(mask="readings")`` keeps such pixels out of the loss, and further frames of the room fill them (``ObservedFuser``).  A
@@ -98,6 +99,30 @@ def refine_view(room_box, S):
     room = [float(x) for x in torch.as_tensor(room_box).detach().cpu().reshape(-1).tolist()]
     K, R, t = DR.get_cam_mat([room], "cpu")
     return K[0].contiguous(), R[0].contiguous(), t.reshape(3).contiguous(), float(DR.inter_out)
+
+
+def look_at_view(eye, at):
+    """A further view of a room in ``get_cam_mat``'s convention (``p_cam = R p_world + t``, ``K`` in pixels of ``diff_render.inter_out``): the
+    camera at ``eye`` [3] looking at ``at`` [3], both in room coordinates (y up), without roll -> (K [3, 3], R [3, 3], t [3], orig_size) float32
+    on the host - what ``refine_view`` returns for the refinement camera, and what ``RefineBatch(views=)`` takes per view.  ``K`` is
+    ``get_cam_mat``'s; ``R = c2cv [right; up; back]`` with back = (eye - at) / |eye - at|, right = y x back normalised, up = back x right and
+    the ``c2cv`` flip diag(1, -1, -1); ``t = -R eye``.  Computed in float64 and rounded once.  With ``get_cam_mat``'s eye and a point on its
+    axis this is ``get_cam_mat``'s camera.  Refused: non-finite input, ``eye == at``, a view straight up or down (no roll is defined)."""
+    e, a = (torch.as_tensor(x).detach().cpu().double().reshape(-1) for x in (eye, at))
+    if e.numel() != 3 or a.numel() != 3 or not (torch.isfinite(e).all() and torch.isfinite(a).all()):
+        raise ValueError("look_at_view: eye and at are finite points [3]")
+    back = e - a
+    if not float(back.norm()) > 0:
+        raise ValueError("look_at_view: eye and at coincide")
+    back = back / back.norm()
+    right = torch.linalg.cross(torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64), back)
+    if not float(right.norm()) > 1e-9:
+        raise ValueError("look_at_view: a view along the y axis has no roll-free orientation")
+    right = right / right.norm()
+    up = torch.linalg.cross(back, right)
+    R = torch.diag(torch.tensor([1.0, -1.0, -1.0], dtype=torch.float64)) @ torch.stack((right, up, back))
+    K = DR.get_cam_mat([[0.0] * 6], "cpu")[0][0]
+    return K.contiguous(), R.float().contiguous(), (-(R @ e)).float().contiguous(), float(DR.inter_out)
 
 
 def scene_as_source(K_tgt, orig_size, S):

@@ -676,6 +676,22 @@ typedef struct {
 } SlnPlacementRoom;
 int sln_place_forward_rooms(const SlnPlacementRoom* rooms /* device */, int R, int F_max, void* stream);
 int sln_place_backward_rooms(const SlnPlacementRoom* rooms /* device */, int R, int n_max, void* stream);
+/* Several target views per room: the placement of sln_place_forward / _backward_rooms (models/diff_render.py:76-159, once per room)
+ * projected through V cameras per room instead of get_cam_mat's one (:13-46; the projection, the cull :346-356 and fill_back per view).
+ * Image b = r * V + v; `cams` is a DEVICE array [R * V] in get_cam_mat's convention (p_cam = R p_world + t, K in pixels of orig_size).
+ * A room's faces_out / grad_faces point at its view 0; view v lies v * view_stride floats behind it.  P.K / P.R / P.t and the head
+ * fields of the table are not read (boxes / angles are).  A face culled in a view is (0, 0, 0) in that view only and adds nothing
+ * to the gradients from it; face rows beyond a room's 2 P.F stay untouched in every view.  sizes / size_loss / the size-loss
+ * gradient once per room; grad_boxes / grad_angles = the sum over the views, one writer per row, no atomics.  With V = 1 and the room's
+ * own camera in `cams`: the bits of sln_place_forward_rooms / sln_place_backward_rooms.  One launch each, no allocation, no
+ * synchronisation: legal in a linear capture.  SLN_E_BADARG, nothing launched: a null pointer, R < 1, V < 1, V > SLN_PLACE_MAX_VIEWS,
+ * F_max < 1 / n_max < 1, view_stride < 18. */
+#define SLN_PLACE_MAX_VIEWS 64
+typedef struct { float K[9], R[9], t[3]; } SlnPlacementCamera;
+int sln_place_forward_views(const SlnPlacementRoom* rooms /* device [R] */, const SlnPlacementCamera* cams /* device [R * V] */, int R, int V,
+                            int F_max, int64_t view_stride, void* stream);
+int sln_place_backward_views(const SlnPlacementRoom* rooms, const SlnPlacementCamera* cams, int R, int V, int n_max, int64_t view_stride,
+                             void* stream);
 /* sln_refine_sgd over R parameter copies: for every room r and every range k: p[r * stride + off_k + i] -= step * g[...], g = 0
  * (i < len_k; off_k, len_k multiples of 4 floats; n_ranges <= 96: the decoder's parameters are the three *_dc embedding tables in
  * front and the trailing gconv_net_dc / box_net / angle_net run - encoder-only parameters have zero gradients in this loop and are

@@ -1,5 +1,7 @@
 """Timing of the R-rooms-in-flight refinement loop (host/refine.py::RefineBatch) at train.py's defaults, 256 x 256: ms per iteration
-(slope between runs of `iters` and 2 x `iters` iterations) and set-up per room, eager and under hipGraph replay.  GPU box."""
+(slope between runs of `iters` and 2 x `iters` iterations) and set-up per room, eager and under hipGraph replay.  GPU box.
+VIEWS=V (default 0: ``views=None``): refine every room against V target views - view 0 is ``refine_view``'s camera, the others look from the
+room's upper corners at its centre (``look_at_view``)."""
 import importlib, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,6 +9,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 R = importlib.import_module("3d_sln_amd.host.refine")
 M = importlib.import_module("3d_sln_amd.host.Sg2ScVAE_model")
 syn = importlib.import_module("3d_sln_amd.host.synthetic")
+RP = importlib.import_module("3d_sln_amd.host.reproject")
 
 
 def bench_rooms(n_rooms, n_obj=12, seed=0, dev="cuda"):
@@ -25,8 +28,24 @@ def bench_rooms(n_rooms, n_obj=12, seed=0, dev="cuda"):
     return rooms, names
 
 
+_CORNERS = ((0.9, 0.9, 0.9), (0.1, 0.9, 0.9), (0.9, 0.9, 0.1), (0.1, 0.9, 0.1))
+
+
+def room_views(rooms, V):
+    """(K [R, V, 3, 3], Rm, t [R, V, 3]) on the host; None for V = 0"""
+    if V < 1:
+        return None
+    cams = []
+    for rm in rooms:
+        ext = rm["boxes"][-1, 3:].cpu().double().numpy()
+        cams.append([RP.refine_view(rm["boxes"][-1], 256)[:3]] +
+                    [RP.look_at_view(ext * _CORNERS[(v - 1) % 4] * (1.0 - 0.1 * ((v - 1) // 4)), ext / 2)[:3] for v in range(1, V)])
+    return tuple(torch.stack([torch.stack([c[v][j] for v in range(V)]) for c in cams]) for j in range(3))
+
+
 def main():
     iters = int(os.environ.get("ITERS", "60"))
+    n_views = int(os.environ.get("VIEWS", "0"))
     torch.manual_seed(1)
     model = M.Sg2ScVAEModel(vocab=syn.default_vocab(), batch_size=1, train_3d=True, decoder_cat=True, embedding_dim=64, gconv_mode='feedforward',
                             gconv_num_layers=5, mlp_normalization='batch', vec_noise_dim=0, layout_noise_dim=32, use_AE=False).cuda().eval()
@@ -38,25 +57,26 @@ def main():
     for nr in [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "1,4,16").split(",")]:
         rooms, names = bench_rooms(nr)
         bank = R.MeshBank(names, "cuda", seed=3)
+        views = room_views(rooms, n_views)
         with torch.cuda.stream(st):
             for capture in (False, True):
                 res = []; enq = []
                 for n_it in (iters, 2 * iters, iters, 2 * iters, iters, 2 * iters):
                     torch.cuda.synchronize(); t0 = time.perf_counter()
                     G = int(os.environ.get("GROUPS", "1"))
-                    rb = R.RefineBatch(model, rooms, bank=bank, iters=n_it)
+                    rb = R.RefineBatch(model, rooms, bank=bank, iters=n_it, views=views)
                     torch.cuda.synchronize(); t1 = time.perf_counter()
                     rb.run(capture=capture)
                     t_enq = time.perf_counter() - t1                  # host time to enqueue everything (the GPU may still be running)
                     torch.cuda.synchronize(); t2 = time.perf_counter()
                     enq.append(t_enq / n_it)
-                    lv = rb.live.cpu(); live = (float((lv == 3).sum()) / nr, float((lv == 1).sum()) / nr)
+                    lv = rb.live.cpu(); live = (float((lv == 3).sum()) / lv.shape[0], float((lv == 1).sum()) / lv.shape[0])
                     res.append((n_it, t1 - t0, t2 - t1)); info = rb.launches(); fin = bool(torch.isfinite(rb.losses).all()); rb.close()
                 a = sorted(x[2] for x in res if x[0] == iters)[1]; b = sorted(x[2] for x in res if x[0] == 2 * iters)[1]
                 setup = sorted(x[1] for x in res)[len(res) // 2]
-                print("rooms %2d %s: %.3f ms / iteration (%.4f per room-iteration), run-intercept %.2f ms, set-up %.2f ms per room, %s, finite %s"
-                      % (nr, "graph" if capture else "eager", (b - a) / iters * 1e3, (b - a) / iters * 1e3 / nr, (a - (b - a)) * 1e3, setup * 1e3 / nr, info, fin), flush=True)
-                print("   host enqueue time per iteration: %.3f ms (min over runs); planes per room: %.1f live, %.1f constant" % (min(enq) * 1e3, live[0], live[1]), flush=True)
+                print("rooms %2d views %d %s: %.3f ms / iteration (%.4f per room-iteration), run-intercept %.2f ms, set-up %.2f ms per room, %s, finite %s"
+                      % (nr, n_views, "graph" if capture else "eager", (b - a) / iters * 1e3, (b - a) / iters * 1e3 / nr, (a - (b - a)) * 1e3, setup * 1e3 / nr, info, fin), flush=True)
+                print("   host enqueue time per iteration: %.3f ms (min over runs); planes per image: %.1f live, %.1f constant" % (min(enq) * 1e3, live[0], live[1]), flush=True)
 
 
 if __name__ == "__main__":
