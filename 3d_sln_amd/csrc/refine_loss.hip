@@ -47,6 +47,16 @@ __global__ void null_mask_kernel(const float* __restrict__ img, RefineDims d, un
   null[i] = s < 0.5f ? 1 : 0;
 }
 
+// w0 * a + w1 * b of a bilinear stage with its one fused multiply-add spelled out.  Both pooling kernels form every sample through this
+// function: left to the compiler's contraction, pool_kernel and pool_lds_kernel - and the packed and the scalar copy of one loop -
+// fused different halves of the sum and differed in the last bit of a third of their outputs (tests/test_refine_loss_family_gpu.py).
+__device__ __forceinline__ float lerp2(const float w0, const float a, const float w1, const float b) { return fmaf(w0, a, w1 * b); }
+// upsample_bilinear2d's expression h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11)
+__device__ __forceinline__ float bilerp(const float h0, const float h1, const float w0, const float w1, const float v00, const float v01,
+                                        const float v10, const float v11) {
+  return lerp2(h0, lerp2(w0, v00, w1, v01), h1, lerp2(w0, v10, w1, v11));
+}
+
 // pooled[b][s][cc][oy][ox], cc = channel - sem0 over the n_sem + n_dep loss channels.  One thread resamples one pooled pixel
 // of CG consecutive channels: the 12 table entries that locate its 16 taps are loaded once per thread, not once per channel.
 constexpr int CG = 8;
@@ -90,17 +100,17 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ img
           v00 = nm[(long)y0 * d.S + x0] ? 1.f : v00; v01 = nm[(long)y0 * d.S + x1] ? 1.f : v01;
           v10 = nm[(long)y1 * d.S + x0] ? 1.f : v10; v11 = nm[(long)y1 * d.S + x1] ? 1.f : v11;
         }
-        inter[a][e] = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11);     // upsample_bilinear2d's expression
+        inter[a][e] = bilerp(h0, h1, w0, w1, v00, v01, v10, v11);
       }
     }
-    dst[(long)cc * pp] = ly0 * (lx0 * inter[0][0] + lx1 * inter[0][1]) + ly1 * (lx0 * inter[1][0] + lx1 * inter[1][1]);
+    dst[(long)cc * pp] = bilerp(ly0, ly1, lx0, lx1, inter[0][0], inter[0][1], inter[1][0], inter[1][1]);
   }
 }
 
 // The same resampling with the INTERMEDIATE image of a (plane, scale) in LDS (round 5): one workgroup per (image b, loss channel,
 // scale).  Phase A evaluates the align_corners=True stage once per intermediate pixel (4 image taps each: sz^2 evaluations instead of
 // the 4 P^2 the per-pixel kernel above repeats - 16 640 against 147 456 per plane over the four scales), phase B the second stage
-// from LDS with coalesced stores.  Same expressions, same order: the results are bit-identical to pool_kernel's.  With 16 rooms in
+// from LDS with coalesced stores.  Same expressions (bilerp), same order: the results are bit-identical to pool_kernel's.  With 16 rooms in
 // flight pool_kernel was the largest kernel of a refinement iteration (510 us: 680 M scattered 4-byte taps).
 constexpr int POOL_LDS_MAX = 96;
 __global__ __launch_bounds__(256) void pool_lds_kernel(const float* __restrict__ img, const unsigned char* __restrict__ null, const int null_fill,
@@ -140,7 +150,7 @@ __global__ __launch_bounds__(256) void pool_lds_kernel(const float* __restrict__
       v00 = nm[(long)y0 * d.S + x0] ? 1.f : v00; v01 = nm[(long)y0 * d.S + x1] ? 1.f : v01;
       v10 = nm[(long)y1 * d.S + x0] ? 1.f : v10; v11 = nm[(long)y1 * d.S + x1] ? 1.f : v11;
     }
-    inter[i] = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11);
+    inter[i] = bilerp(h0, h1, w0, w1, v00, v01, v10, v11);
   }
   __syncthreads();
   float* dst = pooled + ((long)(b * d.n_scales + s) * nc + cc) * ((long)d.P * d.P);
@@ -148,7 +158,7 @@ __global__ __launch_bounds__(256) void pool_lds_kernel(const float* __restrict__
     const int oy = o / d.P, ox = o % d.P;
     const int ky0 = s2_k0[s * d.P + oy], ky1 = s2_k1[s * d.P + oy], kx0 = s2_k0[s * d.P + ox], kx1 = s2_k1[s * d.P + ox];
     const float ly1 = s2_l1[s * d.P + oy], lx1 = s2_l1[s * d.P + ox], ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-    dst[o] = ly0 * (lx0 * inter[ky0 * sz + kx0] + lx1 * inter[ky0 * sz + kx1]) + ly1 * (lx0 * inter[ky1 * sz + kx0] + lx1 * inter[ky1 * sz + kx1]);
+    dst[o] = bilerp(ly0, ly1, lx0, lx1, inter[ky0 * sz + kx0], inter[ky0 * sz + kx1], inter[ky1 * sz + kx0], inter[ky1 * sz + kx1]);
   }
 }
 
