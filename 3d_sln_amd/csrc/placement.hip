@@ -15,6 +15,7 @@
 // The *_views kernels project one room's placement through V cameras (several target views per room): a face is placed once and
 // projected, culled and stored per view; the views' adjoints sum in world space into the same twelve accumulators.
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -354,6 +355,110 @@ __device__ __forceinline__ void place_backward_reduce(const SlnPlacement& P, con
   }
 }
 
+// Refinement of the camera poses of the target views (models/diff_render.py:13-46 builds the camera, :346-356 culls): the adjoint that
+// face_adjoint() carries from the image plane into camera space - (gx, gy, gzc), its statements in their order, BEFORE the multiplication
+// by R - reduced per (room, view) to the gradient of a rigid motion applied in the camera frame, p_cam' = exp([w]x) p_cam + tau, at
+// w = tau = 0:  dL/dtau = sum g_cam,  dL/dw = sum p_cam x g_cam  over the three corners of every face of the room that the view keeps
+// (the shell's faces included: they carry most of a camera's signal).  One workgroup per (room, view); a lane walks the faces
+// f = lane, lane + 256, ..; the products in float32, the six sums per lane and their reduction (shuffle, then a fixed LDS tree over the
+// four wavefronts) in float64: one writer, no atomics, the same bits run to run.  Thread 0 writes grad_pose, and - the view free, a
+// step non-zero - moves the float64 master pose by w = -rot_step dL/dw, tau = -trans_step dL/dtau (R <- E R, t <- E t + tau, E by
+// Rodrigues, by its series below |w| = 1e-8) and stores its float32 rounding into the camera table.  K is never written; with both
+// steps 0 or the view not free nothing but grad_pose is.
+__global__ __launch_bounds__(256) void place_pose_step_views_kernel(const SlnPlacementRoom* __restrict__ rooms, SlnPlacementCamera* cams,
+                                                                    double* __restrict__ pose, double* __restrict__ grad_pose,
+                                                                    const uint8_t* __restrict__ pose_free, int V, long view_stride,
+                                                                    float rot_step, float trans_step) {
+  const SlnPlacementRoom& r = rooms[blockIdx.y];
+  const SlnPlacement& P = r.P;
+  const long b = (long)blockIdx.y * V + blockIdx.x;
+  float K[9], R[9], t[3];                            // the OLD camera, in registers: thread 0 overwrites the table entry at the end
+#pragma unroll
+  for (int j = 0; j < 9; ++j) { K[j] = cams[b].K[j]; R[j] = cams[b].R[j]; }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) t[j] = cams[b].t[j];
+  const float* gf = r.grad_faces + blockIdx.x * view_stride;
+  const float s2 = 2.f / P.orig_size;
+  double acc[6];                                     // d omega (3), d tau (3)
+#pragma unroll
+  for (int j = 0; j < 6; ++j) acc[j] = 0.0;
+  int k_of_x = -1;
+  ObjXform x;
+  for (int f = threadIdx.x; f < P.F; f += 256) {
+    const int k = object_of_face(P, f);
+    if (k < P.n_vis && k != k_of_x) { x = object_xform(P, r.boxes, r.angles, k); k_of_x = k; }
+    Corner c[3];
+    bool cull = false;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      float p[3];
+      place_corner(P, x, k, P.faces[3 * f + q], p);
+      c[q] = project(P, K, R, t, p);
+      cull = cull || c[q].z < P.cull_eps;
+    }
+    if (cull) continue;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const float* a = gf + 9L * f + 3 * q;
+      const float* bk = gf + 9L * (P.F + f) + 3 * (2 - q);
+      const float gu = a[0] + bk[0], gv = a[1] + bk[1], gz = a[2] + bk[2];
+      const float iz = 1.f / (c[q].z + P.proj_eps);
+      const float gxh = s2 * (gu * K[0] - gv * K[3]);
+      const float gyh = s2 * (gu * K[1] - gv * K[4]);
+      const float gx = gxh * iz, gy = gyh * iz;
+      const float gzc = gz - (gxh * c[q].x + gyh * c[q].y) * iz * iz;
+      acc[0] += (double)(c[q].y * gzc) - (double)(c[q].z * gy);
+      acc[1] += (double)(c[q].z * gx) - (double)(c[q].x * gzc);
+      acc[2] += (double)(c[q].x * gy) - (double)(c[q].y * gx);
+      acc[3] += (double)gx; acc[4] += (double)gy; acc[5] += (double)gzc;
+    }
+  }
+  __shared__ double red[4][6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double v = acc[j];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = v;
+  }
+  __syncthreads();                                   // (every lane's reads of the table entry lie in front of this barrier)
+  if (threadIdx.x != 0) return;
+  double g[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) { g[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]); grad_pose[6 * b + j] = g[j]; }
+  if ((rot_step == 0.f && trans_step == 0.f) || (pose_free != nullptr && pose_free[b] == 0)) return;
+  const double w[3] = {-(double)rot_step * g[0], -(double)rot_step * g[1], -(double)rot_step * g[2]};
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
+  // E = I + A [w]x + B [w]x^2,  A = sin(th) / th,  B = (1 - cos(th)) / th^2 = 2 sin^2(th / 2) / th^2
+  double A, B;
+  if (th < 1e-8) { A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; }
+  else { const double sh = sin(0.5 * th); A = sin(th) / th; B = 2.0 * sh * sh / th2; }
+  const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+  double E[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double W2 = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
+      E[3 * i + j] = (i == j ? 1.0 : 0.0) + A * W[3 * i + j] + B * W2;
+    }
+  double* m = pose + 12 * b;                          // the master: R row-major, t
+  double o[12], nw[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) o[j] = m[j];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) nw[3 * i + j] = E[3 * i] * o[j] + E[3 * i + 1] * o[3 + j] + E[3 * i + 2] * o[6 + j];
+    nw[9 + i] = (E[3 * i] * o[9] + E[3 * i + 1] * o[10] + E[3 * i + 2] * o[11]) - (double)trans_step * g[3 + i];
+  }
+#pragma unroll
+  for (int j = 0; j < 12; ++j) m[j] = nw[j];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) cams[b].R[j] = (float)nw[j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) cams[b].t[j] = (float)nw[9 + j];
+}
+
 __global__ __launch_bounds__(256) void place_backward_kernel(SlnPlacement P, const float* __restrict__ boxes, const float* __restrict__ angles,
                                                              const float* __restrict__ size_target, const float* __restrict__ gf,
                                                              const float* __restrict__ g_size_loss, float* __restrict__ g_boxes,
@@ -568,6 +673,16 @@ int sln_place_backward_views(const SlnPlacementRoom* rooms, const SlnPlacementCa
                              void* stream) {
   if (!rooms || !cams || R < 1 || V < 1 || V > SLN_PLACE_MAX_VIEWS || n_max < 1 || view_stride < 18) return SLN_E_BADARG;
   hipLaunchKernelGGL(place_backward_views_kernel, dim3(n_max, R), dim3(256), 0, (hipStream_t)stream, rooms, cams, V, (long)view_stride);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_place_pose_step_views(const SlnPlacementRoom* rooms, SlnPlacementCamera* cams, double* pose, double* grad_pose, const uint8_t* pose_free,
+                              int R, int V, int64_t view_stride, float rot_step, float trans_step, void* stream) {
+  if (!rooms || !cams || !pose || !grad_pose || R < 1 || V < 1 || V > SLN_PLACE_MAX_VIEWS || view_stride < 18) return SLN_E_BADARG;
+  if (!(rot_step >= 0.f) || !(trans_step >= 0.f) || !std::isfinite(rot_step) || !std::isfinite(trans_step)) return SLN_E_BADARG;
+  hipLaunchKernelGGL(place_pose_step_views_kernel, dim3(V, R), dim3(256), 0, (hipStream_t)stream, rooms, cams, pose, grad_pose, pose_free, V,
+                     (long)view_stride, rot_step, trans_step);
   SLN_CHECK_LAUNCH();
   return 0;
 }

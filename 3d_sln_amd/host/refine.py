@@ -32,6 +32,7 @@ from . import diff_render as DR
 from . import evaluate as EV
 from . import mesh_prep as MP
 from . import observe as OB
+from . import reproject as RP
 from . import retrieve as RT
 from . import scene_pictures as SP
 from . import synthetic
@@ -654,6 +655,53 @@ def check_views(views, rooms=None, observed=None, mask=None, report=None, pictur
     if rooms is None:
         K, Rm, t = K[None], Rm[None], t[None]
     return K.contiguous(), Rm.contiguous(), t.contiguous()
+
+
+POSE_KEYS = ("rot_step", "trans_step", "free", "start")
+POSE_ORTHO_TOL = 1e-4    # a start rotation further than this from orthonormal (max |R R^T - I|) is refused
+
+
+def check_poses(poses, views, rooms=None):
+    """the ``poses=`` argument of the refinement entry points (DESIGN §4 "Camera poses of the target views"), refused before anything is
+    launched.  ``poses``: None, or ``dict(rot_step=, trans_step=, free=None | bool [R, V], start=None | (Rm [R, V, 3, 3], t [R, V, 3]))``;
+    ``views``: what ``check_views`` returned; ``rooms``: R, or None for the one-room form (``free`` [V], ``start`` ([V, 3, 3], [V, 3])).
+    -> None, or dict(rot_step, trans_step: floats; free: bool [R, V] host tensor or None; start: (Rm, t) float32 host tensors - the camera
+    table is float32 - or None).  Refused: poses without views, unknown keys, a negative or non-finite step, ``free`` that is no bool tensor
+    [R, V], ``start`` that is no pair of float32 / float64 tensors of those shapes, a start rotation with max |R R^T - I| > 1e-4."""
+    if poses is None:
+        return None
+    if views is None:
+        raise ValueError("poses needs views: the poses refined are those of the target views")
+    if not isinstance(poses, dict):
+        raise ValueError("poses is a dict with the keys %s" % (POSE_KEYS,))
+    unknown = sorted(set(poses) - set(POSE_KEYS))
+    if unknown:
+        raise ValueError("poses: unknown keys %s (known: %s)" % (unknown, POSE_KEYS))
+    steps = {}
+    for k in ("rot_step", "trans_step"):
+        v = poses.get(k, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError("poses: %s is a finite number >= 0, got %r" % (k, v))
+        steps[k] = float(v)
+    R, V = int(views[0].shape[0]), int(views[0].shape[1])
+    lead = (V,) if rooms is None else (R, V)
+    free, start = poses.get("free"), poses.get("start")
+    if free is not None:
+        if not torch.is_tensor(free) or free.dtype != torch.bool or tuple(free.shape) != lead:
+            raise ValueError("poses: free is a bool tensor %s" % (list(lead),))
+        free = free.detach().cpu().reshape(R, V).contiguous()
+    if start is not None:
+        ok = isinstance(start, (tuple, list)) and len(start) == 2 and all(torch.is_tensor(x) and x.dtype in (torch.float32, torch.float64) for x in start)
+        if not ok or tuple(start[0].shape) != lead + (3, 3) or tuple(start[1].shape) != lead + (3,):
+            raise ValueError("poses: start is (Rm %s, t %s), float32 or float64 tensors" % (list(lead) + [3, 3], list(lead) + [3]))
+        Rm, t = (x.detach().cpu().double().reshape((R, V) + tuple(x.shape[len(lead):])) for x in start)
+        if not (bool(torch.isfinite(Rm).all()) and bool(torch.isfinite(t).all())):
+            raise ValueError("poses: a start pose with a non-finite entry")
+        off = float((torch.matmul(Rm, Rm.transpose(-1, -2)) - torch.eye(3, dtype=torch.float64)).abs().max())
+        if off > POSE_ORTHO_TOL:
+            raise ValueError("poses: a start rotation is not orthonormal (max |R R^T - I| = %.3g > %g)" % (off, POSE_ORTHO_TOL))
+        start = (Rm.float().contiguous(), t.float().contiguous())
+    return dict(rot_step=steps["rot_step"], trans_step=steps["trans_step"], free=free, start=start)
 
 
 def _one_room_overlap(overlap_weight, overlap_rows, class_names, n, dev):
@@ -1299,13 +1347,23 @@ class RefineBatch:
     (``RefineScene.with_view``), or ``observed`` frames: ``observed`` and a tensor ``mask`` are then ``[R, V, S, S]``, ``target_status`` and
     ``mask_status`` ``[R, V]``.  A room with fewer than V views passes an all-zero ``mask`` for the missing ones - the divisor stays V;
     there is no other ragged form.  The camera table is uploaded once at set-up.  Out of scope, and refused: ``report``, ``pictures`` and
-    ``retrieve=True`` together with ``views``."""
+    ``retrieve=True`` together with ``views``.
+
+    ``poses``: None (default: the views' cameras are exact, the launches are those above and the camera table stays the one uploaded at
+    set-up), or ``dict(rot_step=, trans_step=, free=None | bool [R, V], start=None | (Rm [R, V, 3, 3], t [R, V, 3]))`` - needs ``views``
+    (DESIGN §4 "Camera poses of the target views").  Every iteration then issues one more launch behind sln_place_backward_views,
+    sln_place_pose_step_views: per (room, view) the gradient of the room's loss with respect to a rigid motion of the camera frame
+    (``pose_grad`` [iters, R, V, 6] float64: d omega, d tau - recorded on the device), and for the views marked ``free`` (None: all) the step
+    ``omega = -rot_step dL/domega``, ``tau = -trans_step dL/dtau`` on a float64 master copy of the poses, whose float32 rounding is the
+    camera table the next iteration projects through.  ``K`` is not refined.  ``start``: the cameras the loop begins from when they
+    differ from those the targets were rendered through (``views``) - the synthetic experiment; with ``observed`` there is nothing to
+    distinguish, and ``views`` are the start.  After ``run()``: ``poses()`` -> (Rm, t) float64, ``pose_error(Rm_ref, t_ref)``."""
 
     def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
-                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None):
+                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None):
         self.model, self.R, self.iters, self.lr, self.S = model, len(rooms), int(iters), float(learning_rate), int(image_size)
         dev = model.flat_params.device
-        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev, views)      # every refusal, in front of the first launch
+        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev, views, poses)      # every refusal, in front of the first launch
         if self._views is not None:      # from here on an image is b = r * V + v: observed frames and a mask tensor lose their room axis
             fold = lambda x: x.reshape(self.R * self.V, self.S, self.S) if torch.is_tensor(x) else x
             observed, mask = None if observed is None else tuple(fold(x) for x in observed), fold(mask)
@@ -1340,12 +1398,13 @@ class RefineBatch:
         if not torch.cuda.is_current_stream_capturing():
             _lib.lib().sln_side_stream_prepare(_lib.current_stream_ptr())
 
-    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev, views=None):
+    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev, views=None, poses=None):
         """refuses what cannot run; leaves ``_report_at`` (frozenset) and ``_pictures_at`` ({iteration: slot}), None when not asked for, + "all" flags,
-        ``_views`` (``check_views``: the cameras on the host, or None) and ``V``"""
+        ``_views`` (``check_views``: the cameras on the host, or None), ``V`` and ``_poses`` (``check_poses``, or None)"""
         if self.R < 1:
             raise ValueError("RefineBatch needs at least one room")
         self._views = check_views(views, self.R, observed, mask, report, pictures, retrieve)
+        self._poses = check_poses(poses, self._views, self.R)
         self.V = 1 if self._views is None else int(self._views[0].shape[1])
         shape = (self.R, self.S, self.S) if self._views is None else (self.R, self.V, self.S, self.S)
         check_observed(observed, shape, dev, cuda=True, choice=retrieve)
@@ -1545,7 +1604,32 @@ class RefineBatch:
         if self._views is not None and getattr(self, "_cams", None) is None:
             # the camera table [R * V] of SlnPlacementCamera (K[9], R[9], t[3]), uploaded once
             self._cams = torch.cat([x.reshape(R * V, -1) for x in self._views], 1).contiguous().to(dev)
+            if self._poses is not None:
+                self._pose_buffers(dev)
         self.scene_ws = torch.empty(int(_lib.lib().sln_scene_workspace_bytes(R * V, self.F2, self.S)), dtype=torch.uint8, device=dev)
+
+    def _pose_buffers(self, dev):
+        """poses: the loop's starting cameras in the table, the float64 master [R * V, 12] = double(float32 entry) (R row-major, then t), the
+        free flags and the record of the gradients"""
+        R, V, ps = self.R, self.V, self._poses
+        if ps["start"] is not None:
+            self._cams[:, 9:] = torch.cat([x.reshape(R * V, -1) for x in ps["start"]], 1).to(dev)
+        self._pose = self._cams[:, 9:].double().contiguous()
+        self._pose_free = None if ps["free"] is None else ps["free"].reshape(-1).to(torch.uint8).to(dev).contiguous()
+        self.pose_grad = torch.zeros(max(self.iters, 1), R, V, 6, dtype=torch.float64, device=dev)
+
+    def poses(self):
+        """(Rm [R, V, 3, 3], t [R, V, 3]) float64: the master copy of the refined poses (needs ``poses=``)"""
+        if self._poses is None:
+            raise ValueError("no poses are refined: RefineBatch(views=, poses=)")
+        m = self._pose.view(self.R, self.V, 12)
+        return m[..., :9].reshape(self.R, self.V, 3, 3).clone(), m[..., 9:].clone()
+
+    def pose_error(self, Rm_ref, t_ref):
+        """``reproject.pose_error`` of the refined poses against reference poses [R, V, 3, 3], [R, V, 3] -> (angle [R, V] in radians, distance
+        of the camera centres [R, V]) float64 on the poses' device"""
+        Rm, t = self.poses()
+        return RP.pose_error(Rm, t, torch.as_tensor(Rm_ref).to(Rm.device), torch.as_tensor(t_ref).to(Rm.device))
 
     def _retrieve_iterates(self):
         """retrieve=True: the iterates' meshes are those retrieved for the FIRST iterate's boxes (testing/test_render_refine.py:324-326:
@@ -1602,10 +1686,11 @@ class RefineBatch:
         _lib.check(_lib.lib().sln_vae_group_launches(self._group, C.byref(f), C.byref(b), C.byref(s1)), "sln_vae_group_launches")
         return dict(decoder_forward=f.value, decoder_backward=b.value, single_room_fallbacks=s1.value)
 
-    def _iteration(self, noise, out, report_out=None, pictures_out=None, overlap_out=None):
+    def _iteration(self, noise, out, report_out=None, pictures_out=None, overlap_out=None, pose_out=None):
         """one iteration of every room on the current stream; ``noise`` [N], ``out`` [R] receives the rooms' losses, ``report_out``
         [R, 3] (a reported iteration) the report, ``pictures_out`` (a pictured iteration) = (depth8, labels, rgb, status) of one slot,
-        ``overlap_out`` [R] float64 (with the penalty on) the rooms' unweighted penalties"""
+        ``overlap_out`` [R] float64 (with the penalty on) the rooms' unweighted penalties, ``pose_out`` [R, V, 6] float64 (with ``poses``) the
+        gradients of the views' poses"""
         L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
         N, R, na, S, B = self.N, self.R, self.model.Nangle, self.S, self.R * self.V
         self._forward_to_placement(noise)
@@ -1634,6 +1719,9 @@ class RefineBatch:
                                         P(self.g_image), P(self.g_faces), st), "sln_scene_backward")
         if self._views is not None:     # the views' adjoints meet in world space: one launch, one writer per row
             _lib.check(L.sln_place_backward_views(P(self._place_tab), P(self._cams), R, self.V, self.n_max, 9 * self.F2, st), "sln_place_backward_views")
+            if pose_out is not None:    # behind the placement's backward, which still reads the old cameras: the table is stepped in place
+                _lib.check(L.sln_place_pose_step_views(P(self._place_tab), P(self._cams), P(self._pose), P(pose_out), P(self._pose_free), R, self.V,
+                                                       9 * self.F2, self._poses["rot_step"], self._poses["trans_step"], st), "sln_place_pose_step_views")
         else:
             _lib.check(L.sln_place_backward_rooms(P(self._place_tab), R, self.n_max, st), "sln_place_backward_rooms")
         if overlap_out is not None:
@@ -1667,7 +1755,8 @@ class RefineBatch:
         if capture and self._graph_out is None:       # what the graph writes: copied to the iteration's own rows after every captured step
             self._graph_out = (self.loss_out.new_empty(self.R), self.loss_out.new_empty(self.R, 3) if self._report_all else None,
                                tuple(torch.empty_like(t[0]) for t in self.pictures[:4]) if self._pictures_all else None,
-                               torch.empty_like(self.overlap[0]) if self.overlap is not None else None)
+                               torch.empty_like(self.overlap[0]) if self.overlap is not None else None,
+                               torch.empty_like(self.pose_grad[0]) if self._poses is not None else None)
         if n > 0 and self.k == 0:
             self._first_iterate_sizes()
             if self._retrieve and self.models is None:
@@ -1689,8 +1778,11 @@ class RefineBatch:
                     dst.copy_(src)
                 if self.overlap is not None:
                     self.overlap[k].copy_(self._graph_out[3])
+                if self._poses is not None:
+                    self.pose_grad[k].copy_(self._graph_out[4])
             else:
-                self._iteration(self.noise_all[k], self.losses[k], rep, pic, self.overlap[k] if self.overlap is not None else None)
+                self._iteration(self.noise_all[k], self.losses[k], rep, pic, self.overlap[k] if self.overlap is not None else None,
+                                self.pose_grad[k] if self._poses is not None else None)
             self.k += 1
         return self.losses[:self.k]
 
@@ -1716,21 +1808,24 @@ class RefineBatch:
 
 
 def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None,
-                            pictures=None, retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None):
+                            pictures=None, retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
     noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
     ``report`` is given, the report [iters, R, 3] as a further element; only when ``pictures`` is given, the pair
     (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask`` / ``overlap_weight`` / ``overlap_rows`` /
-    ``views``: as ``RefineBatch``'s (``views`` combines with neither ``report``, ``pictures`` nor ``retrieve=True``)."""
+    ``views``: as ``RefineBatch``'s (``views`` combines with neither ``report``, ``pictures`` nor ``retrieve=True``).  ``poses``: as
+    ``RefineBatch``'s; only when it is given, the pair (``RefineBatch.poses()``, ``RefineBatch.pose_grad``) is the last element."""
     rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report,
                      pictures=pictures, retrieve=retrieve, observed=observed, mask=mask, overlap_weight=overlap_weight, overlap_rows=overlap_rows,
-                     views=views)
+                     views=views, poses=poses)
     try:
         out = (rb.run(capture=capture).clone(), [(b.clone(), i.clone()) for b, i in rb.results()])
         if report is not None:
             out += (rb.report.clone(),)
         if pictures is not None:
             out += ((rb.pictures, rb.target_pictures),)             # (buffers of their own: nothing of the batch's is referenced)
+        if poses is not None:
+            out += ((rb.poses(), rb.pose_grad.clone()),)
     finally:
         rb.close()
     return out
@@ -1738,7 +1833,7 @@ def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-
 
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,
                  learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None,
-                 views=None):
+                 views=None, poses=None):
     """finetune_VAE's inner loop for ONE room (test_render_refine.py:265-359) on synthetic meshes.
     ``observed`` / ``mask``: as ``finetune_vae_fast``'s, on the boxes' device whichever it is - the target from ``observed_target_torch`` on
     the room's class tables, the loss from ``refinement_loss_masked``.  ``overlap_weight`` / ``overlap_rows``: as ``finetune_vae_fast``'s (on CPU
@@ -1746,9 +1841,16 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
     ``views``: None, or ``(K [V, 3, 3], Rm [V, 3, 3], t [V, 3])`` - ``RefineBatch``'s ``views`` for one room, in autograd: every view is
     rendered with ``render_fn(..., camera=(K, Rm, t))``, the loss is ``mean_v L_v + 2 size_loss`` with ``L_v`` the view's depth and semantic
     terms over its own image; ``observed`` and a tensor ``mask`` are then ``[V, S, S]``.  The yardstick of the view kernels' loop.
-    Returns the list of per-iteration losses and the final (boxes_pred, angles_idx)."""
+    ``poses``: None, or ``RefineBatch``'s ``poses`` for one room (``free`` [V], ``start`` (Rm [V, 3, 3], t [V, 3])), in autograd: per view the
+    pose is a leaf ``(omega, tau)`` at 0, the world vertices are moved to ``E (Rm v + t) + tau`` in torch (``E = I + [omega]x + [omega]x^2 / 2``:
+    ``exp`` to the order the gradient at 0 needs) in front of ``render_fn(..., camera=(K, I, 0))``, the leaf is stepped by ``RefineBatch``'s
+    rule and folded into the float64 ``(Rm, t)`` with ``reproject.pose_step_torch`` after every iteration; the view's camera is the float32
+    rounding of that pair.  The yardstick of sln_place_pose_step_views inside the loop.
+    Returns the list of per-iteration losses and the final (boxes_pred, angles_idx); with ``poses``, the final ``(Rm [V, 3, 3], t [V, 3])``
+    float64 as a third element."""
     render_fn, dev = render_fn or DR.scene_render, boxes_gt.device
     cams = check_views(views, None, observed, mask)
+    pose = check_poses(poses, cams)
     if cams is None:
         observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, False, bank)
     else:
@@ -1778,6 +1880,11 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
             _, chan, dch = DR.class_tables(ranges.keys())
             target, _ = OB.observed_target_torch(observed[0], observed[1], chan, dch, nch=DR.N_SCENE_CHANNELS)
     valid, labels = valid_and_labels(mask, target)
+    if pose is not None:                 # the float64 pair the loop steps; K stays the view's
+        pose_R, pose_t = (x[0].double() for x in (pose["start"] if pose["start"] is not None else (torch.stack([c[1] for c in cams])[None],
+                                                                                                     torch.stack([c[2] for c in cams])[None])))
+        pose_free = [True] * len(cams) if pose["free"] is None else pose["free"][0].tolist()
+        eye3 = torch.eye(3, dtype=torch.float32, device=dev)
     size_target = None                   # the sizes of the FIRST iterate (:319-327: size_infos), not the target's (its sizes are "unused_sizes")
     losses = []
     for k in range(iters):
@@ -1795,9 +1902,18 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         if size_target is None:
             size_target = [s.clone() for s in sizes_k]
         if cams is not None:            # mean over the views of each view's own loss, the size loss once
-            per_view = []
+            per_view, leaves = [], []
             for vi, cam in enumerate(cams):
-                image = render_fn(v, f, ranges, room_box, image_size=image_size, camera=cam)
+                if pose is not None:    # the view's camera applied in torch, the leaf's rigid motion behind it, an identity camera for the render
+                    om, ta = (torch.zeros(3, dtype=torch.float32, device=dev, requires_grad=True) for _ in range(2))
+                    leaves.append((om, ta))
+                    W = RP._skew(om)
+                    E = eye3 + W + torch.matmul(W, W) / 2.0
+                    Rm32, t32 = pose_R[vi].float().to(dev), pose_t[vi].float().to(dev)
+                    moved = torch.matmul(torch.matmul(v, Rm32.t()) + t32, E.t()) + ta
+                    image = render_fn(moved, f, ranges, room_box, image_size=image_size, camera=(cam[0], eye3, torch.zeros(3)))
+                else:
+                    image = render_fn(v, f, ranges, room_box, image_size=image_size, camera=cam)
                 tgt, lab = target[vi:vi + 1], [t[vi:vi + 1] for t in labels]
                 if valid is not None:
                     per_view.append(refinement_loss_masked(image, tgt, lab, 0.0, valid[vi:vi + 1]))
@@ -1816,9 +1932,16 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         opt.zero_grad()
         loss.backward()
         opt.step()
+        if pose is not None:
+            for vi, (om, ta) in enumerate(leaves):
+                if pose_free[vi] and (pose["rot_step"] != 0.0 or pose["trans_step"] != 0.0):
+                    pose_R[vi], pose_t[vi] = RP.pose_step_torch(pose_R[vi], pose_t[vi], -pose["rot_step"] * om.grad.double().cpu(),
+                                                                -pose["trans_step"] * ta.grad.double().cpu())
         if hasattr(model, "params_changed"):
             model.params_changed()
         losses.append(float(loss.detach()))
         if log:
             log("iter %d: loss %.4f (depth %.4f, semantic %.4f)" % (k, losses[-1], float(dl), float(sl)))
+    if pose is not None:
+        return losses, (boxes_pred.detach(), idx.detach()), (pose_R, pose_t)
     return losses, (boxes_pred.detach(), idx.detach())

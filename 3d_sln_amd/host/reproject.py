@@ -12,6 +12,8 @@ pixel out of the rasterizer's maps.
     gives every target pixel to the frame with the nearest surface there - the z-buffer rule - and says which frame won, how many
     frames saw the pixel and how many of them agree with the winner's depth; ``fuse_torch`` / ``reproject_views_torch`` restate it
     (DESIGN §4 "Several observed frames per room");
+  * ``pose_step_torch``, ``rotation_exp``, ``pose_error``   the float64 restatement of a pose step of ``RefineBatch(poses=)`` and the
+    distance of two poses (DESIGN §4 "Camera poses of the target views");
   * ``relative_pose``, ``refine_view``, ``look_at_view``, ``scene_as_source``   the cameras: source -> target pose from two world poses,
     the refinement view of a room row, a further view of the room from an eye and a point it looks at (``RefineBatch(views=)``), and the
     source intrinsics under which a scene tensor's own planes are a frame of their own camera.
@@ -123,6 +125,51 @@ def look_at_view(eye, at):
     R = torch.diag(torch.tensor([1.0, -1.0, -1.0], dtype=torch.float64)) @ torch.stack((right, up, back))
     K = DR.get_cam_mat([[0.0] * 6], "cpu")[0][0]
     return K.contiguous(), R.float().contiguous(), (-(R @ e)).float().contiguous(), float(DR.inter_out)
+
+
+SMALL_ANGLE = 1e-8       # below it exp([w]x) is evaluated by its series (csrc/placement.hip, place_pose_step_views_kernel)
+
+
+def _skew(w):
+    z = torch.zeros_like(w[..., 0])
+    return torch.stack((torch.stack((z, -w[..., 2], w[..., 1]), -1), torch.stack((w[..., 2], z, -w[..., 0]), -1),
+                        torch.stack((-w[..., 1], w[..., 0], z), -1)), -2)
+
+
+def rotation_exp(omega, series=None):
+    """``exp([omega]x)`` [..., 3, 3] in float64: ``I + A W + B W^2`` with ``A = sin(th) / th``, ``B = 2 sin^2(th / 2) / th^2`` (Rodrigues), and
+    below ``|omega| = 1e-8`` their series ``A = 1 - th^2 / 6``, ``B = 1 / 2 - th^2 / 24``.  ``series``: None (by the angle), True or False
+    (one branch everywhere: for comparing the two)."""
+    w = torch.as_tensor(omega).double()
+    th2 = (w * w).sum(-1)
+    th = th2.sqrt()
+    small = (th < SMALL_ANGLE) if series is None else torch.full_like(th, bool(series), dtype=torch.bool)
+    safe = torch.where(th > 0, th, torch.ones_like(th))
+    A = torch.where(small, 1.0 - th2 / 6.0, torch.sin(safe) / safe)
+    B = torch.where(small, 0.5 - th2 / 24.0, 2.0 * torch.sin(0.5 * safe) ** 2 / (safe * safe))
+    W = _skew(w)
+    eye = torch.eye(3, dtype=torch.float64, device=w.device).expand_as(W)
+    return eye + A[..., None, None] * W + B[..., None, None] * torch.matmul(W, W)
+
+
+def pose_step_torch(Rm, t, omega, tau):
+    """One pose step in float64 (DESIGN §4 "Camera poses of the target views"): the rigid motion ``p_cam' = exp([omega]x) p_cam + tau``
+    applied in the camera frame of ``p_cam = Rm p_world + t``:  ``Rm <- E Rm``, ``t <- E t + tau``.  ``Rm`` [..., 3, 3], ``t``, ``omega``,
+    ``tau`` [..., 3] -> (Rm, t) float64.  The restatement of the update of sln_place_pose_step_views."""
+    Rm, t, tau = (torch.as_tensor(x).double() for x in (Rm, t, tau))
+    E = rotation_exp(omega)
+    return torch.matmul(E, Rm), torch.matmul(E, t[..., None])[..., 0] + tau
+
+
+def pose_error(Rm_a, t_a, Rm_b, t_b):
+    """-> (angle of ``Rm_a Rm_b^T`` in radians, distance of the two camera centres ``-Rm^T t``), float64, per leading index"""
+    Ra, ta, Rb, tb = (torch.as_tensor(x).double() for x in (Rm_a, t_a, Rm_b, t_b))
+    rel = (Ra[..., :, None, :] * Rb[..., None, :, :]).sum(-1)          # Ra Rb^T, symmetric by bits for Ra == Rb: a pose against itself gives 0
+    cos = (rel.diagonal(dim1=-2, dim2=-1).sum(-1) - 1.0) / 2.0
+    sin = torch.stack((rel[..., 2, 1] - rel[..., 1, 2], rel[..., 0, 2] - rel[..., 2, 0], rel[..., 1, 0] - rel[..., 0, 1]), -1).norm(dim=-1) / 2.0
+    ca = -torch.matmul(Ra.transpose(-1, -2), ta[..., None])[..., 0]
+    cb = -torch.matmul(Rb.transpose(-1, -2), tb[..., None])[..., 0]
+    return torch.atan2(sin, cos), (ca - cb).norm(dim=-1)
 
 
 def scene_as_source(K_tgt, orig_size, S):

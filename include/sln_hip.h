@@ -692,6 +692,22 @@ int sln_place_forward_views(const SlnPlacementRoom* rooms /* device [R] */, cons
                             int F_max, int64_t view_stride, void* stream);
 int sln_place_backward_views(const SlnPlacementRoom* rooms, const SlnPlacementCamera* cams, int R, int V, int n_max, int64_t view_stride,
                              void* stream);
+/* Refinement of the camera poses of the target views (DESIGN §4 "Camera poses of the target views"; the camera of
+ * models/diff_render.py:13-46, the cull of :346-356).  Issued AFTER sln_place_backward_views of the iteration, on the same operands:
+ * per (room, view) the camera-space adjoint of every corner of every face the view keeps (sln_place_backward_views' own, before its
+ * multiplication by R; the shell's faces count) is reduced to the gradient of a rigid motion applied in the camera frame,
+ * p_cam' = exp([w]x) p_cam + tau, at w = tau = 0:  grad_pose [R * V, 6] = (sum p_cam x g_cam, sum g_cam), float64 sums of float32 products,
+ * written on every call.  A view with pose_free != 0 (NULL: every view) is then moved by w = -rot_step dL/dw, tau = -trans_step dL/dtau:
+ * R <- E R, t <- E t + tau with E = exp([w]x), in the float64 master `pose` [R * V, 12] (R row-major, then t; the caller fills it with
+ * double(cams entry)), and the view's cams entry receives the float32 rounding of the master's R and t.  K is never written; with both
+ * steps 0, or for a view that is not free, neither pose nor cams is written.  grad_faces carries the loss's 1 / V: the gradient is that
+ * of the ROOM's loss.  Grid (V, R), one writer per (room, view), no atomics, no allocation, no synchronisation: legal in a linear
+ * capture.  SLN_E_BADARG, nothing launched: a null rooms / cams / pose / grad_pose, R < 1, V < 1, V > SLN_PLACE_MAX_VIEWS,
+ * view_stride < 18, a negative or non-finite step. */
+int sln_place_pose_step_views(const SlnPlacementRoom* rooms /* device [R] */, SlnPlacementCamera* cams /* device [R * V], updated in place */,
+                              double* pose /* device [R * V, 12] */, double* grad_pose /* device [R * V, 6]: d omega, d tau */,
+                              const uint8_t* pose_free /* device [R * V] or NULL = all */, int R, int V, int64_t view_stride,
+                              float rot_step, float trans_step, void* stream);
 /* sln_refine_sgd over R parameter copies: for every room r and every range k: p[r * stride + off_k + i] -= step * g[...], g = 0
  * (i < len_k; off_k, len_k multiples of 4 floats; n_ranges <= 96: the decoder's parameters are the three *_dc embedding tables in
  * front and the trailing gconv_net_dc / box_net / angle_net run - encoder-only parameters have zero gradients in this loop and are

@@ -1,7 +1,8 @@
 """Timing of the R-rooms-in-flight refinement loop (host/refine.py::RefineBatch) at train.py's defaults, 256 x 256: ms per iteration
 (slope between runs of `iters` and 2 x `iters` iterations) and set-up per room, eager and under hipGraph replay.  GPU box.
 VIEWS=V (default 0: ``views=None``): refine every room against V target views - view 0 is ``refine_view``'s camera, the others look from the
-room's upper corners at its centre (``look_at_view``)."""
+room's upper corners at its centre (``look_at_view``).  POSES=1 (needs VIEWS): refine the views' poses as well (``poses=``; ROT_STEP / TRANS_STEP,
+default 1e-6 each) - one more launch per iteration, sln_place_pose_step_views."""
 import importlib, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,13 +59,16 @@ def main():
         rooms, names = bench_rooms(nr)
         bank = R.MeshBank(names, "cuda", seed=3)
         views = room_views(rooms, n_views)
+        poses = None
+        if os.environ.get("POSES", "0") != "0":
+            poses = dict(rot_step=float(os.environ.get("ROT_STEP", "1e-6")), trans_step=float(os.environ.get("TRANS_STEP", "1e-6")))
         with torch.cuda.stream(st):
             for capture in (False, True):
                 res = []; enq = []
                 for n_it in (iters, 2 * iters, iters, 2 * iters, iters, 2 * iters):
                     torch.cuda.synchronize(); t0 = time.perf_counter()
                     G = int(os.environ.get("GROUPS", "1"))
-                    rb = R.RefineBatch(model, rooms, bank=bank, iters=n_it, views=views)
+                    rb = R.RefineBatch(model, rooms, bank=bank, iters=n_it, views=views, poses=poses)
                     torch.cuda.synchronize(); t1 = time.perf_counter()
                     rb.run(capture=capture)
                     t_enq = time.perf_counter() - t1                  # host time to enqueue everything (the GPU may still be running)
@@ -74,8 +78,8 @@ def main():
                     res.append((n_it, t1 - t0, t2 - t1)); info = rb.launches(); fin = bool(torch.isfinite(rb.losses).all()); rb.close()
                 a = sorted(x[2] for x in res if x[0] == iters)[1]; b = sorted(x[2] for x in res if x[0] == 2 * iters)[1]
                 setup = sorted(x[1] for x in res)[len(res) // 2]
-                print("rooms %2d views %d %s: %.3f ms / iteration (%.4f per room-iteration), run-intercept %.2f ms, set-up %.2f ms per room, %s, finite %s"
-                      % (nr, n_views, "graph" if capture else "eager", (b - a) / iters * 1e3, (b - a) / iters * 1e3 / nr, (a - (b - a)) * 1e3, setup * 1e3 / nr, info, fin), flush=True)
+                print("rooms %2d views %d%s %s: %.3f ms / iteration (%.4f per room-iteration), run-intercept %.2f ms, set-up %.2f ms per room, %s, finite %s"
+                      % (nr, n_views, " poses" if poses else "", "graph" if capture else "eager", (b - a) / iters * 1e3, (b - a) / iters * 1e3 / nr, (a - (b - a)) * 1e3, setup * 1e3 / nr, info, fin), flush=True)
                 print("   host enqueue time per iteration: %.3f ms (min over runs); planes per image: %.1f live, %.1f constant" % (min(enq) * 1e3, live[0], live[1]), flush=True)
 
 
