@@ -355,6 +355,62 @@ __device__ __forceinline__ void place_backward_reduce(const SlnPlacement& P, con
   }
 }
 
+// corner q of the kept face f: face_adjoint()'s statements in their order up to the camera-space adjoint (gx, gy, gzc), and the six
+// pose sums of it (float32 products, float64 sums).  Out: su = s2 gu, sv = s2 gv (the image gradient in pixels of orig_size - the face's
+// plus its fill_back copy's - as the intrinsics' sums take it) and the reciprocal iz.
+__device__ __forceinline__ void pose_corner_sums(const SlnPlacement& P, const float* __restrict__ K, const float* __restrict__ gf, int f, int q,
+                                                 const Corner& c, float s2, double acc[6], float& su, float& sv, float& iz) {
+  const float* a = gf + 9L * f + 3 * q;
+  const float* bk = gf + 9L * (P.F + f) + 3 * (2 - q);
+  const float gu = a[0] + bk[0], gv = a[1] + bk[1], gz = a[2] + bk[2];
+  iz = 1.f / (c.z + P.proj_eps);
+  const float gxh = s2 * (gu * K[0] - gv * K[3]);
+  const float gyh = s2 * (gu * K[1] - gv * K[4]);
+  const float gx = gxh * iz, gy = gyh * iz;
+  const float gzc = gz - (gxh * c.x + gyh * c.y) * iz * iz;
+  acc[0] += (double)(c.y * gzc) - (double)(c.z * gy);
+  acc[1] += (double)(c.z * gx) - (double)(c.x * gzc);
+  acc[2] += (double)(c.x * gy) - (double)(c.y * gx);
+  acc[3] += (double)gx; acc[4] += (double)gy; acc[5] += (double)gzc;
+  su = s2 * gu; sv = s2 * gv;
+}
+
+// thread 0's pose update of image b from the gradient g (d omega, d tau): the float64 master, then its float32 rounding into the table
+__device__ __forceinline__ void pose_master_step(SlnPlacementCamera* cams, double* __restrict__ pose, long b, const double g[6], float rot_step,
+                                                 float trans_step) {
+  const double w[3] = {-(double)rot_step * g[0], -(double)rot_step * g[1], -(double)rot_step * g[2]};
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
+  // E = I + A [w]x + B [w]x^2,  A = sin(th) / th,  B = (1 - cos(th)) / th^2 = 2 sin^2(th / 2) / th^2
+  double A, B;
+  if (th < 1e-8) { A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; }
+  else { const double sh = sin(0.5 * th); A = sin(th) / th; B = 2.0 * sh * sh / th2; }
+  const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+  double E[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double W2 = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
+      E[3 * i + j] = (i == j ? 1.0 : 0.0) + A * W[3 * i + j] + B * W2;
+    }
+  double* m = pose + 12 * b;                          // the master: R row-major, t
+  double o[12], nw[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) o[j] = m[j];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) nw[3 * i + j] = E[3 * i] * o[j] + E[3 * i + 1] * o[3 + j] + E[3 * i + 2] * o[6 + j];
+    nw[9 + i] = (E[3 * i] * o[9] + E[3 * i + 1] * o[10] + E[3 * i + 2] * o[11]) - (double)trans_step * g[3 + i];
+  }
+#pragma unroll
+  for (int j = 0; j < 12; ++j) m[j] = nw[j];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) cams[b].R[j] = (float)nw[j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) cams[b].t[j] = (float)nw[9 + j];
+}
+
 // Refinement of the camera poses of the target views (models/diff_render.py:13-46 builds the camera, :346-356 culls): the adjoint that
 // face_adjoint() carries from the image plane into camera space - (gx, gy, gzc), its statements in their order, BEFORE the multiplication
 // by R - reduced per (room, view) to the gradient of a rigid motion applied in the camera frame, p_cam' = exp([w]x) p_cam + tau, at
@@ -399,18 +455,8 @@ __global__ __launch_bounds__(256) void place_pose_step_views_kernel(const SlnPla
     if (cull) continue;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      const float* a = gf + 9L * f + 3 * q;
-      const float* bk = gf + 9L * (P.F + f) + 3 * (2 - q);
-      const float gu = a[0] + bk[0], gv = a[1] + bk[1], gz = a[2] + bk[2];
-      const float iz = 1.f / (c[q].z + P.proj_eps);
-      const float gxh = s2 * (gu * K[0] - gv * K[3]);
-      const float gyh = s2 * (gu * K[1] - gv * K[4]);
-      const float gx = gxh * iz, gy = gyh * iz;
-      const float gzc = gz - (gxh * c[q].x + gyh * c[q].y) * iz * iz;
-      acc[0] += (double)(c[q].y * gzc) - (double)(c[q].z * gy);
-      acc[1] += (double)(c[q].z * gx) - (double)(c[q].x * gzc);
-      acc[2] += (double)(c[q].x * gy) - (double)(c[q].y * gx);
-      acc[3] += (double)gx; acc[4] += (double)gy; acc[5] += (double)gzc;
+      float su, sv, iz;
+      pose_corner_sums(P, K, gf, f, q, c[q], s2, acc, su, sv, iz);
     }
   }
   __shared__ double red[4][6];
@@ -426,37 +472,99 @@ __global__ __launch_bounds__(256) void place_pose_step_views_kernel(const SlnPla
 #pragma unroll
   for (int j = 0; j < 6; ++j) { g[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]); grad_pose[6 * b + j] = g[j]; }
   if ((rot_step == 0.f && trans_step == 0.f) || (pose_free != nullptr && pose_free[b] == 0)) return;
-  const double w[3] = {-(double)rot_step * g[0], -(double)rot_step * g[1], -(double)rot_step * g[2]};
-  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
-  // E = I + A [w]x + B [w]x^2,  A = sin(th) / th,  B = (1 - cos(th)) / th^2 = 2 sin^2(th / 2) / th^2
-  double A, B;
-  if (th < 1e-8) { A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; }
-  else { const double sh = sin(0.5 * th); A = sin(th) / th; B = 2.0 * sh * sh / th2; }
-  const double W[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
-  double E[9];
+  pose_master_step(cams, pose, b, g, rot_step, trans_step);
+}
+
+// Refinement of the intrinsics of the target views, in ONE launch with the pose step (two launches would each read the camera the other
+// has just overwritten): place_pose_step_views_kernel's walk with four more sums per lane.  With s2 = 2 / orig_size, (gu, gv) a kept
+// corner's image gradient (the face's plus its fill_back copy's) and project()'s u = xh K[0] + yh K[1] + K[2],
+// v = os - (xh K[3] + yh K[4] + K[5]):
+//   dL/dfx = sum s2 gu xh,   dL/dfy = sum -s2 gv yh,   dL/dcx = sum s2 gu,   dL/dcy = sum -s2 gv      (fx = K[0], fy = K[4], cx = K[2], cy = K[5])
+// The float32 expressions, each operation rounded once (the unit keeps -ffp-contract=off):
+//   su = s2 * gu, sv = s2 * gv;  iz = 1.f / (z + proj_eps): the adjoint's reciprocal, NOT project()'s quotient x / (z + proj_eps);
+//   xh = x * iz, yh = y * iz;  the four terms  su * xh,  -(sv * yh),  su,  -sv  - converted to float64 and summed there, lane sums and
+// reduction as the pose sums'.  The six pose sums are pose_corner_sums()' statements in the pose kernel's order: grad_pose has that
+// kernel's bits.  Thread 0 writes grad_pose and grad_intr, then both updates from the OLD camera (every lane read it into registers in
+// front of the barrier): the pose update by the pose kernel's rule and code, and - the view intr_free, a step non-zero - on the float64
+// master `intr` (fx, fy, cx, cy):  fx <- fx exp(sx), fy <- fy exp(sy) with sx = -focal_step fx dL/dfx, sy = -focal_step fy dL/dfy, or
+// with tie_focal sx = sy = -focal_step (fx dL/dfx + fy dL/dfy); cx <- cx - center_step dL/dcx, cy likewise; sx, sy are held to
+// [-SLN_FOCAL_LOG_MAX, SLN_FOCAL_LOG_MAX]: whatever the gradient, a focal length stays positive and finite.  K[0], K[4], K[2], K[5] of
+// the table entry receive the float32 rounding of the master; K[1], K[3], K[6..8] are read and never written.
+__global__ __launch_bounds__(256) void place_camera_step_views_kernel(const SlnPlacementRoom* __restrict__ rooms, SlnPlacementCamera* cams,
+                                                                      double* __restrict__ pose, double* __restrict__ grad_pose,
+                                                                      const uint8_t* __restrict__ pose_free, double* __restrict__ intr,
+                                                                      double* __restrict__ grad_intr, const uint8_t* __restrict__ intr_free,
+                                                                      int V, long view_stride, float rot_step, float trans_step,
+                                                                      float focal_step, float center_step, int tie_focal) {
+  const SlnPlacementRoom& r = rooms[blockIdx.y];
+  const SlnPlacement& P = r.P;
+  const long b = (long)blockIdx.y * V + blockIdx.x;
+  float K[9], R[9], t[3];                            // the OLD camera, in registers: thread 0 overwrites the table entry at the end
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int j = 0; j < 9; ++j) { K[j] = cams[b].K[j]; R[j] = cams[b].R[j]; }
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const double W2 = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-      E[3 * i + j] = (i == j ? 1.0 : 0.0) + A * W[3 * i + j] + B * W2;
+  for (int j = 0; j < 3; ++j) t[j] = cams[b].t[j];
+  const float* gf = r.grad_faces + blockIdx.x * view_stride;
+  const float s2 = 2.f / P.orig_size;
+  double acc[10];                                    // d omega (3), d tau (3), d fx, d fy, d cx, d cy
+#pragma unroll
+  for (int j = 0; j < 10; ++j) acc[j] = 0.0;
+  int k_of_x = -1;
+  ObjXform x;
+  for (int f = threadIdx.x; f < P.F; f += 256) {
+    const int k = object_of_face(P, f);
+    if (k < P.n_vis && k != k_of_x) { x = object_xform(P, r.boxes, r.angles, k); k_of_x = k; }
+    Corner c[3];
+    bool cull = false;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      float p[3];
+      place_corner(P, x, k, P.faces[3 * f + q], p);
+      c[q] = project(P, K, R, t, p);
+      cull = cull || c[q].z < P.cull_eps;
     }
-  double* m = pose + 12 * b;                          // the master: R row-major, t
-  double o[12], nw[12];
+    if (cull) continue;
 #pragma unroll
-  for (int j = 0; j < 12; ++j) o[j] = m[j];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) nw[3 * i + j] = E[3 * i] * o[j] + E[3 * i + 1] * o[3 + j] + E[3 * i + 2] * o[6 + j];
-    nw[9 + i] = (E[3 * i] * o[9] + E[3 * i + 1] * o[10] + E[3 * i + 2] * o[11]) - (double)trans_step * g[3 + i];
+    for (int q = 0; q < 3; ++q) {
+      float su, sv, iz;
+      pose_corner_sums(P, K, gf, f, q, c[q], s2, acc, su, sv, iz);
+      const float xh = c[q].x * iz, yh = c[q].y * iz;
+      acc[6] += (double)(su * xh);
+      acc[7] += (double)(-(sv * yh));
+      acc[8] += (double)su;
+      acc[9] += (double)(-sv);
+    }
   }
+  __shared__ double red[4][10];
 #pragma unroll
-  for (int j = 0; j < 12; ++j) m[j] = nw[j];
+  for (int j = 0; j < 10; ++j) {
+    double v = acc[j];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][j] = v;
+  }
+  __syncthreads();                                   // (every lane's reads of the table entry lie in front of this barrier)
+  if (threadIdx.x != 0) return;
+  double g[10];
 #pragma unroll
-  for (int j = 0; j < 9; ++j) cams[b].R[j] = (float)nw[j];
+  for (int j = 0; j < 10; ++j) g[j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
 #pragma unroll
-  for (int j = 0; j < 3; ++j) cams[b].t[j] = (float)nw[9 + j];
+  for (int j = 0; j < 6; ++j) grad_pose[6 * b + j] = g[j];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) grad_intr[4 * b + j] = g[6 + j];
+  if (!((rot_step == 0.f && trans_step == 0.f) || (pose_free != nullptr && pose_free[b] == 0)))
+    pose_master_step(cams, pose, b, g, rot_step, trans_step);
+  if ((focal_step == 0.f && center_step == 0.f) || (intr_free != nullptr && intr_free[b] == 0)) return;
+  double* m = intr + 4 * b;                           // the master: fx, fy, cx, cy
+  const double fx = m[0], fy = m[1], fs = (double)focal_step, cs = (double)center_step;
+  double sx = -fs * (fx * g[6]), sy = -fs * (fy * g[7]);
+  if (tie_focal) sx = sy = -fs * (fx * g[6] + fy * g[7]);
+  const double lim = SLN_FOCAL_LOG_MAX;
+  sx = sx > lim ? lim : (sx < -lim ? -lim : sx);
+  sy = sy > lim ? lim : (sy < -lim ? -lim : sy);
+  const double nw[4] = {fx * exp(sx), fy * exp(sy), m[2] - cs * g[8], m[3] - cs * g[9]};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m[j] = nw[j];
+  cams[b].K[0] = (float)nw[0]; cams[b].K[4] = (float)nw[1]; cams[b].K[2] = (float)nw[2]; cams[b].K[5] = (float)nw[3];
 }
 
 __global__ __launch_bounds__(256) void place_backward_kernel(SlnPlacement P, const float* __restrict__ boxes, const float* __restrict__ angles,
@@ -683,6 +791,23 @@ int sln_place_pose_step_views(const SlnPlacementRoom* rooms, SlnPlacementCamera*
   if (!(rot_step >= 0.f) || !(trans_step >= 0.f) || !std::isfinite(rot_step) || !std::isfinite(trans_step)) return SLN_E_BADARG;
   hipLaunchKernelGGL(place_pose_step_views_kernel, dim3(V, R), dim3(256), 0, (hipStream_t)stream, rooms, cams, pose, grad_pose, pose_free, V,
                      (long)view_stride, rot_step, trans_step);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_place_camera_step_views(const SlnPlacementRoom* rooms, SlnPlacementCamera* cams, double* pose, double* grad_pose, const uint8_t* pose_free,
+                                double* intr, double* grad_intr, const uint8_t* intr_free, int R, int V, int64_t view_stride, float rot_step,
+                                float trans_step, float focal_step, float center_step, int tie_focal, void* stream) {
+  if (!rooms || !cams || !pose || !grad_pose || R < 1 || V < 1 || V > SLN_PLACE_MAX_VIEWS || view_stride < 18) return SLN_E_BADARG;
+  if (!(rot_step >= 0.f) || !(trans_step >= 0.f) || !std::isfinite(rot_step) || !std::isfinite(trans_step)) return SLN_E_BADARG;
+  if (!(focal_step >= 0.f) || !(center_step >= 0.f) || !std::isfinite(focal_step) || !std::isfinite(center_step)) return SLN_E_BADARG;
+  if ((intr == nullptr) != (grad_intr == nullptr) || (!intr && intr_free)) return SLN_E_BADARG;
+  if (!intr)                                         // no intrinsics: the call IS the pose step - its kernel, its bits
+    hipLaunchKernelGGL(place_pose_step_views_kernel, dim3(V, R), dim3(256), 0, (hipStream_t)stream, rooms, cams, pose, grad_pose, pose_free, V,
+                       (long)view_stride, rot_step, trans_step);
+  else
+    hipLaunchKernelGGL(place_camera_step_views_kernel, dim3(V, R), dim3(256), 0, (hipStream_t)stream, rooms, cams, pose, grad_pose, pose_free,
+                       intr, grad_intr, intr_free, V, (long)view_stride, rot_step, trans_step, focal_step, center_step, tie_focal);
   SLN_CHECK_LAUNCH();
   return 0;
 }

@@ -704,6 +704,63 @@ def check_poses(poses, views, rooms=None):
     return dict(rot_step=steps["rot_step"], trans_step=steps["trans_step"], free=free, start=start)
 
 
+INTRINSICS_KEYS = ("focal_step", "center_step", "tie_focal", "free", "start")
+
+
+def _check_pinhole(K, what):
+    """a K the intrinsics' refinement can step: finite, zero skew (K[0, 1] = K[1, 0] = 0), fx, fy > 0, last row (0, 0, 1)"""
+    if not bool(torch.isfinite(K).all()):
+        raise ValueError("intrinsics: %s has a non-finite entry" % what)
+    if bool((K[..., 0, 1] != 0).any()) or bool((K[..., 1, 0] != 0).any()):
+        raise ValueError("intrinsics: %s has non-zero skew (K[0, 1], K[1, 0]): skew is not refined and the update assumes none" % what)
+    if bool((K[..., 0, 0] <= 0).any()) or bool((K[..., 1, 1] <= 0).any()):
+        raise ValueError("intrinsics: %s has a focal length that is not positive" % what)
+    if not bool((K[..., 2, :] == torch.tensor([0.0, 0.0, 1.0], dtype=K.dtype)).all()):
+        raise ValueError("intrinsics: the last row of %s is not (0, 0, 1)" % what)
+
+
+def check_intrinsics(intrinsics, views, rooms=None):
+    """the ``intrinsics=`` argument of the refinement entry points (DESIGN §4 "Intrinsics of the target views"), refused before anything is
+    launched.  ``intrinsics``: None, or ``dict(focal_step=, center_step=, tie_focal=True, free=None | bool [R, V], start=None | K [R, V, 3, 3])``;
+    ``views``: what ``check_views`` returned; ``rooms``: R, or None for the one-room form (``free`` [V], ``start`` [V, 3, 3]).
+    -> None, or dict(focal_step, center_step: floats; tie_focal: bool; free: bool [R, V] host tensor or None; start: K float32 host tensor
+    [R, V, 3, 3] - the camera table is float32 - or None).  Refused: intrinsics without views, unknown keys, a negative or non-finite step,
+    a ``tie_focal`` that is no bool, ``free`` that is no bool tensor [R, V], ``start`` that is no float32 / float64 tensor [R, V, 3, 3], and a
+    ``K`` - the views' or the start's - with a non-finite entry, non-zero skew, a focal length <= 0 or a last row other than (0, 0, 1)."""
+    if intrinsics is None:
+        return None
+    if views is None:
+        raise ValueError("intrinsics needs views: the intrinsics refined are those of the target views")
+    if not isinstance(intrinsics, dict):
+        raise ValueError("intrinsics is a dict with the keys %s" % (INTRINSICS_KEYS,))
+    unknown = sorted(set(intrinsics) - set(INTRINSICS_KEYS))
+    if unknown:
+        raise ValueError("intrinsics: unknown keys %s (known: %s)" % (unknown, INTRINSICS_KEYS))
+    steps = {}
+    for k in ("focal_step", "center_step"):
+        v = intrinsics.get(k, 0.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError("intrinsics: %s is a finite number >= 0, got %r" % (k, v))
+        steps[k] = float(v)
+    tie = intrinsics.get("tie_focal", True)
+    if not isinstance(tie, bool):
+        raise ValueError("intrinsics: tie_focal is True or False, got %r" % (tie,))
+    R, V = int(views[0].shape[0]), int(views[0].shape[1])
+    lead = (V,) if rooms is None else (R, V)
+    free, start = intrinsics.get("free"), intrinsics.get("start")
+    if free is not None:
+        if not torch.is_tensor(free) or free.dtype != torch.bool or tuple(free.shape) != lead:
+            raise ValueError("intrinsics: free is a bool tensor %s" % (list(lead),))
+        free = free.detach().cpu().reshape(R, V).contiguous()
+    _check_pinhole(views[0], "a K of views")
+    if start is not None:
+        if not torch.is_tensor(start) or start.dtype not in (torch.float32, torch.float64) or tuple(start.shape) != lead + (3, 3):
+            raise ValueError("intrinsics: start is K %s, a float32 or float64 tensor" % (list(lead) + [3, 3],))
+        start = start.detach().cpu().reshape(R, V, 3, 3).float().contiguous()
+        _check_pinhole(start, "a K of start")
+    return dict(focal_step=steps["focal_step"], center_step=steps["center_step"], tie_focal=tie, free=free, start=start)
+
+
 def _one_room_overlap(overlap_weight, overlap_rows, class_names, n, dev):
     """the one-room loops' checked penalty arguments -> None (weight 0), or the tensors of ``_overlap_term``: (collide uint8 [n], room_of_row
     int32 [n], room_id int32 [n]) on ``dev``"""
@@ -1357,13 +1414,23 @@ class RefineBatch:
     ``omega = -rot_step dL/domega``, ``tau = -trans_step dL/dtau`` on a float64 master copy of the poses, whose float32 rounding is the
     camera table the next iteration projects through.  ``K`` is not refined.  ``start``: the cameras the loop begins from when they
     differ from those the targets were rendered through (``views``) - the synthetic experiment; with ``observed`` there is nothing to
-    distinguish, and ``views`` are the start.  After ``run()``: ``poses()`` -> (Rm, t) float64, ``pose_error(Rm_ref, t_ref)``."""
+    distinguish, and ``views`` are the start.  After ``run()``: ``poses()`` -> (Rm, t) float64, ``pose_error(Rm_ref, t_ref)``.
+
+    ``intrinsics``: None (default: ``K`` of every view is exact; the launches and the bits are those above), or ``dict(focal_step=,
+    center_step=, tie_focal=True, free=None | bool [R, V], start=None | K [R, V, 3, 3])`` - needs ``views``, combines with ``poses`` or stands
+    alone (DESIGN §4 "Intrinsics of the target views").  The iteration then issues sln_place_camera_step_views in the place of the pose
+    launch (pose steps 0 when ``poses`` is None): beside the pose gradient it records ``intr_grad`` [iters, R, V, 4] float64 = (dL/dfx, dL/dfy,
+    dL/dcx, dL/dcy) on the device, and steps the views marked ``free`` (None: all) on a float64 master: ``fx <- fx exp(-focal_step fx
+    dL/dfx)``, ``fy`` likewise - with ``tie_focal`` both by the one log-scale ``-focal_step (fx dL/dfx + fy dL/dfy)`` - and ``cx <- cx -
+    center_step dL/dcx``, ``cy`` likewise (``reproject.intrinsics_step_torch``).  Skew and the last row of ``K`` stay; a ``K`` with skew is
+    refused.  ``start``: the ``K`` the loop begins from, as for poses.  After ``run()``: ``intrinsics()`` -> K float64,
+    ``intrinsics_error(K_ref)``."""
 
     def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
-                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None):
+                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None, intrinsics=None):
         self.model, self.R, self.iters, self.lr, self.S = model, len(rooms), int(iters), float(learning_rate), int(image_size)
         dev = model.flat_params.device
-        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev, views, poses)      # every refusal, in front of the first launch
+        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev, views, poses, intrinsics)      # every refusal, in front of the first launch
         if self._views is not None:      # from here on an image is b = r * V + v: observed frames and a mask tensor lose their room axis
             fold = lambda x: x.reshape(self.R * self.V, self.S, self.S) if torch.is_tensor(x) else x
             observed, mask = None if observed is None else tuple(fold(x) for x in observed), fold(mask)
@@ -1398,13 +1465,14 @@ class RefineBatch:
         if not torch.cuda.is_current_stream_capturing():
             _lib.lib().sln_side_stream_prepare(_lib.current_stream_ptr())
 
-    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev, views=None, poses=None):
+    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev, views=None, poses=None, intrinsics=None):
         """refuses what cannot run; leaves ``_report_at`` (frozenset) and ``_pictures_at`` ({iteration: slot}), None when not asked for, + "all" flags,
-        ``_views`` (``check_views``: the cameras on the host, or None), ``V`` and ``_poses`` (``check_poses``, or None)"""
+        ``_views`` (``check_views``: the cameras on the host, or None), ``V``, ``_poses`` (``check_poses``, or None) and ``_intr`` (``check_intrinsics``, or None)"""
         if self.R < 1:
             raise ValueError("RefineBatch needs at least one room")
         self._views = check_views(views, self.R, observed, mask, report, pictures, retrieve)
         self._poses = check_poses(poses, self._views, self.R)
+        self._intr = check_intrinsics(intrinsics, self._views, self.R)
         self.V = 1 if self._views is None else int(self._views[0].shape[1])
         shape = (self.R, self.S, self.S) if self._views is None else (self.R, self.V, self.S, self.S)
         check_observed(observed, shape, dev, cuda=True, choice=retrieve)
@@ -1604,23 +1672,51 @@ class RefineBatch:
         if self._views is not None and getattr(self, "_cams", None) is None:
             # the camera table [R * V] of SlnPlacementCamera (K[9], R[9], t[3]), uploaded once
             self._cams = torch.cat([x.reshape(R * V, -1) for x in self._views], 1).contiguous().to(dev)
-            if self._poses is not None:
+            if self._poses is not None or self._intr is not None:
                 self._pose_buffers(dev)
+            if self._intr is not None:
+                self._intr_buffers(dev)
         self.scene_ws = torch.empty(int(_lib.lib().sln_scene_workspace_bytes(R * V, self.F2, self.S)), dtype=torch.uint8, device=dev)
 
     def _pose_buffers(self, dev):
         """poses: the loop's starting cameras in the table, the float64 master [R * V, 12] = double(float32 entry) (R row-major, then t), the
         free flags and the record of the gradients"""
-        R, V, ps = self.R, self.V, self._poses
+        R, V, ps = self.R, self.V, self._poses or dict(start=None, free=None)      # (intrinsics alone: the poses are held, their steps 0)
         if ps["start"] is not None:
             self._cams[:, 9:] = torch.cat([x.reshape(R * V, -1) for x in ps["start"]], 1).to(dev)
         self._pose = self._cams[:, 9:].double().contiguous()
         self._pose_free = None if ps["free"] is None else ps["free"].reshape(-1).to(torch.uint8).to(dev).contiguous()
         self.pose_grad = torch.zeros(max(self.iters, 1), R, V, 6, dtype=torch.float64, device=dev)
 
+    def _intr_buffers(self, dev):
+        """intrinsics: the loop's starting K in the table, the float64 master [R * V, 4] = double(float32 entry) (fx, fy, cx, cy), the free
+        flags and the record of the gradients"""
+        R, V, it = self.R, self.V, self._intr
+        if it["start"] is not None:
+            self._cams[:, :9] = it["start"].reshape(R * V, 9).to(dev)
+        self._intr_master = self._cams[:, [0, 4, 2, 5]].double().contiguous()
+        self._intr_free = None if it["free"] is None else it["free"].reshape(-1).to(torch.uint8).to(dev).contiguous()
+        self.intr_grad = torch.zeros(max(self.iters, 1), R, V, 4, dtype=torch.float64, device=dev)
+
+    def intrinsics(self):
+        """K [R, V, 3, 3] float64: the master copy of the refined focal lengths and principal points in the views' K, whose other entries
+        are the table's (needs ``intrinsics=``)"""
+        if self._intr is None:
+            raise ValueError("no intrinsics are refined: RefineBatch(views=, intrinsics=)")
+        K = self._cams[:, :9].double()
+        K[:, [0, 4, 2, 5]] = self._intr_master
+        return K.view(self.R, self.V, 3, 3)
+
+    def intrinsics_error(self, K_ref):
+        """``reproject.intrinsics_error`` of the refined K against a reference K [R, V, 3, 3] -> (relative focal error [R, V], distance of the
+        principal points in pixels [R, V]) float64 on the device"""
+        K = self.intrinsics()
+        return RP.intrinsics_error(K, torch.as_tensor(K_ref).to(K.device))
+
     def poses(self):
-        """(Rm [R, V, 3, 3], t [R, V, 3]) float64: the master copy of the refined poses (needs ``poses=``)"""
-        if self._poses is None:
+        """(Rm [R, V, 3, 3], t [R, V, 3]) float64: the master copy of the refined poses (needs ``poses=``; with ``intrinsics=`` alone the poses
+        the loop holds)"""
+        if self._poses is None and self._intr is None:
             raise ValueError("no poses are refined: RefineBatch(views=, poses=)")
         m = self._pose.view(self.R, self.V, 12)
         return m[..., :9].reshape(self.R, self.V, 3, 3).clone(), m[..., 9:].clone()
@@ -1686,11 +1782,11 @@ class RefineBatch:
         _lib.check(_lib.lib().sln_vae_group_launches(self._group, C.byref(f), C.byref(b), C.byref(s1)), "sln_vae_group_launches")
         return dict(decoder_forward=f.value, decoder_backward=b.value, single_room_fallbacks=s1.value)
 
-    def _iteration(self, noise, out, report_out=None, pictures_out=None, overlap_out=None, pose_out=None):
+    def _iteration(self, noise, out, report_out=None, pictures_out=None, overlap_out=None, pose_out=None, intr_out=None):
         """one iteration of every room on the current stream; ``noise`` [N], ``out`` [R] receives the rooms' losses, ``report_out``
         [R, 3] (a reported iteration) the report, ``pictures_out`` (a pictured iteration) = (depth8, labels, rgb, status) of one slot,
         ``overlap_out`` [R] float64 (with the penalty on) the rooms' unweighted penalties, ``pose_out`` [R, V, 6] float64 (with ``poses``) the
-        gradients of the views' poses"""
+        gradients of the views' poses, ``intr_out`` [R, V, 4] float64 (with ``intrinsics``, then together with ``pose_out``) those of their intrinsics"""
         L, st, P = _lib.lib(), _lib.current_stream_ptr(), _lib.ptr
         N, R, na, S, B = self.N, self.R, self.model.Nangle, self.S, self.R * self.V
         self._forward_to_placement(noise)
@@ -1719,7 +1815,13 @@ class RefineBatch:
                                         P(self.g_image), P(self.g_faces), st), "sln_scene_backward")
         if self._views is not None:     # the views' adjoints meet in world space: one launch, one writer per row
             _lib.check(L.sln_place_backward_views(P(self._place_tab), P(self._cams), R, self.V, self.n_max, 9 * self.F2, st), "sln_place_backward_views")
-            if pose_out is not None:    # behind the placement's backward, which still reads the old cameras: the table is stepped in place
+            if intr_out is not None:    # in the pose launch's place: ONE launch steps pose and K, both from the gradients of the old camera
+                ps, it = self._poses or dict(rot_step=0.0, trans_step=0.0), self._intr
+                _lib.check(L.sln_place_camera_step_views(P(self._place_tab), P(self._cams), P(self._pose), P(pose_out), P(self._pose_free),
+                                                         P(self._intr_master), P(intr_out), P(self._intr_free), R, self.V, 9 * self.F2, ps["rot_step"],
+                                                         ps["trans_step"], it["focal_step"], it["center_step"], int(it["tie_focal"]), st),
+                           "sln_place_camera_step_views")
+            elif pose_out is not None:  # behind the placement's backward, which still reads the old cameras: the table is stepped in place
                 _lib.check(L.sln_place_pose_step_views(P(self._place_tab), P(self._cams), P(self._pose), P(pose_out), P(self._pose_free), R, self.V,
                                                        9 * self.F2, self._poses["rot_step"], self._poses["trans_step"], st), "sln_place_pose_step_views")
         else:
@@ -1752,11 +1854,13 @@ class RefineBatch:
         for name, at, is_all in (("report", self._report_at, self._report_all), ("pictures", self._pictures_at, self._pictures_all)):
             if capture and at is not None and not is_all:
                 raise ValueError("run(capture=True) replays one graph for every iteration: %s must be 'all' or None" % name)
+        camera = self._poses is not None or self._intr is not None        # a camera step is issued: pose_grad is recorded
         if capture and self._graph_out is None:       # what the graph writes: copied to the iteration's own rows after every captured step
             self._graph_out = (self.loss_out.new_empty(self.R), self.loss_out.new_empty(self.R, 3) if self._report_all else None,
                                tuple(torch.empty_like(t[0]) for t in self.pictures[:4]) if self._pictures_all else None,
                                torch.empty_like(self.overlap[0]) if self.overlap is not None else None,
-                               torch.empty_like(self.pose_grad[0]) if self._poses is not None else None)
+                               torch.empty_like(self.pose_grad[0]) if camera else None,
+                               torch.empty_like(self.intr_grad[0]) if self._intr is not None else None)
         if n > 0 and self.k == 0:
             self._first_iterate_sizes()
             if self._retrieve and self.models is None:
@@ -1778,11 +1882,13 @@ class RefineBatch:
                     dst.copy_(src)
                 if self.overlap is not None:
                     self.overlap[k].copy_(self._graph_out[3])
-                if self._poses is not None:
+                if camera:
                     self.pose_grad[k].copy_(self._graph_out[4])
+                if self._intr is not None:
+                    self.intr_grad[k].copy_(self._graph_out[5])
             else:
                 self._iteration(self.noise_all[k], self.losses[k], rep, pic, self.overlap[k] if self.overlap is not None else None,
-                                self.pose_grad[k] if self._poses is not None else None)
+                                self.pose_grad[k] if camera else None, self.intr_grad[k] if self._intr is not None else None)
             self.k += 1
         return self.losses[:self.k]
 
@@ -1808,16 +1914,18 @@ class RefineBatch:
 
 
 def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None,
-                            pictures=None, retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None):
+                            pictures=None, retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None,
+                            intrinsics=None):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
     noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
     ``report`` is given, the report [iters, R, 3] as a further element; only when ``pictures`` is given, the pair
     (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask`` / ``overlap_weight`` / ``overlap_rows`` /
     ``views``: as ``RefineBatch``'s (``views`` combines with neither ``report``, ``pictures`` nor ``retrieve=True``).  ``poses``: as
-    ``RefineBatch``'s; only when it is given, the pair (``RefineBatch.poses()``, ``RefineBatch.pose_grad``) is the last element."""
+    ``RefineBatch``'s; only when it is given, the pair (``RefineBatch.poses()``, ``RefineBatch.pose_grad``) is a further element.
+    ``intrinsics``: as ``RefineBatch``'s; only when it is given, the pair (``RefineBatch.intrinsics()``, ``RefineBatch.intr_grad``) is the last one."""
     rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report,
                      pictures=pictures, retrieve=retrieve, observed=observed, mask=mask, overlap_weight=overlap_weight, overlap_rows=overlap_rows,
-                     views=views, poses=poses)
+                     views=views, poses=poses, intrinsics=intrinsics)
     try:
         out = (rb.run(capture=capture).clone(), [(b.clone(), i.clone()) for b, i in rb.results()])
         if report is not None:
@@ -1826,6 +1934,8 @@ def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-
             out += ((rb.pictures, rb.target_pictures),)             # (buffers of their own: nothing of the batch's is referenced)
         if poses is not None:
             out += ((rb.poses(), rb.pose_grad.clone()),)
+        if intrinsics is not None:
+            out += ((rb.intrinsics(), rb.intr_grad.clone()),)
     finally:
         rb.close()
     return out
@@ -1833,7 +1943,7 @@ def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-
 
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,
                  learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None,
-                 views=None, poses=None):
+                 views=None, poses=None, intrinsics=None):
     """finetune_VAE's inner loop for ONE room (test_render_refine.py:265-359) on synthetic meshes.
     ``observed`` / ``mask``: as ``finetune_vae_fast``'s, on the boxes' device whichever it is - the target from ``observed_target_torch`` on
     the room's class tables, the loss from ``refinement_loss_masked``.  ``overlap_weight`` / ``overlap_rows``: as ``finetune_vae_fast``'s (on CPU
@@ -1846,11 +1956,18 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
     ``exp`` to the order the gradient at 0 needs) in front of ``render_fn(..., camera=(K, I, 0))``, the leaf is stepped by ``RefineBatch``'s
     rule and folded into the float64 ``(Rm, t)`` with ``reproject.pose_step_torch`` after every iteration; the view's camera is the float32
     rounding of that pair.  The yardstick of sln_place_pose_step_views inside the loop.
+    ``intrinsics``: None, or ``RefineBatch``'s ``intrinsics`` for one room (``free`` [V], ``start`` K [V, 3, 3]), in autograd: per view a leaf
+    ``(sx, sy, dcx, dcy)`` at 0; the camera-space vertices are moved in torch to ``x' = e^sx x + dcx (z + proj_eps) / fx``, ``y' = e^sy y + dcy
+    (z + proj_eps) / fy`` in front of ``render_fn(..., camera=(K, I, 0))``, so that the unchanged ``K`` (zero skew) projects them where
+    ``K`` with ``fx e^sx, fy e^sy, cx + dcx, cy + dcy`` would; the leaf's gradient is ``(fx dL/dfx, fy dL/dfy, dL/dcx, dL/dcy)``, stepped by
+    ``RefineBatch``'s rule and folded into the float64 ``K`` with ``reproject.intrinsics_step_torch`` after every iteration; the view's ``K``
+    is the float32 rounding of it.  Composes with the pose leaf.  The yardstick of sln_place_camera_step_views inside the loop.
     Returns the list of per-iteration losses and the final (boxes_pred, angles_idx); with ``poses``, the final ``(Rm [V, 3, 3], t [V, 3])``
-    float64 as a third element."""
+    float64 as a further element; with ``intrinsics``, the final ``K [V, 3, 3]`` float64 as the last one."""
     render_fn, dev = render_fn or DR.scene_render, boxes_gt.device
     cams = check_views(views, None, observed, mask)
     pose = check_poses(poses, cams)
+    intr = check_intrinsics(intrinsics, cams)
     if cams is None:
         observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, False, bank)
     else:
@@ -1884,6 +2001,10 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         pose_R, pose_t = (x[0].double() for x in (pose["start"] if pose["start"] is not None else (torch.stack([c[1] for c in cams])[None],
                                                                                                      torch.stack([c[2] for c in cams])[None])))
         pose_free = [True] * len(cams) if pose["free"] is None else pose["free"][0].tolist()
+    if intr is not None:                 # the float64 K the loop steps
+        intr_K = (intr["start"][0] if intr["start"] is not None else torch.stack([c[0] for c in cams])).double()
+        intr_free = [True] * len(cams) if intr["free"] is None else intr["free"][0].tolist()
+    if pose is not None or intr is not None:
         eye3 = torch.eye(3, dtype=torch.float32, device=dev)
     size_target = None                   # the sizes of the FIRST iterate (:319-327: size_infos), not the target's (its sizes are "unused_sizes")
     losses = []
@@ -1902,16 +2023,23 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
         if size_target is None:
             size_target = [s.clone() for s in sizes_k]
         if cams is not None:            # mean over the views of each view's own loss, the size loss once
-            per_view, leaves = [], []
+            per_view, leaves, intr_leaves = [], [], []
             for vi, cam in enumerate(cams):
-                if pose is not None:    # the view's camera applied in torch, the leaf's rigid motion behind it, an identity camera for the render
-                    om, ta = (torch.zeros(3, dtype=torch.float32, device=dev, requires_grad=True) for _ in range(2))
-                    leaves.append((om, ta))
-                    W = RP._skew(om)
-                    E = eye3 + W + torch.matmul(W, W) / 2.0
-                    Rm32, t32 = pose_R[vi].float().to(dev), pose_t[vi].float().to(dev)
-                    moved = torch.matmul(torch.matmul(v, Rm32.t()) + t32, E.t()) + ta
-                    image = render_fn(moved, f, ranges, room_box, image_size=image_size, camera=(cam[0], eye3, torch.zeros(3)))
+                if pose is not None or intr is not None:    # the view's camera applied in torch, the leaves' motions behind it, an identity pose for the render
+                    Rm32, t32 = (pose_R[vi].float().to(dev), pose_t[vi].float().to(dev)) if pose is not None else (cam[1].to(dev), cam[2].to(dev))
+                    moved, K32 = torch.matmul(v, Rm32.t()) + t32, cam[0]
+                    if pose is not None:
+                        om, ta = (torch.zeros(3, dtype=torch.float32, device=dev, requires_grad=True) for _ in range(2))
+                        leaves.append((om, ta))
+                        W = RP._skew(om)
+                        E = eye3 + W + torch.matmul(W, W) / 2.0
+                        moved = torch.matmul(moved, E.t()) + ta
+                    if intr is not None:
+                        sc = torch.zeros(4, dtype=torch.float32, device=dev, requires_grad=True)
+                        intr_leaves.append(sc)
+                        K32 = intr_K[vi].float()
+                        moved = RP.intrinsics_move(moved, sc, float(K32[0, 0]), float(K32[1, 1]))
+                    image = render_fn(moved, f, ranges, room_box, image_size=image_size, camera=(K32, eye3, torch.zeros(3)))
                 else:
                     image = render_fn(v, f, ranges, room_box, image_size=image_size, camera=cam)
                 tgt, lab = target[vi:vi + 1], [t[vi:vi + 1] for t in labels]
@@ -1937,11 +2065,20 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
                 if pose_free[vi] and (pose["rot_step"] != 0.0 or pose["trans_step"] != 0.0):
                     pose_R[vi], pose_t[vi] = RP.pose_step_torch(pose_R[vi], pose_t[vi], -pose["rot_step"] * om.grad.double().cpu(),
                                                                 -pose["trans_step"] * ta.grad.double().cpu())
+        if intr is not None:
+            for vi, sc in enumerate(intr_leaves):
+                if intr_free[vi] and (intr["focal_step"] != 0.0 or intr["center_step"] != 0.0):
+                    g, K32 = sc.grad.double().cpu(), intr_K[vi].float().double()
+                    grad = torch.stack((g[0] / K32[0, 0], g[1] / K32[1, 1], g[2], g[3]))
+                    intr_K[vi] = RP.intrinsics_step_torch(intr_K[vi], grad, intr["focal_step"], intr["center_step"], intr["tie_focal"])
         if hasattr(model, "params_changed"):
             model.params_changed()
         losses.append(float(loss.detach()))
         if log:
             log("iter %d: loss %.4f (depth %.4f, semantic %.4f)" % (k, losses[-1], float(dl), float(sl)))
+    out = (losses, (boxes_pred.detach(), idx.detach()))
     if pose is not None:
-        return losses, (boxes_pred.detach(), idx.detach()), (pose_R, pose_t)
-    return losses, (boxes_pred.detach(), idx.detach())
+        out += ((pose_R, pose_t),)
+    if intr is not None:
+        out += (intr_K,)
+    return out

@@ -14,6 +14,8 @@ pixel out of the rasterizer's maps.
     (DESIGN §4 "Several observed frames per room");
   * ``pose_step_torch``, ``rotation_exp``, ``pose_error``   the float64 restatement of a pose step of ``RefineBatch(poses=)`` and the
     distance of two poses (DESIGN §4 "Camera poses of the target views");
+  * ``intrinsics_step_torch``, ``intrinsics_error``   the same for a step of ``RefineBatch(intrinsics=)`` on focal lengths and principal
+    point (DESIGN §4 "Intrinsics of the target views");
   * ``relative_pose``, ``refine_view``, ``look_at_view``, ``scene_as_source``   the cameras: source -> target pose from two world poses,
     the refinement view of a room row, a further view of the room from an eye and a point it looks at (``RefineBatch(views=)``), and the
     source intrinsics under which a scene tensor's own planes are a frame of their own camera.
@@ -170,6 +172,46 @@ def pose_error(Rm_a, t_a, Rm_b, t_b):
     ca = -torch.matmul(Ra.transpose(-1, -2), ta[..., None])[..., 0]
     cb = -torch.matmul(Rb.transpose(-1, -2), tb[..., None])[..., 0]
     return torch.atan2(sin, cos), (ca - cb).norm(dim=-1)
+
+
+FOCAL_LOG_MAX = 1.0      # SLN_FOCAL_LOG_MAX of include/sln_hip.h: one step scales a focal length by e^-1 .. e at the most
+
+
+def intrinsics_step_torch(K, grad, focal_step, center_step, tie_focal=True):
+    """One intrinsics step in float64 (DESIGN §4 "Intrinsics of the target views"): ``K`` [..., 3, 3], ``grad`` [..., 4] = (dL/dfx, dL/dfy,
+    dL/dcx, dL/dcy) -> K float64 with  ``fx <- fx exp(sx)``, ``fy <- fy exp(sy)``,  ``sx = -focal_step fx dL/dfx``, ``sy = -focal_step fy dL/dfy``
+    or, tied, the one log-scale ``sx = sy = -focal_step (fx dL/dfx + fy dL/dfy)`` - each held to ``[-FOCAL_LOG_MAX, FOCAL_LOG_MAX]``, so that
+    a focal length stays positive and finite whatever the gradient - and ``cx <- cx - center_step dL/dcx``, ``cy`` likewise (pixels of
+    ``orig_size``).  Every other entry of ``K`` is returned as it came.  The restatement of the update of sln_place_camera_step_views."""
+    K, g = torch.as_tensor(K).double().clone(), torch.as_tensor(grad).double()
+    fs, cs = float(focal_step), float(center_step)
+    fx, fy = K[..., 0, 0].clone(), K[..., 1, 1].clone()
+    sx, sy = -fs * (fx * g[..., 0]), -fs * (fy * g[..., 1])
+    if tie_focal:
+        sx = sy = -fs * (fx * g[..., 0] + fy * g[..., 1])
+    sx, sy = sx.clamp(-FOCAL_LOG_MAX, FOCAL_LOG_MAX), sy.clamp(-FOCAL_LOG_MAX, FOCAL_LOG_MAX)
+    K[..., 0, 0], K[..., 1, 1] = fx * torch.exp(sx), fy * torch.exp(sy)
+    K[..., 0, 2], K[..., 1, 2] = K[..., 0, 2] - cs * g[..., 2], K[..., 1, 2] - cs * g[..., 3]
+    return K
+
+
+def intrinsics_move(p_cam, leaf, fx, fy, proj_eps=1e-9):
+    """The camera-space points ``p_cam`` [..., 3] moved so that an UNCHANGED zero-skew ``K`` with focal lengths ``fx``, ``fy`` projects them where
+    ``K`` with ``fx e^sx, fy e^sy, cx + dcx, cy + dcy`` would project ``p_cam``; ``leaf`` = (sx, sy, dcx, dcy):  ``x' = e^sx x + dcx (z +
+    proj_eps) / fx``, ``y'`` likewise, ``z`` as it is (``proj_eps``: the projection's ``xh = x / (z + proj_eps)``).  Differentiable in ``leaf``:
+    its gradient at 0 is ``(fx dL/dfx, fy dL/dfy, dL/dcx, dL/dcy)`` - how ``finetune_vae(intrinsics=)`` reaches K through a renderer that
+    takes it as a constant."""
+    zz = p_cam[..., 2] + proj_eps
+    return torch.stack((torch.exp(leaf[0]) * p_cam[..., 0] + leaf[2] * zz / fx, torch.exp(leaf[1]) * p_cam[..., 1] + leaf[3] * zz / fy,
+                        p_cam[..., 2]), -1)
+
+
+def intrinsics_error(K_a, K_b):
+    """-> (relative focal error ``max(|fx_a - fx_b| / fx_b, |fy_a - fy_b| / fy_b)``, distance of the principal points in pixels), float64,
+    per leading index; ``K_b`` is the reference"""
+    Ka, Kb = torch.as_tensor(K_a).double(), torch.as_tensor(K_b).double()
+    rel = torch.maximum((Ka[..., 0, 0] - Kb[..., 0, 0]).abs() / Kb[..., 0, 0], (Ka[..., 1, 1] - Kb[..., 1, 1]).abs() / Kb[..., 1, 1])
+    return rel, torch.stack((Ka[..., 0, 2] - Kb[..., 0, 2], Ka[..., 1, 2] - Kb[..., 1, 2]), -1).norm(dim=-1)
 
 
 def scene_as_source(K_tgt, orig_size, S):

@@ -708,6 +708,30 @@ int sln_place_pose_step_views(const SlnPlacementRoom* rooms /* device [R] */, Sl
                               double* pose /* device [R * V, 12] */, double* grad_pose /* device [R * V, 6]: d omega, d tau */,
                               const uint8_t* pose_free /* device [R * V] or NULL = all */, int R, int V, int64_t view_stride,
                               float rot_step, float trans_step, void* stream);
+/* Refinement of the intrinsics of the target views together with their poses (DESIGN §4 "Intrinsics of the target views"): ONE launch in
+ * the place of sln_place_pose_step_views, since two launches would each read the camera the other has just overwritten.  Per (room,
+ * view), over the corners that sln_place_pose_step_views sums, with (gu, gv) a corner's image gradient, s2 = 2 / orig_size and
+ * xh = x / (z + proj_eps), yh = y / (z + proj_eps) its normalised camera coordinates:
+ *   grad_intr [R * V, 4] = (dL/dfx, dL/dfy, dL/dcx, dL/dcy) = (sum s2 gu xh, sum -s2 gv yh, sum s2 gu, sum -s2 gv)
+ * for fx = K[0], fy = K[4], cx = K[2], cy = K[5]: float64 sums of float32 products, written on every call like grad_pose, which has
+ * sln_place_pose_step_views' bits.  The pose update is that entry point's, from the same arguments.  A view with intr_free != 0 (NULL:
+ * every view) is then stepped in the float64 master `intr` [R * V, 4] = (fx, fy, cx, cy), which the caller fills with double(cams entry):
+ *   fx <- fx exp(sx), fy <- fy exp(sy);  sx = -focal_step fx dL/dfx, sy = -focal_step fy dL/dfy, or with tie_focal != 0 the one log-scale
+ *   sx = sy = -focal_step (fx dL/dfx + fy dL/dfy);  sx, sy are held to [-SLN_FOCAL_LOG_MAX, SLN_FOCAL_LOG_MAX];
+ *   cx <- cx - center_step dL/dcx, cy <- cy - center_step dL/dcy   (pixels of orig_size)
+ * and K[0], K[4], K[2], K[5] of the view's cams entry receive the float32 rounding of the master.  Both updates use the gradients of
+ * the camera the call found.  K[1], K[3] and K[6..8] are read and never written; with focal_step == center_step == 0, or for a view that
+ * is not intr_free, neither intr nor any K entry is written.  intr, grad_intr and intr_free may be NULL together: the call is then
+ * sln_place_pose_step_views.  One writer per (room, view), no atomics, no allocation, no synchronisation: legal in a linear capture.
+ * SLN_E_BADARG, nothing launched: what sln_place_pose_step_views refuses, intr without grad_intr or the reverse, intr_free without intr,
+ * a negative or non-finite focal_step / center_step. */
+#define SLN_FOCAL_LOG_MAX 1.0
+int sln_place_camera_step_views(const SlnPlacementRoom* rooms /* device [R] */, SlnPlacementCamera* cams /* device [R * V], updated in place */,
+                                double* pose /* device [R * V, 12] */, double* grad_pose /* device [R * V, 6] */,
+                                const uint8_t* pose_free /* device [R * V] or NULL = all */, double* intr /* device [R * V, 4] or NULL */,
+                                double* grad_intr /* device [R * V, 4] or NULL */, const uint8_t* intr_free /* device [R * V] or NULL = all */,
+                                int R, int V, int64_t view_stride, float rot_step, float trans_step, float focal_step, float center_step,
+                                int tie_focal, void* stream);
 /* sln_refine_sgd over R parameter copies: for every room r and every range k: p[r * stride + off_k + i] -= step * g[...], g = 0
  * (i < len_k; off_k, len_k multiples of 4 floats; n_ranges <= 96: the decoder's parameters are the three *_dc embedding tables in
  * front and the trailing gconv_net_dc / box_net / angle_net run - encoder-only parameters have zero gradients in this loop and are

@@ -2,7 +2,10 @@
 (slope between runs of `iters` and 2 x `iters` iterations) and set-up per room, eager and under hipGraph replay.  GPU box.
 VIEWS=V (default 0: ``views=None``): refine every room against V target views - view 0 is ``refine_view``'s camera, the others look from the
 room's upper corners at its centre (``look_at_view``).  POSES=1 (needs VIEWS): refine the views' poses as well (``poses=``; ROT_STEP / TRANS_STEP,
-default 1e-6 each) - one more launch per iteration, sln_place_pose_step_views."""
+default 1e-6 each) - one more launch per iteration, sln_place_pose_step_views.  INTRINSICS=1 (needs VIEWS; with or without POSES): refine
+the views' focal lengths and principal points as well (``intrinsics=``; FOCAL_STEP, default 1e-6, CENTER_STEP, default 1e-4) - the one launch
+is then sln_place_camera_step_views.  Every line also gives the smallest and the largest of the three slopes (run i of 2 x `iters` against
+run i of `iters`)."""
 import importlib, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,13 +65,16 @@ def main():
         poses = None
         if os.environ.get("POSES", "0") != "0":
             poses = dict(rot_step=float(os.environ.get("ROT_STEP", "1e-6")), trans_step=float(os.environ.get("TRANS_STEP", "1e-6")))
+        intrinsics = None
+        if os.environ.get("INTRINSICS", "0") != "0":
+            intrinsics = dict(focal_step=float(os.environ.get("FOCAL_STEP", "1e-6")), center_step=float(os.environ.get("CENTER_STEP", "1e-4")))
         with torch.cuda.stream(st):
             for capture in (False, True):
                 res = []; enq = []
                 for n_it in (iters, 2 * iters, iters, 2 * iters, iters, 2 * iters):
                     torch.cuda.synchronize(); t0 = time.perf_counter()
                     G = int(os.environ.get("GROUPS", "1"))
-                    rb = R.RefineBatch(model, rooms, bank=bank, iters=n_it, views=views, poses=poses)
+                    rb = R.RefineBatch(model, rooms, bank=bank, iters=n_it, views=views, poses=poses, **(dict(intrinsics=intrinsics) if intrinsics else {}))
                     torch.cuda.synchronize(); t1 = time.perf_counter()
                     rb.run(capture=capture)
                     t_enq = time.perf_counter() - t1                  # host time to enqueue everything (the GPU may still be running)
@@ -78,8 +84,9 @@ def main():
                     res.append((n_it, t1 - t0, t2 - t1)); info = rb.launches(); fin = bool(torch.isfinite(rb.losses).all()); rb.close()
                 a = sorted(x[2] for x in res if x[0] == iters)[1]; b = sorted(x[2] for x in res if x[0] == 2 * iters)[1]
                 setup = sorted(x[1] for x in res)[len(res) // 2]
-                print("rooms %2d views %d%s %s: %.3f ms / iteration (%.4f per room-iteration), run-intercept %.2f ms, set-up %.2f ms per room, %s, finite %s"
-                      % (nr, n_views, " poses" if poses else "", "graph" if capture else "eager", (b - a) / iters * 1e3, (b - a) / iters * 1e3 / nr, (a - (b - a)) * 1e3, setup * 1e3 / nr, info, fin), flush=True)
+                slopes = [(res[i + 1][2] - res[i][2]) / iters * 1e3 for i in (0, 2, 4)]
+                print("rooms %2d views %d%s%s %s: %.3f ms / iteration (min-max of the three slopes %.3f-%.3f; %.4f per room-iteration), run-intercept %.2f ms, set-up %.2f ms per room, %s, finite %s"
+                      % (nr, n_views, " poses" if poses else "", " intrinsics" if intrinsics else "", "graph" if capture else "eager", (b - a) / iters * 1e3, min(slopes), max(slopes), (b - a) / iters * 1e3 / nr, (a - (b - a)) * 1e3, setup * 1e3 / nr, info, fin), flush=True)
                 print("   host enqueue time per iteration: %.3f ms (min over runs); planes per image: %.1f live, %.1f constant" % (min(enq) * 1e3, live[0], live[1]), flush=True)
 
 
