@@ -75,7 +75,7 @@ class SlnRefineLoss(C.Structure):
                                        "stage1_stride")] + \
                [(n, C.c_void_p) for n in ("s2_k0", "s2_k1", "s2_l1", "s1_i0", "s1_i1", "s1_l1", "col_ptr", "col_out", "col_w")] + \
                [("max_col_entries", C.c_int), ("per_room", C.c_int), ("live_planes", C.c_void_p), ("null_mask", C.c_void_p), ("pooled_ones", C.c_void_p),
-                ("valid_pooled", C.c_void_p), ("valid_image", C.c_void_p), ("depth_count", C.c_void_p)]
+                ("valid_pooled", C.c_void_p), ("valid_image", C.c_void_p), ("depth_count", C.c_void_p), ("conf_sum", C.c_void_p)]
 
 
 class SlnPlacementRoom(C.Structure):
@@ -378,6 +378,8 @@ SIGNATURES = {
     "sln_refine_loss_backward": (C.c_int, [C.POINTER(SlnRefineLoss), C.c_void_p, c_f32p, c_f32p, C.c_void_p]),
     "sln_refine_loss_mask": (C.c_int, [C.POINTER(SlnRefineLoss), C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "sln_refine_loss_confidence": (C.c_int, [C.POINTER(SlnRefineLoss), C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "sln_spade_input_workspace_bytes": (C.c_int64, [C.c_int]),
     "sln_spade_input_forward": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p]),

@@ -12,6 +12,11 @@
 // operator (a bilinear DOWN-sample without anti-aliasing reads few input pixels, so the image gradient is sparse; every
 // input pixel sums the few pooled pixels that read it - no atomics).  The target's pooled depth maps and labels are
 // constants of a room; the host derives them from sln_refine_pool of the target (the same resampling kernel).
+//
+// Three routes through the loss, finalize and report kernels, chosen by the descriptor: unmasked; under a validity mask of the target
+// (valid_pooled / valid_image / depth_count, set up by sln_refine_loss_mask); under a per-pixel confidence of the target (the same
+// fields holding bytes 0..255 plus conf_sum, set up by sln_refine_loss_confidence: a pooled pixel weighs c / 255, every mean is divided
+// by the sum of its weights).  A {0, 255} confidence gives the masked route's bits, all 255 the unmasked route's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -170,13 +175,21 @@ __global__ __launch_bounds__(256) void pool_lds_kernel(const float* __restrict__
 // and gd comes from the room's count of valid pooled pixels (depth_count) instead of the closed form; one mask byte per lane, loaded
 // once in front of the channel loops.  The semantic part needs nothing: sln_refine_loss_mask has set the labels to -100.  The
 // unmasked instantiation is the kernel of before.
+//
+// MODE 2, per-pixel confidence (SlnRefineLoss::conf_sum): valid_pooled holds the pooled confidence byte c, w = (float)c / 255.f.  The
+// depth part sums w * |diff| and stores +-(gd * w), gd from the room's pooled sum of c (conf_sum row 0) / 255 in place of N; the
+// semantic part scales the pixel's k by w (sln_refine_loss_confidence has set the labels under c == 0 to -100 and put the sum of
+// c / 255 over the kept labels into inv_count).  c == 0 is selected away as on the masked route.  With every c in {0, 255} w is
+// exactly 1.f, (double)(255 N) / 255.0 exactly N and a product with 1.f exact under either contraction: the bits of MODE 1.
 constexpr int DCH = 8;               // depth channels per thread of loss_kernel's parts 1..
-template <int NSEM, bool MASKED>
+constexpr int LOSS_PLAIN = 0, LOSS_MASKED = 1, LOSS_CONF = 2;
+template <int NSEM, int MODE>
 __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, RefineDims d, const float* __restrict__ tgt_depth,
                                                    const int* __restrict__ labels, const float* __restrict__ inv_count,
                                                    float2* __restrict__ partial, const unsigned char* __restrict__ live,
                                                    const float* __restrict__ pooled_ones, const unsigned char* __restrict__ valid_pooled,
-                                                   const int32_t* __restrict__ depth_count) {
+                                                   const int32_t* __restrict__ depth_count, const int64_t* __restrict__ conf_sum) {
+  constexpr bool MASKED = MODE != LOSS_PLAIN, CONF = MODE == LOSS_CONF;
   const int nc = d.n_sem + d.n_dep;
   const long pp = (long)d.P * d.P;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -207,7 +220,8 @@ __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, R
 #pragma unroll
         for (int c = 0; c < NSEM; ++c) z += expf(v[c] - m);
         const float lse = m + logf(z);
-        const float k = inv_count[d.per_room ? b * d.n_scales + s : s] * (1.f / 800.f);
+        float k = inv_count[d.per_room ? b * d.n_scales + s : s] * (1.f / 800.f);
+        if (CONF) k *= (float)valid_pooled[i] / 255.f;                              // kw = k * w (a kept label has c > 0)
         float vt = 0.f;
 #pragma unroll
         for (int c = 0; c < NSEM; ++c) {
@@ -227,6 +241,12 @@ __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, R
         gd = nv > 0 ? 50.f / (float)((double)d.n_dep * nv) : 0.f;
         ok = valid_pooled[i] != 0;
       }
+      float w = 1.f;
+      if (CONF) {                                                                   // numel = n_dep * W, W = (pooled sum of c) / 255
+        const long long sc = conf_sum[b];
+        w = (float)valid_pooled[i] / 255.f;
+        gd = sc > 0 ? 50.f / (float)((double)d.n_dep * ((double)sc / 255.0)) * w : 0.f;
+      }
       const float* tg = tgt_depth + ((long)(b * d.n_scales + s) * d.n_dep) * pp + pix;
       float* q = p + (long)d.n_sem * pp;
       const int c0 = ((int)blockIdx.y - 1) * DCH;
@@ -245,7 +265,7 @@ __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, R
       for (int u = 0; u < DCH; ++u) {
         if (c0 + u < d.n_dep) {
           const float diff = a[u] - t[u];
-          l_abs += ok ? fabsf(diff) : 0.f;
+          l_abs += ok ? (CONF ? w * fabsf(diff) : fabsf(diff)) : 0.f;
           if (!cst[u]) q[(c0 + u) * pp] = !ok ? 0.f : (diff > 0.f ? gd : (diff < 0.f ? -gd : 0.f));
         }
       }
@@ -264,8 +284,10 @@ __global__ __launch_bounds__(128) void loss_kernel(float* __restrict__ pooled, R
 // per_room: workgroup b sums room b's partials - gx blocks per part row of which the room owns bpr consecutive ones (a block of
 // loss_kernel never straddles two rooms, checked by the launcher) - in the order the B = 1 launch sums its own
 // depth_count (the masked route): the mean's element number is n_dep * depth_count[b] instead of the closed form; 0 gives depth 0
+// conf_sum (the confidence route, with depth_count): n_dep * conf_sum[b] / 255, the partials being sums of w * |diff|
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float2* __restrict__ partial, int n, RefineDims d, float* __restrict__ loss_out,
-                                                            const int gx, const int bpr, const int32_t* __restrict__ depth_count) {
+                                                            const int gx, const int bpr, const int32_t* __restrict__ depth_count,
+                                                            const int64_t* __restrict__ conf_sum) {
   __shared__ double red[4][2];
   double a = 0.0, c = 0.0;
   if (d.per_room) {
@@ -284,6 +306,10 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float2* __rest
       const int nv = depth_count[d.per_room ? blockIdx.x : 0];
       depth = nv > 0 ? 0.5 * a / ((double)d.n_dep * nv) : 0.0;
     }
+    if (conf_sum != nullptr) {                                                      // the confidence route: W = (pooled sum of c) / 255 in place of N
+      const long long sc = conf_sum[d.per_room ? blockIdx.x : 0];
+      depth = sc > 0 ? 0.5 * a / ((double)d.n_dep * ((double)sc / 255.0)) : 0.0;
+    }
     loss_out[0] = (float)(100.0 * depth + 100.0 * c); loss_out[1] = (float)depth; loss_out[2] = (float)c;
   }
 }
@@ -296,11 +322,14 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float2* __rest
 // (a block of loss_kernel lies inside one (room, scale) when P * P is a multiple of 128) in a fixed order.
 // MASKED (SlnRefineLoss::valid_image): a pixel outside the mask adds nothing and its target is not read; the mean's element number is
 // n_dep * the room's valid pixels (depth_count row 1; 0 pixels: depth_l1 = 0).  Same loops, same order.
+// MODE 2 (SlnRefineLoss::conf_sum): valid is the confidence image, a pixel with a byte c > 0 adds (c / 255.f) * |.| and the mean's
+// element number is n_dep * (the room's image sum of c, conf_sum row 1) / 255.
 constexpr int REPORT_BLOCKS = 64;
-template <bool MASKED>
+template <int MODE>
 __global__ __launch_bounds__(256) void report_depth_kernel(const float* __restrict__ img, const float* __restrict__ tgt, const unsigned char* __restrict__ null,
                                                            const unsigned char* __restrict__ live, RefineDims d, double* __restrict__ scratch,
                                                            const unsigned char* __restrict__ valid) {
+  constexpr bool MASKED = MODE != LOSS_PLAIN, CONF = MODE == LOSS_CONF;
   __shared__ double red[4];
   const int b = blockIdx.y;
   const long plane = (long)d.S * d.S, per = (plane + REPORT_BLOCKS - 1) / REPORT_BLOCKS;
@@ -315,10 +344,11 @@ __global__ __launch_bounds__(256) void report_depth_kernel(const float* __restri
     const float cst = (lv & 1) ? 1.f : 0.f;
     float a = 0.f;
     for (long p = p0 + threadIdx.x; p < p1; p += 256) {
-      if (MASKED && !valid[(long)b * plane + p]) continue;
+      const int cf = MASKED ? valid[(long)b * plane + p] : 1;
+      if (MASKED && !cf) continue;
       float v = lv == 3 ? src[c * plane + p] : cst;
       if (last && nm[p]) v = 1.f;
-      a += fabsf(v - tg[c * plane + p]);
+      a += CONF ? ((float)cf / 255.f) * fabsf(v - tg[c * plane + p]) : fabsf(v - tg[c * plane + p]);
     }
     acc += (double)a;
   }
@@ -330,7 +360,7 @@ __global__ __launch_bounds__(256) void report_depth_kernel(const float* __restri
 
 __global__ __launch_bounds__(64) void report_finalize_kernel(const double* __restrict__ scratch, const float2* __restrict__ partial, RefineDims d,
                                                              double* __restrict__ iou_mean, float* __restrict__ report,
-                                                             const int32_t* __restrict__ image_count) {
+                                                             const int32_t* __restrict__ image_count, const int64_t* __restrict__ image_sum) {
   const int b = blockIdx.x, bps = d.P * d.P / 128;                      // blocks of loss_kernel per (room, scale)
   double a = scratch[b * REPORT_BLOCKS + threadIdx.x], c = 0.0;
   const float2* ps = partial + (long)(b * d.n_scales + d.n_scales - 1) * bps;      // part row 0 (the semantic part), the last scale
@@ -342,6 +372,7 @@ __global__ __launch_bounds__(64) void report_finalize_kernel(const double* __res
     report[3 * b + 0] = iou;
     double l1 = a / ((double)d.n_dep * d.S * d.S);
     if (image_count != nullptr) l1 = image_count[b] > 0 ? a / ((double)d.n_dep * image_count[b]) : 0.0;
+    if (image_sum != nullptr) l1 = image_sum[b] > 0 ? a / ((double)d.n_dep * ((double)image_sum[b] / 255.0)) : 0.0;
     report[3 * b + 1] = (float)l1;
     report[3 * b + 2] = (float)(c * 800.0);
   }
@@ -433,6 +464,111 @@ __global__ __launch_bounds__(256) void refine_mask_finalize_kernel(const int* __
       }
     }
     depth_count[b] = n; depth_count[d.B + b] = c_img[b];
+    mask_status[b] = (n == 0 ? 1 : 0) | (none ? 2 : 0);
+  }
+}
+
+// The per-pixel confidence of a target (sln_refine_loss_confidence; once per target, the launch structure of the mask call).
+//   refine_conf_kernel        refine_mask_kernel with the MINIMUM over the 16 taps in place of the AND: the pooled confidence byte; a
+//                             pooled pixel with byte 0 loses its label
+//   refine_conf_image_kernel  the non-zero pixels and the sum of a room's confidence image (the report's normalisers)
+//   sums: the lanes' bytes are added per wavefront (64 * 255 fits an int), the four wavefronts through LDS, then one 64-bit integer
+//   atomic per workgroup and counter (an image's sum of bytes passes 2^31 from S = 4096) - exact, the same in any order.
+//   cnt layout (64-bit, at the head of the pooled maps): [B][n_scales] sum of c over the kept labels, [B][n_scales] pooled pixels with
+//   c > 0, [B][n_scales] sum of c over the pooled pixels, [B] image pixels with c > 0, [B] sum of c over the image
+typedef unsigned long long conf_cnt_t;
+__global__ void refine_conf_clear_kernel(conf_cnt_t* __restrict__ cnt, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) cnt[i] = 0;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void refine_conf_kernel(const unsigned char* __restrict__ conf, RefineDims d,
+                                                          const int* __restrict__ s2_k0, const int* __restrict__ s2_k1,
+                                                          const int* __restrict__ s1_i0, const int* __restrict__ s1_i1,
+                                                          int* __restrict__ labels, unsigned char* __restrict__ conf_pooled,
+                                                          conf_cnt_t* __restrict__ cnt) {
+  const int pp = d.P * d.P;
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  const int s = blockIdx.y % d.n_scales, b = blockIdx.y / d.n_scales;
+  int c = 0, c_lab = 0;
+  if (o < pp) {
+    const int oy = o / d.P, ox = o % d.P;
+    const int ky[2] = {s2_k0[s * d.P + oy], s2_k1[s * d.P + oy]}, kx[2] = {s2_k0[s * d.P + ox], s2_k1[s * d.P + ox]};
+    int yy[4], xx[4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      yy[2 * a] = s1_i0[s * d.pmax + ky[a]]; yy[2 * a + 1] = s1_i1[s * d.pmax + ky[a]];
+      xx[2 * a] = s1_i0[s * d.pmax + kx[a]]; xx[2 * a + 1] = s1_i1[s * d.pmax + kx[a]];
+    }
+    const unsigned char* cm = conf + (long)b * d.S * d.S;
+    c = 255;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) c = min(c, (int)cm[(long)yy[a] * d.S + xx[e]]);
+    const long i = ((long)b * d.n_scales + s) * pp + o;
+    conf_pooled[i] = (unsigned char)c;
+    if (c == 0) labels[i] = -100;
+    c_lab = (c != 0 && labels[i] >= 0) ? c : 0;
+  }
+  __shared__ int red[4][3];
+  const int w_lab = wave_sum(c_lab), w_ok = __popcll(__ballot(c != 0)), w_c = wave_sum(c);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = w_lab; red[threadIdx.x >> 6][1] = w_ok; red[threadIdx.x >> 6][2] = w_c; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int n_lab = red[0][0] + red[1][0] + red[2][0] + red[3][0], n_ok = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+    const int n_c = red[0][2] + red[1][2] + red[2][2] + red[3][2];
+    const int bs = b * d.n_scales + s, nbs = d.B * d.n_scales;
+    if (n_lab) atomicAdd(cnt + bs, (conf_cnt_t)n_lab);                             // (integers: the total does not depend on the order)
+    if (n_ok) { atomicAdd(cnt + nbs + bs, (conf_cnt_t)n_ok); atomicAdd(cnt + 2 * nbs + bs, (conf_cnt_t)n_c); }
+  }
+}
+
+__global__ __launch_bounds__(256) void refine_conf_image_kernel(const unsigned char* __restrict__ conf, RefineDims d, conf_cnt_t* __restrict__ cnt) {
+  const long plane = (long)d.S * d.S, p = (long)blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  const int c = p < plane ? conf[(long)b * plane + p] : 0;
+  __shared__ int red[4][2];
+  const int w_ok = __popcll(__ballot(c != 0)), w_c = wave_sum(c);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = w_ok; red[threadIdx.x >> 6][1] = w_c; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int n = red[0][0] + red[1][0] + red[2][0] + red[3][0], n_c = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+    conf_cnt_t* img = cnt + 3 * d.B * d.n_scales;
+    if (n) { atomicAdd(img + b, (conf_cnt_t)n); atomicAdd(img + d.B + b, (conf_cnt_t)n_c); }
+  }
+}
+
+// one workgroup, a thread per room (strided)
+__global__ __launch_bounds__(256) void refine_conf_finalize_kernel(const conf_cnt_t* __restrict__ cnt, RefineDims d, float* __restrict__ inv_count,
+                                                                   int* __restrict__ depth_count, int64_t* __restrict__ conf_sum,
+                                                                   int* __restrict__ mask_status) {
+  const int ns = d.n_scales;
+  const conf_cnt_t* c_lab = cnt; const conf_cnt_t* c_ok = cnt + d.B * ns; const conf_cnt_t* c_sum = cnt + 2 * d.B * ns;
+  const conf_cnt_t* c_img = cnt + 3 * d.B * ns;
+  for (int b = threadIdx.x; b < d.B; b += 256) {
+    conf_cnt_t n = 0, sc = 0;
+    int none = 0;
+    if (d.per_room) {
+      for (int s = 0; s < ns; ++s) {
+        n += c_ok[b * ns + s]; sc += c_sum[b * ns + s]; none |= c_lab[b * ns + s] == 0;
+        inv_count[b * ns + s] = 1.f / (float)((double)c_lab[b * ns + s] / 255.0);
+      }
+    } else {
+      for (int s = 0; s < ns; ++s) {
+        conf_cnt_t l = 0;
+        for (int r = 0; r < d.B; ++r) { n += c_ok[r * ns + s]; sc += c_sum[r * ns + s]; l += c_lab[r * ns + s]; }
+        none |= l == 0;
+        if (b == 0) inv_count[s] = 1.f / (float)((double)l / 255.0);
+      }
+    }
+    depth_count[b] = (int)n; depth_count[d.B + b] = (int)c_img[b];
+    conf_sum[b] = (int64_t)sc; conf_sum[d.B + b] = (int64_t)c_img[d.B + b];
     mask_status[b] = (n == 0 ? 1 : 0) | (none ? 2 : 0);
   }
 }
@@ -593,6 +729,8 @@ static int check(const SlnRefineLoss* L) {
   // the validity mask: all three fields or none
   const int n_mask = (L->valid_pooled != nullptr) + (L->valid_image != nullptr) + (L->depth_count != nullptr);
   if (n_mask != 0 && n_mask != 3) return SLN_E_BADARG;
+  // the confidence sums reinterpret the three mask fields: never without them
+  if (L->conf_sum != nullptr && n_mask != 3) return SLN_E_BADARG;
   return 0;
 }
 
@@ -675,15 +813,18 @@ int sln_refine_loss_forward(const SlnRefineLoss* L, const float* image, const fl
   launch_pool(L, d, image, ext_mask ? 2 : 1, mask, pooled, live, st);
   const long nl = (long)d.B * d.n_scales * d.P * d.P;
   const dim3 lg((unsigned)((nl + 127) / 128), 1 + sln_cdiv(d.n_dep, DCH));
-  if (L->valid_pooled != nullptr)
-    hipLaunchKernelGGL((loss_kernel<40, true>), lg, dim3(128), 0, st, pooled, d, target_depth_pooled, labels, inv_count, partial, live, L->pooled_ones,
-                       L->valid_pooled, L->depth_count);
+  if (L->conf_sum != nullptr)
+    hipLaunchKernelGGL((loss_kernel<40, LOSS_CONF>), lg, dim3(128), 0, st, pooled, d, target_depth_pooled, labels, inv_count, partial, live,
+                       L->pooled_ones, L->valid_pooled, L->depth_count, L->conf_sum);
+  else if (L->valid_pooled != nullptr)
+    hipLaunchKernelGGL((loss_kernel<40, LOSS_MASKED>), lg, dim3(128), 0, st, pooled, d, target_depth_pooled, labels, inv_count, partial, live,
+                       L->pooled_ones, L->valid_pooled, L->depth_count, (const int64_t*)nullptr);
   else
-    hipLaunchKernelGGL((loss_kernel<40, false>), lg, dim3(128), 0, st, pooled, d, target_depth_pooled, labels, inv_count, partial, live, L->pooled_ones,
-                       (const unsigned char*)nullptr, (const int32_t*)nullptr);
+    hipLaunchKernelGGL((loss_kernel<40, LOSS_PLAIN>), lg, dim3(128), 0, st, pooled, d, target_depth_pooled, labels, inv_count, partial, live,
+                       L->pooled_ones, (const unsigned char*)nullptr, (const int32_t*)nullptr, (const int64_t*)nullptr);
   const long per_room_rows = (long)d.n_scales * d.P * d.P;
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(d.per_room ? d.B : 1), dim3(256), 0, st, partial, (int)(lg.x * lg.y), d, loss_out, (int)lg.x,
-                     (int)(per_room_rows / 128), L->valid_pooled != nullptr ? L->depth_count : (const int32_t*)nullptr);
+                     (int)(per_room_rows / 128), L->valid_pooled != nullptr ? L->depth_count : (const int32_t*)nullptr, L->conf_sum);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -704,6 +845,26 @@ int sln_refine_loss_mask(const SlnRefineLoss* L, const unsigned char* valid, int
                      L->s1_i1, labels, valid_pooled, cnt);
   hipLaunchKernelGGL(refine_mask_image_kernel, dim3(sln_cdiv(d.S * d.S, 256), d.B), dim3(256), 0, st, valid, d, cnt);
   hipLaunchKernelGGL(refine_mask_finalize_kernel, dim3(1), dim3(256), 0, st, cnt, d, inv_count, depth_count, mask_status);
+  SLN_CHECK_LAUNCH();
+  return 0;
+}
+
+int sln_refine_loss_confidence(const SlnRefineLoss* L, const unsigned char* conf, int32_t* labels, unsigned char* conf_pooled, float* inv_count,
+                               int32_t* depth_count, int64_t* conf_sum, int32_t* mask_status, void* workspace, void* stream) {
+  int r = check(L);
+  if (r) return r;
+  if (!conf || !labels || !conf_pooled || !inv_count || !depth_count || !conf_sum || !mask_status || !workspace) return SLN_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const RefineDims d = dims_of(L);
+  float* pooled; unsigned char* mask; float2* partial;
+  carve(L, workspace, &pooled, &mask, &partial);
+  conf_cnt_t* cnt = reinterpret_cast<conf_cnt_t*>(pooled);    // (3 n_scales + 2) B 64-bit counters at the head of the pooled maps, which every forward rewrites
+  const int n_cnt = (3 * d.n_scales + 2) * d.B;
+  hipLaunchKernelGGL(refine_conf_clear_kernel, dim3(sln_cdiv(n_cnt, 256)), dim3(256), 0, st, cnt, n_cnt);
+  hipLaunchKernelGGL(refine_conf_kernel, dim3(sln_cdiv(d.P * d.P, 256), d.B * d.n_scales), dim3(256), 0, st, conf, d, L->s2_k0, L->s2_k1, L->s1_i0,
+                     L->s1_i1, labels, conf_pooled, cnt);
+  hipLaunchKernelGGL(refine_conf_image_kernel, dim3((unsigned)(((long)d.S * d.S + 255) / 256), d.B), dim3(256), 0, st, conf, d, cnt);
+  hipLaunchKernelGGL(refine_conf_finalize_kernel, dim3(1), dim3(256), 0, st, cnt, d, inv_count, depth_count, conf_sum, mask_status);
   SLN_CHECK_LAUNCH();
   return 0;
 }
@@ -742,13 +903,16 @@ int sln_refine_report(const SlnRefineLoss* L, const float* image, const float* t
   const unsigned char* live = live_of(L, d);
   if (live != nullptr && L->null_mask != nullptr) mask = const_cast<unsigned char*>(L->null_mask);
   hipStream_t st = (hipStream_t)stream;
-  if (L->valid_image != nullptr)
-    hipLaunchKernelGGL(report_depth_kernel<true>, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch, L->valid_image);
+  if (L->conf_sum != nullptr)
+    hipLaunchKernelGGL(report_depth_kernel<LOSS_CONF>, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch, L->valid_image);
+  else if (L->valid_image != nullptr)
+    hipLaunchKernelGGL(report_depth_kernel<LOSS_MASKED>, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch, L->valid_image);
   else
-    hipLaunchKernelGGL(report_depth_kernel<false>, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch,
+    hipLaunchKernelGGL(report_depth_kernel<LOSS_PLAIN>, dim3(REPORT_BLOCKS, d.B), dim3(256), 0, st, image, target_depth, mask, live, d, scratch,
                        (const unsigned char*)nullptr);
   hipLaunchKernelGGL(report_finalize_kernel, dim3(d.B), dim3(64), 0, st, scratch, partial, d, iou_mean, report_out,
-                     L->valid_image != nullptr ? L->depth_count + d.B : (const int32_t*)nullptr);
+                     L->valid_image != nullptr ? L->depth_count + d.B : (const int32_t*)nullptr,
+                     L->conf_sum != nullptr ? L->conf_sum + d.B : (const int64_t*)nullptr);
   SLN_CHECK_LAUNCH();
   return 0;
 }

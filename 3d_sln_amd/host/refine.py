@@ -572,6 +572,86 @@ def check_mask(mask, shape, device, observed):
         raise ValueError("mask: a tensor on %s expected, got one on %s" % (device, mask.device))
 
 
+def conf_pooled_torch(conf, sizes=(32, 48, 64, 96)):
+    """``conf`` [B, S, S] uint8 -> uint8 [B, n_scales, P, P]: the minimum of the confidence over a pooled pixel's tap set
+    (``pool_tap_sets``): a pooled pixel is as trustworthy as its least trusted tap.  Integer-exact and separable: rows first, then
+    columns; for a {0, 255} image 255 * ``valid_pooled_torch``."""
+    sets = pool_tap_sets(conf.shape[-1], sizes).to(conf.device)
+    out = []
+    for k in range(len(sizes)):
+        rows = conf[:, sets[k]].amin(dim=2)                        # [B, P, S]
+        out.append(rows[:, :, sets[k]].amin(dim=3))               # [B, P, P]
+    return torch.stack(out, 1)
+
+
+def confidence_counts_torch(conf, labels, per_room, sizes=(32, 48, 64, 96)):
+    """What sln_refine_loss_confidence derives, in torch ops: ``labels`` [B, n_scales, P, P] (as ``RefineLoss`` derives them, -100 = none) ->
+    dict(conf_pooled uint8, labels int32, inv_count float32, depth_count int32 [2, B], conf_sum int64 [2, B], mask_status int32 [B])."""
+    cp = conf_pooled_torch(conf, sizes)
+    c64 = cp.to(torch.int64)
+    lab = torch.where(cp != 0, labels.to(torch.int32), torch.full_like(labels, -100, dtype=torch.int32))
+    kept = torch.where(lab >= 0, c64, torch.zeros_like(c64)).sum(dim=(2, 3))                  # [B, n_scales]: sum of c over the kept labels
+    ok, tot = (cp != 0).sum(dim=(2, 3)), c64.sum(dim=(2, 3))
+    B = cp.shape[0]
+    if not per_room:
+        kept, ok, tot = (t.sum(0, keepdim=True).expand(B, -1) for t in (kept, ok, tot))
+    n, sc = ok.sum(1), tot.sum(1)
+    inv = 1.0 / ((kept if per_room else kept[0]).to(torch.float64) / 255.0).to(torch.float32)
+    status = (sc == 0).to(torch.int32) | ((kept == 0).any(dim=1).to(torch.int32) << 1)
+    return dict(conf_pooled=cp, labels=lab, inv_count=inv,
+                depth_count=torch.stack([n, (conf != 0).sum(dim=(1, 2))]).to(torch.int32),
+                conf_sum=torch.stack([sc, conf.to(torch.int64).sum(dim=(1, 2))]), mask_status=status)
+
+
+def refinement_loss_confidence(iter_image, target, target_container, size_loss, conf, sizes=(32, 48, 64, 96)):
+    """``refinement_loss`` under a per-pixel confidence of the target (DESIGN §4 "Refinement loss under per-pixel confidence"), in torch
+    ops for any dtype and device - the CPU route and the yardstick of csrc/refine_loss.hip's confidence kernels.  ``conf`` [B, S, S]
+    uint8 (0: the target says nothing here, 255: full trust); c the pooled confidence (``conf_pooled_torch``), w = c / 255:
+      depth = 0.5 * sum over the pooled pixels with c > 0 of w |pool(iter) - pool(target)| / (29 * W), W = (sum of c) / 255 over all scales
+              (0 when W is 0); sem = sum_s (sum of w * nll over the labels with c > 0) / W_s / 800 (a scale without one adds 0).
+    Written as ``refinement_loss_masked``: selects, never multiplies by 0, and the iterate enters detached where ``conf`` is 0."""
+    v = (conf != 0)[:, None]
+    cp = conf_pooled_torch(conf, sizes)                                                        # [B, ns, P, P]
+    vp = cp != 0
+    iter_image = torch.where(v, iter_image, iter_image.detach())
+    null = torch.sum(iter_image[:, 41:], dim=1) < 0.5
+    last = iter_image[:, -1]
+    iter_image = torch.cat([iter_image[:, :-1], torch.where(null, torch.ones_like(last), last)[:, None]], 1)
+    clean = torch.where(v, target, torch.zeros_like(target))
+    B, ns, P = vp.shape[0], len(sizes), sizes[-1]
+    w = cp.to(iter_image.dtype) / 255
+    diff = (psp_pool(iter_image[:, 41:], sizes) - psp_pool(clean[:, 41:], sizes)).abs().reshape(B, ns, -1, P, P)
+    sc = int(cp.to(torch.int64).sum())
+    zero = (iter_image[:1, :1, :1, :1] * 0).sum()                    # (of the iterate: a loss without a term still has a - zero - gradient)
+    depth_loss = torch.where(vp[:, :, None], diff * w[:, :, None], torch.zeros_like(diff)).sum() / (diff.shape[2] * (sc / 255.0)) * 0.5 \
+        if sc > 0 else zero
+    sem = zero
+    for k, (pooled, tgt) in enumerate(zip(psp_pool(iter_image[:, 1:41], sizes, as_list=True), target_container)):
+        lab = torch.where(vp[:, k], tgt[:, 0], torch.full_like(tgt[:, 0], -100))
+        kept = int(torch.where(lab >= 0, cp[:, k].to(torch.int64), torch.zeros_like(lab, dtype=torch.int64)).sum())
+        if kept > 0:
+            nll = F.cross_entropy(pooled, lab, reduction="none")                               # 0 at the ignored labels
+            sem = sem + torch.where(lab >= 0, nll * w[:, k], torch.zeros_like(nll)).sum() / (kept / 255.0) / 800.0
+    return depth_loss * 100 + sem * 100 + size_loss * 2.0, depth_loss, sem
+
+
+def check_confidence(confidence, shape, device, mask=None, views=None):
+    """the ``confidence=`` argument of the refinement entry points, refused before anything is launched: None, or a uint8 tensor of ``shape``
+    on ``device`` (with ``views`` the shape carries the V axis).  ``confidence`` is the graded form of ``mask``: the two do not combine."""
+    if confidence is None:
+        return
+    if mask is not None:
+        raise ValueError("confidence is the graded form of mask (0: no say, 255: full trust): give one of the two")
+    if not torch.is_tensor(confidence) or confidence.dtype != torch.uint8:
+        raise ValueError("confidence: a uint8 tensor expected (0: the target says nothing here, 255: full trust)")
+    if tuple(confidence.shape) != tuple(shape):
+        if views is not None:
+            raise ValueError("confidence: with views one image per view is expected, shape %s, got %s" % (list(shape), tuple(confidence.shape)))
+        raise ValueError("confidence: shape %s is not %s" % (tuple(confidence.shape), list(shape)))
+    if confidence.device != torch.device(device):
+        raise ValueError("confidence: a tensor on %s expected, got one on %s" % (device, confidence.device))
+
+
 def check_observed(observed, shape, device, cuda=True, choice=False):
     """the ``observed=`` argument of the refinement entry points, refused before anything is launched: None, or the pair (depth, uint8 labels),
     both tensors of ``shape`` = (rooms, S, S) on ``device``.  ``cuda``: the pair feeds ``ObservedTarget``, whose own check it passes (float32
@@ -810,15 +890,20 @@ class RefineLoss:
     ``rl(image)`` -> tensor [100*depth + 100*sem, depth, sem]; gradients flow to ``image`` through element 0.  The
     workspace holds d loss / d pooled between forward and backward: one outstanding forward per instance."""
 
-    def __init__(self, target, sizes=(32, 48, 64, 96), per_room=False, valid=None):
+    def __init__(self, target, sizes=(32, 48, 64, 96), per_room=False, valid=None, confidence=None):
         """``valid``: None, or [B, S, S] uint8 / bool on the target's device - the validity mask of the target (non-zero: the target
         means something at this pixel).  One ``sln_refine_loss_mask`` call derives ``valid_pooled`` [B, n_scales, P, P],
         masks ``labels``, recounts ``inv_count`` and fills ``mask_count`` [2, B] (valid pooled pixels the depth mean runs over, valid image
-        pixels) and ``mask_status`` [B] (bit 0: no valid pooled pixel; bit 1: a scale without a label); all None without a mask."""
+        pixels) and ``mask_status`` [B] (bit 0: no valid pooled pixel; bit 1: a scale without a label); all None without a mask.
+        ``confidence``: None, or [B, S, S] uint8 on the target's device, not together with ``valid`` - the per-pixel confidence of the target
+        (0: says nothing, 255: full trust).  One ``sln_refine_loss_confidence`` call derives ``conf_pooled`` [B, n_scales, P, P]
+        (the minimum over a pooled pixel's taps), masks ``labels``, fills ``inv_count``, ``mask_count`` and ``mask_status`` as above (for the
+        mask ``confidence != 0``) and ``conf_sum`` int64 [2, B] (pooled and image sums of the bytes); ``conf`` keeps the image."""
         self.per_room = bool(per_room)
         dev = target.device
         B, C, S, _ = target.shape
         check_mask(valid, (B, S, S), dev, None)
+        check_confidence(confidence, (B, S, S), dev, valid)
         P, ns, pmax = sizes[-1], len(sizes), max(sizes)
         # the resampling tables depend on the geometry only (image size, scales), not on the room: built once per geometry and device
         # (python / numpy loops over 4 x 256 image rows: ~5 ms of the ~7 ms per-room set-up of the refinement loop)
@@ -828,7 +913,7 @@ class RefineLoss:
             cached = _REFINE_TABLES[key] = self._build_tables(S, sizes, dev)
         self._keep, max_col = cached
         d = self._describe(B, S, P, C, ns, pmax, max_col)
-        self._finish(d, target, B, S, P, C, ns, dev, valid)
+        self._finish(d, target, B, S, P, C, ns, dev, valid, confidence)
 
     @staticmethod
     def _build_tables(S, sizes, dev):
@@ -868,9 +953,10 @@ class RefineLoss:
         d.per_room = int(getattr(self, "per_room", False))
         return d
 
-    def _finish(self, d, target, B, S, P, C, ns, dev, valid=None):
+    def _finish(self, d, target, B, S, P, C, ns, dev, valid=None, confidence=None):
         self.desc = d
         self.valid = self.valid_pooled = self.mask_count = self.mask_status = None
+        self.conf = self.conf_pooled = self.conf_sum = None
         L = _lib.lib()
         self.ws = torch.empty(int(L.sln_refine_loss_workspace_bytes(B, S, P, ns, 40, C - 41)), dtype=torch.uint8, device=dev)
         _lib.check(L.sln_refine_loss_init(d, _lib.ptr(self.ws), _lib.current_stream_ptr()), "sln_refine_loss_init")
@@ -900,6 +986,20 @@ class RefineLoss:
                                               _lib.ptr(self.mask_count), _lib.ptr(self.mask_status), _lib.ptr(self.ws), _lib.current_stream_ptr()),
                        "sln_refine_loss_mask")
             d.valid_pooled, d.valid_image, d.depth_count = self.valid_pooled.data_ptr(), self.valid.data_ptr(), self.mask_count.data_ptr()
+        if confidence is not None:
+            # the confidence (one call, four launches): the mask's set-up with the minimum over the taps in place of the AND and integer
+            # sums of the bytes beside the counts; the descriptor's mask fields then carry the graded forms
+            self.conf = confidence.contiguous()
+            self.conf_pooled = torch.empty(B, ns, P, P, dtype=torch.uint8, device=dev)
+            self.mask_count = torch.empty(2, B, dtype=torch.int32, device=dev)
+            self.conf_sum = torch.empty(2, B, dtype=torch.int64, device=dev)
+            self.mask_status = torch.empty(B, dtype=torch.int32, device=dev)
+            self.inv_count = torch.empty_like(self.inv_count)
+            _lib.check(L.sln_refine_loss_confidence(d, _lib.ptr(self.conf), _lib.ptr(self.labels), _lib.ptr(self.conf_pooled), _lib.ptr(self.inv_count),
+                                                    _lib.ptr(self.mask_count), _lib.ptr(self.conf_sum), _lib.ptr(self.mask_status), _lib.ptr(self.ws),
+                                                    _lib.current_stream_ptr()), "sln_refine_loss_confidence")
+            d.valid_pooled, d.valid_image, d.depth_count = self.conf_pooled.data_ptr(), self.conf.data_ptr(), self.mask_count.data_ptr()
+            d.conf_sum = self.conf_sum.data_ptr()
 
     def pooled_ones(self):
         """[n_scales, P, P]: what the resampling kernel makes of an all-ones plane (one per geometry and device; see
@@ -911,7 +1011,7 @@ class RefineLoss:
             L, dev = _lib.lib(), self.ws.device
             d1 = type(d).from_buffer_copy(d)
             d1.B, d1.per_room, d1.live_planes, d1.pooled_ones = 1, 0, None, None
-            d1.valid_pooled = d1.valid_image = d1.depth_count = None
+            d1.valid_pooled = d1.valid_image = d1.depth_count = d1.conf_sum = None
             C_, S, P, ns = d.channels, d.image_size, d.pooled_size, d.n_scales
             ws1 = torch.empty(int(L.sln_refine_loss_workspace_bytes(1, S, P, ns, 40, C_ - 41)), dtype=torch.uint8, device=dev)
             pooled = torch.empty(1, ns, C_ - 1, P, P, device=dev)
@@ -1161,6 +1261,15 @@ def valid_and_labels(mask, target, labels=True):
     return valid, target_labels(target if valid is None else torch.where(valid[:, None] != 0, target, torch.zeros_like(target)))
 
 
+def confidence_and_labels(confidence, target, labels=True):
+    """``valid_and_labels`` for a checked ``confidence`` [B, S, S]: -> (the bytes, contiguous; the per-scale labels of the target cleaned under
+    ``confidence > 0``, None with ``labels`` off)"""
+    conf = confidence.contiguous()
+    if not labels:
+        return conf, None
+    return conf, target_labels(torch.where(conf[:, None] != 0, target, torch.zeros_like(target)))
+
+
 def parse_schedule(spec, iters, name):
     """The iterations a per-iteration extra (``report``, ``pictures``) runs in: ``spec`` None, "ends" (0 and the last), "all" or an
     iterable of iteration numbers in [0, max(iters, 1)) -> None, or (sorted tuple of iteration numbers, is it "all")."""
@@ -1230,9 +1339,17 @@ def _one_room_arguments(observed, mask, S, dev, cuda, bank=None):
     return observed, mask
 
 
+def _one_room_confidence(confidence, mask, S, dev):
+    """``confidence`` of the one-room loops, brought from [S, S] to [1, S, S] and checked before anything is launched"""
+    if torch.is_tensor(confidence) and confidence.dim() == 2:
+        confidence = confidence[None]
+    check_confidence(confidence, (1, S, S), dev, mask)
+    return confidence
+
+
 def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, bank=None, learning_rate=1e-4,
                       noise_seed=13, image_size=256, capture=False, log=None, fused_loss=True, fused_head=True, observed=None, mask=None,
-                      overlap_weight=0.0, overlap_rows=None):
+                      overlap_weight=0.0, overlap_rows=None, confidence=None):
     """``finetune_vae`` with the batched ``RefineScene`` and no per-iteration python optimiser objects: the reference builds a
     NEW SGD(momentum=0.1, nesterov) every iteration (test_render_refine.py:286-292), so its step is exactly
     ``p -= lr * (1 + momentum) * grad``; that closed form is applied to ``z`` (lr 2e-4) and to the flat parameter buffer
@@ -1244,11 +1361,13 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
     ``observed``: None, or ``(depth [S, S] or [1, S, S] float32, labels likewise uint8)`` on the device - the target is built from this
     observation with one ``ObservedTarget`` call on the room's class tables instead of rendered from ``boxes_gt`` (``RefineBatch``'s
     ``observed``, for one room).  ``mask``: None, "readings" or a uint8 / bool tensor [S, S] or [1, S, S] - the loss under a validity mask
-    (``RefineBatch``'s ``mask``).  ``overlap_weight`` / ``overlap_rows`` (a bool sequence over the rows): ``RefineBatch``'s, for one room - the loss
-    gains ``overlap_weight * evaluate.overlap_penalty`` of the iterate, followed by autograd.
+    (``RefineBatch``'s ``mask``).  ``confidence``: None, or a uint8 tensor [S, S] or [1, S, S], not together with ``mask`` - the loss under a
+    per-pixel confidence of the target (``RefineBatch``'s ``confidence``).  ``overlap_weight`` / ``overlap_rows`` (a bool sequence over the rows):
+    ``RefineBatch``'s, for one room - the loss gains ``overlap_weight * evaluate.overlap_penalty`` of the iterate, followed by autograd.
     Returns (losses [iters] tensor on the device, (boxes_pred, angle_idx)).  ``log``: called once per iteration, the captured one included."""
     dev, S = boxes_gt.device, int(image_size)
     observed, mask = _one_room_arguments(observed, mask, S, dev, True, bank)
+    confidence = _one_room_confidence(confidence, mask, S, dev)
     overlap = _one_room_overlap(overlap_weight, overlap_rows, class_names, int(boxes_gt.shape[0]), dev)
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
     room = dict(objs=objs, triples=triples, boxes=boxes_gt, angles=angles_gt, attributes=attributes, class_names=class_names)
@@ -1268,7 +1387,10 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
     if observed is not None:                                           # the target from the observation (csrc/observed_target.hip)
         target = OB.ObservedTarget(scene.chan, scene.dch, S, batch=1, device=dev, nch=DR.N_SCENE_CHANNELS)(*observed)[0]
     valid, labels = valid_and_labels(mask, target, labels=not fused_loss)
-    fused = RefineLoss(target, valid=valid) if fused_loss else None    # the PSP / L1 / cross-entropy block as two C calls
+    conf = None
+    if confidence is not None:
+        conf, labels = confidence_and_labels(confidence, target, labels=not fused_loss)
+    fused = RefineLoss(target, valid=valid, confidence=conf) if fused_loss else None    # the PSP / L1 / cross-entropy block as two C calls
     noise = torch.zeros(boxes_gt.shape[0], device=dev)
     losses = torch.zeros(iters, device=dev)
     flat, flat_grad, state = model.flat_params, model.flat_grads, {}
@@ -1300,6 +1422,8 @@ def finetune_vae_fast(model, objs, triples, boxes_gt, angles_gt, attributes, cla
         image, size_loss, _ = scene.render(boxes_full, idx, size_target)
         if fused is not None:
             loss = torch.add(fused(image)[0], size_loss, alpha=2.0)
+        elif conf is not None:
+            loss, _, _ = refinement_loss_confidence(image, target, labels, size_loss, conf)
         elif valid is not None:
             loss, _, _ = refinement_loss_masked(image, target, labels, size_loss, valid)
         else:
@@ -1385,6 +1509,14 @@ class RefineBatch:
     labels of the others ignored, ``report``'s depth_l1 over the valid image pixels.  ``mask_status`` [R] int32 (None without a mask):
     bit 0 - the room has no valid pooled pixel (its depth term is 0), bit 1 - one of its scales keeps no label.
 
+    ``confidence``: None (default: nothing below exists), or a uint8 tensor [R, S, S] on the device, not together with ``mask`` - the per-pixel
+    confidence of the targets (0: the target says nothing here, as ``mask`` 0; 255: full trust; ``reproject.ObservedFuser.confidence`` builds
+    one from the fusion's agreement counts).  The loss then runs under it (``RefineLoss(confidence=)``, DESIGN §4 "Refinement loss under
+    per-pixel confidence"): a pooled pixel weighs c / 255 with c the minimum of the bytes over its taps, every mean is divided by the sum
+    of its weights, ``report``'s depth_l1 likewise over the image.  No launch more per iteration than with ``mask``.  A {0, 255} tensor
+    gives the bits of ``mask``; a constant one cancels (each image is normalised by its own sum): confidence says which pixels of an
+    image matter, not which image.  ``mask_status`` as with ``mask``.  With ``views``: ``[R, V, S, S]``.
+
     ``overlap_weight``: 0.0 (default: nothing below exists, the launches are those above), or a weight > 0 - the loss of a room becomes
     ``... + 2 size_loss + overlap_weight * penalty`` with ``penalty`` the summed intersection volume of the room's colliding furniture
     (``evaluate.overlap_penalty``): what keeps an object whose hidden side the target does not show out of its neighbour.  The head
@@ -1427,13 +1559,14 @@ class RefineBatch:
     ``intrinsics_error(K_ref)``."""
 
     def __init__(self, model, rooms, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, iters=60, report=None, pictures=None,
-                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None, intrinsics=None):
+                 retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None, intrinsics=None,
+                 confidence=None):
         self.model, self.R, self.iters, self.lr, self.S = model, len(rooms), int(iters), float(learning_rate), int(image_size)
         dev = model.flat_params.device
-        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev, views, poses, intrinsics)      # every refusal, in front of the first launch
+        self._check_arguments(rooms, report, pictures, retrieve, observed, mask, dev, views, poses, intrinsics, confidence)      # every refusal, in front of the first launch
         if self._views is not None:      # from here on an image is b = r * V + v: observed frames and a mask tensor lose their room axis
             fold = lambda x: x.reshape(self.R * self.V, self.S, self.S) if torch.is_tensor(x) else x
-            observed, mask = None if observed is None else tuple(fold(x) for x in observed), fold(mask)
+            observed, mask, confidence = None if observed is None else tuple(fold(x) for x in observed), fold(mask), fold(confidence)
         self.overlap_weight = float(overlap_weight)
         self._collide_rows = check_overlap(overlap_weight, overlap_rows, [(int(rm["objs"].shape[0]), list(rm["class_names"])) for rm in rooms])
         self._bank = bank or MeshBank([n for n in set(n for rm in rooms for n in rm["class_names"]) if n not in DO_NOT_VIS and n != "__room__"], dev)
@@ -1448,7 +1581,7 @@ class RefineBatch:
         if self._pictures_at is not None:
             self._picture_buffers(targets, dev)
         all_targets = torch.cat(targets, 0)                   # the loss of all rooms: one descriptor, per-room normalisation
-        self.loss = RefineLoss(all_targets, per_room=True, valid=valid_and_labels(mask, all_targets, labels=False)[0])
+        self.loss = RefineLoss(all_targets, per_room=True, valid=valid_and_labels(mask, all_targets, labels=False)[0], confidence=confidence)
         self.mask_status = self.loss.mask_status
         if self._views is not None and self.mask_status is not None:
             self.mask_status = self.mask_status.view(self.R, self.V)
@@ -1465,7 +1598,7 @@ class RefineBatch:
         if not torch.cuda.is_current_stream_capturing():
             _lib.lib().sln_side_stream_prepare(_lib.current_stream_ptr())
 
-    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev, views=None, poses=None, intrinsics=None):
+    def _check_arguments(self, rooms, report, pictures, retrieve, observed, mask, dev, views=None, poses=None, intrinsics=None, confidence=None):
         """refuses what cannot run; leaves ``_report_at`` (frozenset) and ``_pictures_at`` ({iteration: slot}), None when not asked for, + "all" flags,
         ``_views`` (``check_views``: the cameras on the host, or None), ``V``, ``_poses`` (``check_poses``, or None) and ``_intr`` (``check_intrinsics``, or None)"""
         if self.R < 1:
@@ -1477,6 +1610,7 @@ class RefineBatch:
         shape = (self.R, self.S, self.S) if self._views is None else (self.R, self.V, self.S, self.S)
         check_observed(observed, shape, dev, cuda=True, choice=retrieve)
         check_mask(mask, shape, dev, observed)
+        check_confidence(confidence, shape, dev, mask, self._views)
         at, self._report_all = parse_schedule(report, self.iters, "report") or (None, False)
         self._report_at = None if at is None else frozenset(at)
         at, self._pictures_all = parse_schedule(pictures, self.iters, "pictures") or (None, False)
@@ -1915,17 +2049,17 @@ class RefineBatch:
 
 def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-4, noise_seed=13, image_size=256, capture=False, report=None,
                             pictures=None, retrieve=False, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None, views=None, poses=None,
-                            intrinsics=None):
+                            intrinsics=None, confidence=None):
     """``finetune_vae_fast`` for R rooms at once (see ``RefineBatch``): every room from ``model``'s parameters, its own z, its own
     noise stream (seeded like a single-room call).  -> (losses [iters, R] on the device, [(boxes, angle idx) per room]) and, only when
     ``report`` is given, the report [iters, R, 3] as a further element; only when ``pictures`` is given, the pair
-    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask`` / ``overlap_weight`` / ``overlap_rows`` /
-    ``views``: as ``RefineBatch``'s (``views`` combines with neither ``report``, ``pictures`` nor ``retrieve=True``).  ``poses``: as
+    (``RefineBatch.pictures``, ``RefineBatch.target_pictures``) as the last one.  ``observed`` / ``mask`` / ``confidence`` / ``overlap_weight`` /
+    ``overlap_rows`` / ``views``: as ``RefineBatch``'s (``views`` combines with neither ``report``, ``pictures`` nor ``retrieve=True``).  ``poses``: as
     ``RefineBatch``'s; only when it is given, the pair (``RefineBatch.poses()``, ``RefineBatch.pose_grad``) is a further element.
     ``intrinsics``: as ``RefineBatch``'s; only when it is given, the pair (``RefineBatch.intrinsics()``, ``RefineBatch.intr_grad``) is the last one."""
     rb = RefineBatch(model, rooms, bank=bank, learning_rate=learning_rate, noise_seed=noise_seed, image_size=image_size, iters=iters, report=report,
                      pictures=pictures, retrieve=retrieve, observed=observed, mask=mask, overlap_weight=overlap_weight, overlap_rows=overlap_rows,
-                     views=views, poses=poses, intrinsics=intrinsics)
+                     views=views, poses=poses, intrinsics=intrinsics, confidence=confidence)
     try:
         out = (rb.run(capture=capture).clone(), [(b.clone(), i.clone()) for b, i in rb.results()])
         if report is not None:
@@ -1943,11 +2077,12 @@ def finetune_vae_fast_batch(model, rooms, iters=60, bank=None, learning_rate=1e-
 
 def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_names, iters=60, render_fn=None, bank=None,
                  learning_rate=1e-4, noise_seed=13, image_size=256, log=None, observed=None, mask=None, overlap_weight=0.0, overlap_rows=None,
-                 views=None, poses=None, intrinsics=None):
+                 views=None, poses=None, intrinsics=None, confidence=None):
     """finetune_VAE's inner loop for ONE room (test_render_refine.py:265-359) on synthetic meshes.
     ``observed`` / ``mask``: as ``finetune_vae_fast``'s, on the boxes' device whichever it is - the target from ``observed_target_torch`` on
     the room's class tables, the loss from ``refinement_loss_masked``.  ``overlap_weight`` / ``overlap_rows``: as ``finetune_vae_fast``'s (on CPU
-    tensors the penalty is ``evaluate.overlap_penalty_torch``).
+    tensors the penalty is ``evaluate.overlap_penalty_torch``).  ``confidence``: as ``finetune_vae_fast``'s (``[V, S, S]`` with ``views``), the
+    loss from ``refinement_loss_confidence`` - the autograd yardstick of the confidence kernels' loop.
     ``views``: None, or ``(K [V, 3, 3], Rm [V, 3, 3], t [V, 3])`` - ``RefineBatch``'s ``views`` for one room, in autograd: every view is
     rendered with ``render_fn(..., camera=(K, Rm, t))``, the loss is ``mean_v L_v + 2 size_loss`` with ``L_v`` the view's depth and semantic
     terms over its own image; ``observed`` and a tensor ``mask`` are then ``[V, S, S]``.  The yardstick of the view kernels' loop.
@@ -1970,11 +2105,13 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
     intr = check_intrinsics(intrinsics, cams)
     if cams is None:
         observed, mask = _one_room_arguments(observed, mask, int(image_size), dev, False, bank)
+        confidence = _one_room_confidence(confidence, mask, int(image_size), dev)
     else:
         cams = [tuple(x[0, v] for x in cams) for v in range(int(cams[0].shape[1]))]
         shape = (len(cams), int(image_size), int(image_size))
         check_observed(observed, shape, dev, False, choice=bank is not None and bank.has_choice())
         check_mask(mask, shape, dev, observed)
+        check_confidence(confidence, shape, dev, mask, cams)
     overlap = _one_room_overlap(overlap_weight, overlap_rows, class_names, int(boxes_gt.shape[0]), dev)
     bank = bank or MeshBank([n for n in set(class_names) if n not in DO_NOT_VIS], dev)
     model.eval()
@@ -1997,6 +2134,9 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
             _, chan, dch = DR.class_tables(ranges.keys())
             target, _ = OB.observed_target_torch(observed[0], observed[1], chan, dch, nch=DR.N_SCENE_CHANNELS)
     valid, labels = valid_and_labels(mask, target)
+    conf = None
+    if confidence is not None:
+        conf, labels = confidence_and_labels(confidence, target)
     if pose is not None:                 # the float64 pair the loop steps; K stays the view's
         pose_R, pose_t = (x[0].double() for x in (pose["start"] if pose["start"] is not None else (torch.stack([c[1] for c in cams])[None],
                                                                                                      torch.stack([c[2] for c in cams])[None])))
@@ -2043,7 +2183,9 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
                 else:
                     image = render_fn(v, f, ranges, room_box, image_size=image_size, camera=cam)
                 tgt, lab = target[vi:vi + 1], [t[vi:vi + 1] for t in labels]
-                if valid is not None:
+                if conf is not None:
+                    per_view.append(refinement_loss_confidence(image, tgt, lab, 0.0, conf[vi:vi + 1]))
+                elif valid is not None:
                     per_view.append(refinement_loss_masked(image, tgt, lab, 0.0, valid[vi:vi + 1]))
                 else:
                     per_view.append(refinement_loss(image, tgt, lab, 0.0))
@@ -2051,7 +2193,9 @@ def finetune_vae(model, objs, triples, boxes_gt, angles_gt, attributes, class_na
             loss = loss + size_loss * 2.0
         else:
             image = render_fn(v, f, ranges, room_box, image_size=image_size)
-            if valid is not None:
+            if conf is not None:
+                loss, dl, sl = refinement_loss_confidence(image, target, labels, size_loss, conf)
+            elif valid is not None:
                 loss, dl, sl = refinement_loss_masked(image, target, labels, size_loss, valid)
             else:
                 loss, dl, sl = refinement_loss(image, target, labels, size_loss)

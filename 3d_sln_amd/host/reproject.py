@@ -625,6 +625,19 @@ def fuse(face_index, weight, raster_depth, labels_src, V, gap, depth_out, labels
             "sln_reproject_fuse")
 
 
+def confidence_from_agree(agree, full, out, work):
+    """``agree`` uint8 (frames within ``gap`` of the winner's depth, the winner included; 0 without a winner) -> ``out`` uint8, the confidence
+    byte ``(min(agree, full) * 255 + full // 2) // full``: 0 without a winner, 255 from ``full`` agreeing frames on (128 for one frame at
+    ``full`` = 2).  ``work``: an int32 tensor of ``agree``'s shape.  Integer ops in place: allocates nothing."""
+    full = int(full)
+    if full < 1 or full > 255:
+        raise ValueError("confidence: full is a frame count in [1, 255], got %r" % (full,))
+    work.copy_(agree)
+    work.clamp_(max=full).mul_(255).add_(full // 2)
+    torch.div(work, full, rounding_mode="floor", out=work)
+    return out.copy_(work)
+
+
 class ObservedFuser(_ObservedRoute):
     """``views`` frames per room of ``rooms`` rooms, each ``Hs`` x ``Ws``, fused into one target view of ``S`` x ``S`` per room on the
     device: where several frames see a target pixel, the one with the nearest surface there has it (the z-buffer rule).
@@ -633,6 +646,7 @@ class ObservedFuser(_ObservedRoute):
         depth, labels, source = fu(depth_src, labels_src, k_src, pose, K_tgt, orig_size)
         rb = RefineBatch(model, rooms, observed=(depth, labels), mask=fu.valid(), image_size=256, ...)      # or mask="readings"
         corroborated = (fu.agree >= 2).to(torch.uint8)          # pixels two frames agree on, for mask= - built by the caller
+        rb = RefineBatch(model, rooms, observed=(depth, labels), confidence=fu.confidence(), ...)      # graded: seen once counts half
 
     ``depth_src`` [R, V, Hs, Ws] float32, ``labels_src`` [R, V, Hs, Ws] uint8, ``k_src`` [R, V, 4] float32, ``pose`` [R, V, 3, 4] float32
     - per frame, as ``ObservedReprojector`` takes them; a room with fewer frames pads with frames whose ``k_src`` has fx = 0 -, ``K_tgt``
@@ -655,6 +669,7 @@ class ObservedFuser(_ObservedRoute):
         self.labels, self.source, self.count, self.agree, self._valid = (torch.empty(R, S, S, dtype=torch.uint8, device=dev) for _ in range(5))
         self.hits = torch.zeros(R, dtype=torch.int64, device=dev)
         self.wins = torch.zeros(R, V, dtype=torch.int64, device=dev)
+        self._conf, self._conf_work = torch.empty(R, S, S, dtype=torch.uint8, device=dev), torch.empty(R, S, S, dtype=torch.int32, device=dev)
 
     def check(self, depth_src, labels_src, k_src, pose, K_tgt, orig_size):
         """raises ValueError before anything is launched; reads the instance's sizes, scalars and device only"""
@@ -673,3 +688,11 @@ class ObservedFuser(_ObservedRoute):
     def valid(self):
         """``source > 0`` as uint8 [R, S, S] in a static buffer: the tensor ``RefineBatch(mask=)`` takes (no allocation, nothing read back)"""
         return self._valid.copy_(self.source).clamp_(max=1)
+
+    def confidence(self, full=2):
+        """``(min(agree, full) * 255 + full // 2) // full`` as uint8 [R, S, S] in a static buffer: the tensor ``RefineBatch(confidence=)`` takes
+        - 0 without a winner, 128 for a pixel one frame saw, 255 from ``full`` frames that agree on (no allocation, nothing read back).
+        ``full`` outside [1, 255] is refused, and so is a fuser without the ``agree`` plane."""
+        if getattr(self, "agree", None) is None:
+            raise ValueError("confidence: this fuser was built without the agree plane")
+        return confidence_from_agree(self.agree, full, self._conf, self._conf_work)

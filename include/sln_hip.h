@@ -781,6 +781,13 @@ typedef struct {
   const int32_t* depth_count;                   /* [2, B] (device): row 0 the number N of valid pooled pixels room b's depth mean is divided by
                                                  * (all scales; per_room: the room's own, else the batch's in every entry), row 1 the number of
                                                  * non-zero pixels of valid_image[b] */
+  const int64_t* conf_sum;                      /* optional [2, B] (device), as sln_refine_loss_confidence leaves it; needs the three mask fields
+                                                 * (without all of them: SLN_E_BADARG).  Non-NULL: the per-pixel confidence route - valid_pooled
+                                                 * holds pooled confidence bytes c (weight c / 255.f, 0 as on the masked route), valid_image the
+                                                 * confidence image, and the means are divided by these sums / 255 instead of the counts: row 0
+                                                 * the sum of c over room b's pooled pixels (all scales; per_room: the room's own, else the
+                                                 * batch's in every entry), row 1 the sum over the image's pixels.  NULL: the fields mean what
+                                                 * they meant */
 } SlnRefineLoss;
 int64_t sln_refine_loss_workspace_bytes(int B, int image_size, int pooled_size, int n_scales, int n_sem, int n_dep);
 /* 1 when live_planes / null_mask / pooled_ones of L would be honoured (the refinement loop's shapes), 0 when every plane is processed
@@ -812,6 +819,22 @@ int sln_refine_loss_backward(const SlnRefineLoss* L, const void* workspace, cons
  * forward and its backward this call destroys. */
 int sln_refine_loss_mask(const SlnRefineLoss* L, const unsigned char* valid, int32_t* labels, unsigned char* valid_pooled, float* inv_count,
                          int32_t* depth_count, int32_t* mask_status, void* workspace, void* stream);
+/* The per-pixel confidence of a target, once per target: the mask call with a graded weight (four launches, the first of which clears
+ * the counters; integer sums only, 64-bit: the same from call to call whatever sln_set_deterministic says; no allocation,
+ * synchronisation or read-back, legal under a capture).
+ *   conf         [B, S, S] uint8 in the planes' row order: 0 - the target says nothing here (as valid == 0), 255 - full trust; a
+ *                pixel's weight is conf / 255
+ *   conf_pooled  [B, n_scales, P, P] (out): the MINIMUM of conf over the 16 taps of the pooled pixel (sln_refine_loss_mask's tap sets,
+ *                whatever a tap's weight); for a {0, 255} image 255 * the mask call's valid_pooled
+ *   labels       [B, n_scales, P, P] (in-out): -100 wherever conf_pooled is 0
+ *   inv_count    [B, n_scales] (per_room) or [n_scales] (out): 1.f / (float)((double)(sum of conf_pooled over the labels >= 0 left) / 255.0)
+ *   depth_count  [2, B] (out): the non-zero counts, as the mask call gives them for the mask conf != 0
+ *   conf_sum     [2, B] (out): SlnRefineLoss::conf_sum
+ *   mask_status  [B] (out): bit 0 - conf_sum[0][b] is 0 (depth and its gradient are then 0); bit 1 - a scale keeps no label
+ * The mask fields of L itself are not read; `workspace` is the loss's, whose contents between a forward and its backward this call
+ * destroys.  With every byte in {0, 255} the loss, its gradient and the report are the masked route's bits; all 255: the unmasked ones. */
+int sln_refine_loss_confidence(const SlnRefineLoss* L, const unsigned char* conf, int32_t* labels, unsigned char* conf_pooled, float* inv_count,
+                               int32_t* depth_count, int64_t* conf_sum, int32_t* mask_status, void* workspace, void* stream);
 
 /* =============================================================================================
  * C. SPADE generator (models/SPADE_related.py: SPADEGenerator4 :1507-1605, SPADEResnetBlock4 :1457-1505,

@@ -4,7 +4,8 @@ VIEWS=V (default 0: ``views=None``): refine every room against V target views - 
 room's upper corners at its centre (``look_at_view``).  POSES=1 (needs VIEWS): refine the views' poses as well (``poses=``; ROT_STEP / TRANS_STEP,
 default 1e-6 each) - one more launch per iteration, sln_place_pose_step_views.  INTRINSICS=1 (needs VIEWS; with or without POSES): refine
 the views' focal lengths and principal points as well (``intrinsics=``; FOCAL_STEP, default 1e-6, CENTER_STEP, default 1e-4) - the one launch
-is then sln_place_camera_step_views.  Every line also gives the smallest and the largest of the three slopes (run i of 2 x `iters` against
+is then sln_place_camera_step_views.  CONFIDENCE=1: the loss under a per-pixel confidence (``confidence=``: bands at 255 / 128 and a rectangle at 0
+on every image); MASK=1: under the validity mask on the same support (``mask=``: the confidence's non-zero pixels).  Every line also gives the smallest and the largest of the three slopes (run i of 2 x `iters` against
 run i of `iters`)."""
 import importlib, os, sys, time
 import numpy as np, torch
@@ -47,6 +48,14 @@ def room_views(rooms, V):
     return tuple(torch.stack([torch.stack([c[v][j] for v in range(V)]) for c in cams]) for j in range(3))
 
 
+def confidence_image(n_images, S=256, dev="cuda"):
+    """uint8 [n_images, S, S]: rows in six bands at 255 / 128, a rectangle without a say"""
+    band = torch.tensor([255, 128, 255, 128, 128, 255], dtype=torch.uint8)[torch.arange(S) * 6 // S]
+    c = band[None, :, None].repeat(n_images, 1, S)
+    c[:, S // 4:S // 2, S // 3:2 * S // 3] = 0
+    return c.to(dev).contiguous()
+
+
 def main():
     iters = int(os.environ.get("ITERS", "60"))
     n_views = int(os.environ.get("VIEWS", "0"))
@@ -68,13 +77,18 @@ def main():
         intrinsics = None
         if os.environ.get("INTRINSICS", "0") != "0":
             intrinsics = dict(focal_step=float(os.environ.get("FOCAL_STEP", "1e-6")), center_step=float(os.environ.get("CENTER_STEP", "1e-4")))
+        extra = dict(intrinsics=intrinsics) if intrinsics else {}
+        if os.environ.get("CONFIDENCE", "0") != "0" or os.environ.get("MASK", "0") != "0":
+            conf = confidence_image(nr * max(n_views, 1)).view(*((nr, n_views) if n_views else (nr,)), 256, 256)
+            extra.update(dict(confidence=conf) if os.environ.get("CONFIDENCE", "0") != "0" else dict(mask=(conf != 0).to(torch.uint8)))
+            print("rooms %d: %s" % (nr, "confidence=" if "confidence" in extra else "mask="), flush=True)
         with torch.cuda.stream(st):
             for capture in (False, True):
                 res = []; enq = []
                 for n_it in (iters, 2 * iters, iters, 2 * iters, iters, 2 * iters):
                     torch.cuda.synchronize(); t0 = time.perf_counter()
                     G = int(os.environ.get("GROUPS", "1"))
-                    rb = R.RefineBatch(model, rooms, bank=bank, iters=n_it, views=views, poses=poses, **(dict(intrinsics=intrinsics) if intrinsics else {}))
+                    rb = R.RefineBatch(model, rooms, bank=bank, iters=n_it, views=views, poses=poses, **extra)
                     torch.cuda.synchronize(); t1 = time.perf_counter()
                     rb.run(capture=capture)
                     t_enq = time.perf_counter() - t1                  # host time to enqueue everything (the GPU may still be running)
